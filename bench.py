@@ -9,9 +9,15 @@ position update -> arrival / next waypoint, all on the device, state resident in
 Metric: SFM ticks/s (BASELINE.json "SFM ticks/s and ns/pedestrian-pair"); ns/pair is reported beside it.
 
 Timing protocol.  After W untimed warm-up steps a WINDOW is exactly K steps bracketed by a
-barrier + torch.cuda.synchronize() on both sides, its duration the MAX over ranks.  At least 5 windows are run, and
-more until they add up to >= 3 s (--min-seconds); `value` = K / the MEDIAN window; `windows`, `min`, `max` and the
-mean over all windows are on the line.  `steps` / `warmup` echo the arguments.
+barrier + torch.cuda.synchronize() on both sides, its duration the MAX over ranks.  By default ONE window is run, so the
+timed steps are exactly the K of --steps and `ms_per_step` = that window / K.  --windows N (and --min-seconds S) opt into
+the repeated protocol: at least N windows of K steps, more until they add up to >= S seconds; `value` = K / the MEDIAN
+window.  `windows`, `min`, `max` and the mean over all windows are on the line.  `steps` / `warmup` echo the arguments.
+
+--dump-outputs DIR: after the timed steps, what the timed path computed in its last step -- the state a caller of
+ShardedStepper.step receives, in pedestrian order -- goes to DIR/loc.npy, DIR/vel.npy, DIR/waypoint.npy (float32, the
+device's own values; at most 64 MB in all, a fixed seeded sample of rows beyond that).  Scenarios are seeded, so the
+same arguments give the same inputs on every run and two builds can be compared output for output.
 
 Workloads (--workload overrides the default, and the SAME workload can be run at every G):
   G = 1  -> c2: N = 4 096, pedestrian_force + acceleration_force        (the config the metric is quoted on)
@@ -209,14 +215,35 @@ def timed_windows(step, barrier, reduce_max, steps, min_windows, min_seconds, ma
     return times
 
 
+DUMP_MAX_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """arrays: name -> (N, k) array of per-pedestrian results.  Written as float32 DIR/<name>.npy; when they add up to
+    more than DUMP_MAX_BYTES, the same seeded sample of rows is kept from each (sorted, so the order stays pedestrian order)."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    n = min(len(v) for v in arrays.values())
+    row_bytes = sum(v[0].nbytes for v in arrays.values()) if n else 0
+    if row_bytes * n > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(seed).choice(n, size=DUMP_MAX_BYTES // row_bytes, replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--workload", default="auto", choices=["auto", "c1", "c2", "c3", "c4", "c5"])
-    ap.add_argument("--windows", type=int, default=5, help="minimum number of timed windows of --steps steps")
-    ap.add_argument("--min-seconds", type=float, default=3.0, help="keep adding windows until they total this long (SURVEY.md 8d: >= 3 s)")
+    ap.add_argument("--windows", type=int, default=1,
+                    help="minimum number of timed windows of --steps steps (default 1: exactly --steps timed steps)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="keep adding windows until they total this long (SURVEY.md 8d's repeated protocol: --windows 5 --min-seconds 3)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the last timed step computed as DIR/<name>.npy (loc, vel, waypoint)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-single-ref", action="store_true", help="G > 1: skip the one-GPU run of the same workload")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
@@ -271,7 +298,7 @@ def main():
         s1 = ShardedStepper(e1, sc)
         e1.engine.set_timing(False)
         s1.step(args.warmup)
-        t1 = timed_windows(s1.step, local_barrier, lambda v: v, args.steps, max(3, args.windows), args.min_seconds)
+        t1 = timed_windows(s1.step, local_barrier, lambda v: v, args.steps, args.windows, args.min_seconds)
         single_ref = {"value": args.steps / statistics.median(t1), "unit": "ticks/s", "windows": len(t1),
                       "min": args.steps / max(t1), "max": args.steps / min(t1)}
         e1.close()
@@ -299,6 +326,12 @@ def main():
         st.step(24)               # (a short warm-up: let the stepper finish choosing between the split and the plain tick)
     times = timed_windows(st.step, barrier, reduce_max, args.steps, args.windows, args.min_seconds)
     elapsed = statistics.median(times)
+
+    if args.dump_outputs:
+        # the state the last timed step left (collective when sharded: every rank gathers, rank 0 writes)
+        d_loc, d_vel, d_wp = st.gather_state()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"loc": d_loc, "vel": d_vel, "waypoint": d_wp})
 
     # the crowd must still be a crowd: a NaN or a runaway pedestrian anywhere in this rank's rows fails the run loudly
     _loc, _vel, _ = eng.engine.state()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate the golden vectors in tests/golden/*.npz by running the REFERENCE's own NumPy modules.
 
-Build-container only: needs the upstream checkout at /root/reference (it never travels to the GPU box).
+The reference's outputs need the upstream checkout (UPSTREAM_REFERENCE); --inputs-only does not.
 It imports the reference modules that import cleanly here -- stateutils, ped_mode_manager,
 pedestrian_state, forces -- and executes *their* code on seeded inputs:
 
@@ -15,8 +15,11 @@ pedestrian_simulation.py itself is not imported (it pulls check_traffic -> shape
 the three glue lines above call the reference functions it calls, in its order.
 
 Usage:  python tests/golden/make_golden.py                      (rewrites every fixture)
-        python tests/golden/make_golden.py --out DIR NAME ...   (only the named cases, into DIR: what
-                                                                 tests/test_golden_regen.py does to catch generator drift)
+        python tests/golden/make_golden.py --out DIR NAME ...   (only the named cases, into DIR)
+        python tests/golden/make_golden.py --inputs-only --out DIR NAME ...
+                                        (the inputs of the named cases alone -- scenarios, config, waypoint queues -- built
+                                         by this project's code without the upstream checkout: what tests/test_golden_regen.py
+                                         compares with the committed fixtures to catch generator drift)
 """
 import copy
 import os
@@ -28,19 +31,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 REF = os.environ.get("UPSTREAM_REFERENCE", "/root/reference")
 
-if not os.path.isdir(REF):
-    print(f"make_golden: reference checkout {REF} not present -- nothing to do")
-    sys.exit(0)
-
 sys.dont_write_bytecode = True
-sys.path.insert(0, REF)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import forces as ref_forces                      # noqa: E402  (reference)
-import stateutils as ref_stateutils              # noqa: E402  (reference)
-from ped_mode_manager import PedMode, PedModeManager   # noqa: E402  (reference)
-from pedestrian_state import PedState            # noqa: E402  (reference)
 
 from carla_social_force_model_amd import scenarios          # noqa: E402
 from carla_social_force_model_amd.config import default_sfm_config  # noqa: E402
@@ -111,12 +104,37 @@ def ref_tick(peds, fd):
 
 OUT_DIR = HERE
 ONLY = None            # None = every case; otherwise the set of case names to (re)generate
+INPUTS_ONLY = False    # True: write the inputs alone (no reference code runs)
+
+
+def import_reference():
+    """The reference modules, imported from the upstream checkout; False when it is not present."""
+    global ref_forces, ref_stateutils, PedMode, PedModeManager, PedState
+    if not os.path.isdir(REF):
+        return False
+    sys.path.insert(0, REF)
+    import forces as ref_forces                      # noqa: E402  (reference)
+    import stateutils as ref_stateutils              # noqa: E402  (reference)
+    from ped_mode_manager import PedMode, PedModeManager   # noqa: E402  (reference)
+    from pedestrian_state import PedState            # noqa: E402  (reference)
+    return True
+
+
+def waypoint_queue(sc):
+    rng = np.random.default_rng(sc.seed + 31337)
+    return scenarios._f32(rng.uniform(0.0, max(sc.world_side, 1.0), (sc.n, QUEUE, 2)))
 
 
 def make_case(name, sc, cfg, trajectory=True):
     if ONLY is not None and name not in ONLY:
         return
     out = gio.encode_inputs(sc, cfg, DT)
+    if INPUTS_ONLY:
+        # (a full run writes the queue only when the reference's v' is finite: trajectory cases whose v' is not get none)
+        if trajectory:
+            out["wp_queue"] = waypoint_queue(sc)
+        np.savez_compressed(os.path.join(OUT_DIR, name + ".npz"), **out)
+        return
     with np.errstate(all="ignore"):
         peds = build_ref_state(sc, cfg)
         fd = build_ref_forces(sc, cfg)
@@ -130,8 +148,7 @@ def make_case(name, sc, cfg, trajectory=True):
     out["ref_arrived"] = (np.linalg.norm(d, axis=-1) < ARRIVE_THR)
 
     if trajectory and np.all(np.isfinite(v_new)):
-        rng = np.random.default_rng(sc.seed + 31337)
-        queue = scenarios._f32(rng.uniform(0.0, max(sc.world_side, 1.0), (sc.n, QUEUE, 2)))
+        queue = waypoint_queue(sc)
         out["wp_queue"] = queue
         used = np.zeros(sc.n, dtype=np.int64)
         locs, vels, wps = [], [], []
@@ -157,7 +174,13 @@ def make_case(name, sc, cfg, trajectory=True):
 
 
 def main():
-    print(f"reference at {REF}, numpy {np.__version__}")
+    if INPUTS_ONLY:
+        print(f"inputs only, numpy {np.__version__}")
+    elif not import_reference():
+        print(f"make_golden: reference checkout {REF} not present -- nothing to do")
+        return
+    else:
+        print(f"reference at {REF}, numpy {np.__version__}")
     full = default_sfm_config()
     # seeds x sizes, all five forces, stock parameters
     for seed in (0, 1, 2):
@@ -226,6 +249,9 @@ def main():
 
 if __name__ == "__main__":
     argv = sys.argv[1:]
+    if argv and argv[0] == "--inputs-only":
+        INPUTS_ONLY = True
+        argv = argv[1:]
     if argv and argv[0] == "--out":
         OUT_DIR = argv[1]
         ONLY = set(argv[2:]) or None

@@ -302,6 +302,35 @@ def test_bench_flags_counters_from_another_build_as_stale(tmp_path, monkeypatch)
     assert "SQ_INSTS_VALU" in pmc and "VALU_PER_64_PAIR_STEP" in pmc and stamp["counters_stale"] is False
 
 
+def test_bench_dump_outputs_keeps_float32_under_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as DIR/<name>.npy in float32; above the size cap the same seeded, sorted sample of
+    rows from each array, so two runs (two builds) stay comparable row for row."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(5)
+    arrays = {"loc": rng.normal(size=(1000, 3)), "vel": rng.normal(size=(1000, 3)), "waypoint": rng.normal(size=(1000, 2))}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "all" / (k + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, v.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 4 * 100)             # room for 100 rows of 3 + 3 + 2 floats
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    total = 0
+    for k, v in arrays.items():
+        a, b = np.load(tmp_path / "a" / (k + ".npy")), np.load(tmp_path / "b" / (k + ".npy"))
+        assert a.shape == (100, v.shape[1]) and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= bench.DUMP_MAX_BYTES
+    rows = [int(np.flatnonzero((arrays["loc"].astype(np.float32) == r).all(axis=1))[0]) for r in np.load(tmp_path / "a" / "loc.npy")]
+    assert rows == sorted(rows)
+    assert np.array_equal(np.load(tmp_path / "a" / "vel.npy"), arrays["vel"][rows].astype(np.float32))
+
+
 def test_mode_caches_follow_every_way_a_mode_can_change():
     """Round 4: ``apply_current_mode`` / ``crossing_mask`` are cached arrays, rebuilt when a mode object says that something changed
     (ModeWatch.version).  Every way the reference's callers change a mode or a target speed must get through -- set_mode
