@@ -14,8 +14,12 @@ import numpy as np
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFM_LIB_PATH") or os.path.join(PKG_DIR, "libsfm_hip.so")   # (the override is for A/B builds of the kernels)
-ABI_VERSION = 5
-SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_records": 5}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
+ABI_VERSION = 6
+SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_records": 5,
+         **{n: 6 for n in ("sfm_batch_create", "sfm_batch_destroy", "sfm_batch_set_stream", "sfm_batch_set_params",
+                           "sfm_batch_upload_state", "sfm_batch_set_borders", "sfm_batch_set_static_obstacles",
+                           "sfm_batch_set_dynamic_obstacles", "sfm_batch_tick", "sfm_batch_run", "sfm_batch_download_state",
+                           "sfm_batch_last_error")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
 
 FORCE_NAMES = ("acceleration_force", "pedestrian_force", "border_force",
                "static_obstacle_force", "dynamic_obstacle_force")
@@ -88,6 +92,19 @@ SYMBOLS = {
     "sfm_set_partition": (C.c_int, [_H, C.c_int, C.c_int, _I]),
     "sfm_tick_begin": (C.c_int, [_H, C.c_uint32]),
     "sfm_tick_end": (C.c_int, [_H, C.c_uint32]),
+    # batched scenes (ABI 6)
+    "sfm_batch_create": (C.c_int, [C.c_int, C.POINTER(SfmParamsC), C.c_int, C.POINTER(_H)]),
+    "sfm_batch_destroy": (C.c_int, [_H]),
+    "sfm_batch_set_stream": (C.c_int, [_H, C.c_void_p]),
+    "sfm_batch_set_params": (C.c_int, [_H, C.POINTER(SfmParamsC)]),
+    "sfm_batch_upload_state": (C.c_int, [_H, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _U8]),
+    "sfm_batch_set_borders": (C.c_int, [_H, _I, _I, _F, _F, _F, _F, _F]),
+    "sfm_batch_set_static_obstacles": (C.c_int, [_H, _I, _I, _F, _F, _F, _F]),
+    "sfm_batch_set_dynamic_obstacles": (C.c_int, [_H, _I, _I, _F, _F, _F, _F, _F, _F]),
+    "sfm_batch_tick": (C.c_int, [_H, C.c_uint32]),
+    "sfm_batch_run": (C.c_int, [_H, C.c_int, C.c_uint32]),
+    "sfm_batch_download_state": (C.c_int, [_H, _F, _F, _F, _F, _F, _F]),
+    "sfm_batch_last_error": (C.c_char_p, [_H]),
 }
 
 _lib = None

@@ -1,0 +1,260 @@
+"""Batched scenes: many small, independent crowds stepped by ONE kernel launch per tick (C ABI: sfm_batch_*, ABI 6).
+
+Social-force models are run in bulk as many small scenes -- scenario sampling, RL environments stepped in lock-step, calibration
+sweeps over A / lambda / gamma / tau.  ``SfmBatch`` holds B scenes of 0 .. 1024 pedestrians, each with its own parameters (its own
+sfm_config) and its own borders / obstacles, and steps all of them in one launch.  A scene's result is bitwise the same whatever
+else is in the batch and wherever it sits (for batches of the same kind: planar, or 3-D).  Crowds above 1024 pedestrians belong on
+an ``SfmEngine`` handle.
+
+A scene is a dict in the formats ``SfmEngine`` accepts:
+  loc, vel, waypoint (N,3); target_speed (N,); radius (N,) or None; crossing (N,) bool or None (border force off);
+  borders: list of (P_k,2), border_centers (K,2), border_lengths (K,);
+  static_obstacles / dynamic_obstacles: lists of (center(2), ring(P,2)); dynamic_vel (M,2) or None (at rest).
+Missing geometry keys mean none.  ``vars(scenarios.make_scenario(...))`` is such a dict.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import SfmLibraryError, f32, fptr, iptr, u8ptr
+from .engine import _csr, params_from_config
+
+MAX_SCENE_PEDESTRIANS = 1024     # SFM_BATCH_MAX_N
+
+
+def _rows(a, n, width, name, k):
+    a = np.asarray(a, dtype=np.float64)
+    a = a.reshape(-1, width) if width else a.reshape(-1)
+    if a.shape[0] != n:
+        raise ValueError(f"scene {k}: {name} has {a.shape[0]} rows, expected {n}")
+    return a
+
+
+def _polylines(polys, name, k):
+    out = []
+    for q, pl in enumerate(polys):
+        a = np.asarray(pl, dtype=np.float64)
+        if a.size and (a.ndim != 2 or a.shape[1] != 2):
+            raise ValueError(f"scene {k}: {name} {q} must be a (P,2) array, got shape {a.shape}")
+        out.append(a.reshape(-1, 2))
+    return out
+
+
+def _obstacles(obstacles, name, k):
+    obstacles = [] if obstacles is None else list(obstacles)
+    cs = []
+    for q, ob in enumerate(obstacles):
+        if len(ob) != 2:
+            raise ValueError(f"scene {k}: {name} {q} must be a (center, ring) pair")
+        c = np.asarray(ob[0], dtype=np.float64).reshape(-1)
+        if c.size < 2:
+            raise ValueError(f"scene {k}: {name} {q} has a centre of {c.size} coordinates")
+        cs.append(c[:2])
+    rings = _polylines([ob[1] for ob in obstacles], name, k)
+    return np.array(cs, dtype=np.float64).reshape(-1, 2), rings
+
+
+def _scene_csr(per_scene_polys):
+    """Concatenate per-scene polyline lists: (scene_item_off [B+1] int32, offsets [K+1] int32, px, py)."""
+    item_off = np.zeros(len(per_scene_polys) + 1, dtype=np.int32)
+    for b, polys in enumerate(per_scene_polys):
+        item_off[b + 1] = item_off[b] + len(polys)
+    off, px, py = _csr([pl for polys in per_scene_polys for pl in polys])
+    return item_off, off, px, py
+
+
+def pack_scenes(scenes):
+    """Scenes (list of dicts, see the module docstring) -> the concatenated fp32 SoA and CSR arrays of the C ABI.  Pure NumPy.
+
+    Returns a dict: ``scene_off`` int32 [B+1]; ``x y z vx vy vz wx wy target_speed radius`` float32 [N_total]; ``crossing`` uint8
+    [N_total]; ``planar`` (bool: every scene has a single z and no v_z -- SfmEngine.upload_state's planar=None rule, per scene,
+    applied batch-wide: one 3-D scene makes the whole batch 3-D); ``borders`` = (scene_item_off, offsets, px, py, cx, cy,
+    cull_len); ``static`` = (scene_item_off, offsets, px, py, cx, cy); ``dynamic`` = (scene_item_off, offsets, px, py, cx, cy, vx, vy).
+    Raises ValueError on a scene of more than 1024 pedestrians and on malformed state or geometry."""
+    scenes = list(scenes)
+    if not scenes:
+        raise ValueError("a batch needs at least one scene")
+    B = len(scenes)
+    scene_off = np.zeros(B + 1, dtype=np.int32)
+    cols = {k: [] for k in ("loc", "vel", "wp", "ts", "rad", "cross")}
+    planar = True
+    border_polys, border_c, border_l = [], [], []
+    stat_polys, stat_c = [], []
+    dyn_polys, dyn_c, dyn_v = [], [], []
+    for k, sc in enumerate(scenes):
+        loc = np.asarray(sc["loc"], dtype=np.float64)
+        if loc.size % 3:
+            raise ValueError(f"scene {k}: loc must be (N,3)")
+        loc = loc.reshape(-1, 3)
+        n = loc.shape[0]
+        if n > MAX_SCENE_PEDESTRIANS:
+            raise ValueError(f"scene {k} has {n} pedestrians; a batch takes up to {MAX_SCENE_PEDESTRIANS} per scene "
+                             "(larger crowds belong on an SfmEngine handle)")
+        vel = _rows(sc["vel"], n, 3, "vel", k)
+        wp = _rows(sc["waypoint"], n, 3, "waypoint", k)
+        ts = _rows(sc["target_speed"], n, 0, "target_speed", k)
+        rad = sc.get("radius")
+        rad = np.zeros(n) if rad is None else _rows(rad, n, 0, "radius", k)
+        cr = sc.get("crossing")
+        cr = np.zeros(n, dtype=bool) if cr is None else _rows(cr, n, 0, "crossing", k).astype(bool)
+        if n and not (bool(np.all(loc[:, 2] == loc[0, 2])) and not bool(np.any(vel[:, 2] != 0.0))):
+            planar = False
+        for key, v in zip(("loc", "vel", "wp", "ts", "rad", "cross"), (loc, vel, wp, ts, rad, cr)):
+            cols[key].append(v)
+        scene_off[k + 1] = scene_off[k] + n
+
+        borders = sc.get("borders")
+        borders = _polylines([] if borders is None else borders, "border", k)
+        K = len(borders)
+        cen = sc.get("border_centers")
+        ln = sc.get("border_lengths")
+        cen = np.zeros((0, 2)) if cen is None else np.asarray(cen, dtype=np.float64)
+        ln = np.zeros(0) if ln is None else np.asarray(ln, dtype=np.float64).reshape(-1)
+        if cen.size != 2 * K or ln.size != K:
+            raise ValueError(f"scene {k}: {K} borders need {K} centres and {K} lengths (got {cen.size} centre coordinates "
+                             f"and {ln.size} lengths)")
+        border_polys.append(borders)
+        border_c.append(cen.reshape(K, 2))
+        border_l.append(ln)
+        c, rings = _obstacles(sc.get("static_obstacles"), "static obstacle", k)
+        stat_polys.append(rings)
+        stat_c.append(c)
+        c, rings = _obstacles(sc.get("dynamic_obstacles"), "dynamic obstacle", k)
+        M = len(rings)
+        v = sc.get("dynamic_vel")
+        v = np.zeros((M, 2)) if v is None else np.asarray(v, dtype=np.float64)
+        if v.size != 2 * M:
+            raise ValueError(f"scene {k}: {M} dynamic obstacles need {M} velocities (got {v.size / 2:g})")
+        dyn_polys.append(rings)
+        dyn_c.append(c)
+        dyn_v.append(v.reshape(M, 2))
+
+    cat = lambda key, width: (np.concatenate(cols[key], axis=0) if cols[key] else np.zeros((0, width) if width else 0))
+    loc, vel, wp = cat("loc", 3), cat("vel", 3), cat("wp", 3)
+    bc, sc_, dc, dv = (np.concatenate(a, axis=0) for a in (border_c, stat_c, dyn_c, dyn_v))
+    return {
+        "scene_off": scene_off,
+        "x": f32(loc[:, 0]), "y": f32(loc[:, 1]), "z": f32(loc[:, 2]),
+        "vx": f32(vel[:, 0]), "vy": f32(vel[:, 1]), "vz": f32(vel[:, 2]),
+        "wx": f32(wp[:, 0]), "wy": f32(wp[:, 1]),
+        "target_speed": f32(cat("ts", 0)), "radius": f32(cat("rad", 0)),
+        "crossing": np.ascontiguousarray(cat("cross", 0), dtype=np.uint8),
+        "planar": planar,
+        "borders": (*_scene_csr(border_polys), f32(bc[:, 0]), f32(bc[:, 1]), f32(np.concatenate(border_l))),
+        "static": (*_scene_csr(stat_polys), f32(sc_[:, 0]), f32(sc_[:, 1])),
+        "dynamic": (*_scene_csr(dyn_polys), f32(dc[:, 0]), f32(dc[:, 1]), f32(dv[:, 0]), f32(dv[:, 1])),
+    }
+
+
+def batch_params(configs, step_lengths, B=None, honour_file_keys=False):
+    """One config (dict) or a list of B configs, one step length or B of them -> a ctypes array of B SfmParams
+    (``params_from_config`` per scene)."""
+    cfgs = [configs] if isinstance(configs, dict) else list(configs)
+    steps = np.atleast_1d(np.asarray(step_lengths, dtype=np.float64))
+    if B is None:
+        B = max(len(cfgs), len(steps))
+    if len(cfgs) not in (1, B) or len(steps) not in (1, B):
+        raise ValueError(f"{len(cfgs)} configs and {len(steps)} step lengths for {B} scenes")
+    arr = (_lib.SfmParamsC * B)()
+    for k in range(B):
+        arr[k] = params_from_config(cfgs[k if len(cfgs) > 1 else 0], float(steps[k if len(steps) > 1 else 0]), honour_file_keys)
+    return arr
+
+
+class SfmBatch:
+    """B independent scenes on one GPU, one launch per tick.  Raises SfmLibraryError on any failure; never falls back to the CPU."""
+
+    def __init__(self, configs, step_lengths, device=0, honour_file_keys=False, B=None):
+        self._lib = _lib.load()
+        self._b = C.c_void_p()
+        self.params = batch_params(configs, step_lengths, B, honour_file_keys)
+        self.B = len(self.params)
+        rc = self._lib.sfm_batch_create(self.B, self.params, int(device), C.byref(self._b))
+        if rc != 0:
+            msg = self._lib.sfm_batch_last_error(None)
+            self._b = C.c_void_p()
+            raise SfmLibraryError(f"sfm_batch_create failed ({rc}): {msg.decode() if msg else '?'}")
+        self.scene_off = None
+        self.planar = True
+        self._z = None
+
+    def _check(self, rc, what):
+        if rc != 0:
+            msg = self._lib.sfm_batch_last_error(self._b)
+            raise SfmLibraryError(f"{what} failed ({rc}): {msg.decode() if msg else '?'}")
+
+    def close(self):
+        if getattr(self, "_b", None) is not None and self._b:
+            self._lib.sfm_batch_destroy(self._b)
+            self._b = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, stream_ptr):
+        self._check(self._lib.sfm_batch_set_stream(self._b, C.c_void_p(int(stream_ptr))), "sfm_batch_set_stream")
+
+    def set_params(self, configs, step_lengths, honour_file_keys=False):
+        params = batch_params(configs, step_lengths, self.B, honour_file_keys)
+        self._check(self._lib.sfm_batch_set_params(self._b, params), "sfm_batch_set_params")
+        self.params = params
+
+    def upload(self, scenes, planar=None):
+        """State and geometry of every scene (a list of B scene dicts).  ``planar`` None = pack_scenes' decision."""
+        scenes = list(scenes)
+        if len(scenes) != self.B:
+            raise ValueError(f"{len(scenes)} scenes for a batch of {self.B}")
+        self.upload_packed(pack_scenes(scenes), planar)
+
+    def upload_packed(self, pk, planar=None):
+        """``upload`` from the output of ``pack_scenes`` (pack once, upload many times)."""
+        planar = pk["planar"] if planar is None else bool(planar)
+        L = self._lib
+        so = pk["scene_off"]
+        if len(so) != self.B + 1:
+            raise ValueError(f"packed scenes hold {len(so) - 1} scenes, the batch {self.B}")
+        bo, st, dy = pk["borders"], pk["static"], pk["dynamic"]
+        self._check(L.sfm_batch_set_borders(self._b, *(iptr(a) for a in bo[:2]), *(fptr(a) for a in bo[2:])), "sfm_batch_set_borders")
+        self._check(L.sfm_batch_set_static_obstacles(self._b, *(iptr(a) for a in st[:2]), *(fptr(a) for a in st[2:])),
+                    "sfm_batch_set_static_obstacles")
+        self._check(L.sfm_batch_set_dynamic_obstacles(self._b, *(iptr(a) for a in dy[:2]), *(fptr(a) for a in dy[2:])),
+                    "sfm_batch_set_dynamic_obstacles")
+        z, vz = (None, None) if planar else (pk["z"], pk["vz"])
+        self._check(L.sfm_batch_upload_state(self._b, iptr(so), fptr(pk["x"]), fptr(pk["y"]), fptr(z), fptr(pk["vx"]),
+                                             fptr(pk["vy"]), fptr(vz), fptr(pk["wx"]), fptr(pk["wy"]), fptr(pk["target_speed"]),
+                                             fptr(pk["radius"]), u8ptr(pk["crossing"])), "sfm_batch_upload_state")
+        self.scene_off = so.copy()
+        self.planar = planar
+        self._z = pk["z"].copy()          # a planar batch keeps each scene's z on the host (the device holds x / y only)
+
+    def tick(self, integrate=False):
+        self._check(self._lib.sfm_batch_tick(self._b, _lib.TICK_INTEGRATE if integrate else 0), "sfm_batch_tick")
+
+    def run(self, ticks):
+        self._check(self._lib.sfm_batch_run(self._b, int(ticks), _lib.TICK_INTEGRATE), "sfm_batch_run")
+
+    def state_arrays(self):
+        """Concatenated state: (loc (N_total,3), vel (N_total,3)) float64."""
+        if self.scene_off is None:
+            raise SfmLibraryError("SfmBatch.state: upload() has not been called")
+        n = int(self.scene_off[-1])
+        a = {k: np.zeros(n, np.float32) for k in ("x", "y", "z", "vx", "vy", "vz")}
+        if self.planar:
+            a["z"][:] = self._z
+        self._check(self._lib.sfm_batch_download_state(self._b, *(fptr(a[k]) for k in ("x", "y", "z", "vx", "vy", "vz"))),
+                    "sfm_batch_download_state")
+        loc = np.stack([a["x"], a["y"], a["z"]], axis=1).astype(np.float64)
+        vel = np.stack([a["vx"], a["vy"], a["vz"]], axis=1).astype(np.float64)
+        return loc, vel
+
+    def state(self):
+        """Per scene (loc (N_b,3), vel (N_b,3)) float64, in scene order."""
+        loc, vel = self.state_arrays()
+        so = self.scene_off
+        return [(loc[so[b]:so[b + 1]], vel[so[b]:so[b + 1]]) for b in range(self.B)]

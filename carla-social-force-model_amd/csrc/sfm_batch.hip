@@ -1,0 +1,218 @@
+// sfm_batch.hip -- batched scenes for gfx950 (MI355X): B independent crowds of 0 .. 1024 pedestrians, ONE launch per tick.
+//
+// Social-force models are run in bulk as many small scenes (scenario sampling, RL environments in lock-step, calibration sweeps over
+// A / lambda / gamma / tau ...).  A handle per scene costs a launch per scene per tick and leaves most of the GPU idle; here a
+// workgroup owns one scene and the whole batch is one grid.  Per scene, the tick of sfm_tick_kernel:
+//   F_i = acceleration + pedestrian (Moussaid, N_b x N_b) + border + static + dynamic obstacle forces (each scene's own switches,
+//   parameter tables and polylines),  v' = cap(v + dt F, max_speed_factor v0),  with SFM_TICK_INTEGRATE also x' = x + dt v'.
+//
+// Shape (workgroup b, 4 waves):
+//   1. the scene's pedestrians are staged in LDS once (x, y, vx, vy [, z, vz], radius: <= 28 KiB);
+//   2. pair sums: a lane owns row i and sums over ALL j of its j-slice in ascending order (the full N_b^2 terms -- at this size the
+//      antisymmetric F_ji = -F_ij trick does not pay for its reduction).  N_b <= 64: the four waves take a quarter of j each, N_b <= 128:
+//      a half; their partial sums meet in LDS in slice order.  Larger scenes: one slice, rows dealt to the 256 lanes in passes;
+//   3. geometry: each lane scans its scene's polylines (lane_nearest, a polyline at a time for the whole wave);
+//   4. epilogue: the forces in the reference's dict order, cap, integrate, store.
+// Planar bodies (moussaid_planar / moussaid_spatial) with the exact body (moussaid<.., EXACT>) recomputing a slice whose sum came out
+// NaN (coincident pair, or two pedestrians above one another in 3-D), as the handle's kernels do.
+// Determinism: no atomics, every order is a function of the scene alone (N_b, its rows, its polylines) -- a scene's result is
+// bitwise the same whatever else is in the batch and wherever it sits.  The state is updated in place: a scene's rows are read
+// (into LDS) and written by its own workgroup only, and every read comes before the barrier that precedes the first store.
+#include "sfm_device.h"
+#include "sfm_interaction.h"
+
+namespace sfm {
+
+template <bool Z3>
+struct BatchShared {
+    float4 pk[BATCH_MAX_N];                        // {x, y, vx, vy}
+    float2 zv[Z3 ? BATCH_MAX_N : 1];               // {z, vz}
+    float r[BATCH_MAX_N];                          // radius
+    float part[BLOCK][3];                          // j-slice partial sums, slot = slice * rows + row
+    __attribute__((aligned(16))) float2 row[WAVES_PER_BLOCK][WAVE];   // lane_nearest's per-wave rows
+};
+
+// Pedestrian force on row i from rows [j0, j1) of the scene, without the factor -A; j == i is dropped (stateutils.py:41-49)
+template <bool Z3, bool RAD>
+__device__ __forceinline__ void batch_pair_sum(const IxConst& c, const BatchShared<Z3>& sh, int i, int j0, int j1,
+                                               float& gx, float& gy, float& gz) {
+    const float4 si = sh.pk[i];
+    const float zi = Z3 ? sh.zv[i].x : 0.0f, vzi = Z3 ? sh.zv[i].y : 0.0f;
+    const float ri = RAD ? sh.r[i] : 0.0f;
+    gx = 0.0f; gy = 0.0f; gz = 0.0f;
+    for (int j = j0; j < j1; ++j) {                                    // wave-uniform: the LDS reads are broadcasts
+        const float4 pj = sh.pk[j];
+        const float dx = pj.x - si.x, dy = pj.y - si.y;
+        const float rsum = RAD ? ri + sh.r[j] : 0.0f;
+        float cx, cy, cz = 0.0f;
+        if (Z3) {
+            const float2 zj = sh.zv[j];
+            const float dz = zj.x - zi;
+            moussaid_spatial<RAD, false>(c, dx, dy, dz, fmaf(dx, dx, fmaf(dy, dy, dz * dz)), c.lam * (si.z - pj.z), c.lam * (si.w - pj.w),
+                                         c.lam * (vzi - zj.y), rsum, cx, cy, cz);
+        } else {
+            moussaid_planar<RAD, false>(c, dx, dy, fmaf(dx, dx, dy * dy), c.lam * (si.z - pj.z), c.lam * (si.w - pj.w), rsum, cx, cy);
+        }
+        const bool valid = j != i;                                     // select, so the diagonal's NaN never leaks
+        gx += valid ? cx : 0.0f;
+        gy += valid ? cy : 0.0f;
+        if (Z3) gz += valid ? cz : 0.0f;
+    }
+    // a NaN sum: a coincident pair (or, in 3-D, a pair above one another) needs the reference's zero-vector conventions -> this
+    // lane redoes its slice with the exact body (rare; the lane's own decision, so the result still depends on the scene only)
+    if (__builtin_isnan(gx) || __builtin_isnan(gy) || (Z3 && __builtin_isnan(gz))) {
+        gx = 0.0f; gy = 0.0f; gz = 0.0f;
+        for (int j = j0; j < j1; ++j) {
+            const float4 pj = sh.pk[j];
+            const float zj = Z3 ? sh.zv[j].x : 0.0f, vzj = Z3 ? sh.zv[j].y : 0.0f;
+            float cx = 0.0f, cy = 0.0f, cz = 0.0f, rinv;
+            moussaid<Z3, RAD, true>(c, pj.x - si.x, pj.y - si.y, zj - zi, si.z - pj.z, si.w - pj.w, vzi - vzj,
+                                    RAD ? ri + sh.r[j] : 0.0f, cx, cy, cz, rinv);
+            const bool valid = j != i;
+            gx += valid ? cx : 0.0f;
+            gy += valid ? cy : 0.0f;
+            if (Z3) gz += valid ? cz : 0.0f;
+        }
+    }
+}
+
+// Border / static / dynamic obstacle forces on one pedestrian per lane from the scene's polylines, in polyline order per kind:
+// BorderForce._get_force (forces.py:145-167) and ObstacleForce._get_force (forces.py:217-275) with the strict-< culls of the reference
+// (|x - centre| < section_length, :149-150; < perception_threshold, :222-223) and np.argmin's first-minimum rule (lane_nearest).
+template <bool RAD>
+__device__ __forceinline__ void batch_geometry(const BatchArgs& a, const BatchParams& p, int b, float x, float y, float vx, float vy,
+                                               float r, bool live, bool walk, float2* row, int lane, float (&f)[6]) {
+#pragma unroll 1
+    for (int kind = 0; kind < 3; ++kind) {
+        const bool on = kind == 0 ? p.en_border : kind == 1 ? p.en_static : p.en_dynamic;
+        if (!on) continue;                                             // uniform
+        const BatchGeo g = kind == 0 ? a.geo[0] : kind == 1 ? a.geo[1] : a.geo[2];    // (selects: no indexed copy in scratch)
+        const int k0 = g.item_off[b], k1 = g.item_off[b + 1];
+        const float thr2 = kind == 1 ? p.stat.thr2 : p.dyn.thr2;
+#pragma unroll 1
+        for (int k = k0; k < k1; ++k) {
+            const float4 c = g.ctr[k];
+            const int o0 = g.off[k], o1 = g.off[k + 1];
+            const float cdx = x - c.x, cdy = y - c.y;
+            const float d2c = fmaf(cdx, cdx, cdy * cdy);
+            const bool keep = kind == 0 ? (walk && d2c < c.z) : (live && d2c < thr2);
+            if (!__any(keep)) continue;                                // no lane of the wave keeps it
+            const float2 sp = lane_nearest(g.pts, o0, o1, x, y, row, lane);
+            if (!keep) continue;
+            if (kind == 0) {
+                const float ddx = x - sp.x, ddy = y - sp.y;
+                const float d = sqrtf(fmaf(ddx, ddx, ddy * ddy));
+                const float inv = (d == 0.0f) ? 1.0f : 1.0f / d;               // stateutils.normalize zero guard
+                const float dist = RAD ? d - r : d;                             // forces.py:160-161
+                const float mag = p.border_a * ex2(dist * p.border_nlb);        // a*exp(-dist/b), :163
+                f[0] = fmaf(ddx * inv, mag, f[0]);
+                f[1] = fmaf(ddy * inv, mag, f[1]);
+            } else {
+                const bool moving = kind == 2;                                  // static obstacles: v = 0 (:212-213)
+                const float ovx = moving ? c.z : 0.0f, ovy = moving ? c.w : 0.0f;
+                float gx = 0.f, gy = 0.f, gz = 0.f, unused;
+                moussaid<false, RAD, true>(moving ? p.dyn : p.stat, sp.x - x, sp.y - y, 0.0f, vx - ovx, vy - ovy, 0.0f, r,
+                                           gx, gy, gz, unused);
+                if (moving) { f[4] += gx; f[5] += gy; } else { f[2] += gx; f[3] += gy; }
+            }
+        }
+    }
+}
+
+template <bool Z3, bool RAD>
+__device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParams& p, BatchShared<Z3>& sh, int b, int s0, int n) {
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wave = uniform(tid >> 6);
+    // j split over the waves of a small scene: S slices of R rows each (R a multiple of 64, so a wave's slice is uniform)
+    const int S = n <= WAVE ? 4 : n <= 2 * WAVE ? 2 : 1;
+    const int R = BLOCK / S;
+    const int slice = uniform(tid / R), rloc = tid - slice * R;
+    const int chunk = (n + S - 1) / S;
+    const int j0 = min(n, slice * chunk), j1 = min(n, j0 + chunk);
+#pragma unroll 1
+    for (int base = 0; base < n; base += R) {                          // S > 1: one pass
+        const int i = base + rloc;
+        const bool live = i < n;
+        const int ii = live ? i : n - 1;
+        float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+        if (p.en_ped) batch_pair_sum<Z3, RAD>(p.ped, sh, ii, j0, j1, gx, gy, gz);
+        if (S > 1) {                                                   // partial sums meet in LDS, slice order
+            sh.part[tid][0] = gx; sh.part[tid][1] = gy; sh.part[tid][2] = gz;
+            __syncthreads();
+            if (slice != 0) return;                                    // (the last barrier of this workgroup)
+            gx = sh.part[rloc][0]; gy = sh.part[rloc][1]; gz = sh.part[rloc][2];
+            for (int s = 1; s < S; ++s) {
+                gx += sh.part[s * R + rloc][0];
+                gy += sh.part[s * R + rloc][1];
+                gz += sh.part[s * R + rloc][2];
+            }
+        }
+        float fpx = 0.f, fpy = 0.f, fpz = 0.f;
+        if (p.en_ped) { fpx = p.ped.negA * gx; fpy = p.ped.negA * gy; fpz = Z3 ? p.ped.negA * gz : 0.f; }
+
+        const float4 s = sh.pk[ii];
+        const float x = s.x, y = s.y, vx = s.z, vy = s.w;
+        const float z = Z3 ? sh.zv[ii].x : 0.0f, vz = Z3 ? sh.zv[ii].y : 0.0f;
+        const float r = RAD ? sh.r[ii] : 0.0f;
+        const bool walk = live && !(a.crossing && a.crossing[s0 + ii]);   // forces.py:140-141,176-177
+        float f[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        batch_geometry<RAD>(a, p, b, x, y, vx, vy, r, live, walk, sh.row[wave], lane, f);
+        const float fbx = f[0], fby = f[1];
+        const float fsx = p.stat.negA * f[2], fsy = p.stat.negA * f[3];
+        const float fdx = p.dyn.negA * f[4], fdy = p.dyn.negA * f[5];
+        if (!live) continue;
+
+        const float4 o = a.own[s0 + i];
+        const float ts = o.z;
+        // AccelerationForce (forces.py:46-53, stateutils.py:7-15)
+        float fax = 0.f, fay = 0.f, faz = 0.f;
+        if (p.en_acc) {
+            const float tx_ = o.x - x, ty_ = o.y - y;
+            const float nrm = sqrtf(fmaf(tx_, tx_, ty_ * ty_));
+            const float inv = (nrm == 0.0f) ? 1.0f : 1.0f / nrm;
+            fax = (ts * (tx_ * inv) - vx) * p.inv_tau;
+            fay = (ts * (ty_ * inv) - vy) * p.inv_tau;
+            faz = (0.0f - vz) * p.inv_tau;
+        }
+        // sum in the dict order acceleration, pedestrian, border, static, dynamic (pedestrian_simulation.py:37-48,81)
+        const float Fx = (((fax + fpx) + fbx) + fsx) + fdx;
+        const float Fy = (((fay + fpy) + fby) + fsy) + fdy;
+        const float Fz = faz + fpz;
+        // calculate_new_velocities + cap_velocity (pedestrian_simulation.py:117-124, stateutils.py:18-23)
+        float nvx = fmaf(p.dt, Fx, vx), nvy = fmaf(p.dt, Fy, vy), nvz = fmaf(p.dt, Fz, vz);
+        float sp = sqrtf(fmaf(nvx, nvx, fmaf(nvy, nvy, nvz * nvz)));
+        sp = (sp == 0.0f) ? 1.0f : sp;
+        const float fac = fminf(1.0f, (ts * p.max_speed_factor) / sp);
+        nvx *= fac; nvy *= fac; nvz *= fac;
+        float nx = x, ny = y, nz = z;
+        if (a.flags & 1u) { nx = fmaf(p.dt, nvx, x); ny = fmaf(p.dt, nvy, y); nz = fmaf(p.dt, nvz, z); }
+        a.pk[s0 + i] = make_float4(nx, ny, nvx, nvy);
+        if (Z3) a.zv[s0 + i] = make_float2(nz, nvz);
+    }
+}
+
+template <bool Z3>
+__global__ __launch_bounds__(BLOCK) void sfm_batch_tick_kernel(const BatchArgs a) {
+    __shared__ BatchShared<Z3> sh;
+    const int b = blockIdx.x;
+    const int s0 = a.scene_off[b], n = a.scene_off[b + 1] - s0;       // 0 <= n <= BATCH_MAX_N (checked on the host)
+    if (n <= 0) return;
+    const BatchParams& p = a.prm[b];                                    // (read through the pointer: uniform scalar loads)
+    for (int t = threadIdx.x; t < n; t += BLOCK) {
+        sh.pk[t] = a.pk[s0 + t];
+        if (Z3) sh.zv[t] = a.zv[s0 + t];
+        sh.r[t] = a.own[s0 + t].w;
+    }
+    __syncthreads();
+    if (p.rad) batch_scene<Z3, true>(a, p, sh, b, s0, n);
+    else batch_scene<Z3, false>(a, p, sh, b, s0, n);
+}
+
+hipError_t launch_batch_tick(bool z3, const BatchArgs& a, int B, hipStream_t st) {
+    if (z3) hipLaunchKernelGGL(sfm_batch_tick_kernel<true>, dim3(B), dim3(BLOCK), 0, st, a);
+    else hipLaunchKernelGGL(sfm_batch_tick_kernel<false>, dim3(B), dim3(BLOCK), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace sfm

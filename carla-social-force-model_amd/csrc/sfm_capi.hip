@@ -45,6 +45,7 @@ hipError_t launch_gather(const uint32_t* src, int N, const float4* pk_in, float4
 hipError_t launch_tile_bounds(const float4* pk, const float2* zv, int N, float4* box, float* vmax, hipStream_t st, int t_lo = 0,
                               int t_hi = -1);
 int probe_dpp_direction(hipStream_t st);
+hipError_t launch_batch_tick(bool z3, const BatchArgs& a, int B, hipStream_t st);
 hipError_t launch_dynamic_boxes(float4* ctr, const int* off, const float2* local, const float2* rot, float2* pts, int M,
                                 float dt, int advance, hipStream_t st);
 }  // namespace sfm
@@ -2091,5 +2092,362 @@ int sfm_get_pair_work(SfmHandle* h, long long* tile_pair_items, long long* pair_
     if (pair_terms) *pair_terms = (items - diag_items) * (long long)(WAVE * WAVE) + t_own * (long long)(WAVE * WAVE / 2);
     return SFM_OK;
 }
+
+}  // extern "C"
+
+// ======================================================================================================
+// Batched scenes (ABI 6): B independent crowds, ONE launch of sfm_batch_tick_kernel per tick (sfm_batch.hip)
+// ======================================================================================================
+struct BatchGeoDev {
+    int* item_off = nullptr;   // [B+1], zero-filled while the kind has no polylines
+    int* off = nullptr;        // [K+1]
+    float2* pts = nullptr;     // [P]
+    float4* ctr = nullptr;     // [K]
+    int K = 0;
+};
+
+struct SfmBatch {
+    int device = 0;
+    int B = 0;
+    hipStream_t stream = nullptr;
+    BatchParams* d_prm = nullptr;      // [B]
+    int* d_scene_off = nullptr;        // [B+1]
+    int n_total = 0;
+    size_t cap = 0;                    // rows the state arrays hold
+    bool z3 = false;
+    bool have_state = false;
+    float4* pk = nullptr;              // {x, y, vx, vy}
+    float2* zv = nullptr;              // {z, vz}
+    float4* own = nullptr;             // {wx, wy, target_speed, radius}
+    uint8_t* crossing = nullptr;
+    bool any_rad = false;
+    BatchGeoDev geo[3];                // borders, static, dynamic obstacles
+    std::string err;
+};
+
+static int bfail(SfmBatch* b, int code, const std::string& msg) {
+    if (b) b->err = msg; else g_create_error = msg;
+    return code;
+}
+
+static int bbind(SfmBatch* b) {
+    if (!b) return SFM_ERR_INVALID;
+    hipError_t e = hipSetDevice(b->device);
+    if (e != hipSuccess) { b->err = std::string("hipSetDevice: ") + hipGetErrorString(e); return SFM_ERR_HIP; }
+    return SFM_OK;
+}
+
+// one scene's parameters, folded as fill_args folds a handle's
+static BatchParams batch_params(const SfmParams& p) {
+    BatchParams q;
+    memset(&q, 0, sizeof(q));
+    q.ped = fold(p.pedestrian);
+    q.stat = fold(p.static_obstacle);
+    q.dyn = fold(p.dynamic_obstacle);
+    q.border_a = p.border_a;
+    q.border_nlb = (float)(-1.4426950408889634 / (double)p.border_b);
+    q.inv_tau = (float)(1.0 / (double)p.tau);
+    q.dt = p.step_length;
+    q.max_speed_factor = p.max_speed_factor;
+    q.en_acc = p.enabled[SFM_FORCE_ACCELERATION] != 0;
+    q.en_ped = p.enabled[SFM_FORCE_PEDESTRIAN] != 0;
+    q.en_border = p.enabled[SFM_FORCE_BORDER] != 0;
+    q.en_static = p.enabled[SFM_FORCE_STATIC_OBSTACLE] != 0;
+    q.en_dynamic = p.enabled[SFM_FORCE_DYNAMIC_OBSTACLE] != 0;
+    q.rad = p.use_ped_radius != 0;
+    return q;
+}
+
+static int check_batch_params(SfmBatch* b, int B, const SfmParams* params) {
+    if (!params) return bfail(b, SFM_ERR_INVALID, "params is NULL");
+    for (int k = 0; k < B; ++k) {
+        const char* why = nullptr;
+        if (!check_params(&params[k], &why)) return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(k) + ": " + why);
+    }
+    return SFM_OK;
+}
+
+// scene_off-style CSR over B entries: off[0] = 0, non-decreasing; *total receives off[B]
+static int check_scene_csr(SfmBatch* b, const int32_t* off, const char* name, int max_per_scene, int* total) {
+    if (!off) return bfail(b, SFM_ERR_INVALID, std::string(name) + " is NULL");
+    if (off[0] != 0) return bfail(b, SFM_ERR_INVALID, std::string(name) + "[0] must be 0");
+    for (int k = 0; k < b->B; ++k) {
+        if (off[k + 1] < off[k]) return bfail(b, SFM_ERR_INVALID, std::string(name) + " must be non-decreasing (scene " + std::to_string(k) + ")");
+        if (max_per_scene > 0 && off[k + 1] - off[k] > max_per_scene)
+            return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(k) + " has " + std::to_string(off[k + 1] - off[k]) +
+                                             " pedestrians; a batch takes up to " + std::to_string(max_per_scene) + " per scene (larger crowds belong on a handle)");
+    }
+    *total = off[b->B];
+    return SFM_OK;
+}
+
+static void free_batch_geo(BatchGeoDev& g) {
+    if (g.off) hipFree(g.off);
+    if (g.pts) hipFree(g.pts);
+    if (g.ctr) hipFree(g.ctr);
+    g.off = nullptr; g.pts = nullptr; g.ctr = nullptr; g.K = 0;
+}
+
+// one kind of per-scene CSR polylines; ctr4[K] built by the caller
+static int set_batch_geo(SfmBatch* b, int kind, const int32_t* scene_item_off, const int32_t* offsets, const float* px, const float* py,
+                         const std::vector<float4>& ctr4, int K) {
+    BatchGeoDev& g = b->geo[kind];
+    const int P = K > 0 ? offsets[K] : 0;
+    HIP_TRY(b, hipStreamSynchronize(b->stream));                 // a tick in flight may still read the arrays
+    free_batch_geo(g);
+    HIP_TRY(b, hipMemcpy(g.item_off, scene_item_off, sizeof(int) * ((size_t)b->B + 1), hipMemcpyHostToDevice));
+    if (K == 0) return SFM_OK;
+    std::vector<float2> pts((size_t)(P > 0 ? P : 1));
+    for (int p = 0; p < P; ++p) pts[p] = make_float2(px[p], py[p]);
+    HIP_TRY(b, dev_realloc(g.off, (size_t)K + 1));
+    HIP_TRY(b, dev_realloc(g.pts, pts.size()));
+    HIP_TRY(b, dev_realloc(g.ctr, (size_t)K));
+    HIP_TRY(b, hipMemcpy(g.off, offsets, sizeof(int) * ((size_t)K + 1), hipMemcpyHostToDevice));
+    HIP_TRY(b, hipMemcpy(g.pts, pts.data(), sizeof(float2) * pts.size(), hipMemcpyHostToDevice));
+    HIP_TRY(b, hipMemcpy(g.ctr, ctr4.data(), sizeof(float4) * (size_t)K, hipMemcpyHostToDevice));
+    g.K = K;
+    return SFM_OK;
+}
+
+// validation shared by the three geometry calls: *K = polylines over all scenes
+static int check_batch_geo(SfmBatch* b, const int32_t* scene_item_off, const int32_t* offsets, const float* px, const float* py,
+                           const float* cx, const float* cy, int* K) {
+    int rc = check_scene_csr(b, scene_item_off, "scene_item_off", 0, K);
+    if (rc) return rc;
+    if (*K == 0) return SFM_OK;
+    if (!offsets) return bfail(b, SFM_ERR_INVALID, "offsets is NULL");
+    if (offsets[0] != 0) return bfail(b, SFM_ERR_INVALID, "offsets[0] must be 0");
+    for (int k = 0; k < *K; ++k)
+        if (offsets[k + 1] < offsets[k]) return bfail(b, SFM_ERR_INVALID, "offsets must be non-decreasing");
+    if (offsets[*K] > 0 && (!px || !py)) return bfail(b, SFM_ERR_INVALID, "point arrays are NULL");
+    if (!cx || !cy) return bfail(b, SFM_ERR_INVALID, "centre arrays are NULL");
+    return SFM_OK;
+}
+
+static int batch_launch(SfmBatch* b, uint32_t flags) {
+    BatchArgs a;
+    memset(&a, 0, sizeof(a));
+    a.scene_off = b->d_scene_off;
+    a.prm = b->d_prm;
+    a.pk = b->pk;
+    a.zv = b->z3 ? b->zv : nullptr;
+    a.own = b->own;
+    a.crossing = b->crossing;
+    for (int k = 0; k < 3; ++k) a.geo[k] = BatchGeo{b->geo[k].item_off, b->geo[k].off, b->geo[k].pts, b->geo[k].ctr};
+    a.flags = flags;
+    HIP_TRY(b, launch_batch_tick(b->z3, a, b->B, b->stream));
+    return SFM_OK;
+}
+
+extern "C" {
+
+int sfm_batch_create(int B, const SfmParams* params, int device_id, SfmBatch** out) {
+    if (!out) return bfail(nullptr, SFM_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (B < 1) return bfail(nullptr, SFM_ERR_INVALID, "B must be >= 1");
+    int rc = check_batch_params(nullptr, B, params);
+    if (rc) return rc;
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) return bfail(nullptr, SFM_ERR_NO_DEVICE, "no HIP device visible (libsfm_hip needs an MI355X)");
+    if (device_id < 0 || device_id >= ndev) return bfail(nullptr, SFM_ERR_INVALID, "device_id out of range");
+    e = hipSetDevice(device_id);
+    if (e != hipSuccess) return bfail(nullptr, SFM_ERR_HIP, hipGetErrorString(e));
+    SfmBatch* b = new SfmBatch();
+    b->device = device_id;
+    b->B = B;
+    std::vector<BatchParams> q((size_t)B);
+    for (int k = 0; k < B; ++k) q[k] = batch_params(params[k]);
+    std::vector<int> zeros((size_t)B + 1, 0);
+    bool ok = dev_realloc(b->d_prm, (size_t)B) == hipSuccess && dev_realloc(b->d_scene_off, (size_t)B + 1) == hipSuccess &&
+              hipMemcpy(b->d_prm, q.data(), sizeof(BatchParams) * (size_t)B, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(b->d_scene_off, zeros.data(), sizeof(int) * ((size_t)B + 1), hipMemcpyHostToDevice) == hipSuccess;
+    for (int k = 0; k < 3 && ok; ++k)
+        ok = dev_realloc(b->geo[k].item_off, (size_t)B + 1) == hipSuccess &&
+             hipMemcpy(b->geo[k].item_off, zeros.data(), sizeof(int) * ((size_t)B + 1), hipMemcpyHostToDevice) == hipSuccess;
+    for (int k = 0; k < B && ok; ++k) b->any_rad = b->any_rad || params[k].use_ped_radius != 0;
+    if (!ok) {
+        sfm_batch_destroy(b);
+        return bfail(nullptr, SFM_ERR_HIP, "device allocation for the batch failed");
+    }
+    *out = b;
+    return SFM_OK;
+}
+
+int sfm_batch_destroy(SfmBatch* b) {
+    if (!b) return SFM_ERR_INVALID;
+    hipSetDevice(b->device);
+    hipStreamSynchronize(b->stream);
+    for (int k = 0; k < 3; ++k) {
+        free_batch_geo(b->geo[k]);
+        if (b->geo[k].item_off) hipFree(b->geo[k].item_off);
+    }
+    if (b->d_prm) hipFree(b->d_prm);
+    if (b->d_scene_off) hipFree(b->d_scene_off);
+    if (b->pk) hipFree(b->pk);
+    if (b->zv) hipFree(b->zv);
+    if (b->own) hipFree(b->own);
+    if (b->crossing) hipFree(b->crossing);
+    delete b;
+    return SFM_OK;
+}
+
+int sfm_batch_set_stream(SfmBatch* b, void* hip_stream) {
+    if (!b) return SFM_ERR_INVALID;
+    b->stream = reinterpret_cast<hipStream_t>(hip_stream);
+    return SFM_OK;
+}
+
+int sfm_batch_set_params(SfmBatch* b, const SfmParams* params) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    rc = check_batch_params(b, b->B, params);
+    if (rc) return rc;
+    bool any_rad = false;
+    for (int k = 0; k < b->B; ++k) any_rad = any_rad || params[k].use_ped_radius != 0;
+    if (any_rad && b->have_state && b->n_total > 0 && !b->any_rad)
+        return bfail(b, SFM_ERR_STATE, "use_ped_radius on a batch whose state was uploaded without radii: upload the state again");
+    std::vector<BatchParams> q((size_t)b->B);
+    for (int k = 0; k < b->B; ++k) q[k] = batch_params(params[k]);
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    HIP_TRY(b, hipMemcpy(b->d_prm, q.data(), sizeof(BatchParams) * (size_t)b->B, hipMemcpyHostToDevice));
+    b->any_rad = any_rad;
+    return SFM_OK;
+}
+
+int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x, const float* y, const float* z,
+                           const float* vx, const float* vy, const float* vz, const float* wx, const float* wy,
+                           const float* target_speed, const float* radius, const uint8_t* crossing_mask) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    int N = 0;
+    rc = check_scene_csr(b, scene_off, "scene_off", BATCH_MAX_N, &N);
+    if (rc) return rc;
+    if (N > 0 && (!x || !y || !vx || !vy || !wx || !wy || !target_speed))
+        return bfail(b, SFM_ERR_INVALID, "a required state array is NULL");
+    if ((z == nullptr) != (vz == nullptr)) return bfail(b, SFM_ERR_INVALID, "z and vz must be given together");
+    if (b->any_rad && N > 0 && !radius) return bfail(b, SFM_ERR_INVALID, "use_ped_radius needs radius");
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    const size_t n = (size_t)N;
+    if (n > b->cap) {
+        HIP_TRY(b, dev_realloc(b->pk, n));
+        HIP_TRY(b, dev_realloc(b->zv, n));
+        HIP_TRY(b, dev_realloc(b->own, n));
+        HIP_TRY(b, dev_realloc(b->crossing, n));
+        b->cap = n;
+    }
+    b->have_state = false;
+    if (n > 0) {
+        std::vector<float4> pk(n), own(n);
+        std::vector<float2> zv(n);
+        std::vector<uint8_t> cm(n);
+        for (size_t i = 0; i < n; ++i) {
+            pk[i] = make_float4(x[i], y[i], vx[i], vy[i]);
+            own[i] = make_float4(wx[i], wy[i], target_speed[i], radius ? radius[i] : 0.f);
+            zv[i] = z ? make_float2(z[i], vz[i]) : make_float2(0.f, 0.f);
+            cm[i] = crossing_mask ? (crossing_mask[i] != 0) : 0;
+        }
+        HIP_TRY(b, hipMemcpy(b->pk, pk.data(), sizeof(float4) * n, hipMemcpyHostToDevice));
+        HIP_TRY(b, hipMemcpy(b->zv, zv.data(), sizeof(float2) * n, hipMemcpyHostToDevice));
+        HIP_TRY(b, hipMemcpy(b->own, own.data(), sizeof(float4) * n, hipMemcpyHostToDevice));
+        HIP_TRY(b, hipMemcpy(b->crossing, cm.data(), n, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(b, hipMemcpy(b->d_scene_off, scene_off, sizeof(int) * ((size_t)b->B + 1), hipMemcpyHostToDevice));
+    b->n_total = N;
+    b->z3 = z != nullptr;
+    b->have_state = true;
+    return SFM_OK;
+}
+
+int sfm_batch_set_borders(SfmBatch* b, const int32_t* scene_item_off, const int32_t* offsets, const float* px, const float* py,
+                          const float* cx, const float* cy, const float* cull_len) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    int K = 0;
+    rc = check_batch_geo(b, scene_item_off, offsets, px, py, cx, cy, &K);
+    if (rc) return rc;
+    if (K > 0 && !cull_len) return bfail(b, SFM_ERR_INVALID, "border length array is NULL");
+    std::vector<float4> c4((size_t)K);
+    for (int k = 0; k < K; ++k) c4[k] = make_float4(cx[k], cy[k], (float)((double)cull_len[k] * (double)cull_len[k]), 0.f);
+    return set_batch_geo(b, 0, scene_item_off, offsets, px, py, c4, K);
+}
+
+int sfm_batch_set_static_obstacles(SfmBatch* b, const int32_t* scene_item_off, const int32_t* offsets, const float* px,
+                                   const float* py, const float* cx, const float* cy) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    int K = 0;
+    rc = check_batch_geo(b, scene_item_off, offsets, px, py, cx, cy, &K);
+    if (rc) return rc;
+    std::vector<float4> c4((size_t)K);
+    for (int k = 0; k < K; ++k) c4[k] = make_float4(cx[k], cy[k], 0.f, 0.f);
+    return set_batch_geo(b, 1, scene_item_off, offsets, px, py, c4, K);
+}
+
+int sfm_batch_set_dynamic_obstacles(SfmBatch* b, const int32_t* scene_item_off, const int32_t* offsets, const float* px,
+                                    const float* py, const float* cx, const float* cy, const float* vx, const float* vy) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    int K = 0;
+    rc = check_batch_geo(b, scene_item_off, offsets, px, py, cx, cy, &K);
+    if (rc) return rc;
+    if ((vx == nullptr) != (vy == nullptr)) return bfail(b, SFM_ERR_INVALID, "vx and vy must be given together");
+    std::vector<float4> c4((size_t)K);
+    for (int k = 0; k < K; ++k)       // velocities default to 0 like ObstacleForce (forces.py:212-213)
+        c4[k] = make_float4(cx[k], cy[k], vx ? vx[k] : 0.f, vy ? vy[k] : 0.f);
+    return set_batch_geo(b, 2, scene_item_off, offsets, px, py, c4, K);
+}
+
+int sfm_batch_tick(SfmBatch* b, uint32_t flags) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (flags & ~(uint32_t)SFM_TICK_INTEGRATE) return bfail(b, SFM_ERR_INVALID, "a batch tick takes SFM_TICK_INTEGRATE only");
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    return batch_launch(b, flags);
+}
+
+int sfm_batch_run(SfmBatch* b, int ticks, uint32_t flags) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (ticks < 0) return bfail(b, SFM_ERR_INVALID, "ticks < 0");
+    if (flags & ~(uint32_t)SFM_TICK_INTEGRATE) return bfail(b, SFM_ERR_INVALID, "a batch run takes SFM_TICK_INTEGRATE only");
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    for (int t = 0; t < ticks; ++t) {
+        rc = batch_launch(b, SFM_TICK_INTEGRATE);
+        if (rc) return rc;
+    }
+    return SFM_OK;
+}
+
+int sfm_batch_download_state(SfmBatch* b, float* x, float* y, float* z, float* vx, float* vy, float* vz) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    const size_t n = (size_t)b->n_total;
+    if (n == 0) return SFM_OK;
+    std::vector<float4> pk(n);
+    HIP_TRY(b, hipMemcpy(pk.data(), b->pk, sizeof(float4) * n, hipMemcpyDeviceToHost));
+    std::vector<float2> zv;
+    if (b->z3 && (z || vz)) {
+        zv.resize(n);
+        HIP_TRY(b, hipMemcpy(zv.data(), b->zv, sizeof(float2) * n, hipMemcpyDeviceToHost));
+    }
+    for (size_t i = 0; i < n; ++i) {
+        if (x) x[i] = pk[i].x;
+        if (y) y[i] = pk[i].y;
+        if (vx) vx[i] = pk[i].z;
+        if (vy) vy[i] = pk[i].w;
+        if (b->z3) {
+            if (z) z[i] = zv[i].x;
+            if (vz) vz[i] = zv[i].y;
+        } else if (vz) {
+            vz[i] = 0.f;
+        }
+    }
+    return SFM_OK;
+}
+
+const char* sfm_batch_last_error(const SfmBatch* b) { return b ? b->err.c_str() : g_create_error.c_str(); }
 
 }  // extern "C"

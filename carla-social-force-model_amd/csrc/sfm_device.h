@@ -190,6 +190,35 @@ struct FusedArgs {
                               //    front of a run; 1: integrate by one tick, store, then the pairs of the new state
 };
 
+// Batched scenes (sfm_batch.hip, sfm_batch_* in the C ABI): B independent crowds of up to BATCH_MAX_N pedestrians, stepped by ONE
+// launch per tick, a workgroup per scene.  State is fp32 SoA over all scenes concatenated (scene b owns rows
+// [scene_off[b], scene_off[b+1])); every scene carries its own parameters and geometry.
+constexpr int BATCH_MAX_N = 1024;
+struct BatchParams {          // one scene's SfmParams, folded on the host like the handle's (fold(), fill_args)
+    IxConst ped, stat, dyn;
+    float border_a, border_nlb;   // a, -log2(e)/b
+    float inv_tau, dt, max_speed_factor;
+    int en_acc, en_ped, en_border, en_static, en_dynamic;
+    int rad;                  // use_ped_radius
+    int pad;
+};
+struct BatchGeo {             // per-scene CSR polylines: scene b owns polylines [item_off[b], item_off[b+1]) of the concatenated set
+    const int* item_off;      // [B+1]
+    const int* off;           // [K+1] into pts
+    const float2* pts;        // [P]
+    const float4* ctr;        // [K] borders: {cx, cy, section_length^2, 0}; obstacles: {cx, cy, vx, vy}
+};
+struct BatchArgs {
+    const int* scene_off;     // [B+1]
+    const BatchParams* prm;   // [B]
+    float4* pk;               // {x, y, vx, vy}, updated in place (a scene is read and written by its own workgroup only)
+    float2* zv;               // {z, vz}: 3-D batches only
+    const float4* own;        // {wx, wy, target_speed, radius}
+    const uint8_t* crossing;  // border-force mask
+    BatchGeo geo[3];          // borders, static obstacles, dynamic obstacles
+    uint32_t flags;           // SFM_TICK_INTEGRATE only
+};
+
 // Block-major packing for sharded runs (sfm_set_partition, sfm_reorder.hip): the row order is cut into gx columns by x, each
 // column into gy blocks by y -- block b = column * gy + position holds rows [bound[b], bound[b+1]) -- and every block is
 // strip-packed on its own, so a rank's contiguous row range is a compact rectangle of the map instead of a slab across it.

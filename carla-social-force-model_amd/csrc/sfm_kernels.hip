@@ -18,6 +18,7 @@
 // No MFMA: the pair body is ~60 dependent VALU ops with 5 transcendentals, not a contraction.  No atomics on forces, fixed
 // summation orders: every result is deterministic run to run.
 #include "sfm_device.h"
+#include "sfm_interaction.h"
 
 #ifndef SFM_X2
 #define SFM_X2 1                       // 1: the fused tick's planar step (no use_ped_radius) evaluates TWO pairs per lane on packed fp32 (A/B, round 4)
@@ -40,204 +41,6 @@ static inline const char* exp_env(const char* name) {
     (void)name;
     return nullptr;
 #endif
-}
-
-__device__ __forceinline__ float rsq(float x) { return __builtin_amdgcn_rsqf(x); }
-__device__ __forceinline__ float rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ float uniform(float v) {
-    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
-}
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// atan2(s, c) for (s, c) not both zero; minimax odd polynomial of degree 15 on [0,1]
-// (fit error 8.9e-8), octant fix-up by selects.  GUARD handles (0,0) -> 0 like np.arctan2.
-template <bool GUARD>
-__device__ __forceinline__ float atan2_poly(float s, float c) {
-    const float ax = fabsf(c), ay = fabsf(s);
-    const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-    float r = mn * rcp(mx);
-    if (GUARD) r = (mx == 0.0f) ? 0.0f : r;
-    const float z = r * r;
-    float p = -0.00478021258342167f;
-    p = fmaf(p, z, 0.02455628334061523f);
-    p = fmaf(p, z, -0.0599035729461461f);
-    p = fmaf(p, z, 0.09942682328546971f);
-    p = fmaf(p, z, -0.1402939336508994f);
-    p = fmaf(p, z, 0.1997137085401642f);
-    p = fmaf(p, z, -0.33332093252900674f);
-    p = fmaf(p, z, 0.9999999113883665f);
-    float phi = p * r;
-    phi = (ay > ax) ? (1.57079632679489662f - phi) : phi;
-    phi = (c < 0.0f) ? (3.14159265358979324f - phi) : phi;
-    return copysignf(phi, s);
-}
-
-// atan2(s, c) for a UNIT vector (s, c) (2-D fast path: both directions are normalised), half-angle form:
-//   tan(theta/2) = s / (1 + c)  ->  theta = 2 atan(s / (1 + |c|)) for c >= 0, sign(s)*pi - that for c < 0.
-// The ratio is in [-1, 1] for every quadrant, so there is no octant swap, and theta = r * P(r^2) keeps
-// full RELATIVE precision for small angles (head-on encounters, where the force is largest).
-// 8-coefficient minimax fit of 2*atan(r)/r on [0,1], relative error 8.9e-8 (below the 2^-22 rad resolution of
-// the angle between two fp32-rounded directions).  (0,0) -> 0.
-__device__ __forceinline__ float atan2_unit(float s, float c) {
-    const float r = s * rcp(1.0f + fabsf(c));
-    const float z = r * r;
-    float p = -0.0095607885413262813f;
-    p = fmaf(p, z, 0.049113825228842972f);
-    p = fmaf(p, z, -0.11980885478692463f);
-    p = fmaf(p, z, 0.1988547939908939f);
-    p = fmaf(p, z, -0.28058826128196529f);
-    p = fmaf(p, z, 0.39942748114880167f);
-    p = fmaf(p, z, -0.66664186893326649f);
-    p = fmaf(p, z, 1.9999998228145017f);
-    const float a = p * r;
-    return (c < 0.0f) ? (copysignf(3.14159265358979324f, s) - a) : a;
-}
-
-// One Moussaid interaction (forces.py:85-115 / :241-270) without the common factor -A:
-//   (dx,dy,dz) = other - self, (dvx,dvy,dvz) = v_self - v_other, rsum = radii to subtract.
-// Adds e1*t + g*n to (gx,gy,gz), n = (-t_y, t_x, 0).
-// EXACT reproduces the reference's zero-vector conventions (stateutils.normalize's divide-by-1,
-// np.arctan2(0,0) = 0, -0/0 = NaN); the fast form differs from it only for coincident pairs, which the
-// caller detects through `rinv_out` and recomputes.
-template <bool Z3, bool RAD, bool EXACT>
-__device__ __forceinline__ void moussaid(const IxConst& c, float dx, float dy, float dz, float dvx,
-                                         float dvy, float dvz, float rsum, float& gx, float& gy, float& gz,
-                                         float& rinv_out) {
-    const float d2 = fmaf(dx, dx, fmaf(dy, dy, Z3 ? fmaf(dz, dz, TINY) : TINY));
-    const float rinv = rsq(d2);
-    rinv_out = rinv;
-    float d = d2 * rinv;
-    const float ex = dx * rinv, ey = dy * rinv;
-    const float ez = Z3 ? dz * rinv : 0.0f;
-    const float Dx = fmaf(c.lam, dvx, ex), Dy = fmaf(c.lam, dvy, ey);
-    const float Dz = Z3 ? fmaf(c.lam, dvz, ez) : 0.0f;
-    const float D2 = fmaf(Dx, Dx, fmaf(Dy, Dy, Z3 ? fmaf(Dz, Dz, TINY) : TINY));
-    const float rD = rsq(D2);
-    float Dn = D2 * rD;                        // |D|
-    const float tx = Dx * rD, ty = Dy * rD;
-    const float tz = Z3 ? Dz * rD : 0.0f;
-    float sn, cs, aL;
-    if (EXACT) {
-        const bool e_flat = (dx == 0.0f) & (dy == 0.0f);             // xy part of e is the zero vector
-        const bool t_flat = (Dx == 0.0f) & (Dy == 0.0f);
-        const bool coincident = e_flat & (Z3 ? (dz == 0.0f) : true);
-        const bool d_zero = t_flat & (Z3 ? (Dz == 0.0f) : true);
-        const float exa = e_flat ? 1.0f : ex;                         // arctan2(0,0) = 0 = angle of (1,0)
-        const float txa = t_flat ? 1.0f : tx;
-        sn = fmaf(txa, ey, -(ty * exa));
-        cs = fmaf(txa, exa, ty * ey);
-        d = coincident ? 0.0f : d;
-        Dn = d_zero ? 0.0f : Dn;
-        const float deff = RAD ? d - rsum : d;
-        aL = deff * c.c1 * (1.0f / Dn);                               // -d/B*log2e; B = 0 -> -inf or NaN
-    } else {
-        sn = fmaf(tx, ey, -(ty * ex));                                // sin / cos of angle(e) - angle(t)
-        cs = fmaf(tx, ex, ty * ey);
-        const float deff = RAD ? d - rsum : d;
-        aL = deff * (rD * c.c1);
-    }
-    // == wrapped atan2 difference (stateutils.py:104-112); planar fast path: (sn, cs) is a unit vector
-    const float ang = (EXACT || Z3) ? atan2_poly<EXACT>(sn, cs) : atan2_unit(sn, cs);
-    const float theta = fmaf(-c.eg, Dn, ang);                         // forces.py:101
-    const float q = Dn * theta;
-    const float q2 = q * q;
-    const float e1 = ex2(fmaf(q2, c.k1, aL));                         // exp(-d/B - (n' B theta)^2)
-    const float e2 = ex2(fmaf(q2, c.k2, aL));                         // exp(-d/B - (n  B theta)^2)
-    float g = copysignf(e2, theta);                                   // sign(theta) * e2
-    if (EXACT) g = (theta == 0.0f) ? 0.0f : g;                        // np.sign(0) = 0 (forces.py:108)
-    gx = fmaf(e1, tx, gx);
-    gx = fmaf(-g, ty, gx);
-    gy = fmaf(e1, ty, gy);
-    gy = fmaf(g, tx, gy);
-    if (Z3) gz = fmaf(e1, tz, gz);
-}
-
-// The wrapped angle between two planar directions, biased (stateutils.py:104-112, forces.py:94,101), from S = m sin, C = m cos of
-// the angle, m > 0 the common scale:  theta = atan2(S, C) - eg Dn.
-// Half-angle form: tan(angle / 2) = S / (m + C); with |C| in the denominator the ratio stays in [-1, 1] for every quadrant and
-//   angle = 2 atan(r) for C >= 0,  sign(S) pi - 2 atan(r) for C < 0,  r = S / (m + |C|),
-// 2 atan(r) = r P(r^2): 8-coefficient minimax fit on [0, 1], relative error 9.9e-8 (below the 2^-22 rad that the angle between two
-// fp32-rounded directions resolves), full relative precision for small angles (head-on encounters, where the force is largest).
-// Round 4: the C < 0 branch is sign arithmetic instead of v_cmp + v_cndmask (issue cost of that pair on MI355X: 16 cycles, as much as
-// 6.7 fmas -- tools/valu_microbench.hip): with s = copysign(1, C) the denominator s (m + |C|) = s m + C hands the ratio the sign that
-// the branch would have given 2 atan(r), and what is left of the branch is the constant k = (1 - s) copysign(pi / 2, S) = 0 or
-// sign(S) pi, added by the fma that finishes the polynomial.  Same values as the branch (C >= 0: p r + 0; C < 0: sign(S) pi - p |r|..)
-// up to the rounding of the denominator; a NaN in m (coincident pair) still comes out as NaN.
-__device__ __forceinline__ float half_angle_theta(float S, float C, float m, float eg, float Dn) {
-#ifndef SFM_ATAN_TERMS
-#define SFM_ATAN_TERMS 8
-#endif
-#if SFM_FIXUP_BRANCH
-    const float r = S * rcp(m + fabsf(C));
-#else
-    const float sc = copysignf(1.0f, C);
-    const float r = S * rcp(fmaf(sc, m, C));
-#endif
-    const float z = r * r;
-#if SFM_ATAN_TERMS == 8
-    float p = -0.0095607885413262813f;
-    p = fmaf(p, z, 0.049113825228842972f);
-    p = fmaf(p, z, -0.11980885478692463f);
-    p = fmaf(p, z, 0.1988547939908939f);
-    p = fmaf(p, z, -0.28058826128196529f);
-    p = fmaf(p, z, 0.39942748114880167f);
-    p = fmaf(p, z, -0.66664186893326649f);
-    p = fmaf(p, z, 1.9999998228145017f);
-#else                                         // 7 coefficients: relative error 6.5e-7 (A/B only)
-    float p = 0.015726754441857338f;
-    p = fmaf(p, z, -0.07402600347995758f);
-    p = fmaf(p, z, 0.16774238646030426f);
-    p = fmaf(p, z, -0.26974382996559143f);
-    p = fmaf(p, z, 0.39762964844703674f);
-    p = fmaf(p, z, -0.6665303111076355f);
-    p = fmaf(p, z, 1.999998688697815f);
-#endif
-#if SFM_FIXUP_BRANCH
-    const float a = p * r;
-    const float ang = (C < 0.0f) ? (copysignf(3.14159265358979324f, S) - a) : a;
-    return fmaf(-eg, Dn, ang);
-#else
-    const float h = copysignf(1.57079632679489662f, S);
-    const float k = fmaf(-eg, Dn, fmaf(-sc, h, h));                    // 0 or sign(S) pi (pi / 2 doubles exactly), minus the bias eps B
-    return fmaf(p, r, k);
-#endif
-}
-
-// The same interaction for the symmetric kernel's planar fast path, arranged for the fewest issued instructions:
-//   (dx,dy) = other - self and d2 = dx^2 + dy^2 come from the caller (it has already tested d2 against the reach);
-//   (wx,wy) = lambda (v_self - v_other) -- both velocities are pre-multiplied by lambda once per tile, so D = w + e is one
-//   fma per component and e itself is never formed: sin / cos of the angle come out scaled by d, S = t x (dx,dy) = d sin,
-//   C = t . (dx,dy) = d cos, and the half-angle ratio is S / (d + |C|).
-// d2 is NOT padded: a coincident pair gives rsq(0) = inf -> d = NaN -> a NaN term, which the epilogue takes as the
-// signal to recompute the tile with the exact body (the reference's conventions for zero vectors, forces.py:97,105).
-// CUT: once -d/B is known (two of the five transcendentals in), a step whose 64 exponents are ALL below -41 is dropped: both
-// exponentials of every lane are then < 2^-41, the term < 2^-40 A (the same policy as the tile and the reach tests, now with the
-// pair's actual |D| instead of a speed bound).  A NaN exponent (coincident pair) never counts as small.  Returns false if dropped.
-template <bool RAD, bool CUT>
-__device__ __forceinline__ bool moussaid_planar(const IxConst& c, float dx, float dy, float d2, float wx, float wy, float rsum,
-                                                float& cx, float& cy) {
-    const float rinv = rsq(d2);
-    const float d = d2 * rinv;
-    const float Dx = fmaf(dx, rinv, wx), Dy = fmaf(dy, rinv, wy);
-    const float D2 = fmaf(Dx, Dx, fmaf(Dy, Dy, TINY));
-    const float rD = rsq(D2);
-    const float deff = RAD ? d - rsum : d;
-    const float aL = deff * (rD * c.c1);
-    if (CUT && !__any(!(aL <= -41.0f))) return false;
-    const float Dn = D2 * rD;                                          // |D|
-    const float tx = Dx * rD, ty = Dy * rD;
-    const float S = fmaf(tx, dy, -(ty * dx));                          // d sin(angle(e) - angle(t))
-    const float C = fmaf(tx, dx, ty * dy);                             // d cos
-    const float theta = half_angle_theta(S, C, d, c.eg, Dn);          // forces.py:94,101
-    const float q = Dn * theta;
-    const float q2 = q * q;
-    const float e1 = ex2(fmaf(q2, c.k1, aL));
-    const float e2 = ex2(fmaf(q2, c.k2, aL));
-    const float g = copysignf(e2, theta);
-    cx = fmaf(e1, tx, -(g * ty));
-    cy = fmaf(e1, ty, g * tx);
-    return true;
 }
 
 // The planar body on PACKED fp32 instructions (round 4).  v_pk_add / v_pk_mul / v_pk_fma_f32 issue in 4.3 cycles per wave on MI355X
@@ -348,41 +151,6 @@ __device__ __forceinline__ void moussaid_planar_x2(const IxConst& c, float pjx, 
     const v2f g = copysign2(e2, theta);
     cx = fma2(e1, tx, -(g * ty));
     cy = fma2(e1, ty, g * tx);
-}
-
-// The same for a 3-D crowd (round 3; pedestrian_state.py:17-19 keeps 3-component positions and velocities and forces.py:75-117
-// takes 3-component norms): e, D and t are 3-vectors, the force is f_v t + f_theta n with n = (-t_y, t_x, 0), and the angle is the
-// one between the xy-projections of e and t (stateutils.angle_diff_2d uses components 0 and 1 only) -- neither projection is a unit
-// vector, so the half-angle ratio is S / (h + |C|) with h = sqrt(S^2 + C^2) (one more rsq).  d2 is the 3-D squared distance.
-// Two pedestrians above one another (e_xy = 0) or a vertical D give h = 0 -> rsq(0) = inf -> NaN, the signal for the exact body
-// (np.arctan2(0, 0) = 0 there), like a coincident pair in the planar body.
-template <bool RAD, bool CUT>
-__device__ __forceinline__ bool moussaid_spatial(const IxConst& c, float dx, float dy, float dz, float d2, float wx, float wy, float wz,
-                                                 float rsum, float& cx, float& cy, float& cz) {
-    const float rinv = rsq(d2);
-    const float d = d2 * rinv;
-    const float Dx = fmaf(dx, rinv, wx), Dy = fmaf(dy, rinv, wy), Dz = fmaf(dz, rinv, wz);
-    const float D2 = fmaf(Dx, Dx, fmaf(Dy, Dy, fmaf(Dz, Dz, TINY)));
-    const float rD = rsq(D2);
-    const float deff = RAD ? d - rsum : d;
-    const float aL = deff * (rD * c.c1);
-    if (CUT && !__any(!(aL <= -41.0f))) return false;
-    const float Dn = D2 * rD;                                          // |D|
-    const float tx = Dx * rD, ty = Dy * rD, tz = Dz * rD;
-    const float S = fmaf(tx, dy, -(ty * dx));                          // |t_xy| |d_xy| sin(angle(e_xy) - angle(t_xy))
-    const float C = fmaf(tx, dx, ty * dy);                             // ... cos
-    const float h2 = fmaf(S, S, C * C);
-    const float h = h2 * rsq(h2);
-    const float theta = half_angle_theta(S, C, h, c.eg, Dn);          // forces.py:94,101
-    const float q = Dn * theta;
-    const float q2 = q * q;
-    const float e1 = ex2(fmaf(q2, c.k1, aL));
-    const float e2 = ex2(fmaf(q2, c.k2, aL));
-    const float g = copysignf(e2, theta);
-    cx = fmaf(e1, tx, -(g * ty));
-    cy = fmaf(e1, ty, g * tx);
-    cz = e1 * tz;
-    return true;
 }
 
 // Two pairs per lane for a 3-D crowd (round 4, late; the fused tick's 8-wave form -- all forces at N = 4096: 24.0 -> 22.5 us): moussaid_spatial's
@@ -513,66 +281,6 @@ __device__ __forceinline__ bool tiles_negligible(const float4 ba, const float va
     const float gy = fmaxf(0.0f, fmaxf(ba.y - bb.w, bb.y - ba.w));
     const float reach = fmaf(cut_scale, fmaf(lam, va + vb, 1.0f), cut_pad);
     return fmaf(gx, gx, gy * gy) > reach * reach;
-}
-
-// ---- nearest sampled point of a polyline: np.argmin's first-minimum rule (forces.py:154,228) -------------
-// One LANE per pedestrian, the polyline [o0,o1) is wave-uniform.  A trip brings 64 points in with one coalesced
-// load (the next trip's load is in flight meanwhile), parks them in the wave's LDS row, and every lane walks them
-// through broadcast ds_read_b128 (two points each).  The running minimum is kept per GROUP of 8 points (4 ops
-// per distance + one min3 tree + one compare per group instead of a compare-select pair per point); at the end
-// of the trip a lane whose minimum moved re-reads its winning group from the row and takes the first slot
-// whose distance -- recomputed with the same operations, so bit-identical -- equals the minimum.
-// Groups in ascending order with a strict `<`, first equal slot inside the group: np.argmin's first-minimum rule.
-// Slots past the end hold copies of the last point (they can tie with it, never beat it, and come later).
-// LDS operations of one wave execute in order, so the row needs no barrier.
-// An empty polyline yields a far-away sentinel whose force term underflows to exactly 0.
-__device__ __forceinline__ float dist2(float x, float y, float px, float py) {
-    const float ax = x - px, ay = y - py;
-    return fmaf(ax, ax, ay * ay);
-}
-__device__ __forceinline__ float2 lane_nearest(const float2* __restrict__ pts, int o0, int o1, float x, float y,
-                                               float2* __restrict__ row, int lane) {
-    float bd = __builtin_inff();
-    float2 sp = make_float2(3.0e15f, 3.0e15f);
-    if (o1 <= o0) return sp;
-    const int last = o1 - 1;
-    float2 nxt = pts[min(o0 + lane, last)];
-    for (int p = o0; p < o1; p += WAVE) {
-        row[lane] = nxt;
-        if (p + WAVE < o1) nxt = pts[min(p + WAVE + lane, last)];
-        __builtin_amdgcn_wave_barrier();
-        const int cnt = min(WAVE, o1 - p);
-        int bl = -1;
-        auto group = [&](int u8) {
-            const float4* q = reinterpret_cast<const float4*>(row + u8);
-            const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-            const float d0 = dist2(x, y, q0.x, q0.y), d1 = dist2(x, y, q0.z, q0.w);
-            const float d2 = dist2(x, y, q1.x, q1.y), d3 = dist2(x, y, q1.z, q1.w);
-            const float d4 = dist2(x, y, q2.x, q2.y), d5 = dist2(x, y, q2.z, q2.w);
-            const float d6 = dist2(x, y, q3.x, q3.y), d7 = dist2(x, y, q3.z, q3.w);
-            const float m = fminf(fminf(fminf(fminf(d0, d1), d2), fminf(fminf(d3, d4), d5)), fminf(d6, d7));
-            const bool take = m < bd;
-            bd = take ? m : bd;
-            bl = take ? u8 : bl;
-        };
-#pragma unroll
-        for (int u8 = 0; u8 < WAVE; u8 += 8)
-            if (u8 < cnt) group(u8);                                   // uniform
-        if (bl >= 0) {                                                 // this lane's minimum moved: which slot?
-            const float4* q = reinterpret_cast<const float4*>(row + bl);
-            const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-            sp = make_float2(q3.z, q3.w);
-            if (dist2(x, y, q3.x, q3.y) == bd) sp = make_float2(q3.x, q3.y);
-            if (dist2(x, y, q2.z, q2.w) == bd) sp = make_float2(q2.z, q2.w);
-            if (dist2(x, y, q2.x, q2.y) == bd) sp = make_float2(q2.x, q2.y);
-            if (dist2(x, y, q1.z, q1.w) == bd) sp = make_float2(q1.z, q1.w);
-            if (dist2(x, y, q1.x, q1.y) == bd) sp = make_float2(q1.x, q1.y);
-            if (dist2(x, y, q0.z, q0.w) == bd) sp = make_float2(q0.z, q0.w);
-            if (dist2(x, y, q0.x, q0.y) == bd) sp = make_float2(q0.x, q0.y);
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    return sp;
 }
 
 __device__ __forceinline__ uint32_t mix32(uint32_t a) {   // lowbias32

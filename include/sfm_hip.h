@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SFM_ABI_VERSION 5   /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records (additions only) */
+#define SFM_ABI_VERSION 6   /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_* (additions only) */
 
 typedef struct SfmHandle SfmHandle;
 
@@ -266,6 +266,49 @@ const char* sfm_kernel_variant(const SfmHandle* h);
  * pair of a two-sided item).  SFM_ERR_STATE if the last tick used the ordered kernel. */
 int sfm_get_pair_work(SfmHandle* h, long long* tile_pair_items, long long* pair_terms);
 int sfm_abi_version(void);
+
+/* ---- batched scenes (ABI 6) ------------------------------------------------------------------------ */
+
+/* Many small, independent crowds stepped together (no reference counterpart: the reference steps one PedestrianSimulation per
+ * process; this is B of them, pedestrian_simulation.py:57-83 per scene).  A batch holds B scenes of 0 .. SFM_BATCH_MAX_N pedestrians
+ * each, every scene with its own SfmParams (a parameter sweep is one batch) and its own borders / obstacles; each tick is ONE kernel
+ * launch for the whole batch (sfm_batch.hip, a workgroup per scene).  A scene's result is bitwise the same whatever else is in the
+ * batch and wherever it sits.  Larger crowds belong on a handle.  Not supported on a batch: device-side vehicles, waypoint redraw,
+ * the mode state machine, force records, sharding.  Host arrays are fp32 SoA over all scenes concatenated; scene b owns rows
+ * [scene_off[b], scene_off[b+1]).  Geometry is per-scene CSR: scene b owns polylines [scene_item_off[b], scene_item_off[b+1]) of the
+ * concatenated set, whose points are offsets[k] .. offsets[k+1]-1 (offsets[0] = 0).  Errors as for a handle: a negative SfmStatus,
+ * the message in sfm_batch_last_error(b) (or sfm_batch_last_error(NULL) after a failed sfm_batch_create); nothing is launched on
+ * bad input and the batch stays usable. */
+#define SFM_BATCH_MAX_N 1024
+typedef struct SfmBatch SfmBatch;
+
+/* B >= 1 scenes, params[B]; the batch starts with no state and no geometry. */
+int sfm_batch_create(int B, const SfmParams* params, int device_id, SfmBatch** out);
+int sfm_batch_destroy(SfmBatch* b);
+int sfm_batch_set_stream(SfmBatch* b, void* hip_stream);                 /* hipStream_t; NULL = null stream */
+int sfm_batch_set_params(SfmBatch* b, const SfmParams* params);          /* params[B] */
+/* The state of every scene, as sfm_upload_state per scene: z / vz both NULL = a planar batch (2-D bodies); given = the 3-D bodies
+ * for every scene; radius may be NULL when no scene has use_ped_radius; crossing_mask may be NULL (all zero).  scene_off[B+1]:
+ * scene_off[0] = 0, non-decreasing, every scene <= SFM_BATCH_MAX_N pedestrians. */
+int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x, const float* y, const float* z,
+                           const float* vx, const float* vy, const float* vz, const float* wx, const float* wy,
+                           const float* target_speed, const float* radius, const uint8_t* crossing_mask);
+/* Borders of every scene (sfm_set_borders per scene); scene_item_off[B] = 0 clears them all. */
+int sfm_batch_set_borders(SfmBatch* b, const int32_t* scene_item_off, const int32_t* offsets, const float* px, const float* py,
+                          const float* cx, const float* cy, const float* cull_len);
+int sfm_batch_set_static_obstacles(SfmBatch* b, const int32_t* scene_item_off, const int32_t* offsets, const float* px,
+                                   const float* py, const float* cx, const float* cy);
+/* The vehicles as the caller last set them (vx / vy NULL: at rest); a batch does not move them. */
+int sfm_batch_set_dynamic_obstacles(SfmBatch* b, const int32_t* scene_item_off, const int32_t* offsets, const float* px,
+                                    const float* py, const float* cx, const float* cy, const float* vx, const float* vy);
+/* One tick of every scene: flags 0 or SFM_TICK_INTEGRATE (anything else is an error); v' (and x') in place. */
+int sfm_batch_tick(SfmBatch* b, uint32_t flags);
+/* `ticks` integrating ticks, one launch each (SFM_TICK_INTEGRATE implied; other flags are an error). */
+int sfm_batch_run(SfmBatch* b, int ticks, uint32_t flags);
+/* Current state of every scene (synchronises the batch's stream); NULL skips a column.  A planar batch leaves z alone and
+ * writes vz = 0. */
+int sfm_batch_download_state(SfmBatch* b, float* x, float* y, float* z, float* vx, float* vy, float* vz);
+const char* sfm_batch_last_error(const SfmBatch* b);
 
 #ifdef __cplusplus
 }

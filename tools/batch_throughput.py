@@ -1,0 +1,122 @@
+"""Scene-ticks per second of batched scenes (SfmBatch: one launch per tick for the whole batch) against one SfmEngine handle per
+scene.  One part per call, so that tools/batch_throughput.sh can run each under its own time limit:
+
+  --part batch     B in {64, 1024, 8192} scenes of N_b in {20, 64, 256}: pedestrian + acceleration forces, then all five forces
+                   with 40 border points (two borders of 20) and 4 obstacles (2 static, 2 vehicles) per scene
+  --part handles   the same scenes on B separate handles stepped with run(1) in a loop, B in {64, 1024}, N_b = 64
+  --part trace     B = 1024, N_b = 64, pedestrian + acceleration: a fixed number of batch ticks, for rocprofv3 --kernel-trace --stats
+
+Times are host wall clock around K back-to-back ticks after a warm-up, closed by a device synchronisation (the work is issued on
+the null stream).  A pool of distinct scenes is generated once per shape and repeated to fill the batch.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from carla_social_force_model_amd import scenarios  # noqa: E402
+from carla_social_force_model_amd.batch import SfmBatch, pack_scenes  # noqa: E402
+from carla_social_force_model_amd.config import default_sfm_config  # noqa: E402
+from carla_social_force_model_amd.engine import SfmEngine  # noqa: E402
+
+PED = ("acceleration_force", "pedestrian_force")
+POOL = 32
+
+
+def _pool(n, geo):
+    kw = dict(n_borders=2, n_static=2, n_dynamic=2, border_len=(2.0, 2.0)) if geo else {}
+    return [vars(scenarios.make_scenario(n, 7000 + k, **kw)) for k in range(POOL)]
+
+
+def _sync():
+    import torch
+    torch.cuda.synchronize()
+
+
+def _time_batch(B, n, geo, ticks):
+    pool = _pool(n, geo)
+    scenes = [pool[k % POOL] for k in range(B)]
+    cfg = default_sfm_config(scenarios.ALL_FORCES if geo else PED)
+    b = SfmBatch(cfg, 0.05, B=B)
+    try:
+        b.upload_packed(pack_scenes(scenes))
+        b.run(3)
+        _sync()
+        t0 = time.perf_counter()
+        b.run(ticks)
+        _sync()
+        dt = time.perf_counter() - t0
+        assert all(np.isfinite(v).all() for _, v in b.state()[:POOL])
+    finally:
+        b.close()
+    return dt / ticks
+
+
+def _time_handles(B, n, geo, ticks):
+    pool = _pool(n, geo)
+    cfg = default_sfm_config(scenarios.ALL_FORCES if geo else PED)
+    engs = []
+    try:
+        for k in range(B):
+            sc = pool[k % POOL]
+            e = SfmEngine(cfg, 0.05)
+            engs.append(e)
+            e.set_timing(False)                      # no HIP-event bracket per call: the handles' best case
+            if geo:
+                e.set_borders(sc["borders"], sc["border_centers"], sc["border_lengths"])
+                e.set_static_obstacles(sc["static_obstacles"])
+                e.set_dynamic_obstacles(sc["dynamic_obstacles"], sc["dynamic_vel"])
+            e.upload_state(sc["loc"], sc["vel"], sc["waypoint"], sc["target_speed"], sc["radius"], None)
+        for e in engs:
+            e.run(1)
+        _sync()
+        t0 = time.perf_counter()
+        for _ in range(ticks):
+            for e in engs:
+                e.run(1)
+        _sync()
+        dt = time.perf_counter() - t0
+    finally:
+        for e in engs:
+            e.close()
+    return dt / ticks
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--part", choices=("batch", "handles", "trace"), required=True)
+    ap.add_argument("--ticks", type=int, default=50)
+    args = ap.parse_args()
+    if args.part == "batch":
+        print("# batch: one launch per tick for the whole batch (SfmBatch.run)")
+        print(f"{'forces':<10} {'B':>6} {'N_b':>5} {'us/tick':>10} {'scene-ticks/s':>14} {'ped-ticks/s':>12}")
+        for geo in (False, True):
+            for B in (64, 1024, 8192):
+                for n in (20, 64, 256):
+                    t = _time_batch(B, n, geo, args.ticks)
+                    print(f"{'all five' if geo else 'ped+acc':<10} {B:>6} {n:>5} {t * 1e6:>10.1f} {B / t:>14.3e} {B * n / t:>12.3e}",
+                          flush=True)
+    elif args.part == "handles":
+        print("# handles: B separate SfmEngine handles, run(1) each in a loop (HIP-event timing off), N_b = 64")
+        print(f"{'forces':<10} {'B':>6} {'N_b':>5} {'us/tick':>10} {'scene-ticks/s':>14} {'batch us/tick':>14} {'batch speed-up':>15}")
+        for geo in (False, True):
+            for B in (64, 1024):
+                th = _time_handles(B, 64, geo, max(3, args.ticks // 5))
+                tb = _time_batch(B, 64, geo, args.ticks)
+                print(f"{'all five' if geo else 'ped+acc':<10} {B:>6} {64:>5} {th * 1e6:>10.1f} {B / th:>14.3e} {tb * 1e6:>14.1f} "
+                      f"{th / tb:>14.1f}x", flush=True)
+    else:
+        t = _time_batch(1024, 64, False, args.ticks)
+        print(f"# trace: B = 1024, N_b = 64, ped+acc: {args.ticks} timed + 3 warm-up batch ticks = {args.ticks + 3} launches "
+              f"of sfm_batch_tick_kernel expected; {t * 1e6:.1f} us per tick (wall clock, under the tracer)")
+
+
+if __name__ == "__main__":
+    main()
