@@ -106,3 +106,34 @@ def geometry_tie_exposure(O, loc, vel, waypoint, target_speed, radius, crossing,
     with np.errstate(all="ignore"):
         O.tick_forces(loc, vel, waypoint, target_speed, radius, crossing, geom, geo_only, theta_tol=THETA_TOL, tie_rel=TIE_REL, diag=diag)
     return np.nan_to_num(diag["total"][0])
+
+
+FP32_UPDATE = 2.0 ** -23   # one rounding per component of v + dt F (an fma, or a multiply and an add), as a fraction of |v'|
+
+
+def check_force_from_velocity(name, v_dev, v_in, dt, F_ref, absum, expo, max_speed, rtol=RTOL):
+    """A force read back through one uncapped velocity update, for kernels that cannot record their forces:
+    F_dev = (v'_dev - v_in) / dt in float64, held to ``check_force``'s bound plus one stated fp32 floor for the update,
+    2^-23 |v'_dev| / dt.  Only valid where the cap cannot act: the oracle's v_in + dt F_ref must stay a factor of 10 below
+    ``max_speed`` (target_speed * max_speed_factor, per row) -- asserted here.  Tests run it at dt = 1 with max_speed_factor =
+    1e4, where the floor is ~2e-7 m/s^2.  Returns (worst |dF| / max(|F|, A) once the exposure, ATOL and the floor are taken off
+    |dF| -- the part of the error the 1e-5 has to cover;  rows that needed the floor)."""
+    v_dev, v_in, F_ref = (np.asarray(a, dtype=np.float64) for a in (v_dev, v_in, F_ref))
+    nan_g, nan_r = np.isnan(v_dev).any(axis=1), np.isnan(F_ref).any(axis=1)
+    assert np.array_equal(nan_g, nan_r), f"{name}: NaN rows differ (got {nan_g.sum()}, ref {nan_r.sum()})"
+    ok = ~nan_r
+    v_ref = v_in[ok] + dt * F_ref[ok]
+    ms = np.broadcast_to(np.asarray(max_speed, dtype=np.float64), nan_r.shape)[ok]
+    assert (np.linalg.norm(v_ref, axis=1) < 0.1 * ms).all(), f"{name}: a row comes within a factor of 10 of the speed cap"
+    got = (v_dev[ok] - v_in[ok]) / dt
+    err = np.linalg.norm(got - F_ref[ok], axis=1)
+    scale = np.maximum(np.linalg.norm(F_ref[ok], axis=1), np.nan_to_num(absum[ok]))
+    allow = rtol * scale + np.nan_to_num(expo[ok]) * 1.001 + ATOL
+    floor = FP32_UPDATE * np.linalg.norm(v_dev[ok], axis=1) / dt
+    bad = err > allow + floor
+    ratio = err / np.maximum(scale, 1e-300)
+    assert not bad.any(), (f"{name}: {bad.sum()} of {ok.sum()} pedestrians out of tolerance; worst err/scale "
+                           f"{np.max(ratio[bad]):.3e} (rtol {rtol}), worst err {np.max(err[bad]):.3e} m/s^2 at |F| "
+                           f"{np.linalg.norm(F_ref[ok], axis=1)[bad][np.argmax(err[bad])]:.3e}")
+    beyond = np.maximum(err - np.nan_to_num(expo[ok]) * 1.001 - ATOL - floor, 0.0) / np.maximum(scale, 1e-300)
+    return (float(beyond.max()) if err.size else 0.0), int((err > allow).sum())
