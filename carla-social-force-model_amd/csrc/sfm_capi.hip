@@ -130,16 +130,12 @@ struct SfmHandle {
     int box_cur = 0;
     bool boxes_valid = false;
     bool count_zeroed = false;             // the last epilogue left the list counter at 0
-    int carry_mode = -1;                   // SFM_CARRY=0: boxes / list counter are rebuilt every tick (A/B)
-    int geo_slices_override = 0;           // SFM_GEO_SLICES / SFM_STRIPS / SFM_DEBUG_STEPS, read once at sfm_create (tests, probes)
+    int geo_slices_override = 0;           // SFM_GEO_SLICES / SFM_STRIPS, read once at sfm_create (tests, probes)
     int strips_override = -1;
-    int debug_steps = -1;
     uint32_t* work = nullptr;
     int* work_count = nullptr;
     size_t work_cap = 0;
     int cut_mode = -1;                     // SFM_CUTOFF: 0 off, 1 on, -1 auto (on above AUTO_CUTOFF_N pedestrians)
-    unsigned long long* stamps = nullptr;  // SFM_STAMPS diagnostic: per-workgroup timestamps of the symmetric pair kernel
-    unsigned long long* geo_stamps = nullptr;   // SFM_GEO_STAMPS diagnostic: per-workgroup phase stamps of the geometry kernel
     // spatial reordering: row s holds the caller's pedestrian perm[s] (strips in x, each sorted by y: sfm_reorder.hip), so the 64-tiles
     // are compact squares; every download translates back.  Identity when off.
     std::vector<uint32_t> perm;
@@ -173,9 +169,7 @@ struct SfmHandle {
     float4* own_alt = nullptr;             // the waypoints ping-pong with the state
     int own_alt_cap = 0;
     int pair_geo_mode = -1;                // SFM_PAIR_GEO=0: the geometry kernel always gets a launch of its own (A/B, tests)
-    int list_merge_mode = -1;              // SFM_LIST_MERGE=0: the flat tile-pair list always gets a launch of its own (A/B, tests)
     int fused_mode = -1;                   // SFM_FUSED=0: always the two-kernel tick (A/B, tests)
-    int fused_waves = 16, fused_blocked = 1;   // SFM_FUSED_WAVES=8 / SFM_FUSED_BLOCKED=0: its A/B variants (tests)
     float2* fgeo = nullptr;                // [2][FUSED_GEO_SLICES_MAX][N_pad] border + obstacle forces of the fused tick, one float2 per pedestrian and slice, ping-pong
     size_t fgeo_cap = 0;
     float4* dyn_ctr_alt = nullptr;         // device-side vehicles in the fused tick: the NEXT tick's centres / rings (ping-pong with dynamics.ctr / .pts)
@@ -186,9 +180,6 @@ struct SfmHandle {
     size_t down_stage_cap = 0;
     std::vector<float> step_cols;          // sfm_step_packed: the packed block taken apart into the columns sfm_upload_state consumes
     std::vector<uint8_t> step_mask;
-    unsigned long long* fused_stamps = nullptr;   // experiments build, SFM_FUSED_STAMPS=<file>: phase stamps of the last fused launch
-    int fused_geo_slices = 0;              // SFM_FUSED_GEO_SLICES: A/B
-    int fused_geo_mode = -1;               // SFM_FUSED_GEO=0: crowds with border / obstacle forces keep the two-launch tick (A/B, tests)
     bool used_fused = false;
     // A fused run ends with the partial forces of its final state already in fslab: the next sfm_run / sfm_tick carries on from
     // there (one launch per tick, no start-up launch) provided NOTHING else was called on the handle in between -- api_seq counts
@@ -220,7 +211,6 @@ struct SfmHandle {
     // sharded runs: the geometry forces of tick t+1 only need this rank's own rows of the new state, so they are launched on the
     // side stream right after tick t's epilogue -- beside the all-gather the caller issues next -- and tick t+1 only joins them
     bool geo_ahead = false;
-    int geo_ahead_mode = -1;               // SFM_GEO_AHEAD=0 switches it off
     // split tick of a shard (sfm_tick_begin / sfm_tick_end): the own-own tile pairs are listed and evaluated before the other
     // ranks' rows have arrived; their list lives in work2 / work_count[1]
     uint32_t* work2 = nullptr;
@@ -228,7 +218,6 @@ struct SfmHandle {
     bool begin_done = false, begin_forked = false, last_split = false;
     int begin_geo_slices = 0;              // > 0: sfm_tick_begin put the geometry workgroups into its pair launch, in this many slices per tile
     uint32_t begin_flags = 0;
-    int split_mode = -1;                   // SFM_SPLIT=0: sfm_tick_begin never does anything (A/B, tests)
     int timed_ticks = 0, timed_launches = 0;
     bool timing_valid = false;
     bool timing_on = true;                 // sfm_set_timing: the two event records per call cost ~11 us (a 20-tick sfm_run of c2: 3 %)
@@ -300,18 +289,9 @@ static IxConst fold(const SfmInteraction& s) {
     return c;
 }
 
-// Environment knobs.  The product build reads eleven (SFM_SYM, SFM_IPW, SFM_TEAM, SFM_CUTOFF, SFM_REORDER,
-// SFM_RESORT_EVERY, SFM_FUSED, SFM_STRIPS, SFM_PAIR_GEO, SFM_GEO_SLICES, SFM_NO_STRAIGHT -- each selects a SHIPPING path the tests must be able to
-// reach at a small size).  Everything else -- A/B arrangements measured and dropped, diagnostic stamps, timing probes -- only exists
-// in a build with -DSFM_EXPERIMENTS (make EXPERIMENTS=1).
-static inline const char* exp_env(const char* name) {
-#ifdef SFM_EXPERIMENTS
-    return getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
+// Environment knobs.  The library reads thirteen (SFM_SYM, SFM_IPW, SFM_TEAM, SFM_CUTOFF, SFM_REORDER,
+// SFM_RESORT_EVERY, SFM_FUSED, SFM_STRIPS, SFM_PAIR_GEO, SFM_GEO_SLICES, SFM_NO_STRAIGHT, SFM_POOL, SFM_POOL_PER_TILE), and each
+// selects a SHIPPING path the tests must be able to reach at a small size.
 
 static int check_params(const SfmParams* p, const char** why) {
     if (!p) { *why = "params is NULL"; return 0; }
@@ -350,7 +330,6 @@ int sfm_create(const SfmParams* params, int device_id, SfmHandle** out) {
         h->aux = nullptr;
         h->overlap_geo = false;
     }
-    if (exp_env("SFM_NO_OVERLAP")) h->overlap_geo = false;
     const char* ov = getenv("SFM_IPW");
     if (ov) h->ipw_override = atoi(ov);
     ov = getenv("SFM_TEAM");
@@ -359,53 +338,18 @@ int sfm_create(const SfmParams* params, int device_id, SfmHandle** out) {
     if (ov) h->sym_mode = atoi(ov);
     ov = getenv("SFM_CUTOFF");
     if (ov) h->cut_mode = atoi(ov);
-    ov = exp_env("SFM_CARRY");
-    if (ov) h->carry_mode = atoi(ov);
-    ov = exp_env("SFM_SPLIT");
-    if (ov) h->split_mode = atoi(ov);
-    ov = exp_env("SFM_GEO_AHEAD");
-    if (ov) h->geo_ahead_mode = atoi(ov);
     ov = getenv("SFM_PAIR_GEO");
     if (ov) h->pair_geo_mode = atoi(ov);
-    ov = exp_env("SFM_LIST_MERGE");
-    if (ov) h->list_merge_mode = atoi(ov);
     ov = getenv("SFM_FUSED");
     if (ov) h->fused_mode = atoi(ov);
-    ov = exp_env("SFM_FUSED_WAVES");
-    if (ov && atoi(ov) == 8) h->fused_waves = 8;
-    ov = exp_env("SFM_FUSED_BLOCKED");
-    if (ov) h->fused_blocked = atoi(ov);
-    ov = exp_env("SFM_FUSED_GEO");
-    if (ov) h->fused_geo_mode = atoi(ov);
-    ov = exp_env("SFM_FUSED_GEO_SLICES");
-    if (ov) h->fused_geo_slices = atoi(ov);
     ov = getenv("SFM_REORDER");
     if (ov) h->reorder_mode = atoi(ov);
     ov = getenv("SFM_GEO_SLICES");
     if (ov) h->geo_slices_override = std::min(GEO_SLICES_MAX, std::max(1, atoi(ov)));
     ov = getenv("SFM_STRIPS");
     if (ov) h->strips_override = atoi(ov) != 0 ? 1 : 0;
-    ov = exp_env("SFM_DEBUG_STEPS");
-    if (ov) h->debug_steps = atoi(ov);
     ov = getenv("SFM_RESORT_EVERY");
     if (ov) { h->resort_every = atoi(ov); h->resort_every_set = true; }
-    if (exp_env("SFM_STAMPS")) {
-        if (hipMalloc(reinterpret_cast<void**>(&h->stamps), sizeof(unsigned long long) * 3 * PAIR_STAMP_WGS) != hipSuccess) h->stamps = nullptr;
-        else {
-            hipMemset(h->stamps, 0, sizeof(unsigned long long) * 3 * PAIR_STAMP_WGS);
-            FILE* f = fopen(exp_env("SFM_STAMPS"), "w");   // the address is read back by the diagnostic script through the dump below
-            if (f) fclose(f);
-        }
-    }
-    if (exp_env("SFM_FUSED_STAMPS")) {
-        const size_t words = (size_t)FUSED_STAMP_STRIDE * FUSED_STAMP_WGS;
-        if (hipMalloc(reinterpret_cast<void**>(&h->fused_stamps), sizeof(unsigned long long) * words) != hipSuccess) h->fused_stamps = nullptr;
-        else hipMemset(h->fused_stamps, 0, sizeof(unsigned long long) * words);
-    }
-    if (exp_env("SFM_GEO_STAMPS")) {
-        if (hipMalloc(reinterpret_cast<void**>(&h->geo_stamps), sizeof(unsigned long long) * 4 * 8192) != hipSuccess) h->geo_stamps = nullptr;
-        else hipMemset(h->geo_stamps, 0, sizeof(unsigned long long) * 4 * 8192);
-    }
     h->dpp_dir = probe_dpp_direction(nullptr);
     *out = h;
     return SFM_OK;
@@ -424,38 +368,6 @@ int sfm_destroy(SfmHandle* h) {
     if (!h) return SFM_OK;
     hipSetDevice(h->device);
     hipStreamSynchronize(h->stream);
-    if (h->stamps && exp_env("SFM_STAMPS")) {       // diagnostic: dump the last launch's per-workgroup stamps
-        std::vector<unsigned long long> st((size_t)3 * PAIR_STAMP_WGS);
-        if (hipMemcpy(st.data(), h->stamps, sizeof(unsigned long long) * st.size(), hipMemcpyDeviceToHost) == hipSuccess) {
-            FILE* f = fopen(exp_env("SFM_STAMPS"), "w");
-            if (f) { for (size_t b = 0; b < (size_t)PAIR_STAMP_WGS; ++b) if (st[3 * b + 1]) fprintf(f, "%llu %llu %llu\n", st[3 * b], st[3 * b + 1], st[3 * b + 2]); fclose(f); }
-        }
-        hipFree(h->stamps);
-    }
-    if (h->fused_stamps && exp_env("SFM_FUSED_STAMPS")) {   // diagnostic: the last fused launch's per-workgroup phase stamps
-        std::vector<unsigned long long> st((size_t)FUSED_STAMP_STRIDE * FUSED_STAMP_WGS);
-        if (hipMemcpy(st.data(), h->fused_stamps, sizeof(unsigned long long) * st.size(), hipMemcpyDeviceToHost) == hipSuccess) {
-            FILE* f = fopen(exp_env("SFM_FUSED_STAMPS"), "w");
-            if (f) {
-                for (size_t b = 0; b < (size_t)FUSED_STAMP_WGS; ++b) {
-                    if (!st[FUSED_STAMP_STRIDE * b]) continue;
-                    fprintf(f, "%zu", b);
-                    for (int k = 0; k < 5 + 32; ++k) fprintf(f, " %llu", st[FUSED_STAMP_STRIDE * b + k]);
-                    fprintf(f, "\n");
-                }
-                fclose(f);
-            }
-        }
-        hipFree(h->fused_stamps);
-    }
-    if (h->geo_stamps && exp_env("SFM_GEO_STAMPS")) {   // diagnostic: dump the last launch's per-workgroup phase stamps
-        std::vector<unsigned long long> st(4 * 8192);
-        if (hipMemcpy(st.data(), h->geo_stamps, sizeof(unsigned long long) * st.size(), hipMemcpyDeviceToHost) == hipSuccess) {
-            FILE* f = fopen(exp_env("SFM_GEO_STAMPS"), "w");
-            if (f) { for (size_t b = 0; b < 8192; ++b) fprintf(f, "%llu %llu %llu %llu\n", st[4 * b], st[4 * b + 1], st[4 * b + 2], st[4 * b + 3]); fclose(f); }
-        }
-        hipFree(h->geo_stamps);
-    }
     for (int b = 0; b < 2; ++b) { if (h->pk[b]) hipFree(h->pk[b]); if (h->zv[b]) hipFree(h->zv[b]); }
     if (h->own) hipFree(h->own);
     if (h->radius) hipFree(h->radius);
@@ -1065,7 +977,7 @@ static void fill_args(SfmHandle* h, TickArgs& a, uint32_t flags) {
     // into every test -- and a 3-D crowd's largest speed includes v_z)
     // (a cutoff for small crowds -- workgroups testing their own tile pair, a cost-balanced deal of the items -- was built and
     //  measured in round 2: on c2 it cost as much in boxes, dealer and re-packs as it saved in steps.  Removed in round 3)
-    const bool carry = cut && h->dpp_dir == 1 && h->i_begin == 0 && h->i_end == h->N && h->sym_mode != 0 && h->carry_mode != 0 && !h->fsm_on;
+    const bool carry = cut && h->dpp_dir == 1 && h->i_begin == 0 && h->i_end == h->N && h->sym_mode != 0 && !h->fsm_on;
     a.tile_box_out = carry ? h->tile_box + (size_t)(h->box_cur ^ 1) * h->n_t : nullptr;
     a.tile_vmax_out = carry ? h->tile_vmax + (size_t)(h->box_cur ^ 1) * h->n_t : nullptr;
     a.cut_scale = (float)((double)p.pedestrian.gamma * 41.0 * 0.6931471805599453 * 1.001);
@@ -1091,7 +1003,6 @@ static void fill_args(SfmHandle* h, TickArgs& a, uint32_t flags) {
     a.seed = h->seed;
     a.world_side = h->world_side;
     a.arrive_thr2 = (float)((double)h->arrive_thr * (double)h->arrive_thr);
-    a.geo_stamps = h->geo_stamps;
     a.borders = Geo{h->borders.off, h->borders.pts, h->borders.ctr, h->borders.seg, h->borders.K};
     a.statics = Geo{h->statics.off, h->statics.pts, h->statics.ctr, nullptr, h->statics.K};
     a.dynamics = Geo{h->dynamics.off, h->dynamics.pts, h->dynamics.ctr, nullptr, h->dynamics.K};
@@ -1187,11 +1098,11 @@ static bool sym_reserve(SfmHandle* h, bool list, bool split) {
 }
 
 // the symmetric path's view of one tick: slab or row pool, tile-pair list (cutoff on), strips, own tile range
-static SymArgs make_sym_args(const SfmHandle* h, const TickArgs& a, int tps, int n_strips, int debug_steps, unsigned long long* stamps) {
+static SymArgs make_sym_args(const SfmHandle* h, const TickArgs& a, int tps, int n_strips) {
     const bool list = a.tile_box != nullptr;
-    SymArgs sa{h->slab, h->z3 ? h->slabz : nullptr, h->n_t, slab_stride(h->n_t), debug_steps,
+    SymArgs sa{h->slab, h->z3 ? h->slabz : nullptr, h->n_t, slab_stride(h->n_t),
                list ? h->work : nullptr, list ? h->work_count : nullptr, list ? a.tile_vmax : nullptr,
-               a.cut_scale, a.cut_pad, stamps, h->strip_box, h->strip_vmax, tps, n_strips,
+               a.cut_scale, a.cut_pad, h->strip_box, h->strip_vmax, tps, n_strips,
                h->i_begin / WAVE, (h->i_end + WAVE - 1) / WAVE,
                (list && a.tile_box_out) ? 1 : 0,      // (shards: run_ticks sets it, it knows whether the tick integrates)
                nullptr, 0u, 0u, nullptr, h->tick_serial};
@@ -1214,7 +1125,7 @@ static int fused_launch(SfmHandle* h, uint32_t flags, int mode, int* sl) {
     TickArgs a;
     fill_args(h, a, flags);
     const bool geo = a.geo != nullptr;
-    int slices = 0, nw = h->fused_waves;
+    int slices = 0, nw = 16;
     const int n_pair = fused_pair_workgroups(n_g);
     if (geo) {
         // a geometry workgroup's time is the longest chain of kept polylines on one of its waves (each a dependent load -> scan), so
@@ -1222,7 +1133,6 @@ static int fused_launch(SfmHandle* h, uint32_t flags, int mode, int* sl) {
         // 6 tiles on (all forces, N = 512 / 1024: 11.4 / 12.5 -> 10.9 / 11.3 us; N = 64 / 256: no change; 8 at N = 2048: 12.1 -> 15.1)
         slices = h->n_t <= 64 ? 4 : 2;
         if (h->n_t >= 6) slices = std::max(slices, std::min(FUSED_GEO_SLICES_MAX, (256 - n_pair) / h->n_t));
-        if (h->fused_geo_slices > 0) slices = std::min(FUSED_GEO_SLICES_MAX, h->fused_geo_slices);
         // two 16-wave workgroups fill a CU: when pair + geometry workgroups do not fit in 512 such slots the launch runs 8-wave
         // workgroups (four per CU; the pair phase is within a few per cent at 4 waves per SIMD)
         if (n_pair + h->n_t * slices > 512) nw = 8;
@@ -1241,9 +1151,9 @@ static int fused_launch(SfmHandle* h, uint32_t flags, int mode, int* sl) {
     }
     const FusedArgs f{h->fslab + (size_t)(*sl ^ 1) * rows, h->fslab + (size_t)*sl * rows,
                       h->z3 ? h->fslabz + (size_t)(*sl ^ 1) * rows : nullptr, h->z3 ? h->fslabz + (size_t)*sl * rows : nullptr,
-                      h->own, h->own_alt, n_g, h->n_t, (h->fused_blocked != 0 && n_g % 8 == 0) ? 1 : 0,
+                      h->own, h->own_alt, n_g, h->n_t, n_g % 8 == 0 ? 1 : 0,
                       geo ? h->fgeo + (size_t)(*sl ^ 1) * grow : nullptr, geo ? h->fgeo + (size_t)*sl * grow : nullptr, slices,
-                      geo ? h->n_t * slices : 0, n_pair, h->fused_stamps, mode};
+                      geo ? h->n_t * slices : 0, n_pair, mode};
     HIP_TRY(h, launch_fused_tick(h->rad, a, f, h->stream, nw));
     if (mode != 0) {
         h->cur ^= 1;
@@ -1319,10 +1229,7 @@ static int run_fused(SfmHandle* h, int ticks, uint32_t flags, bool carry, bool g
 // from 1024 tiles on (where they are spread over the grid).  Measured, all forces (tools/mid_crowd_probe.py, c3): N = 512: 16.6 /
 // 14.3 / 14.0 us per tick at 4 / 8 / 16; N = 2048: 21.0 / 16.4 / 16.4; N = 4096: 27.7 / 23.2 / 24.8 / 26.7 at 2 / 4 / 8 / 16;
 // c3 (256 tiles): 47.3 / 35.2 / 34.9 / 44 at 1 / 2 / 4 / 8; c5: 777 / 781 / 797 at 1 / 2 / 4.
-static int merged_geo_slices(int tiles, int slices) {
-    static const int ov = exp_env("SFM_PG_SLICES") ? atoi(exp_env("SFM_PG_SLICES")) : 0;      // A/B only
-    (void)slices;
-    if (ov > 0) return std::min(GEO_SLICES_MAX, ov);
+static int merged_geo_slices(int tiles) {
     // (a shard of a large crowd -- 512 own tiles of 4096: c5, one rank of 8 -- 150.3 us per tick at 4, 146.3 at 2, tools/shard_rank_time.py)
     return tiles >= 1024 ? 1 : tiles >= 512 ? 2 : tiles >= 64 ? 4 : tiles > 32 ? 8 : 16;
 }
@@ -1360,7 +1267,7 @@ static int plan_ticks(SfmHandle* h, uint32_t flags, int phase, bool device_run, 
         p.order_pays = probe.geo != nullptr || probe.tile_box != nullptr;
         p.list_cut = probe.tile_box != nullptr;
         p.plain = probe.geo == nullptr && probe.tile_box == nullptr && probe.adv.M == 0;
-        p.fused_geo = probe.geo != nullptr && probe.tile_box == nullptr && h->fused_geo_mode != 0;     // (SFM_FUSED=0 switches both off)
+        p.fused_geo = probe.geo != nullptr && probe.tile_box == nullptr;
     }
     // symmetric path: the whole crowd on this handle, or -- tile-pair list on -- a shard of whole tiles: pairs with a tile of another
     // rank are then evaluated one-sided by both ranks
@@ -1369,14 +1276,13 @@ static int plan_ticks(SfmHandle* h, uint32_t flags, int phase, bool device_run, 
                             h->n_t < 32768;
     const bool sym_wanted = (p.whole || tile_shard) && h->dpp_dir == 1 && h->sym_mode != 0 && h->prm.enabled[SFM_FORCE_PEDESTRIAN] &&
                             (h->sym_mode == 1 || h->N >= 256 || device_run || carry);
-    const bool sym_any_size = sym_wanted && sym_reserve(h, p.list_cut, !p.whole && h->split_mode != 0);
+    const bool sym_any_size = sym_wanted && sym_reserve(h, p.list_cut, !p.whole);
     // ---- a device-resident run of a whole crowd below the list cutoff: one launch per tick (sfm_fused_tick_kernel).
     //      Every sfm_run / sfm_run_recorded takes it, whatever its length -- what a device-resident run computes must not depend on
     //      how the caller cuts it into calls (a lone sfm_run(1) pays a launch in front like the two-launch tick pays its epilogue) --
     //      and a single sfm_tick when it carries on from such a run.
     p.fusable = p.whole && (p.plain || p.fused_geo) && phase == PHASE_FULL && (device_run || carry) && h->fused_mode != 0 &&
-                (flags & SFM_TICK_INTEGRATE) && !(flags & SFM_TICK_RECORD_FORCES) && !h->fsm_on && h->debug_steps < 0 && !h->stamps &&
-                !h->geo_stamps && h->N >= 2;
+                (flags & SFM_TICK_INTEGRATE) && !(flags & SFM_TICK_RECORD_FORCES) && !h->fsm_on && h->N >= 2;
     // Auto mode keeps host-in-the-loop ticks of crowds under 256 pedestrians on the ordered kernel (one launch against the symmetric
     // path's two); their device-resident runs are one launch per tick on the fused kernel like everybody else's (round 3: c1).
     const bool small_run = h->sym_mode < 0 && h->N < 256 && p.fusable;
@@ -1403,7 +1309,7 @@ static int fork_geometry(SfmHandle* h, const TickArgs& a) {
 //      on the side stream).  Anything that cannot be split: nothing happens here and sfm_tick_end runs the whole tick.
 static int shard_begin(SfmHandle* h, const TickPlan& p, uint32_t flags) {
     h->begin_done = false;
-    if (!(p.sym && !p.whole && p.list_cut && !h->fsm_on && (flags & SFM_TICK_INTEGRATE) && p.n_local > 0 && h->split_mode != 0)) return SFM_OK;
+    if (!(p.sym && !p.whole && p.list_cut && !h->fsm_on && (flags & SFM_TICK_INTEGRATE) && p.n_local > 0)) return SFM_OK;
     const size_t items = (size_t)h->n_t * (size_t)(h->n_t / 2 + 1);
     if (items > h->work2_cap) { HIP_TRY(h, dev_realloc(h->work2, items)); h->work2_cap = items; }
     if (h->timing_on) HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
@@ -1416,17 +1322,17 @@ static int shard_begin(SfmHandle* h, const TickPlan& p, uint32_t flags) {
                                   t_lo, t_hi));
     const bool ahead = h->geo_ahead && a.geo;
     h->geo_ahead = false;
-    const bool merged = a.geo && !ahead && a.en_ped && h->pair_geo_mode != 0 && h->debug_steps < 0 && !h->geo_stamps;
+    const bool merged = a.geo && !ahead && a.en_ped && h->pair_geo_mode != 0;
     h->begin_forked = a.geo != nullptr && !merged;
     h->begin_geo_slices = 0;
     if (a.geo && !ahead && !merged) { const int rc = fork_geometry(h, a); if (rc) return rc; }
-    SymArgs sa = make_sym_args(h, a, p.tps, 0, h->debug_steps, nullptr);
+    SymArgs sa = make_sym_args(h, a, p.tps, 0);
     sa.work = h->work2;
     sa.work_count = h->work_count + 1;
     sa.row_base = h->pool_main;                       // the own-own list's row pairs sit behind the main list's
     HIP_TRY(h, launch_sym_list(a, sa, h->stream, LIST_OWN, h->count_zeroed));
     if (merged) {
-        a.geo_slices = merged_geo_slices(t_hi - t_lo, a.geo_slices);
+        a.geo_slices = merged_geo_slices(t_hi - t_lo);
         h->begin_geo_slices = a.geo_slices;
         HIP_TRY(h, launch_sym_pair_geo(h->rad, a, sa, h->stream));
     } else {
@@ -1482,14 +1388,13 @@ static int tick_geometry(SfmHandle* h, const TickPlan& p, TickArgs& a, bool fini
     const bool ahead = (h->geo_ahead && a.geo && p.n_local > 0 && p.sym) ||   // launched at the end of the previous tick ...
                        (finishing && h->begin_forked);                         // ... or by sfm_tick_begin: join only
     h->geo_ahead = false;
-    static const int fork_ov = exp_env("SFM_FORK") ? atoi(exp_env("SFM_FORK")) : -1;      // A/B only: 0 / 1 = in line / side stream with carried boxes
-    const bool fork_carried = fork_ov >= 0 ? fork_ov == 1 : h->n_t >= 1024;
+    const bool fork_carried = h->n_t >= 1024;
     const bool plain_grid = !a.tile_box;                           // no cutoff: the pair kernel runs its 2-D grid
-    s.geo_in_pair = !ahead && a.geo && p.n_local > 0 && p.sym && !finishing && a.en_ped && h->N > 1 && h->debug_steps < 0 &&
-                    !h->stamps && !h->geo_stamps && h->pair_geo_mode != 0 && (p.list_cut || plain_grid);
+    s.geo_in_pair = !ahead && a.geo && p.n_local > 0 && p.sym && !finishing && a.en_ped && h->N > 1 &&
+                    h->pair_geo_mode != 0 && (p.list_cut || plain_grid);
     s.fork = !s.geo_in_pair && a.geo && p.n_local > 0 && p.sym && ((h->overlap_geo && (!p.whole || fork_carried)) || finishing);
     s.list_in_geo = false;
-    if (s.geo_in_pair) a.geo_slices = merged_geo_slices((h->i_end + WAVE - 1) / WAVE - h->i_begin / WAVE, a.geo_slices);
+    if (s.geo_in_pair) a.geo_slices = merged_geo_slices((h->i_end + WAVE - 1) / WAVE - h->i_begin / WAVE);
     if (finishing && h->begin_geo_slices > 0) a.geo_slices = h->begin_geo_slices;      // sfm_tick_begin's pair launch held the geometry workgroups
     s.begun_merged = finishing && h->begin_geo_slices > 0;        // the geometry forces of this tick are already there
     if (s.geo_in_pair || s.begun_merged || ahead) return SFM_OK;
@@ -1499,7 +1404,7 @@ static int tick_geometry(SfmHandle* h, const TickPlan& p, TickArgs& a, bool fini
         ++*launches;
     } else if (a.geo && p.n_local > 0) {
         s.list_in_geo = p.sym && p.whole && s.carried && h->count_zeroed && p.list_cut && p.n_strips == 0 && !finishing && a.en_ped &&
-                        h->N > 1 && h->list_merge_mode != 0;
+                        h->N > 1;
         if (s.list_in_geo) { a.list_work = h->work; a.list_count = h->work_count; a.list_n_t = h->n_t; a.list_idx = h->pooled ? h->pair_idx : nullptr; a.list_cap = h->pool_main; }
         HIP_TRY(h, launch_geometry(h->rad, a, h->stream));
         ++*launches;
@@ -1509,7 +1414,7 @@ static int tick_geometry(SfmHandle* h, const TickPlan& p, TickArgs& a, bool fini
 
 // the symmetric path's launches of one tick: [strip boxes] -> [tile-pair list] -> pair kernel (+ geometry workgroups) -> epilogue
 static int tick_symmetric(SfmHandle* h, const TickPlan& p, const TickArgs& a, bool finishing, TickShape& s, int* launches) {
-    const SymArgs sa = make_sym_args(h, a, p.tps, p.n_strips, h->debug_steps, h->stamps);
+    const SymArgs sa = make_sym_args(h, a, p.tps, p.n_strips);
     h->last_list = sa.work != nullptr;
     if (sa.work && p.n_strips > 0 && !s.merged_bounds) {
         HIP_TRY(h, launch_strip_bounds(a.tile_box, a.tile_vmax, h->n_t, p.tps, p.n_strips, h->strip_box, h->strip_vmax, h->stream));
@@ -1517,7 +1422,7 @@ static int tick_symmetric(SfmHandle* h, const TickPlan& p, const TickArgs& a, bo
     }
     // a shard's epilogue leaves the list counter(s) at zero as well (its boxes cannot be carried -- the other ranks' rows
     // arrive in between -- but the memset can go)
-    const bool shard_zero = !p.whole && p.list_cut && h->carry_mode != 0;
+    const bool shard_zero = !p.whole && p.list_cut;
     if (sa.work && !s.list_in_geo) {
         HIP_TRY(h, launch_sym_list(a, sa, h->stream, finishing ? LIST_REMOTE : LIST_ALL, (s.carried || !p.whole) && h->count_zeroed));
         ++*launches;
@@ -1537,7 +1442,7 @@ static int tick_symmetric(SfmHandle* h, const TickPlan& p, const TickArgs& a, bo
 static int tick_carry(SfmHandle* h, const TickPlan& p, const TickArgs& a, uint32_t flags, bool last, const TickShape& s, int* launches) {
     // a shard's next geometry forces only need its own new rows: start them now, beside the exchange the caller issues next
     //  (not when the geometry workgroups ride in the pair launches: then the next sfm_tick_begin / sfm_tick hosts them)
-    if (p.sym && s.fork && !s.begun_merged && !p.whole && (flags & SFM_TICK_INTEGRATE) && !h->fsm_on && h->geo_ahead_mode != 0 && last &&
+    if (p.sym && s.fork && !s.begun_merged && !p.whole && (flags & SFM_TICK_INTEGRATE) && !h->fsm_on && last &&
         !(flags & SFM_TICK_RECORD_FORCES)) {
         TickArgs nx;
         fill_args(h, nx, flags);
@@ -1704,7 +1609,7 @@ int sfm_profile_dominant_kernel(SfmHandle* h, int reps, float* avg_us) {
     TickArgs a;
     fill_args(h, a, 0);
     if (h->used_sym) a.geo = nullptr;
-    const SymArgs sa = make_sym_args(h, a, tps, n_strips, -1, nullptr);
+    const SymArgs sa = make_sym_args(h, a, tps, n_strips);
     if (a.tile_box) HIP_TRY(h, launch_tile_bounds(a.pk_cur, h->z3 ? a.zv_cur : nullptr, h->N, const_cast<float4*>(a.tile_box), const_cast<float*>(a.tile_vmax), h->stream));
     if (sa.work && n_strips > 0)
         HIP_TRY(h, launch_strip_bounds(a.tile_box, a.tile_vmax, h->n_t, tps, n_strips, h->strip_box, h->strip_vmax, h->stream));

@@ -116,7 +116,6 @@ struct TickArgs {
     int list_n_t, list_block0;
     uint32_t* list_idx;       // ... and the pool's index table (SymArgs::idx), null: dense slab
     uint32_t list_cap;        // ... and its capacity in row pairs
-    unsigned long long* geo_stamps;   // diagnostic runs only (SFM_GEO_STAMPS): per geometry workgroup {start, after find, after scan, end} of s_memrealtime
 };
 
 // Symmetric (antisymmetry-exploiting) pedestrian-force path, single shard only.
@@ -125,14 +124,12 @@ struct SymArgs {
     float* slabz;        // 3-D crowds: its z component, same indexing (null: planar)
     int n_t;             // number of 64-pedestrian tiles
     int stride;          // n_t * 64
-    int debug_steps;     // < 0: normal; >= 0: run only this many systolic steps per wave (timing probe, wrong results)
     const uint32_t* work;    // cutoff on: compacted list of (bx | shift << 16) tile-pair items, else null
     const int* work_count;
     // vmax (largest speed per tile, this tick's input state) is set whenever the list cutoff is on: the pair kernel then also
     // skips the systolic steps whose 64 pairs are all beyond the reach of the two tiles' speeds, or below the exponent bound
     const float* vmax;
     float cut_scale, cut_pad;
-    unsigned long long* stamps;   // diagnostic builds of a run only (SFM_STAMPS): per workgroup {start, end} of s_memrealtime + HW id
     // two-level list building (large crowds): boxes / largest speeds of runs of `tps` consecutive tiles (= the x-strips of
     // the spatial packing); n_strips = 0: flat
     const float4* sbox;
@@ -167,10 +164,9 @@ struct SpillArgs {       // (device memory; read only by an item that spills and
 // four tiles from the previous launch's partial forces (every workgroup that needs a tile recomputes it -- the same arithmetic on
 // the same operands, so all agree bit for bit; the workgroup of the group's diagonal item is the one that stores it), then
 // evaluates its tile pairs of the NEW state.  State, waypoints and partial forces ping-pong between launches.
-constexpr int PAIR_STAMP_WGS = 65536;   // experiments build: workgroups of the symmetric pair kernel whose {start, end, HW id} stamps are kept
-constexpr int FUSED_STAMP_STRIDE = 40, FUSED_STAMP_WGS = 4096;   // experiments build: phase stamps of the fused tick (words per workgroup, workgroups kept)
 constexpr int FUSED_GEO_SLICES_MAX = 8;  // geometry workgroups per tile of the fused tick (each leaves one partial sum per pedestrian)
-struct FusedArgs {
+// (16-byte aligned: it follows TickArgs in the kernel arguments, and at an 8-byte offset c1's tick measured 8.7 instead of 8.5 us)
+struct alignas(16) FusedArgs {
     const float2* slab_prev;  // [n_g][N_pad]: slab[r][i] = -A-less force on pedestrian i from the pedestrians of group r, previous state
     float2* slab_next;        // the same for the state this launch integrates to
     const float* slabz_prev;  // 3-D crowds: the z components, same indexing (null: planar)
@@ -185,7 +181,6 @@ struct FusedArgs {
     int geo_slices;           // <= FUSED_GEO_SLICES_MAX
     int n_geo_wg;             // geometry workgroups in front of the grid = n_t * geo_slices (0: the crowd has no such forces)
     int n_pair_wg;            // pair workgroups behind them
-    unsigned long long* stamps;   // experiments build only (SFM_FUSED_STAMPS): per workgroup FUSED_STAMP_STRIDE x s_memrealtime -- entry, column sums in, state in LDS, pairs done, end; per wave: steps done, past the barrier
     int mode;                 // 0: the stored state is the state (nothing to integrate, nothing stored but slab_next): the launch in
                               //    front of a run; 1: integrate by one tick, store, then the pairs of the new state
 };

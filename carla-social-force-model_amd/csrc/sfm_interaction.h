@@ -129,17 +129,9 @@ __device__ __forceinline__ void moussaid(const IxConst& c, float dx, float dy, f
 // sign(S) pi, added by the fma that finishes the polynomial.  Same values as the branch (C >= 0: p r + 0; C < 0: sign(S) pi - p |r|..)
 // up to the rounding of the denominator; a NaN in m (coincident pair) still comes out as NaN.
 __device__ __forceinline__ float half_angle_theta(float S, float C, float m, float eg, float Dn) {
-#ifndef SFM_ATAN_TERMS
-#define SFM_ATAN_TERMS 8
-#endif
-#if SFM_FIXUP_BRANCH
-    const float r = S * rcp(m + fabsf(C));
-#else
     const float sc = copysignf(1.0f, C);
     const float r = S * rcp(fmaf(sc, m, C));
-#endif
     const float z = r * r;
-#if SFM_ATAN_TERMS == 8
     float p = -0.0095607885413262813f;
     p = fmaf(p, z, 0.049113825228842972f);
     p = fmaf(p, z, -0.11980885478692463f);
@@ -148,24 +140,9 @@ __device__ __forceinline__ float half_angle_theta(float S, float C, float m, flo
     p = fmaf(p, z, 0.39942748114880167f);
     p = fmaf(p, z, -0.66664186893326649f);
     p = fmaf(p, z, 1.9999998228145017f);
-#else                                         // 7 coefficients: relative error 6.5e-7 (A/B only)
-    float p = 0.015726754441857338f;
-    p = fmaf(p, z, -0.07402600347995758f);
-    p = fmaf(p, z, 0.16774238646030426f);
-    p = fmaf(p, z, -0.26974382996559143f);
-    p = fmaf(p, z, 0.39762964844703674f);
-    p = fmaf(p, z, -0.6665303111076355f);
-    p = fmaf(p, z, 1.999998688697815f);
-#endif
-#if SFM_FIXUP_BRANCH
-    const float a = p * r;
-    const float ang = (C < 0.0f) ? (copysignf(3.14159265358979324f, S) - a) : a;
-    return fmaf(-eg, Dn, ang);
-#else
     const float h = copysignf(1.57079632679489662f, S);
     const float k = fmaf(-eg, Dn, fmaf(-sc, h, h));                    // 0 or sign(S) pi (pi / 2 doubles exactly), minus the bias eps B
     return fmaf(p, r, k);
-#endif
 }
 
 // The same interaction for the symmetric kernel's planar fast path, arranged for the fewest issued instructions:

@@ -20,28 +20,10 @@
 #include "sfm_device.h"
 #include "sfm_interaction.h"
 
-#ifndef SFM_X2
-#define SFM_X2 1                       // 1: the fused tick's planar step (no use_ped_radius) evaluates TWO pairs per lane on packed fp32 (A/B, round 4)
-#endif
-#ifndef SFM_PK
-#define SFM_PK 1                       // 1: the fused tick's planar systolic step on packed fp32 instructions (A/B, round 4)
-#endif
-
 #include <algorithm>
 #include <type_traits>
-#include <cstdlib>
 
 namespace sfm {
-
-// launch-shape A/B knobs exist only in a build with -DSFM_EXPERIMENTS (sfm_capi.hip: exp_env)
-static inline const char* exp_env(const char* name) {
-#ifdef SFM_EXPERIMENTS
-    return getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
 
 // The planar body on PACKED fp32 instructions (round 4).  v_pk_add / v_pk_mul / v_pk_fma_f32 issue in 4.3 cycles per wave on MI355X
 // against 2 x 2.4 for the two scalar instructions they replace (tools/valu_microbench.hip), and the interaction is full of x / y pairs:
@@ -530,9 +512,7 @@ __device__ __forceinline__ void list_emit(bool keep, uint32_t item, uint32_t* __
     }
 }
 
-#ifndef GEO_DIRECT_PER_WAVE
-#define GEO_DIRECT_PER_WAVE 64
-#endif
+constexpr int GEO_DIRECT_PER_WAVE = 64;
 template <int GW>
 struct GeoShared {                              // LDS of one geometry workgroup: ~4 KiB per wave
     float2 row[GW][WAVE];
@@ -548,8 +528,7 @@ struct GeoShared {                              // LDS of one geometry workgroup
 // pair + geometry launch of the list-cutoff workloads the third inlined copy of the scan spills registers, their crowds have hundreds
 // of polylines per wave, and a variant build with it measured the same on c3 / c5 and on the host-in-the-loop tick).
 template <bool RAD, int GW, bool DIRECT = false>
-__device__ __forceinline__ void geometry_forces(const TickArgs& a, GeoShared<GW>& sh, GeoLane& me, int slice, int n_slices, int tid,
-                                                unsigned long long* st1) {
+__device__ __forceinline__ void geometry_forces(const TickArgs& a, GeoShared<GW>& sh, GeoLane& me, int slice, int n_slices, int tid) {
     const int lane = tid & (WAVE - 1);
     const int wave = uniform((int)(tid >> 6));
     const float inf = __builtin_inff();
@@ -577,7 +556,7 @@ __device__ __forceinline__ void geometry_forces(const TickArgs& a, GeoShared<GW>
     const int gwave = slice * GW + wave, n_gwaves = GW * n_slices;       // small crowds: the tile's polylines are split over n_slices workgroups
     // Up to GEO_DIRECT_PER_WAVE polylines per wave (one trip of find per kind): every wave scans what it keeps on the spot -- no list,
     // no barrier, no second deal.  Their fixed cost is most of a small crowd's geometry workgroup, and up to 26 polylines per wave
-    // the on-the-spot form measured 10-35 % better on the whole tick (tools/direct_scan_probe.py; more per wave: not measured)
+    // the on-the-spot form measured 10-35 % better on the whole tick (tools/direct_scan_probe.py, since removed; more per wave: not measured)
     const int k_all = (a.en_border ? a.borders.K : 0) + (a.en_static ? a.statics.K : 0) + (a.en_dynamic ? a.dynamics.K : 0);
     if (DIRECT && k_all <= GEO_DIRECT_PER_WAVE * n_gwaves) {
         geo_find<RAD, true>(a, me, tb, sh.item[wave], row, lane, gwave, n_gwaves, f, 0);
@@ -589,7 +568,6 @@ __device__ __forceinline__ void geometry_forces(const TickArgs& a, GeoShared<GW>
     const int n_found = geo_find<RAD, false>(a, me, tb, sh.item[wave], row, lane, gwave, n_gwaves, f);
     if (lane == 0) sh.count[wave] = min(n_found, GEO_ITEMS);
     __syncthreads();
-    if (st1) *st1 = __builtin_amdgcn_s_memrealtime();
 
     // ---- phase 2: scan, items dealt round-robin in (wave, index) order
     {
@@ -615,14 +593,12 @@ __device__ __forceinline__ void geometry_forces(const TickArgs& a, GeoShared<GW>
     __syncthreads();
 }
 
-// The border / obstacle forces of tile (a.i_begin / 64 + bx), slice slice_y of n_slices: the body of sfm_geometry_kernel, callable
-// from another kernel's workgroups as well (sfm_pair_geo_kernel).  n_bx only places the diagnostic stamps.
+// The border / obstacle forces of tile (a.i_begin / 64 + bx), slice `slice` of n_slices: the body of sfm_geometry_kernel, callable
+// from another kernel's workgroups as well (sfm_pair_geo_kernel).
 template <bool RAD, int GW>
-__device__ __forceinline__ void geometry_block(const TickArgs& a, GeoShared<GW>& sh, int bx, int slice_y, int n_slices, int n_bx, int tid) {
+__device__ __forceinline__ void geometry_block(const TickArgs& a, GeoShared<GW>& sh, int bx, int slice, int n_slices, int tid) {
     const int lane = tid & (WAVE - 1);
     const int wave = uniform((int)(tid >> 6));
-    unsigned long long st0 = 0, st1 = 0, st2 = 0;
-    if (a.geo_stamps) st0 = __builtin_amdgcn_s_memrealtime();
     const int t = (a.i_begin >> 6) + bx;                      // tile index
     const int p0 = max(a.i_begin, t * WAVE), p1 = min(a.i_end, (t + 1) * WAVE);
     const int i = t * WAVE + lane;
@@ -635,9 +611,7 @@ __device__ __forceinline__ void geometry_block(const TickArgs& a, GeoShared<GW>&
         me.r = a.own[i].w;
     }
     me.walk = me.live && !(a.crossing && a.crossing[i]);              // forces.py:140-141,176-177
-    const int slice = slice_y;
-    geometry_forces<RAD, GW>(a, sh, me, slice, n_slices, tid, a.geo_stamps ? &st1 : nullptr);
-    if (a.geo_stamps) st2 = __builtin_amdgcn_s_memrealtime();
+    geometry_forces<RAD, GW>(a, sh, me, slice, n_slices, tid);
     for (int q = wave; q < 6 && me.live; q += GW) {                    // wave w finishes component w (and w + GW)
         float v = 0.0f;
 #pragma unroll
@@ -645,10 +619,6 @@ __device__ __forceinline__ void geometry_block(const TickArgs& a, GeoShared<GW>&
         if (q >= 4) v *= a.dyn.negA;
         else if (q >= 2) v *= a.stat.negA;
         a.geo[((size_t)slice * 6 + q) * a.N_pad + i] = v;
-    }
-    if (a.geo_stamps && tid == 0) {
-        unsigned long long* o = a.geo_stamps + 4 * ((size_t)slice_y * n_bx + bx);
-        o[0] = st0; o[1] = st1; o[2] = st2; o[3] = __builtin_amdgcn_s_memrealtime();
     }
 }
 
@@ -670,7 +640,7 @@ __global__ __launch_bounds__(GW * WAVE, 8) void sfm_geometry_kernel(const TickAr
         }
         return;
     }
-    geometry_block<RAD, GW>(a, sh, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.y, (int)gridDim.x, (int)threadIdx.x);
+    geometry_block<RAD, GW>(a, sh, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.y, (int)threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1393,8 +1363,6 @@ __device__ __forceinline__ void pair_block(const float4* __restrict__ pk, const 
     const int wave = uniform(tid >> 6);
     const int n_t = sa.n_t;
     const int half_up = (sa.t_hi - sa.t_lo + 1) >> 1;      // diagonal items pair own tile bx with bx + half_up
-    unsigned long long t_start = 0;
-    if (sa.stamps) t_start = __builtin_amdgcn_s_memrealtime();
     // work items: the (bx, shift) of the 2-D grid, or -- cutoff on -- entries of the compacted list, strided
     const int n_items = sa.work ? *sa.work_count : 1;
     // list mode: a workgroup takes a contiguous run of the list (consecutive items share a tile: its rows stay hot in this
@@ -1408,7 +1376,7 @@ __device__ __forceinline__ void pair_block(const float4* __restrict__ pk, const 
         const uint32_t w = sa.work[item];
         bx = (int)(w & 0xffffu); shift = (int)((w >> 16) & 0x7fffu); one_sided = (w & WORK_ONE_SIDED) != 0u;
     }
-    int ta, tb, sig0, nsteps;
+    int ta, tb, sig0;
     bool diag = false;
     if (shift == 0) {
         // diagonal tiles are half the work (32 steps): two of them share a workgroup, two waves each
@@ -1418,7 +1386,6 @@ __device__ __forceinline__ void pair_block(const float4* __restrict__ pk, const 
         tb = ta;
         diag = true;
         sig0 = 1 + 16 * (wave & 1);               // sigma 1..16 / 17..32 (sigma = 32 is one-sided)
-        nsteps = 16;
     } else {
         // Antipodal pairs (even n_t, shift n_t/2) appear twice in the 2-D grid: the upper half leaves.  The list
         // builders have already dropped that duplicate for own-own pairs, and a ONE-SIDED antipodal item (partner tile
@@ -1428,9 +1395,7 @@ __device__ __forceinline__ void pair_block(const float4* __restrict__ pk, const 
         tb = bx + shift;
         if (tb >= n_t) tb -= n_t;
         sig0 = 16 * wave;
-        nsteps = 16;
     }
-    if (sa.debug_steps >= 0) nsteps = min(sa.debug_steps, 16);   // (the doubled LDS image holds slots lane + sig0 + s <= 127 only for s < 16)
 
     float fxi = 0.f, fyi = 0.f, fxj = 0.f, fyj = 0.f;
     float fzi = 0.f, fzj = 0.f;                   // 3-D crowds (Z3): the z components (forces.py:112-117 keeps 3-component forces)
@@ -1465,7 +1430,7 @@ __device__ __forceinline__ void pair_block(const float4* __restrict__ pk, const 
         const float* radt = &sh.radt[tsel][lane + sig0];
         const float2* travz = &sh.travz[tsel][lane + sig0];
         // sigma = 32 on a diagonal tile meets every unordered pair {l, l+32} in BOTH lanes: one-sided there
-        const int one_sided_from = one_sided ? 0 : ((diag && (sig0 + nsteps - 1 == 32)) ? nsteps - 1 : nsteps);   // uniform
+        const int one_sided_from = one_sided ? 0 : ((diag && (sig0 + 15 == 32)) ? 15 : 16);   // uniform
         float4 T = trav[0];
         float ri = RAD ? radt[0] : 0.f;
         float2 Tz = make_float2(0.f, 0.f);
@@ -1481,7 +1446,6 @@ __device__ __forceinline__ void pair_block(const float4* __restrict__ pk, const 
             if (Z3) Tzn = travz[s_ + 1];
             __builtin_amdgcn_sched_barrier(0);
             bool done = false;
-#if SFM_PK
             {                                     // the step on packed fp32 instructions (round 4): x / y pairs packed, z scalar
                 v2f pjv, ujv, Tv, Uv, cv;
                 float cz = 0.f;
@@ -1496,41 +1460,16 @@ __device__ __forceinline__ void pair_block(const float4* __restrict__ pk, const 
                     done = true;
                 }
             }
-#else
-            {
-            const float dx = pj.x - T.x, dy = pj.y - T.y;
-            const float dz = Z3 ? zj - Tz.x : 0.f;
-            const float d2 = Z3 ? fmaf(dx, dx, fmaf(dy, dy, dz * dz)) : fmaf(dx, dx, dy * dy);
-            if (!CUT || __any(!(d2 > reach2))) {
-                float cx, cy, cz = 0.f;
-                const bool kept = Z3 ? moussaid_spatial<RAD, CUT>(c, dx, dy, dz, d2, T.z - ujx, T.w - ujy, Tz.y - ujz, RAD ? ri + rj : 0.f, cx, cy, cz)
-                                     : moussaid_planar<RAD, CUT>(c, dx, dy, d2, T.z - ujx, T.w - ujy, RAD ? ri + rj : 0.f, cx, cy);
-                if (kept) {
-                    // the sums of the pedestrian this lane has just met were in lane + 1 a step ago: rotation and add in one
-                    fxi = rot_in(fxi) + cx;
-                    fyi = rot_in(fyi) + cy;
-                    if (Z3) fzi = rot_in(fzi) + cz;
-                    if (s_ < one_sided_from) { fxj -= cx; fyj -= cy; if (Z3) fzj -= cz; }
-                    done = true;
-                }
-            }
-            }
-#endif
             if (CUT && !done) { fxi = rot_in(fxi); fyi = rot_in(fyi); if (Z3) fzi = rot_in(fzi); }
             T = Tn;
             ri = rin;
             Tz = Tzn;
             __builtin_amdgcn_sched_barrier(0);
         };
-        if (nsteps == 16) {                      // the normal case: fixed trip count
 #pragma unroll 4
-            for (int s_ = 0; s_ < 16; ++s_) step(s_);
-        } else {                                 // timing probe (SymArgs::debug_steps)
-#pragma unroll 1
-            for (int s_ = 0; s_ < nsteps; ++s_) step(s_);
-        }
-        i_end_loc = (lane + sig0 + nsteps - 1) & (WAVE - 1);
-        if (SFM_PK) { fxj = fjv.x; fyj = fjv.y; }
+        for (int s_ = 0; s_ < 16; ++s_) step(s_);
+        i_end_loc = (lane + sig0 + 15) & (WAVE - 1);
+        fxj = fjv.x; fyj = fjv.y;
       }
     }
     sh.fi[wave][i_end_loc] = make_float2(fxi, fyi);
@@ -1591,16 +1530,6 @@ __device__ __forceinline__ void pair_block(const float4* __restrict__ pk, const 
     }
     if (sa.work) __syncthreads();                 // LDS is reused by the next item
   }
-    if (sa.stamps && tid == 0 && (size_t)bid_y * grid_x + bid_x < (size_t)PAIR_STAMP_WGS) {
-        const size_t b = (size_t)bid_y * grid_x + bid_x;
-        unsigned hw;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        sa.stamps[3 * b] = t_start;
-        sa.stamps[3 * b + 1] = __builtin_amdgcn_s_memrealtime();
-        sa.stamps[3 * b + 2] = ((unsigned long long)xcc << 32) | hw;
-    }
 }
 
 // CUT: the provably negligible part of a tile pair is not evaluated.  reach = the distance beyond which a
@@ -1632,7 +1561,7 @@ __global__ __launch_bounds__(BLOCK) void sfm_pair_geo_kernel(const TickArgs a, c
     const bool is_geo = g < n_geo && bid == g * geo_stride;
     if (is_geo) {
         geometry_block<RAD, WAVES_PER_BLOCK>(a, *reinterpret_cast<GeoShared<WAVES_PER_BLOCK>*>(smem), g % geo_tiles, g / geo_tiles, a.geo_slices,
-                                             geo_tiles, (int)threadIdx.x);
+                                             (int)threadIdx.x);
     } else {
         const int pb = bid - min(n_geo, g + 1);   // index among the pair workgroups: a run of the list, or (bx, shift) of the 2-D grid
         if (sa.work) pair_block<RAD, CUT, Z3>(a.pk_cur, a.zv_cur, a.radius, a.ped, sa, *reinterpret_cast<PairShared*>(smem), pb, 0, (int)gridDim.x - n_geo, (int)threadIdx.x);
@@ -1664,9 +1593,7 @@ __device__ __forceinline__ size_t pool_slot(const SymArgs& sa, int t, int u, uin
 }
 
 constexpr int EPI_WAVES = 16;
-#ifndef EPI_INFLIGHT
-#define EPI_INFLIGHT 8                     // slab-row loads a wave keeps in flight under a cutoff (a multiple of 4; the sum's association follows it)
-#endif
+constexpr int EPI_INFLIGHT = 8;            // slab-row loads a wave keeps in flight under a cutoff (a multiple of 4; the sum's association follows it)
 
 template <bool RAD, int EW, bool Z3>
 __global__ __launch_bounds__(EW * WAVE) void sfm_sym_epilogue_kernel(const TickArgs a, const SymArgs sa) {
@@ -2023,8 +1950,10 @@ constexpr int GROUP = 2 * WAVE;                  // pedestrians per group of two
 // from the neighbouring lane and takes this step's term in one instruction).  60 -> 54 issued VALU instructions per step: c2 17.55
 // -> 16.54 us.  Needs wave_rol:1 to hand lane l the value of lane l+1 (probed at init; otherwise the symmetric path is off).
 // (Measured and dropped: the sums in LDS as well, by ds_add_f32 -- LDS float atomics run at ~2 cycles per LANE: 88.8 against 17.5 us.)
-// Z3: a 3-D crowd -- {z, lambda vz} travel beside (one more ds_read_b64), the body is moussaid_spatial, the sums have a z component
-// that goes through slabz rows, and the integration is the 3-D one of sfm_sym_epilogue_kernel.
+// Round 4: every lane evaluates two pairs per double step on packed fp32 (moussaid_planar_x2 / moussaid_spatial_x2), so the tile sits
+// in LDS as four planes x, y, lambda vx, lambda vy and a lane reads its two travelling pedestrians with one ds_read2_b32 per plane.
+// Z3: a 3-D crowd -- {z, lambda vz} travel beside as two more planes, the sums have a z component that goes through slabz rows, and
+// the integration is the 3-D one of sfm_sym_epilogue_kernel.
 // GEO (round 3): the crowd also feels border / obstacle forces.  Their workgroups are a second ROLE of the same launch -- blocks
 // [0, n_geo_wg): one workgroup per (tile, slice of the polylines); it integrates its tile's group exactly like a pair workgroup
 // does (same code, same bits, nothing stored) and then runs the geometry kernel's body on the new state, leaving ONE float2 per
@@ -2045,9 +1974,8 @@ struct FusedShared {                             // LDS of one pair-role workgro
     float2 fj[NW][WAVE];
     float fiz[Z3 ? NW : 1][WAVE];                // (3-D: z components; these four arrays are one block of (NW / 2) * 2 * GROUP * 12 bytes = q + qz)
     float fjz[Z3 ? NW : 1][WAVE];
-    static constexpr bool X2 = SFM_X2;           // two pairs per lane: every form of the pair role (round 4, late: also with radii, also 3-D)
-    float2 fi2[X2 ? NW : 1][WAVE];               // ... the sums of a wave's second travelling chain
-    float fi2z[(X2 && Z3) ? NW : 1][WAVE];
+    float2 fi2[NW][WAVE];                        // two pairs per lane (every form of the pair role): the sums of a wave's second travelling chain
+    float fi2z[Z3 ? NW : 1][WAVE];
     float4 trav[4][2 * WAVE];                    // the four tiles as travelling operands, each twice back to back (two pairs per lane: as four
                                                  // planes x, y, lambda vx, lambda vy of [4][2 * WAVE] floats -- a lane reads its two pedestrians' x as one ds_read2_b32)
     float radt[RAD ? 4 : 1][2 * WAVE];
@@ -2060,23 +1988,11 @@ struct FusedShared {                             // LDS of one pair-role workgro
     }
 };
 
-#ifdef SFM_EXPERIMENTS
-// per workgroup FUSED_STAMP_STRIDE words: [0, 5) thread 0 at entry, column sums in, state in LDS, its steps done, its row stored; then per
-// WAVE [5 + w] the end of its last systolic step and [5 + 16 + w] the end of its share of the row store (round 4: is "steps done ->
-// rows stored" of thread 0 a store tail or the skew between the workgroup's waves?)
-#define FUSED_STAMP(k) do { if (f.stamps && threadIdx.x == 0 && blockIdx.x < FUSED_STAMP_WGS) f.stamps[FUSED_STAMP_STRIDE * (size_t)blockIdx.x + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define FUSED_WAVE_STAMP(k) do { if (f.stamps && (threadIdx.x & 63) == 0 && blockIdx.x < FUSED_STAMP_WGS) f.stamps[FUSED_STAMP_STRIDE * (size_t)blockIdx.x + 5 + (k) * 16 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define FUSED_STAMP(k) do { } while (0)
-#define FUSED_WAVE_STAMP(k) do { } while (0)
-#endif
-
 template <bool RAD, int NW, bool Z3, bool GEO>   // NW waves per workgroup (8 or 16): 256 / NW systolic steps each
 __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_tick_kernel(const TickArgs a, const FusedArgs f) {   // 8 waves per SIMD: two 16-wave (four 8-wave) workgroups per CU (3-D, 8 waves: LDS allows three)
     constexpr int PARTS = NW / 2;                // the slab rows are split over this many 128-thread parts
     constexpr int SPW = 4 * WAVE / NW;           // systolic steps per wave
     constexpr int D = NW / 8;                    // waves per diagonal tile
-    constexpr bool X2 = FusedShared<RAD, NW, Z3>::X2;   // two pairs per lane (moussaid_planar_x2 / moussaid_spatial_x2)
     using Sh = FusedShared<RAD, NW, Z3>;
     constexpr size_t LDS = (GEO && sizeof(GeoShared<NW>) > sizeof(Sh)) ? sizeof(GeoShared<NW>) : sizeof(Sh);
     __shared__ __attribute__((aligned(16))) char smem[LDS];
@@ -2085,7 +2001,6 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
                           offsetof(Sh, fj) == offsetof(Sh, fi) + sizeof(sh.fi) && offsetof(Sh, fiz) == offsetof(Sh, fj) + sizeof(sh.fj) &&
                           offsetof(Sh, fjz) == offsetof(Sh, fiz) + sizeof(sh.fiz)),
                   "3-D: q / qz are laid over fi | fj | fiz | fjz, which must be one block of exactly that size");
-    FUSED_STAMP(0);
     const int tid = threadIdx.x;
     const int lane = tid & (WAVE - 1);
     const int wave = uniform(tid >> 6);
@@ -2245,34 +2160,23 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
         sh.qv()[part][2 * pp + 1] = make_float2(acc4.z, acc4.w);
         if (Z3) { sh.qzv()[part][2 * pp] = accz.x; sh.qzv()[part][2 * pp + 1] = accz.y; }
     }
-    FUSED_STAMP(1);
     __syncthreads();
     // the arithmetic of sfm_sym_epilogue_kernel without border / obstacle forces (pedestrian_simulation.py:57-83,
     // forces.py:40-52): acceleration towards the waypoint, capped velocity, position, arrival -> next waypoint
     auto put_state = [&](const float4 ns, const float2 nsz) {   // pedestrian slot p of the workgroup in the state the pairs are evaluated on
         sh.st[p] = ns;
         const float4 t = make_float4(ns.x, ns.y, a.ped.lam * ns.z, a.ped.lam * ns.w);
-        if (X2) {
-            float* pl = reinterpret_cast<float*>(sh.trav) + (p >> 6) * 2 * WAVE + (p & (WAVE - 1));      // plane c at + c * 4 * 2 * WAVE
-            pl[0] = t.x; pl[WAVE] = t.x;
-            pl[8 * WAVE] = t.y; pl[9 * WAVE] = t.y;
-            pl[16 * WAVE] = t.z; pl[17 * WAVE] = t.z;
-            pl[24 * WAVE] = t.w; pl[25 * WAVE] = t.w;
-        } else {
-        sh.trav[p >> 6][p & (WAVE - 1)] = t;
-        sh.trav[p >> 6][(p & (WAVE - 1)) + WAVE] = t;
-        }
+        float* pl = reinterpret_cast<float*>(sh.trav) + (p >> 6) * 2 * WAVE + (p & (WAVE - 1));      // plane c at + c * 4 * 2 * WAVE
+        pl[0] = t.x; pl[WAVE] = t.x;
+        pl[8 * WAVE] = t.y; pl[9 * WAVE] = t.y;
+        pl[16 * WAVE] = t.z; pl[17 * WAVE] = t.z;
+        pl[24 * WAVE] = t.w; pl[25 * WAVE] = t.w;
         if (Z3) {
             sh.stz[Z3 ? p : 0] = nsz;
             const float2 tz = make_float2(nsz.x, a.ped.lam * nsz.y);
-            if (X2) {
-                float* plz = reinterpret_cast<float*>(sh.travz) + (p >> 6) * 2 * WAVE + (p & (WAVE - 1));   // planes z | lambda vz of [4][2 * WAVE] floats
-                plz[0] = tz.x; plz[WAVE] = tz.x;
-                plz[8 * WAVE] = tz.y; plz[9 * WAVE] = tz.y;
-            } else {
-            sh.travz[Z3 ? (p >> 6) : 0][p & (WAVE - 1)] = tz;
-            sh.travz[Z3 ? (p >> 6) : 0][(p & (WAVE - 1)) + WAVE] = tz;
-            }
+            float* plz = reinterpret_cast<float*>(sh.travz) + (p >> 6) * 2 * WAVE + (p & (WAVE - 1));   // planes z | lambda vz of [4][2 * WAVE] floats
+            plz[0] = tz.x; plz[WAVE] = tz.x;
+            plz[8 * WAVE] = tz.y; plz[9 * WAVE] = tz.y;
         }
     };
     auto finish = [&](const float2 g, const float gz) {
@@ -2381,7 +2285,7 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
         me.walk = me.live && !(a.crossing && a.crossing[ig]);          // forces.py:140-141,176-177
         __syncthreads();                                               // the geometry body's LDS lies over the prologue's
         GeoShared<NW>& gs = *reinterpret_cast<GeoShared<NW>*>(smem);
-        geometry_forces<RAD, NW, true>(a, gs, me, geo_slice, f.geo_slices, tid, nullptr);
+        geometry_forces<RAD, NW, true>(a, gs, me, geo_slice, f.geo_slices, tid);
         if (wave < 2 && me.live) {                                     // wave 0: x, wave 1: y -- border, static, dynamic in that order
             float vb = 0.f, vs = 0.f, vd = 0.f;
 #pragma unroll
@@ -2391,7 +2295,6 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
         return;
     }
 
-    FUSED_STAMP(2);
     // ---- 2. this workgroup's tile pairs on the new state: every wave SPW systolic steps (sfm_pair_sym_kernel's step)
     int ia, ib, sig0;                             // LDS slots of the travelling / resident tile's lane 0, first rotation
     bool diag = false, work = true;
@@ -2420,9 +2323,9 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
     }
     float fxi = 0.f, fyi = 0.f, fxj = 0.f, fyj = 0.f, fzi = 0.f, fzj = 0.f;
     int i_end_loc = lane;
-    float fxb = 0.f, fyb = 0.f, fzb = 0.f;        // X2: the sums of the second travelling chain, and where they end up
+    float fxb = 0.f, fyb = 0.f, fzb = 0.f;        // the sums of the second travelling chain, and where they end up
     int i_end_b = lane;
-    if (X2 && work) {
+    if (work) {
         // Two pairs per lane: the wave's SPW steps are SPW / 2 double steps; chain A meets sigma0 .. sigma0 + SPW/2 - 1, chain B the same
         // XB further on -- half a tile pair (32) away, on a diagonal tile half of ITS 32 rotations (16) -- so the waves of a tile pair
         // still cover every rotation once.  A lane's two travelling pedestrians are XB slots apart in the doubled image: one
@@ -2485,89 +2388,21 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
         fxj = fjx.x + fjx.y;
         fyj = fjy.x + fjy.y;
         if (Z3) fzj = fjzv.x + fjzv.y;
-    } else
-    if (work) {
-        const IxConst& c = a.ped;
-        const float4 pj = sh.st[ib + lane];
-        const float ujx = c.lam * pj.z, ujy = c.lam * pj.w;
-        float rj = 0.f;
-        if (RAD) rj = sh.rad[ib + lane];
-        float zj = 0.f, ujz = 0.f;
-        if (Z3) { const float2 qz = sh.stz[Z3 ? ib + lane : 0]; zj = qz.x; ujz = c.lam * qz.y; }
-        // step s meets pedestrian (lane + sig0 + s) mod 64 of the travelling tile: slot lane + sig0 + s of the doubled image
-        const float4* trav = &sh.trav[ia >> 6][lane + sig0];
-        const float* radt = &sh.radt[RAD ? (ia >> 6) : 0][lane + sig0];
-        const float2* travz = &sh.travz[Z3 ? (ia >> 6) : 0][lane + sig0];
-        // sigma = 32 on a diagonal tile meets every unordered pair {l, l+32} in BOTH lanes: one-sided there
-        const bool tail_one_sided = diag && (sig0 + SPW - 1 == 32);  // uniform
-        float4 T = trav[0];
-        float ri = RAD ? radt[0] : 0.f;
-        float2 Tz = make_float2(0.f, 0.f);
-        if (Z3) Tz = travz[0];
-#if SFM_PK
-        v2f fjv; fjv.x = 0.f; fjv.y = 0.f;       // the resident sums as a register pair (v_pk_add_f32)
-#endif
-#pragma unroll
-        for (int s_ = 0; s_ < SPW; ++s_) {
-            float4 Tn = T;
-            float rin = ri;
-            float2 Tzn = Tz;
-            if (s_ + 1 < SPW) { Tn = trav[s_ + 1]; if (RAD) rin = radt[s_ + 1]; if (Z3) Tzn = travz[s_ + 1]; }   // the next step's operand is in flight during this one
-            __builtin_amdgcn_sched_barrier(0);       // (... so its read is issued here, not where the scheduler would sink it to)
-            const float dx = pj.x - T.x, dy = pj.y - T.y;
-            float cx, cy, cz = 0.f;
-            if (Z3 && SFM_PK) {
-                v2f pjv, ujv, Tv, Uv, cv;
-                pjv.x = pj.x; pjv.y = pj.y; ujv.x = ujx; ujv.y = ujy; Tv.x = T.x; Tv.y = T.y; Uv.x = T.z; Uv.y = T.w;
-                moussaid_spatial_pk<RAD, false>(c, pjv, zj, ujv, ujz, Tv, Tz.x, Uv, Tz.y, RAD ? ri + rj : 0.f, 0.f, cv, cz);
-                cx = cv.x; cy = cv.y;
-            } else if (Z3) {
-                const float dz = zj - Tz.x;
-                moussaid_spatial<RAD, false>(c, dx, dy, dz, fmaf(dx, dx, fmaf(dy, dy, dz * dz)), T.z - ujx, T.w - ujy, Tz.y - ujz, RAD ? ri + rj : 0.f, cx, cy, cz);
-            } else {
-#if SFM_PK
-                v2f pjv, ujv, Tv, Uv;
-                pjv.x = pj.x; pjv.y = pj.y; ujv.x = ujx; ujv.y = ujy; Tv.x = T.x; Tv.y = T.y; Uv.x = T.z; Uv.y = T.w;
-                v2f cv;
-                moussaid_planar_pk<RAD, false>(c, pjv, ujv, Tv, Uv, RAD ? ri + rj : 0.f, 0.f, cv);
-                cx = cv.x; cy = cv.y;
-                if (s_ + 1 < SPW || !tail_one_sided) fjv -= cv;
-#else
-                moussaid_planar<RAD, false>(c, dx, dy, fmaf(dx, dx, dy * dy), T.z - ujx, T.w - ujy, RAD ? ri + rj : 0.f, cx, cy);
-#endif
-            }
-            // the sums of the pedestrian this lane has just met were in lane + 1 a step ago: rotation and add in one instruction
-            fxi = rot_in(fxi) + cx;
-            fyi = rot_in(fyi) + cy;
-            if (Z3) fzi = rot_in(fzi) + cz;
-            if (SFM_PK && !Z3) { fxj = fjv.x; fyj = fjv.y; }
-            else if (s_ + 1 < SPW || !tail_one_sided) { fxj -= cx; fyj -= cy; if (Z3) fzj -= cz; }
-            T = Tn;
-            ri = rin;
-            Tz = Tzn;
-            // steps are not interleaved (measured again in round 3, variant builds: without this barrier 16.44, without either 16.60,
-            // pairs of steps free to interleave 16.51, as here 16.15-16.30 us per c2 tick)
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        i_end_loc = (lane + sig0 + SPW - 1) & (WAVE - 1);
     }
-    FUSED_WAVE_STAMP(0);
     sh.fi[wave][i_end_loc] = make_float2(fxi, fyi);
-    if (X2) sh.fi2[X2 ? wave : 0][i_end_b] = make_float2(fxb, fyb);
-    if (X2 && Z3) sh.fi2z[(X2 && Z3) ? wave : 0][i_end_b] = fzb;
+    sh.fi2[wave][i_end_b] = make_float2(fxb, fyb);
+    if (Z3) sh.fi2z[Z3 ? wave : 0][i_end_b] = fzb;
     sh.fj[wave][lane] = make_float2(fxj, fyj);
     if (Z3) { sh.fiz[Z3 ? wave : 0][i_end_loc] = fzi; sh.fjz[Z3 ? wave : 0][lane] = fzj; }
-    FUSED_STAMP(3);
     __syncthreads();
-    FUSED_WAVE_STAMP(1);
     if (!lower || !present) return;
     const int tl = (p >> 6) & 1, l = lane;       // tile of the group, pedestrian of the tile
     // sums of wave w for pedestrian l of its travelling / resident tile, z in the third component
     auto fi = [&](int w) {
         float2 v = sh.fi[w][l];
-        if (X2) { const float2 v2 = sh.fi2[X2 ? w : 0][l]; v.x += v2.x; v.y += v2.y; }       // (both travelling chains of the wave)
+        const float2 v2 = sh.fi2[w][l]; v.x += v2.x; v.y += v2.y;       // (both travelling chains of the wave)
         float vz_ = Z3 ? sh.fiz[Z3 ? w : 0][l] : 0.f;
-        if (X2 && Z3) vz_ += sh.fi2z[(X2 && Z3) ? w : 0][l];
+        if (Z3) vz_ += sh.fi2z[Z3 ? w : 0][l];
         return make_float3(v.x, v.y, vz_);
     };
     auto fj = [&](int w) { const float2 v = sh.fj[w][l]; return make_float3(v.x, v.y, Z3 ? sh.fjz[Z3 ? w : 0][l] : 0.f); };
@@ -2599,7 +2434,6 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
     }
     f.slab_next[(size_t)row * a.N_pad + i] = make_float2(r.x, r.y);
     if (Z3) f.slabz_next[(size_t)row * a.N_pad + i] = r.z;
-    FUSED_STAMP(4);
 }
 
 // Dynamic obstacles on the device (obstacles.py:297-329 without the simulator): one wave per vehicle moves the centre
@@ -2670,8 +2504,7 @@ hipError_t launch_geometry(bool rad, const TickArgs& a, hipStream_t st) {
     const int n_local = a.i_end - a.i_begin;
     if (n_local <= 0) return hipSuccess;
     const int grid = ((a.i_end + WAVE - 1) >> 6) - (a.i_begin >> 6);      // tiles overlapping the shard
-    static const int gw_ov = exp_env("SFM_GEO_WAVES") ? atoi(exp_env("SFM_GEO_WAVES")) : 0;        // A/B only
-    const bool thin = gw_ov ? gw_ov == 8 : grid >= 1024;
+    const bool thin = grid >= 1024;
     TickArgs b = a;
     int extra = 0;                                  // workgroups that build the flat tile-pair list (TickArgs::list_work)
     if (a.list_work) {
@@ -2709,9 +2542,8 @@ hipError_t launch_sym_list(const TickArgs& a, const SymArgs& sa, hipStream_t st,
 
 template <bool RAD, bool CUT>
 static void launch_sym_pair_t(dim3 grid, const TickArgs& a, const SymArgs& sa, hipStream_t st) {
-    static const int pad_lds = exp_env("SFM_PAIR_LDS") ? atoi(exp_env("SFM_PAIR_LDS")) : 0;   // experiment: limits the resident workgroups per CU
-    if (sa.slabz) hipLaunchKernelGGL((sfm_pair_sym_kernel<RAD, CUT, true>), grid, dim3(BLOCK), (size_t)pad_lds, st, a.pk_cur, a.zv_cur, a.radius, a.ped, sa);
-    else hipLaunchKernelGGL((sfm_pair_sym_kernel<RAD, CUT, false>), grid, dim3(BLOCK), (size_t)pad_lds, st, a.pk_cur, a.zv_cur, a.radius, a.ped, sa);
+    if (sa.slabz) hipLaunchKernelGGL((sfm_pair_sym_kernel<RAD, CUT, true>), grid, dim3(BLOCK), 0, st, a.pk_cur, a.zv_cur, a.radius, a.ped, sa);
+    else hipLaunchKernelGGL((sfm_pair_sym_kernel<RAD, CUT, false>), grid, dim3(BLOCK), 0, st, a.pk_cur, a.zv_cur, a.radius, a.ped, sa);
 }
 
 template <bool RAD, bool CUT>
@@ -2733,9 +2565,7 @@ hipError_t launch_sym_pair(bool rad, const TickArgs& a, const SymArgs& sa, hipSt
         // a resident grid takes contiguous runs of the list: a few times more workgroups than fit at once (8 per CU), short runs
         // interleave better with the geometry kernel's workgroups and even out the tail; measured best 4x at 256 tiles, 16x from
         // 1024 tiles on
-        static const int rounds_ov = exp_env("SFM_ROUNDS") ? atoi(exp_env("SFM_ROUNDS")) : 0;      // A/B only
-        const int rounds = rounds_ov > 0 ? rounds_ov : list_rounds(sa);
-        grid = dim3(256 * 8 * rounds);
+        grid = dim3(256 * 8 * list_rounds(sa));
     }
     const bool cut = sa.vmax != nullptr;           // list cutoff: the per-step reach and exponent tests are on as well
     if (rad) { if (cut) launch_sym_pair_t<true, true>(grid, a, sa, st); else launch_sym_pair_t<true, false>(grid, a, sa, st); }
@@ -2746,14 +2576,10 @@ hipError_t launch_sym_pair(bool rad, const TickArgs& a, const SymArgs& sa, hipSt
 // the pair kernel of a list-cutoff tick with the geometry workgroups of the same tick in front (sfm_pair_geo_kernel)
 hipError_t launch_sym_pair_geo(bool rad, const TickArgs& a, const SymArgs& sa, hipStream_t st) {
     const int tiles = ((a.i_end + WAVE - 1) >> 6) - (a.i_begin >> 6);
-    static const int rounds_ov = exp_env("SFM_ROUNDS") ? atoi(exp_env("SFM_ROUNDS")) : 0;      // A/B only
-    const int rounds = rounds_ov > 0 ? rounds_ov : list_rounds(sa);
-    const int n_geo = tiles * a.geo_slices, n_pair = sa.work ? 256 * 8 * rounds : sa.n_t * (sa.n_t / 2 + 1);
+    const int n_geo = tiles * a.geo_slices, n_pair = sa.work ? 256 * 8 * list_rounds(sa) : sa.n_t * (sa.n_t / 2 + 1);
     const dim3 grid(n_geo + n_pair);
     // more geometry workgroups than the CUs hold in one round beside the pair workgroups: spread them evenly over the grid
-    static const int stride_ov = exp_env("SFM_PG_STRIDE") ? atoi(exp_env("SFM_PG_STRIDE")) : 0;      // A/B only
     int stride = n_geo > 256 * 4 ? std::max(1, (n_geo + n_pair) / n_geo) : 1;
-    if (stride_ov > 0) stride = std::min(stride_ov, std::max(1, (n_geo + n_pair) / n_geo));
     if (stride > 1 && !(stride & 1)) --stride;      // odd: workgroup w runs on CU w mod 256, an even stride would put every geometry workgroup on a few CUs
     const bool cut = sa.vmax != nullptr;           // as launch_sym_pair: list cutoff -> the per-step tests are on
     if (rad) { if (cut) launch_sym_pair_geo_t<true, true>(grid, a, sa, tiles, stride, st); else launch_sym_pair_geo_t<true, false>(grid, a, sa, tiles, stride, st); }
@@ -2799,8 +2625,7 @@ static void launch_sym_epilogue_t(const TickArgs& a, const SymArgs& sa, hipStrea
 // plenty of workgroups and 4 waves per tile measured 2 % better on the c5 tick.
 hipError_t launch_sym_epilogue(bool rad, const TickArgs& a, const SymArgs& sa, hipStream_t st) {
     if (a.N <= 0) return hipSuccess;
-    static const int ew_ov = exp_env("SFM_EPI_WAVES") ? atoi(exp_env("SFM_EPI_WAVES")) : 0;      // A/B only: 4 / 16
-    const bool thin = ew_ov ? ew_ov == 4 : sa.n_t >= 1024;
+    const bool thin = sa.n_t >= 1024;
     if (rad) { if (thin) launch_sym_epilogue_t<true, 4>(a, sa, st); else launch_sym_epilogue_t<true, EPI_WAVES>(a, sa, st); }
     else { if (thin) launch_sym_epilogue_t<false, 4>(a, sa, st); else launch_sym_epilogue_t<false, EPI_WAVES>(a, sa, st); }
     return hipGetLastError();
