@@ -1797,7 +1797,7 @@ int sfm_step_records(SfmHandle* h, int N, const void* records, int64_t stride, c
     const char* base = static_cast<const char*>(records);
     const int o_loc = field_offsets[0], o_vel = field_offsets[1], o_wp = field_offsets[2], o_rad = field_offsets[3], o_ts = field_offsets[4];
     double z0 = 0.0, z_lo = 0.0, z_hi = 0.0, vz_max = 0.0;
-    bool flat = true;
+    bool flat = true, any_nan = false;
     for (size_t i = 0; i < n; ++i) {
         const char* r = base + (size_t)stride * i;
         double l[3], v[3], w[2], rad, t;                   // (memcpy: the float64 fields of a packed record are not 8-byte aligned)
@@ -1810,11 +1810,13 @@ int sfm_step_records(SfmHandle* h, int N, const void* records, int64_t stride, c
         if (i == 0) { z0 = z_lo = z_hi = l[2]; }
         flat = flat && l[2] == z0 && v[2] == 0.0;
         z_lo = std::fmin(z_lo, l[2]); z_hi = std::fmax(z_hi, l[2]); vz_max = std::fmax(vz_max, std::fabs(v[2]));
+        any_nan = any_nan || std::isnan(l[2]) || std::isnan(v[2]);
     }
     // the 2-D kernels iff all z are equal and no pedestrian has a v_z (then the 3-component formulas of forces.py:74-117 and
     // stateutils.py:18-23 reduce to them exactly) -- or, planar_tolerance >= 0, nearly so: every |z - median z| and |v_z| within it
-    // (the facade's documented deviation for walkers on almost level ground)
-    if (!flat && planar_tolerance >= 0.0f && N > 0 && vz_max <= (double)planar_tolerance && z_hi - z_lo <= 2.0 * (double)planar_tolerance) {
+    // (the facade's documented deviation for walkers on almost level ground).  A NaN z or v_z means 3-D, as in the NumPy rule, where
+    // max |z - median| and max |v_z| are then NaN: fmin / fmax above skip NaN, and std::sort must not see one.
+    if (!flat && !any_nan && planar_tolerance >= 0.0f && N > 0 && vz_max <= (double)planar_tolerance && z_hi - z_lo <= 2.0 * (double)planar_tolerance) {
         std::vector<double> zs(n);
         for (size_t i = 0; i < n; ++i) { double l2; memcpy(&l2, base + (size_t)stride * i + o_loc + 2 * sizeof(double), sizeof(l2)); zs[i] = l2; }
         std::sort(zs.begin(), zs.end());

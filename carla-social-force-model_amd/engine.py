@@ -82,6 +82,7 @@ class SfmEngine:
         self.shard = (0, 0)
         self.planar = True
         self._z0 = 0.0            # a flat crowd's common z (the device only holds x / y of a planar crowd)
+        self._dyn_shape = (0, 0, np.zeros(1, np.int32))     # (M, P, ring offsets) of the vehicles the handle holds: dynamic_obstacles()
         if stream is not None:
             self.set_stream(stream)
 
@@ -144,6 +145,7 @@ class SfmEngine:
         if obstacles is None or len(obstacles) == 0:
             self._check(self._lib.sfm_set_dynamic_obstacles(self._h, 0, None, None, None, None, None, None, None),
                         "sfm_set_dynamic_obstacles")
+            self._dyn_shape = (0, 0, np.zeros(1, np.int32))
             return
         M = len(obstacles)
         rings = [r for _, r in obstacles]
@@ -171,6 +173,7 @@ class SfmEngine:
         self._check(self._lib.sfm_set_dynamic_obstacles(self._h, M, iptr(off), fptr(px), fptr(py), fptr(cx), fptr(cy),
                                                         fptr(vx) if velocities is not None else None,
                                                         fptr(vy) if velocities is not None else None), "sfm_set_dynamic_obstacles")
+        self._dyn_shape = (M, P, off)
 
     def set_dynamic_vehicles(self, positions, rings, velocities):
         """The simulator's per-tick vehicle report (obstacles.py:297-329: centres, ring point arrays, velocities) through
@@ -187,13 +190,13 @@ class SfmEngine:
             off[1:] = np.cumsum(lens)
             pts, cv = np.empty((max(int(off[-1]), 1), 2), np.float32), np.zeros((M, 4), np.float32)
             c = self._veh_bufs = (lens, off, pts, cv, off.ctypes.data, pts.ctypes.data, cv.ctypes.data)
-            self._dyn_shape = (M, int(off[-1]), off)
         _, off, pts, cv, p_off, p_pts, p_cv = c
         if off[-1]:
             np.concatenate(rings, axis=0, out=pts[:off[-1]], casting="same_kind")
         cv[:, 0:2] = np.asarray(positions, dtype=np.float64).reshape(M, -1)[:, :2]
         cv[:, 2:4] = 0.0 if velocities is None else np.asarray(velocities, dtype=np.float64).reshape(M, 2)
         self._check(self._lib.sfm_set_dynamic_obstacles_packed(self._h, M, p_off, p_pts, p_cv), "sfm_set_dynamic_obstacles_packed")
+        self._dyn_shape = (M, int(off[-1]), off)
 
     def set_dynamic_boxes(self, centers, yaws, extents, velocities, resolution=0.1):
         """Vehicles as oriented boxes (centre (M,2), yaw rad (M,), half-extents (M,2), velocity (M,2)); ring
@@ -203,6 +206,7 @@ class SfmEngine:
         M = len(centers)
         if M == 0:
             self._check(self._lib.sfm_set_dynamic_boxes(self._h, 0, *([None] * 9)), "sfm_set_dynamic_boxes")
+            self._dyn_shape = (0, 0, np.zeros(1, np.int32))
             return
         locs = [ring_local_offsets(ex, ey, resolution) for ex, ey in np.asarray(extents, dtype=np.float64).reshape(M, 2)]
         off, ux, uy = _csr(locs)
@@ -210,9 +214,9 @@ class SfmEngine:
         v = np.asarray(velocities, dtype=np.float64).reshape(M, 2)
         yaw = np.asarray(yaws, dtype=np.float64).reshape(M)
         arrs = [f32(c[:, 0]), f32(c[:, 1]), f32(np.cos(yaw)), f32(np.sin(yaw)), f32(v[:, 0]), f32(v[:, 1])]
-        self._dyn_shape = (M, int(off[-1]), off)
         self._check(self._lib.sfm_set_dynamic_boxes(self._h, M, iptr(off), fptr(ux), fptr(uy), *(fptr(a) for a in arrs)),
                     "sfm_set_dynamic_boxes")
+        self._dyn_shape = (M, int(off[-1]), off)
 
     def dynamic_obstacles(self):
         """Current device-side vehicles as the reference's list of (center, ring) tuples."""
@@ -252,14 +256,12 @@ class SfmEngine:
         target_speed, radius, border-force-off flag}, ``zvz`` float32 (N, 2) = {z, vz} or None (planar crowd), v' into ``v_out``
         float32 (N, 3).  All three C-contiguous; nothing is allocated or converted here."""
         n = rows.shape[0]
+        if rows.shape != (n, 9) or v_out.shape != (n, 3) or (zvz is not None and zvz.shape != (n, 2)):
+            raise ValueError(f"step_packed: rows {rows.shape}, zvz {None if zvz is None else zvz.shape}, v_out {v_out.shape} for N = {n}")
         self.planar = zvz is None
-        # (the three buffers are prefixes of arrays the caller keeps: their addresses are looked up once per array, not per tick)
-        key = (id(rows.base), id(v_out.base))
-        if getattr(self, "_step_key", None) != key:
-            self._step_key, self._step_ptrs = key, (fptr(rows), fptr(v_out))
-        p_rows, p_out = self._step_ptrs
-        rc = self._lib.sfm_step_packed(self._h, n, p_rows, None if zvz is None else fptr(zvz),
-                                       (_lib.TICK_INTEGRATE if integrate else 0) | (_lib.TICK_REDRAW_WAYPOINTS if redraw else 0), p_out)
+        # (the addresses are taken on every call: a caller may hand in a different array, or another slice of the same one, each tick)
+        rc = self._lib.sfm_step_packed(self._h, n, fptr(rows), fptr(zvz),
+                                       (_lib.TICK_INTEGRATE if integrate else 0) | (_lib.TICK_REDRAW_WAYPOINTS if redraw else 0), fptr(v_out))
         if rc != 0:
             self._check(rc, "sfm_step_packed")
         self.n = n
@@ -269,16 +271,19 @@ class SfmEngine:
         """One host-in-the-loop tick straight from the pedestrian records (sfm_step_records, ABI 5): ``records`` the structured array
         PedestrianState keeps (fields loc, vel, next_waypoint float64 (3,), radius, target_speed float64; any stride), its first ``n`` rows;
         ``border_off`` bool / uint8 (n,) or None; v' into ``v_out`` float32 (n, 3).  Returns whether the planar bodies ran."""
-        key = (id(records), id(v_out.base))
-        if getattr(self, "_rec_key", None) != key:
+        if len(records) < n or v_out.shape != (n, 3):
+            raise ValueError(f"step_records: {len(records)} records, v_out {v_out.shape} for n = {n}")
+        # (the field offsets are worked out once per record layout; the addresses are taken on every call, since a caller may hand in
+        #  a different array, or another slice of the same one, each tick)
+        if getattr(self, "_rec_dtype", None) != records.dtype:
             f = records.dtype.fields
-            off = np.array([f[k][1] for k in ("loc", "vel", "next_waypoint", "radius", "target_speed")], dtype=np.int32)
             for k in ("loc", "vel", "next_waypoint", "radius", "target_speed"):
                 if f[k][0].base != np.dtype(np.float64):
                     raise TypeError(f"record field {k!r} must be float64")
-            # (the arrays themselves are kept: an id can only be trusted while its object is alive)
-            self._rec_key, self._rec_ptrs = key, (records.ctypes.data, int(records.strides[0]), off, off.ctypes.data, fptr(v_out), C.c_int32(0), records, v_out.base)
-        p_rec, stride, _off, p_off, p_out, flag = self._rec_ptrs[:6]
+            off = np.array([f[k][1] for k in ("loc", "vel", "next_waypoint", "radius", "target_speed")], dtype=np.int32)
+            self._rec_dtype, self._rec_off = records.dtype, off
+        self._rec_last = records                   # (state() reads a flat crowd's z from them)
+        p_rec, stride, p_off, p_out, flag = records.ctypes.data, int(records.strides[0]), self._rec_off.ctypes.data, fptr(v_out), C.c_int32(0)
         rc = self._lib.sfm_step_records(self._h, n, p_rec, stride, p_off, None if border_off is None else border_off.ctypes.data,
                                         -1.0 if planar_tolerance is None else float(planar_tolerance),
                                         (_lib.TICK_INTEGRATE if integrate else 0) | (_lib.TICK_REDRAW_WAYPOINTS if redraw else 0), p_out, C.byref(flag))
@@ -376,7 +381,7 @@ class SfmEngine:
                     "sfm_download_state")
         if self.planar:      # rows are in the library's own order: the owned pedestrians are the ones a value came back for
             if self._z0 is None:      # (last upload was sfm_step_records: the flat crowd's z is in the caller's records)
-                self._z0 = float(self._rec_ptrs[6]["loc"][0, 2]) if self.n else 0.0
+                self._z0 = float(self._rec_last["loc"][0, 2]) if self.n else 0.0
             a["z"][~np.isnan(a["x"])] = np.float32(self._z0)
         loc = np.stack([a["x"], a["y"], a["z"]], axis=1).astype(np.float64)
         vel = np.stack([a["vx"], a["vy"], a["vz"]], axis=1).astype(np.float64)
