@@ -1,4 +1,5 @@
-"""Batched scenes: many small, independent crowds stepped by ONE kernel launch per tick (C ABI: sfm_batch_*, ABI 6).
+"""Batched scenes: many small, independent crowds stepped by ONE kernel launch per tick (C ABI: sfm_batch_*, ABI 6; waypoint
+streams and recorded runs, ABI 7).
 
 Social-force models are run in bulk as many small scenes -- scenario sampling, RL environments stepped in lock-step, calibration
 sweeps over A / lambda / gamma / tau.  ``SfmBatch`` holds B scenes of 0 .. 1024 pedestrians, each with its own parameters (its own
@@ -11,6 +12,10 @@ A scene is a dict in the formats ``SfmEngine`` accepts:
   borders: list of (P_k,2), border_centers (K,2), border_lengths (K,);
   static_obstacles / dynamic_obstacles: lists of (center(2), ring(P,2)); dynamic_vel (M,2) or None (at rest).
 Missing geometry keys mean none.  ``vars(scenarios.make_scenario(...))`` is such a dict.
+
+Rollouts longer than one crossing of a scene use per-scene waypoint streams (``set_waypoint_streams`` + ``redraw=True``: on arrival
+a pedestrian takes the next waypoint of its scene's counter-based stream, as a handle does), and ``run_recorded`` returns the
+trajectory of every scene from one launch per tick and one device-to-host copy.
 """
 from __future__ import annotations
 
@@ -20,6 +25,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import SfmLibraryError, f32, fptr, iptr, u8ptr
+
+MAX_RECORD_BYTES = 1 << 30       # SFM_BATCH_MAX_RECORD_BYTES: frames one run_recorded call may hold
 from .engine import _csr, params_from_config
 
 MAX_SCENE_PEDESTRIANS = 1024     # SFM_BATCH_MAX_N
@@ -164,6 +171,48 @@ def batch_params(configs, step_lengths, B=None, honour_file_keys=False):
     return arr
 
 
+def stream_arrays(B, seeds, world_sides, arrive_thresholds=2.0):
+    """Per-scene waypoint stream arguments -> (seed uint32[B], world_side float32[B], arrive_threshold float32[B]).  Each argument is
+    a scalar (broadcast to every scene) or B values.  Seeds are integers (taken mod 2^32, like SfmEngine.set_waypoint_stream); sides
+    and thresholds must be finite and >= 0.  Pure NumPy; raises ValueError."""
+    def col(v, name):
+        a = np.asarray(v)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] not in (1, B)):
+            raise ValueError(f"{name}: expected a scalar or {B} values, got shape {a.shape}")
+        return np.broadcast_to(a.reshape(-1), (B,))
+    s = col(seeds, "seeds")
+    if s.dtype.kind not in "iu":
+        raise ValueError(f"seeds must be integers, got {s.dtype}")
+    out = [np.ascontiguousarray(s.astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)]
+    for v, name in ((world_sides, "world_sides"), (arrive_thresholds, "arrive_thresholds")):
+        a = col(v, name)
+        if a.dtype.kind not in "iuf":
+            raise ValueError(f"{name} must be numbers, got {a.dtype}")
+        a = f32(a)
+        if not (np.isfinite(a).all() and (a >= 0).all()):
+            raise ValueError(f"{name} must be finite and >= 0")
+        out.append(a)
+    return tuple(out)
+
+
+def split_frames(frames, scene_off):
+    """Frames of the concatenated batch, (F, N_total, C), -> a list of B arrays (F, N_b, C), one per scene in scene order (views).
+    Pure NumPy."""
+    so = np.asarray(scene_off)
+    if frames.ndim != 3 or frames.shape[1] != int(so[-1]):
+        raise ValueError(f"frames of shape {frames.shape} for {int(so[-1])} pedestrians")
+    return [frames[:, so[b]:so[b + 1]] for b in range(len(so) - 1)]
+
+
+def n_frames(ticks, stride, max_frames=None):
+    """Frames a recorded run of ``ticks`` ticks keeps: min(max_frames, ceil(ticks / stride)) (0 for invalid arguments, which the
+    library refuses)."""
+    if ticks <= 0 or stride <= 0:
+        return 0
+    f = (ticks + stride - 1) // stride
+    return f if max_frames is None else max(0, min(f, max_frames))
+
+
 class SfmBatch:
     """B independent scenes on one GPU, one launch per tick.  Raises SfmLibraryError on any failure; never falls back to the CPU."""
 
@@ -233,11 +282,55 @@ class SfmBatch:
         self.planar = planar
         self._z = pk["z"].copy()          # a planar batch keeps each scene's z on the host (the device holds x / y only)
 
-    def tick(self, integrate=False):
-        self._check(self._lib.sfm_batch_tick(self._b, _lib.TICK_INTEGRATE if integrate else 0), "sfm_batch_tick")
+    def set_waypoint_streams(self, seeds, world_sides, arrive_thresholds=2.0):
+        """Per-scene waypoint streams for ``redraw=True`` (see ``stream_arrays``; scalars broadcast to every scene).  They stay in
+        effect across ``upload`` and ``set_params``; every upload zeroes the draw counters."""
+        seed, side, thr = stream_arrays(self.B, seeds, world_sides, arrive_thresholds)
+        self._check(self._lib.sfm_batch_set_waypoint_streams(self._b, seed.ctypes.data, fptr(side), fptr(thr)),
+                    "sfm_batch_set_waypoint_streams")
 
-    def run(self, ticks):
-        self._check(self._lib.sfm_batch_run(self._b, int(ticks), _lib.TICK_INTEGRATE), "sfm_batch_run")
+    @staticmethod
+    def _flags(integrate, redraw):
+        return (_lib.TICK_INTEGRATE if integrate else 0) | (_lib.TICK_REDRAW_WAYPOINTS if redraw else 0)
+
+    def tick(self, integrate=False, redraw=False):
+        self._check(self._lib.sfm_batch_tick(self._b, self._flags(integrate, redraw)), "sfm_batch_tick")
+
+    def run(self, ticks, redraw=False):
+        self._check(self._lib.sfm_batch_run(self._b, int(ticks), self._flags(True, redraw)), "sfm_batch_run")
+
+    def run_recorded(self, ticks, stride=1, redraw=False, max_frames=None):
+        """``run`` that records every scene's state before tick 0, stride, 2*stride, ... on the device.  Returns (frames, ticks_idx,
+        zframes): frames a list of B float32 arrays (F, N_b, 4) {x, y, vx, vy}; ticks_idx [0, stride, ...]; zframes a list of
+        (F, N_b, 2) {z, vz} for a 3-D batch, None for a planar one."""
+        if self.scene_off is None:
+            raise SfmLibraryError("SfmBatch.run_recorded: upload() has not been called")
+        n = int(self.scene_off[-1])
+        F = n_frames(int(ticks), int(stride), None if max_frames is None else int(max_frames))
+        frames = np.zeros((F, n, 4), np.float32)
+        zframes = None if self.planar else np.zeros((F, n, 2), np.float32)
+        got = C.c_int(0)
+        self._check(self._lib.sfm_batch_run_recorded(self._b, int(ticks), self._flags(True, redraw), int(stride),
+                                                     fptr(frames) if F else None, fptr(zframes) if F and zframes is not None else None,
+                                                     F if max_frames is None else int(max_frames), C.byref(got)),
+                    "sfm_batch_run_recorded")
+        F = got.value
+        idx = np.arange(F) * int(stride)
+        return (split_frames(frames[:F], self.scene_off), idx,
+                None if zframes is None else split_frames(zframes[:F], self.scene_off))
+
+    def waypoints(self):
+        """Per scene (waypoint (N_b,2) float32, draw counter (N_b,) uint32), in scene order."""
+        if self.scene_off is None:
+            raise SfmLibraryError("SfmBatch.waypoints: upload() has not been called")
+        n = int(self.scene_off[-1])
+        wx, wy = np.zeros(n, np.float32), np.zeros(n, np.float32)
+        draws = np.zeros(n, np.uint32)
+        self._check(self._lib.sfm_batch_download_waypoints(self._b, fptr(wx), fptr(wy), draws.ctypes.data),
+                    "sfm_batch_download_waypoints")
+        wp = np.stack([wx, wy], axis=1)
+        so = self.scene_off
+        return [(wp[so[b]:so[b + 1]], draws[so[b]:so[b + 1]]) for b in range(self.B)]
 
     def state_arrays(self):
         """Concatenated state: (loc (N_total,3), vel (N_total,3)) float64."""

@@ -12,12 +12,16 @@
 //      antisymmetric F_ji = -F_ij trick does not pay for its reduction).  N_b <= 64: the four waves take a quarter of j each, N_b <= 128:
 //      a half; their partial sums meet in LDS in slice order.  Larger scenes: one slice, rows dealt to the 256 lanes in passes;
 //   3. geometry: each lane scans its scene's polylines (lane_nearest, a polyline at a time for the whole wave);
-//   4. epilogue: the forces in the reference's dict order, cap, integrate, store.
+//   4. epilogue: the forces in the reference's dict order, cap, integrate, store; with SFM_TICK_REDRAW_WAYPOINTS the arrival test on the
+//      pre-move position and the next waypoint of the scene's counter-based stream (taking effect next tick).
+// A recording tick (frame != null) also stores the pre-tick state of every row while the scene is staged (frame f of a recorded run
+// is the state before tick f*stride).  Redraw and recording are the EXT instantiations; the plain tick is compiled without them.
 // Planar bodies (moussaid_planar / moussaid_spatial) with the exact body (moussaid<.., EXACT>) recomputing a slice whose sum came out
 // NaN (coincident pair, or two pedestrians above one another in 3-D), as the handle's kernels do.
 // Determinism: no atomics, every order is a function of the scene alone (N_b, its rows, its polylines) -- a scene's result is
 // bitwise the same whatever else is in the batch and wherever it sits.  The state is updated in place: a scene's rows are read
-// (into LDS) and written by its own workgroup only, and every read comes before the barrier that precedes the first store.
+// (into LDS) and written by its own workgroup only, and every read comes before the barrier that precedes the first store; a row's
+// waypoint and draw counter are read and rewritten by the lane that owns the row.
 #include "sfm_device.h"
 #include "sfm_interaction.h"
 
@@ -119,7 +123,7 @@ __device__ __forceinline__ void batch_geometry(const BatchArgs& a, const BatchPa
     }
 }
 
-template <bool Z3, bool RAD>
+template <bool Z3, bool RAD, bool EXT>
 __device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParams& p, BatchShared<Z3>& sh, int b, int s0, int n) {
     const int tid = threadIdx.x;
     const int lane = tid & (WAVE - 1);
@@ -185,6 +189,18 @@ __device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParam
         sp = (sp == 0.0f) ? 1.0f : sp;
         const float fac = fminf(1.0f, (ts * p.max_speed_factor) / sp);
         nvx *= fac; nvy *= fac; nvz *= fac;
+        // arrival on the pre-move position against this tick's waypoint -> next draw of the scene's stream, keyed by the
+        // scene-local index (pedestrian_simulation.py:92-95, run_simulation.py:118-126; the handle's fused tick)
+        if (EXT && (a.flags & 2u)) {
+            const BatchStream st = a.streams[b];
+            const float ax_ = o.x - x, ay_ = o.y - y;
+            if (fmaf(ax_, ax_, ay_ * ay_) < st.arrive_thr2) {
+                const uint32_t nd = a.draws[s0 + i] + 1u;
+                a.own[s0 + i] = make_float4(waypoint_coord(st.seed, (uint32_t)i, nd, 0u, st.world_side),
+                                            waypoint_coord(st.seed, (uint32_t)i, nd, 1u, st.world_side), o.z, o.w);
+                a.draws[s0 + i] = nd;
+            }
+        }
         float nx = x, ny = y, nz = z;
         if (a.flags & 1u) { nx = fmaf(p.dt, nvx, x); ny = fmaf(p.dt, nvy, y); nz = fmaf(p.dt, nvz, z); }
         a.pk[s0 + i] = make_float4(nx, ny, nvx, nvy);
@@ -192,7 +208,7 @@ __device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParam
     }
 }
 
-template <bool Z3>
+template <bool Z3, bool EXT>
 __global__ __launch_bounds__(BLOCK) void sfm_batch_tick_kernel(const BatchArgs a) {
     __shared__ BatchShared<Z3> sh;
     const int b = blockIdx.x;
@@ -200,18 +216,30 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_tick_kernel(const BatchArgs a
     if (n <= 0) return;
     const BatchParams& p = a.prm[b];                                    // (read through the pointer: uniform scalar loads)
     for (int t = threadIdx.x; t < n; t += BLOCK) {
-        sh.pk[t] = a.pk[s0 + t];
-        if (Z3) sh.zv[t] = a.zv[s0 + t];
+        const float4 q = a.pk[s0 + t];
+        sh.pk[t] = q;
+        if (EXT && a.frame) a.frame[s0 + t] = q;                        // recording tick: the pre-tick state, coalesced
+        if (Z3) {
+            const float2 zq = a.zv[s0 + t];
+            sh.zv[t] = zq;
+            if (EXT && a.zframe) a.zframe[s0 + t] = zq;
+        }
         sh.r[t] = a.own[s0 + t].w;
     }
     __syncthreads();
-    if (p.rad) batch_scene<Z3, true>(a, p, sh, b, s0, n);
-    else batch_scene<Z3, false>(a, p, sh, b, s0, n);
+    if (p.rad) batch_scene<Z3, true, EXT>(a, p, sh, b, s0, n);
+    else batch_scene<Z3, false, EXT>(a, p, sh, b, s0, n);
 }
 
-hipError_t launch_batch_tick(bool z3, const BatchArgs& a, int B, hipStream_t st) {
-    if (z3) hipLaunchKernelGGL(sfm_batch_tick_kernel<true>, dim3(B), dim3(BLOCK), 0, st, a);
-    else hipLaunchKernelGGL(sfm_batch_tick_kernel<false>, dim3(B), dim3(BLOCK), 0, st, a);
+// ext: the tick redraws waypoints or records a frame (a.flags & 2, a.frame); otherwise the plain kernel
+hipError_t launch_batch_tick(bool z3, bool ext, const BatchArgs& a, int B, hipStream_t st) {
+    if (z3) {
+        if (ext) hipLaunchKernelGGL((sfm_batch_tick_kernel<true, true>), dim3(B), dim3(BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((sfm_batch_tick_kernel<true, false>), dim3(B), dim3(BLOCK), 0, st, a);
+    } else {
+        if (ext) hipLaunchKernelGGL((sfm_batch_tick_kernel<false, true>), dim3(B), dim3(BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((sfm_batch_tick_kernel<false, false>), dim3(B), dim3(BLOCK), 0, st, a);
+    }
     return hipGetLastError();
 }
 

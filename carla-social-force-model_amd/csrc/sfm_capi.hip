@@ -45,7 +45,7 @@ hipError_t launch_gather(const uint32_t* src, int N, const float4* pk_in, float4
 hipError_t launch_tile_bounds(const float4* pk, const float2* zv, int N, float4* box, float* vmax, hipStream_t st, int t_lo = 0,
                               int t_hi = -1);
 int probe_dpp_direction(hipStream_t st);
-hipError_t launch_batch_tick(bool z3, const BatchArgs& a, int B, hipStream_t st);
+hipError_t launch_batch_tick(bool z3, bool ext, const BatchArgs& a, int B, hipStream_t st);
 hipError_t launch_dynamic_boxes(float4* ctr, const int* off, const float2* local, const float2* rot, float2* pts, int M,
                                 float dt, int advance, hipStream_t st);
 }  // namespace sfm
@@ -2027,8 +2027,14 @@ struct SfmBatch {
     float2* zv = nullptr;              // {z, vz}
     float4* own = nullptr;             // {wx, wy, target_speed, radius}
     uint8_t* crossing = nullptr;
+    uint32_t* draws = nullptr;         // waypoint draw counters (zeroed by every upload)
     bool any_rad = false;
     BatchGeoDev geo[3];                // borders, static, dynamic obstacles
+    BatchStream* d_streams = nullptr;  // [B] once sfm_batch_set_waypoint_streams has been called
+    float4* frames = nullptr;          // sfm_batch_run_recorded: grow-only device frame buffers
+    size_t frames_cap = 0;
+    float2* zframes = nullptr;
+    size_t zframes_cap = 0;
     std::string err;
 };
 
@@ -2131,7 +2137,17 @@ static int check_batch_geo(SfmBatch* b, const int32_t* scene_item_off, const int
     return SFM_OK;
 }
 
-static int batch_launch(SfmBatch* b, uint32_t flags) {
+// flags a batch tick takes: SFM_TICK_INTEGRATE, and SFM_TICK_REDRAW_WAYPOINTS once the streams are set
+static int check_batch_flags(SfmBatch* b, uint32_t flags, const char* what) {
+    const uint32_t ok = SFM_TICK_INTEGRATE | (b->d_streams ? (uint32_t)SFM_TICK_REDRAW_WAYPOINTS : 0u);
+    if (flags & ~ok)
+        return bfail(b, SFM_ERR_INVALID, std::string("a batch ") + what + " takes SFM_TICK_INTEGRATE only, and "
+                                         "SFM_TICK_REDRAW_WAYPOINTS once sfm_batch_set_waypoint_streams has been called");
+    return SFM_OK;
+}
+
+// one tick of the whole batch; frame / zframe: this tick's frame slot of a recorded run (null: not recorded)
+static int batch_launch(SfmBatch* b, uint32_t flags, float4* frame = nullptr, float2* zframe = nullptr) {
     BatchArgs a;
     memset(&a, 0, sizeof(a));
     a.scene_off = b->d_scene_off;
@@ -2142,7 +2158,12 @@ static int batch_launch(SfmBatch* b, uint32_t flags) {
     a.crossing = b->crossing;
     for (int k = 0; k < 3; ++k) a.geo[k] = BatchGeo{b->geo[k].item_off, b->geo[k].off, b->geo[k].pts, b->geo[k].ctr};
     a.flags = flags;
-    HIP_TRY(b, launch_batch_tick(b->z3, a, b->B, b->stream));
+    a.streams = b->d_streams;
+    a.draws = b->draws;
+    a.frame = frame;
+    a.zframe = b->z3 ? zframe : nullptr;
+    const bool ext = (flags & SFM_TICK_REDRAW_WAYPOINTS) || frame;
+    HIP_TRY(b, launch_batch_tick(b->z3, ext, a, b->B, b->stream));
     return SFM_OK;
 }
 
@@ -2195,6 +2216,10 @@ int sfm_batch_destroy(SfmBatch* b) {
     if (b->zv) hipFree(b->zv);
     if (b->own) hipFree(b->own);
     if (b->crossing) hipFree(b->crossing);
+    if (b->draws) hipFree(b->draws);
+    if (b->d_streams) hipFree(b->d_streams);
+    if (b->frames) hipFree(b->frames);
+    if (b->zframes) hipFree(b->zframes);
     delete b;
     return SFM_OK;
 }
@@ -2241,6 +2266,7 @@ int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x
         HIP_TRY(b, dev_realloc(b->zv, n));
         HIP_TRY(b, dev_realloc(b->own, n));
         HIP_TRY(b, dev_realloc(b->crossing, n));
+        HIP_TRY(b, dev_realloc(b->draws, n));
         b->cap = n;
     }
     b->have_state = false;
@@ -2258,6 +2284,7 @@ int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x
         HIP_TRY(b, hipMemcpy(b->zv, zv.data(), sizeof(float2) * n, hipMemcpyHostToDevice));
         HIP_TRY(b, hipMemcpy(b->own, own.data(), sizeof(float4) * n, hipMemcpyHostToDevice));
         HIP_TRY(b, hipMemcpy(b->crossing, cm.data(), n, hipMemcpyHostToDevice));
+        HIP_TRY(b, hipMemset(b->draws, 0, sizeof(uint32_t) * n));
     }
     HIP_TRY(b, hipMemcpy(b->d_scene_off, scene_off, sizeof(int) * ((size_t)b->B + 1), hipMemcpyHostToDevice));
     b->n_total = N;
@@ -2308,7 +2335,8 @@ int sfm_batch_set_dynamic_obstacles(SfmBatch* b, const int32_t* scene_item_off, 
 int sfm_batch_tick(SfmBatch* b, uint32_t flags) {
     int rc = bbind(b);
     if (rc) return rc;
-    if (flags & ~(uint32_t)SFM_TICK_INTEGRATE) return bfail(b, SFM_ERR_INVALID, "a batch tick takes SFM_TICK_INTEGRATE only");
+    rc = check_batch_flags(b, flags, "tick");
+    if (rc) return rc;
     if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
     return batch_launch(b, flags);
 }
@@ -2317,10 +2345,11 @@ int sfm_batch_run(SfmBatch* b, int ticks, uint32_t flags) {
     int rc = bbind(b);
     if (rc) return rc;
     if (ticks < 0) return bfail(b, SFM_ERR_INVALID, "ticks < 0");
-    if (flags & ~(uint32_t)SFM_TICK_INTEGRATE) return bfail(b, SFM_ERR_INVALID, "a batch run takes SFM_TICK_INTEGRATE only");
+    rc = check_batch_flags(b, flags, "run");
+    if (rc) return rc;
     if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
     for (int t = 0; t < ticks; ++t) {
-        rc = batch_launch(b, SFM_TICK_INTEGRATE);
+        rc = batch_launch(b, flags | SFM_TICK_INTEGRATE);
         if (rc) return rc;
     }
     return SFM_OK;
@@ -2352,6 +2381,89 @@ int sfm_batch_download_state(SfmBatch* b, float* x, float* y, float* z, float* v
             vz[i] = 0.f;
         }
     }
+    return SFM_OK;
+}
+
+int sfm_batch_set_waypoint_streams(SfmBatch* b, const uint32_t* seed, const float* world_side, const float* arrive_threshold) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!seed || !world_side || !arrive_threshold) return bfail(b, SFM_ERR_INVALID, "a waypoint stream array is NULL");
+    std::vector<BatchStream> q((size_t)b->B);
+    for (int k = 0; k < b->B; ++k) {
+        const float side = world_side[k], thr = arrive_threshold[k];
+        if (!std::isfinite(side) || side < 0.f || !std::isfinite(thr) || thr < 0.f)
+            return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(k) + ": world_side and arrive_threshold must be finite and >= 0");
+        q[k] = BatchStream{seed[k], side, (float)((double)thr * (double)thr), 0.f};   // thr^2 as the handle rounds it
+    }
+    HIP_TRY(b, hipStreamSynchronize(b->stream));                 // a tick in flight may still read the table
+    if (!b->d_streams) {
+        BatchStream* p = nullptr;
+        HIP_TRY(b, dev_realloc(p, (size_t)b->B));
+        HIP_TRY(b, hipMemcpy(p, q.data(), sizeof(BatchStream) * (size_t)b->B, hipMemcpyHostToDevice));
+        b->d_streams = p;
+    } else {
+        HIP_TRY(b, hipMemcpy(b->d_streams, q.data(), sizeof(BatchStream) * (size_t)b->B, hipMemcpyHostToDevice));
+    }
+    return SFM_OK;
+}
+
+int sfm_batch_download_waypoints(SfmBatch* b, float* wx, float* wy, uint32_t* draws) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    const size_t n = (size_t)b->n_total;
+    if (n == 0) return SFM_OK;
+    if (wx || wy) {
+        std::vector<float4> own(n);
+        HIP_TRY(b, hipMemcpy(own.data(), b->own, sizeof(float4) * n, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) {
+            if (wx) wx[i] = own[i].x;
+            if (wy) wy[i] = own[i].y;
+        }
+    }
+    if (draws) HIP_TRY(b, hipMemcpy(draws, b->draws, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    return SFM_OK;
+}
+
+int sfm_batch_run_recorded(SfmBatch* b, int ticks, uint32_t flags, int stride, float* frames, float* zframes, int max_frames,
+                           int* n_frames) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (ticks < 0 || stride <= 0 || max_frames < 0) return bfail(b, SFM_ERR_INVALID, "ticks < 0, stride <= 0 or max_frames < 0");
+    if (!n_frames) return bfail(b, SFM_ERR_INVALID, "n_frames is NULL");
+    *n_frames = 0;
+    rc = check_batch_flags(b, flags, "recorded run");
+    if (rc) return rc;
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    if (zframes && !b->z3) return bfail(b, SFM_ERR_INVALID, "zframes on a planar batch (it has no z / vz to record)");
+    const int F = (int)std::min<long long>(max_frames, ((long long)ticks + stride - 1) / stride);
+    if (F > 0 && !frames) return bfail(b, SFM_ERR_INVALID, "frames is NULL");
+    const size_t n = (size_t)b->n_total;
+    const size_t recs = n * (size_t)F;
+    const size_t bytes = recs * (sizeof(float4) + (zframes ? sizeof(float2) : 0));
+    if (bytes > SFM_BATCH_MAX_RECORD_BYTES)
+        return bfail(b, SFM_ERR_INVALID, "the frames of this call need " + std::to_string(bytes) + " bytes, more than the " +
+                                         std::to_string((unsigned long long)SFM_BATCH_MAX_RECORD_BYTES) +
+                                         " one call may record: split the run into several sfm_batch_run_recorded calls");
+    if (recs > 0) {
+        HIP_TRY(b, hipStreamSynchronize(b->stream));             // a tick in flight may still write the old buffers
+        HIP_TRY(b, dev_reserve(b->frames, b->frames_cap, recs));
+        if (zframes) HIP_TRY(b, dev_reserve(b->zframes, b->zframes_cap, recs));
+    }
+    for (int t = 0, f = 0; t < ticks; ++t) {
+        const bool rec = t % stride == 0 && f < F && recs > 0;
+        rc = batch_launch(b, flags | SFM_TICK_INTEGRATE, rec ? b->frames + n * (size_t)f : nullptr,
+                          rec && zframes ? b->zframes + n * (size_t)f : nullptr);
+        if (rc) return rc;
+        if (t % stride == 0) ++f;
+    }
+    if (recs > 0) {
+        HIP_TRY(b, hipMemcpyAsync(frames, b->frames, sizeof(float4) * recs, hipMemcpyDeviceToHost, b->stream));
+        if (zframes) HIP_TRY(b, hipMemcpyAsync(zframes, b->zframes, sizeof(float2) * recs, hipMemcpyDeviceToHost, b->stream));
+    }
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    *n_frames = F;
     return SFM_OK;
 }
 

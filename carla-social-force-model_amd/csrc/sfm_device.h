@@ -26,6 +26,17 @@ struct IxConst {
     float pad;
 };
 
+// Counter-based waypoint stream (SFM_TICK_REDRAW_WAYPOINTS): coordinate c of draw `draw` of pedestrian `ped` is
+// side * (mix32(seed ^ mix32(2 ped + c + 0x9E3779B9 draw)) >> 8) * 2^-24.  Shared by the handle's kernels and the batch kernel.
+__device__ __forceinline__ uint32_t mix32(uint32_t a) {   // lowbias32
+    a ^= a >> 16; a *= 0x7FEB352Du; a ^= a >> 15; a *= 0x846CA68Bu; a ^= a >> 16;
+    return a;
+}
+__device__ __forceinline__ float waypoint_coord(uint32_t seed, uint32_t ped, uint32_t draw, uint32_t c, float side) {
+    const uint32_t h = mix32(seed ^ mix32(2u * ped + c + 0x9E3779B9u * draw));
+    return (float)(h >> 8) * 5.9604644775390625e-08f * side;   // 2^-24
+}
+
 struct Geo {                  // CSR polylines / rings
     const int* off;           // [K+1]
     const float2* pts;        // [P] {x, y}
@@ -203,15 +214,25 @@ struct BatchGeo {             // per-scene CSR polylines: scene b owns polylines
     const float2* pts;        // [P]
     const float4* ctr;        // [K] borders: {cx, cy, section_length^2, 0}; obstacles: {cx, cy, vx, vy}
 };
+struct BatchStream {          // one scene's waypoint stream (sfm_batch_set_waypoint_streams)
+    uint32_t seed;
+    float world_side;
+    float arrive_thr2;        // arrival threshold^2, rounded once from double like the handle's
+    float pad;
+};
 struct BatchArgs {
     const int* scene_off;     // [B+1]
     const BatchParams* prm;   // [B]
     float4* pk;               // {x, y, vx, vy}, updated in place (a scene is read and written by its own workgroup only)
     float2* zv;               // {z, vz}: 3-D batches only
-    const float4* own;        // {wx, wy, target_speed, radius}
+    float4* own;              // {wx, wy, target_speed, radius}; wx / wy rewritten on a redraw
     const uint8_t* crossing;  // border-force mask
     BatchGeo geo[3];          // borders, static obstacles, dynamic obstacles
-    uint32_t flags;           // SFM_TICK_INTEGRATE only
+    uint32_t flags;           // SFM_TICK_INTEGRATE (1), SFM_TICK_REDRAW_WAYPOINTS (2: needs streams)
+    const BatchStream* streams;   // [B], null until the caller sets them
+    uint32_t* draws;          // [N_total] waypoint draw counters
+    float4* frame;            // recording tick: the pre-tick {x, y, vx, vy} of every row go here (frame slot of this tick); null: off
+    float2* zframe;           // ... and {z, vz} of a 3-D batch (null: off)
 };
 
 // Block-major packing for sharded runs (sfm_set_partition, sfm_reorder.hip): the row order is cut into gx columns by x, each

@@ -265,15 +265,6 @@ __device__ __forceinline__ bool tiles_negligible(const float4 ba, const float va
     return fmaf(gx, gx, gy * gy) > reach * reach;
 }
 
-__device__ __forceinline__ uint32_t mix32(uint32_t a) {   // lowbias32
-    a ^= a >> 16; a *= 0x7FEB352Du; a ^= a >> 15; a *= 0x846CA68Bu; a ^= a >> 16;
-    return a;
-}
-__device__ __forceinline__ float waypoint_coord(uint32_t seed, uint32_t ped, uint32_t draw, uint32_t c, float side) {
-    const uint32_t h = mix32(seed ^ mix32(2u * ped + c + 0x9E3779B9u * draw));
-    return (float)(h >> 8) * 5.9604644775390625e-08f * side;   // 2^-24
-}
-
 // ------------------------------------------------------------------------------------------------------
 // geometry forces: border + static + dynamic obstacles, one workgroup per tile of 64 pedestrians
 // ------------------------------------------------------------------------------------------------------

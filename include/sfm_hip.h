@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SFM_ABI_VERSION 6   /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_* (additions only) */
+#define SFM_ABI_VERSION 7   /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded (additions only) */
 
 typedef struct SfmHandle SfmHandle;
 
@@ -273,8 +273,8 @@ int sfm_abi_version(void);
  * process; this is B of them, pedestrian_simulation.py:57-83 per scene).  A batch holds B scenes of 0 .. SFM_BATCH_MAX_N pedestrians
  * each, every scene with its own SfmParams (a parameter sweep is one batch) and its own borders / obstacles; each tick is ONE kernel
  * launch for the whole batch (sfm_batch.hip, a workgroup per scene).  A scene's result is bitwise the same whatever else is in the
- * batch and wherever it sits.  Larger crowds belong on a handle.  Not supported on a batch: device-side vehicles, waypoint redraw,
- * the mode state machine, force records, sharding.  Host arrays are fp32 SoA over all scenes concatenated; scene b owns rows
+ * batch and wherever it sits.  Larger crowds belong on a handle.  Waypoint redraw (per-scene streams) and on-device trajectories
+ * are ABI 7.  Not supported on a batch: device-side vehicles, the mode state machine, force records, sharding.  Host arrays are fp32 SoA over all scenes concatenated; scene b owns rows
  * [scene_off[b], scene_off[b+1]).  Geometry is per-scene CSR: scene b owns polylines [scene_item_off[b], scene_item_off[b+1]) of the
  * concatenated set, whose points are offsets[k] .. offsets[k+1]-1 (offsets[0] = 0).  Errors as for a handle: a negative SfmStatus,
  * the message in sfm_batch_last_error(b) (or sfm_batch_last_error(NULL) after a failed sfm_batch_create); nothing is launched on
@@ -301,10 +301,30 @@ int sfm_batch_set_static_obstacles(SfmBatch* b, const int32_t* scene_item_off, c
 /* The vehicles as the caller last set them (vx / vy NULL: at rest); a batch does not move them. */
 int sfm_batch_set_dynamic_obstacles(SfmBatch* b, const int32_t* scene_item_off, const int32_t* offsets, const float* px,
                                     const float* py, const float* cx, const float* cy, const float* vx, const float* vy);
-/* One tick of every scene: flags 0 or SFM_TICK_INTEGRATE (anything else is an error); v' (and x') in place. */
+/* One tick of every scene: flags 0 or SFM_TICK_INTEGRATE, plus SFM_TICK_REDRAW_WAYPOINTS once sfm_batch_set_waypoint_streams has
+ * been called (anything else is an error); v' (and x') in place. */
 int sfm_batch_tick(SfmBatch* b, uint32_t flags);
-/* `ticks` integrating ticks, one launch each (SFM_TICK_INTEGRATE implied; other flags are an error). */
+/* `ticks` integrating ticks, one launch each (SFM_TICK_INTEGRATE implied; SFM_TICK_REDRAW_WAYPOINTS as for sfm_batch_tick; other
+ * flags are an error). */
 int sfm_batch_run(SfmBatch* b, int ticks, uint32_t flags);
+/* Per-scene waypoint streams (ABI 7), the batch form of sfm_set_waypoint_stream: seed[B], world_side[B], arrive_threshold[B] (finite,
+ * >= 0).  With SFM_TICK_REDRAW_WAYPOINTS a pedestrian whose pre-move position is within its scene's threshold of its waypoint
+ * (strict <) takes draw d+1 of the scene's counter-based stream, keyed by its index INSIDE the scene (a one-scene batch draws what a
+ * handle draws); the new waypoint takes effect next tick.  The streams stay in effect across sfm_batch_upload_state and
+ * sfm_batch_set_params; every sfm_batch_upload_state zeroes the draw counters. */
+int sfm_batch_set_waypoint_streams(SfmBatch* b, const uint32_t* seed, const float* world_side, const float* arrive_threshold);
+/* Current waypoints and draw counters of every scene (synchronises the batch's stream); NULL skips a column. */
+int sfm_batch_download_waypoints(SfmBatch* b, float* wx, float* wy, uint32_t* draws);
+/* sfm_batch_run that also records the trajectory of every scene (ABI 7): frame f holds {x, y, vx, vy} (frames, [F][N_total][4]) and,
+ * for a 3-D batch, {z, vz} (zframes, [F][N_total][2], or NULL) of every row in the concatenated scene order, BEFORE tick f*stride --
+ * the handle's sfm_run_recorded convention.  F = min(max_frames, ceil(ticks / stride)) is written to *n_frames; all `ticks` are run.
+ * One launch per tick: the kernel stores the frames into a device buffer of the batch, copied to the host once at the end.  flags:
+ * SFM_TICK_INTEGRATE implied, SFM_TICK_REDRAW_WAYPOINTS as for sfm_batch_run.  Refused before any launch: ticks < 0, stride <= 0,
+ * max_frames < 0, NULL frames with F > 0, NULL n_frames, zframes on a planar batch, other flags, and more than
+ * SFM_BATCH_MAX_RECORD_BYTES of frames in one call (split the run). */
+#define SFM_BATCH_MAX_RECORD_BYTES (1ull << 30)
+int sfm_batch_run_recorded(SfmBatch* b, int ticks, uint32_t flags, int stride, float* frames, float* zframes, int max_frames,
+                           int* n_frames);
 /* Current state of every scene (synchronises the batch's stream); NULL skips a column.  A planar batch leaves z alone and
  * writes vz = 0. */
 int sfm_batch_download_state(SfmBatch* b, float* x, float* y, float* z, float* vx, float* vy, float* vz);

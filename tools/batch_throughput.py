@@ -5,6 +5,12 @@ scene.  One part per call, so that tools/batch_throughput.sh can run each under 
                    with 40 border points (two borders of 20) and 4 obstacles (2 static, 2 vehicles) per scene
   --part handles   the same scenes on B separate handles stepped with run(1) in a loop, B in {64, 1024}, N_b = 64
   --part trace     B = 1024, N_b = 64, pedestrian + acceleration: a fixed number of batch ticks, for rocprofv3 --kernel-trace --stats
+  --part streams   B in {1024, 8192} scenes of 64, pedestrian + acceleration: run(K), run(K, redraw=True) (per-scene waypoint
+                   streams), run_recorded(K, stride=1) (every tick a frame, one device-to-host copy at the end, included in the
+                   time) and, for comparison, the same trajectory taken step-wise (state_arrays() + run(1) per tick), alternated
+  --part plain     the run(K) rows of `streams` only, with the library SFM_LIB_PATH names (A/B of builds: ABI 6 has no streams)
+  --part trace-recorded   B = 1024, N_b = 64: 3 warm-up ticks, then run_recorded(K, stride=1) -- for rocprofv3: K launches of the
+                   recording kernel, one per tick
 
 Times are host wall clock around K back-to-back ticks after a warm-up, closed by a device synchronisation (the work is issued on
 the null stream).  A pool of distinct scenes is generated once per shape and repeated to fill the batch.
@@ -59,6 +65,29 @@ def _time_batch(B, n, geo, ticks):
     return dt / ticks
 
 
+def _streams_batch(B, n):
+    pool = _pool(n, False)
+    b = SfmBatch(default_sfm_config(PED), 0.05, B=B)
+    b.upload_packed(pack_scenes([pool[k % POOL] for k in range(B)]))
+    return b, [pool[k % POOL]["world_side"] for k in range(B)]
+
+
+def _time_mode(b, mode, ticks):
+    """Seconds per tick of one call of `mode` (plain / redraw / recorded) after a 3-tick warm-up of the same kind."""
+    def stepwise(k):
+        for _ in range(k):
+            b.state_arrays()
+            b.run(1)
+    call = {"plain": lambda k: b.run(k), "redraw": lambda k: b.run(k, redraw=True),
+            "recorded": lambda k: b.run_recorded(k, stride=1), "stepwise": stepwise}[mode]
+    call(3)
+    _sync()
+    t0 = time.perf_counter()
+    call(ticks)
+    _sync()
+    return (time.perf_counter() - t0) / ticks
+
+
 def _time_handles(B, n, geo, ticks):
     pool = _pool(n, geo)
     cfg = default_sfm_config(scenarios.ALL_FORCES if geo else PED)
@@ -91,7 +120,8 @@ def _time_handles(B, n, geo, ticks):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=("batch", "handles", "trace"), required=True)
+    ap.add_argument("--part", choices=("batch", "handles", "trace", "streams", "plain", "trace-recorded"), required=True)
+    ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--ticks", type=int, default=50)
     args = ap.parse_args()
     if args.part == "batch":
@@ -112,6 +142,37 @@ def main():
                 tb = _time_batch(B, 64, geo, args.ticks)
                 print(f"{'all five' if geo else 'ped+acc':<10} {B:>6} {64:>5} {th * 1e6:>10.1f} {B / th:>14.3e} {tb * 1e6:>14.1f} "
                       f"{th / tb:>14.1f}x", flush=True)
+    elif args.part in ("streams", "plain"):
+        modes = ("plain", "redraw", "recorded", "stepwise") if args.part == "streams" else ("plain",)
+        lib = "the SFM_LIB_PATH build" if os.environ.get("SFM_LIB_PATH") else "the in-tree build"
+        print(f"# {args.part}: B scenes of 64, ped+acc, {args.ticks} ticks per call, modes alternated in {args.rounds} rounds; "
+              f"library: {lib}")
+        print(f"{'mode':<10} {'B':>6} {'N_b':>5} {'round':>5} {'us/tick':>10} {'scene-ticks/s':>14}")
+        for B in (1024, 8192):
+            b, sides = _streams_batch(B, 64)
+            try:
+                if "redraw" in modes:
+                    b.set_waypoint_streams(np.arange(B), sides, 2.0)
+                for r in range(args.rounds):
+                    for mode in modes:
+                        t = _time_mode(b, mode, args.ticks)
+                        print(f"{mode:<10} {B:>6} {64:>5} {r:>5} {t * 1e6:>10.1f} {B / t:>14.3e}", flush=True)
+                assert all(np.isfinite(v).all() for _, v in b.state()[:POOL])
+                if "redraw" in modes:
+                    print(f"# B = {B}: {sum(int(d.sum()) for _, d in b.waypoints())} waypoint draws in all", flush=True)
+            finally:
+                b.close()
+    elif args.part == "trace-recorded":
+        b, _ = _streams_batch(1024, 64)
+        try:
+            b.run(3)
+            frames, idx, _ = b.run_recorded(args.ticks, stride=1)
+            _sync()
+        finally:
+            b.close()
+        print(f"# trace-recorded: B = 1024, N_b = 64, ped+acc: 3 plain warm-up ticks + run_recorded({args.ticks}, stride=1) -> "
+              f"{len(idx)} frames of {frames[0].shape[1]} pedestrians per scene; expected: 3 launches of "
+              f"sfm_batch_tick_kernel<.., false> and {args.ticks} of the recording sfm_batch_tick_kernel<.., true>")
     else:
         t = _time_batch(1024, 64, False, args.ticks)
         print(f"# trace: B = 1024, N_b = 64, ped+acc: {args.ticks} timed + 3 warm-up batch ticks = {args.ticks + 3} launches "
