@@ -2,7 +2,8 @@
 //
 // Social-force models are run in bulk as many small scenes (scenario sampling, RL environments in lock-step, calibration sweeps over
 // A / lambda / gamma / tau ...).  A handle per scene costs a launch per scene per tick and leaves most of the GPU idle; here a
-// workgroup owns one scene and the whole batch is one grid.  Per scene, the tick of sfm_tick_kernel:
+// workgroup owns one scene and the whole batch is one grid.  Per scene, the handle's tick (acceleration_force, capped_velocity and
+// next_waypoint of sfm_interaction.h, IEEE forms):
 //   F_i = acceleration + pedestrian (Moussaid, N_b x N_b) + border + static + dynamic obstacle forces (each scene's own switches,
 //   parameter tables and polylines),  v' = cap(v + dt F, max_speed_factor v0),  with SFM_TICK_INTEGRATE also x' = x + dt v'.
 //
@@ -169,26 +170,16 @@ __device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParam
 
         const float4 o = a.own[s0 + i];
         const float ts = o.z;
-        // AccelerationForce (forces.py:46-53, stateutils.py:7-15)
         float fax = 0.f, fay = 0.f, faz = 0.f;
-        if (p.en_acc) {
-            const float tx_ = o.x - x, ty_ = o.y - y;
-            const float nrm = sqrtf(fmaf(tx_, tx_, ty_ * ty_));
-            const float inv = (nrm == 0.0f) ? 1.0f : 1.0f / nrm;
-            fax = (ts * (tx_ * inv) - vx) * p.inv_tau;
-            fay = (ts * (ty_ * inv) - vy) * p.inv_tau;
-            faz = (0.0f - vz) * p.inv_tau;
-        }
-        // sum in the dict order acceleration, pedestrian, border, static, dynamic (pedestrian_simulation.py:37-48,81)
+        // (the z lane even in a planar scene, where vz = 0 makes it exactly +0: <Z3, false> is shorter but measured 4% slower at 8192
+        //  scenes, profiles/r07_batch_planar_z_lane.txt)
+        if (p.en_acc) acceleration_force<true, false>(p, o.x, o.y, x, y, vx, vy, vz, ts, fax, fay, faz);
+        // sum in the dict order acceleration, pedestrian, border, static, dynamic (pedestrian_simulation.py:37-48,81), as sfm_tick_kernel
         const float Fx = (((fax + fpx) + fbx) + fsx) + fdx;
         const float Fy = (((fay + fpy) + fby) + fsy) + fdy;
         const float Fz = faz + fpz;
-        // calculate_new_velocities + cap_velocity (pedestrian_simulation.py:117-124, stateutils.py:18-23)
-        float nvx = fmaf(p.dt, Fx, vx), nvy = fmaf(p.dt, Fy, vy), nvz = fmaf(p.dt, Fz, vz);
-        float sp = sqrtf(fmaf(nvx, nvx, fmaf(nvy, nvy, nvz * nvz)));
-        sp = (sp == 0.0f) ? 1.0f : sp;
-        const float fac = fminf(1.0f, (ts * p.max_speed_factor) / sp);
-        nvx *= fac; nvy *= fac; nvz *= fac;
+        float nvx, nvy, nvz;
+        capped_velocity<true, false>(p, vx, vy, vz, Fx, Fy, Fz, ts, nvx, nvy, nvz);
         // arrival on the pre-move position against this tick's waypoint -> next draw of the scene's stream, keyed by the
         // scene-local index (pedestrian_simulation.py:92-95, run_simulation.py:118-126; the handle's fused tick)
         if (EXT && (a.flags & 2u)) {
@@ -196,8 +187,8 @@ __device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParam
             const float ax_ = o.x - x, ay_ = o.y - y;
             if (fmaf(ax_, ax_, ay_ * ay_) < st.arrive_thr2) {
                 const uint32_t nd = a.draws[s0 + i] + 1u;
-                a.own[s0 + i] = make_float4(waypoint_coord(st.seed, (uint32_t)i, nd, 0u, st.world_side),
-                                            waypoint_coord(st.seed, (uint32_t)i, nd, 1u, st.world_side), o.z, o.w);
+                const float2 w = next_waypoint(st.seed, (uint32_t)i, nd, st.world_side);
+                a.own[s0 + i] = make_float4(w.x, w.y, o.z, o.w);
                 a.draws[s0 + i] = nd;
             }
         }

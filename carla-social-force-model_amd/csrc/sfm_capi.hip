@@ -712,7 +712,7 @@ int sfm_upload_state(SfmHandle* h, int N, const float* x, const float* y, const 
     uint8_t* cm = reinterpret_cast<uint8_t*>(h->up_stage + b_cm);
     // padding rows are ghost pedestrians parked far away at distinct positions: every interaction with them
     // underflows to exactly 0 (exp2 of ~ -1e16), so the symmetric kernel needs no masking
-    for (int i = N; i < n_pad; ++i) pk[i] = make_float4(3.0e15f + 1.0e12f * (float)(i - N + 1), 3.0e15f, 0.f, 0.f);
+    for (int i = N; i < n_pad; ++i) pk[i] = make_float4(FAR_AWAY + FAR_STEP * (float)(i - N + 1), FAR_AWAY, 0.f, 0.f);
     // spatial order (sfm_reorder.hip): sort by x, cut into strips of strip_rows rows, sort each strip by y, so every
     // 64-row tile is the content of one axis-aligned rectangle.  Stable sorts on order-preserving integer keys: the
     // order is a pure function of the uploaded state, identical on every rank.
@@ -724,7 +724,7 @@ int sfm_upload_state(SfmHandle* h, int N, const float* x, const float* y, const 
         // strips: about sqrt(#tiles) of them, corrected for the aspect of the crowd's extent so that tiles come out square
         float x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
         for (int i = 0; i < N; ++i) {
-            if (std::fabs(x[i]) < 1.0e12f && std::fabs(y[i]) < 1.0e12f) {
+            if (std::fabs(x[i]) < NEAR_LIMIT && std::fabs(y[i]) < NEAR_LIMIT) {
                 x0 = std::fmin(x0, x[i]); x1 = std::fmax(x1, x[i]); y0 = std::fmin(y0, y[i]); y1 = std::fmax(y1, y[i]);
             }
         }

@@ -13,6 +13,14 @@ constexpr int TILE_J = BLOCK;         // j-records staged per LDS tile (one floa
 constexpr float TINY = 1e-30f;        // added under every rsq: zero vectors normalise to zero without a guard op
 constexpr float COINCIDENT_RINV = 1e14f;  // rsq(d2) above this <=> a coincident (or < 1e-14 m) valid pair
 
+// "Far away": padding rows and despawned pedestrians are ghosts parked near x = FAR_AWAY, FAR_STEP apart (distinct positions), and
+// an empty polyline's nearest point is (FAR_AWAY, FAR_AWAY); every interaction with them underflows to exactly 0.  A row counts in
+// a tile box while |x| < BOX_LIMIT, in the geometry kernel's tile box and the host's crowd extent while |x|, |y| < NEAR_LIMIT.
+constexpr float FAR_AWAY = 3.0e15f;
+constexpr float FAR_STEP = 1.0e12f;
+constexpr float BOX_LIMIT = 1.0e14f;
+constexpr float NEAR_LIMIT = 1.0e12f;
+
 // Moussaid interaction constants, folded on the host in double and rounded once
 // (forces.py:85-109 for pedestrians, :241-264 for obstacles).
 struct IxConst {

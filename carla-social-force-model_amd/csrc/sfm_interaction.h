@@ -14,6 +14,70 @@ __device__ __forceinline__ float uniform(float v) {
 }
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// ---- the per-pedestrian tick update, shared by the tick kernels of sfm_kernels.hip and sfm_batch.hip ---------------------------
+// RSQ picks how 1 / |.| is taken: false -- IEEE sqrt and divide (sfm_tick_kernel, sfm_sym_epilogue_kernel, the batch kernel); true --
+// v_rsq_f32, 1 ulp (the fused tick only: ~35 instructions less in front of every workgroup's first systolic step; the zero vector
+// still normalises to zero, stateutils.py:85-92, and a pedestrian at rest with target speed 0 still stays at rest,
+// stateutils.py:20-23).  Z3: a 3-D crowd; Z3 = false leaves out the z lane (faz = nvz = 0).  sfm_tick_kernel and the batch kernel
+// pass Z3 = true for planar crowds too (vz = 0 makes that lane exactly +0): see there why.
+
+// AccelerationForce (forces.py:46-53, stateutils.py:7-15): (ts * unit(w - x) - v) / tau; the desired direction has no z
+// (stateutils.py:12-13)
+// (P: TickArgs or BatchParams, read where the value is used -- the kernels' scalar loads depend on that order)
+template <bool Z3, bool RSQ, class P>
+__device__ __forceinline__ void acceleration_force(const P& p, float wx, float wy, float x, float y, float vx, float vy, float vz, float ts,
+                                                   float& fax, float& fay, float& faz) {
+    const float tx_ = wx - x, ty_ = wy - y;
+    float inv;
+    if (RSQ) {
+        const float n2 = fmaf(tx_, tx_, ty_ * ty_);
+        inv = (n2 > 0.0f) ? rsq(n2) : 1.0f;
+    } else {
+        const float nrm = sqrtf(fmaf(tx_, tx_, ty_ * ty_));
+        inv = (nrm == 0.0f) ? 1.0f : 1.0f / nrm;
+    }
+    fax = (ts * (tx_ * inv) - vx) * p.inv_tau;
+    fay = (ts * (ty_ * inv) - vy) * p.inv_tau;
+    if (Z3) faz = (0.0f - vz) * p.inv_tau;
+}
+
+// calculate_new_velocities + cap_velocity (pedestrian_simulation.py:117-124, stateutils.py:18-23): v + dt F capped at
+// ts * max_speed_factor, on the 3-D speed in a 3-D crowd
+template <bool Z3, bool RSQ, class P>
+__device__ __forceinline__ void capped_velocity(const P& p, float vx, float vy, float vz, float Fx, float Fy, float Fz, float ts,
+                                                float& nvx, float& nvy, float& nvz) {
+    nvx = fmaf(p.dt, Fx, vx); nvy = fmaf(p.dt, Fy, vy); nvz = Z3 ? fmaf(p.dt, Fz, vz) : 0.0f;
+    const float s2 = Z3 ? fmaf(nvx, nvx, fmaf(nvy, nvy, nvz * nvz)) : fmaf(nvx, nvx, nvy * nvy);
+    float fac;
+    if (RSQ) {
+        fac = (s2 > 0.0f) ? fminf(1.0f, (ts * p.max_speed_factor) * rsq(s2)) : 0.0f;   // (speed 0: the capped velocity is 0 whatever the factor)
+    } else {
+        float sp = sqrtf(s2);
+        sp = (sp == 0.0f) ? 1.0f : sp;
+        fac = fminf(1.0f, (ts * p.max_speed_factor) / sp);
+    }
+    nvx *= fac; nvy *= fac; nvz *= fac;
+}
+
+// The next waypoint of a pedestrian's counter-based stream: draw `draw` under `key` (SFM_TICK_REDRAW_WAYPOINTS)
+__device__ __forceinline__ float2 next_waypoint(uint32_t seed, uint32_t key, uint32_t draw, float side) {
+    return make_float2(waypoint_coord(seed, key, draw, 0u, side), waypoint_coord(seed, key, draw, 1u, side));
+}
+
+// The tile-box rule (the operands of tiles_negligible): a row counts unless it is parked far away (a despawned pedestrian or
+// padding), and its speed bound is rounded up so that it stays a bound.  A tile's box and bound are the union over its rows:
+// the callers start from an empty box (+inf / -inf, 0), put in each row that counts, then tile_box_reduce over the wave.
+__device__ __forceinline__ bool in_tile_box(float x) { return fabsf(x) < BOX_LIMIT; }
+__device__ __forceinline__ float speed_bound(float s2) { return sqrtf(s2) * 1.000001f; }
+__device__ __forceinline__ void tile_box_reduce(float& x0, float& y0, float& x1, float& y1, float& v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        x0 = fminf(x0, __shfl_xor(x0, m)); y0 = fminf(y0, __shfl_xor(y0, m));
+        x1 = fmaxf(x1, __shfl_xor(x1, m)); y1 = fmaxf(y1, __shfl_xor(y1, m));
+        v = fmaxf(v, __shfl_xor(v, m));
+    }
+}
+
 // atan2(s, c) for (s, c) not both zero; minimax odd polynomial of degree 15 on [0,1]
 // (fit error 8.9e-8), octant fix-up by selects.  GUARD handles (0,0) -> 0 like np.arctan2.
 template <bool GUARD>
@@ -234,7 +298,7 @@ __device__ __forceinline__ float dist2(float x, float y, float px, float py) {
 __device__ __forceinline__ float2 lane_nearest(const float2* __restrict__ pts, int o0, int o1, float x, float y,
                                                float2* __restrict__ row, int lane) {
     float bd = __builtin_inff();
-    float2 sp = make_float2(3.0e15f, 3.0e15f);
+    float2 sp = make_float2(FAR_AWAY, FAR_AWAY);
     if (o1 <= o0) return sp;
     const int last = o1 - 1;
     float2 nxt = pts[min(o0 + lane, last)];

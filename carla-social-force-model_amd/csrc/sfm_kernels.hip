@@ -335,7 +335,7 @@ __device__ __forceinline__ void geo_item(const TickArgs& a, const GeoLane& me, c
         // the perpendicular, so np.argmin's scan over all P points (forces.py:154) collapses to the five samples around it --
         // evaluated with the same dist2, in ascending order with a strict `<` (first-minimum rule).  The samples either side of
         // the optimum are > spacing^2 farther in d^2, far above the fp32 rounding of d^2 for any pedestrian that keeps the border.
-        sp = make_float2(3.0e15f, 3.0e15f);
+        sp = make_float2(FAR_AWAY, FAR_AWAY);
         if (keep) {
             const float n_seg = it.s1.z;                                           // P - 1
             const float px = me.x - it.s0.x, py = me.y - it.s0.y;
@@ -525,7 +525,7 @@ __device__ __forceinline__ void geometry_forces(const TickArgs& a, GeoShared<GW>
     const float inf = __builtin_inff();
     me.skip = a.border_skip > 0.0f ? a.border_skip + (RAD ? fmaxf(me.r, 0.0f) : 0.0f) : inf;
     // the tile's bounding box; parked (despawned) pedestrians sit ~3e15 m away, no cull can keep them
-    const bool inbox = me.live && fabsf(me.x) < 1.0e12f && fabsf(me.y) < 1.0e12f;
+    const bool inbox = me.live && fabsf(me.x) < NEAR_LIMIT && fabsf(me.y) < NEAR_LIMIT;
     float x0 = inbox ? me.x : inf, y0 = inbox ? me.y : inf, x1 = inbox ? me.x : -inf, y1 = inbox ? me.y : -inf;
     float skip_max = me.live ? me.skip : 0.0f;
 #pragma unroll
@@ -595,7 +595,7 @@ __device__ __forceinline__ void geometry_block(const TickArgs& a, GeoShared<GW>&
     const int i = t * WAVE + lane;
     GeoLane me;
     me.live = i >= p0 && i < p1;
-    me.x = 3.0e15f; me.y = 3.0e15f; me.vx = 0.f; me.vy = 0.f; me.r = 0.f;
+    me.x = FAR_AWAY; me.y = FAR_AWAY; me.vx = 0.f; me.vy = 0.f; me.r = 0.f;
     if (me.live) {
         const float4 s = a.pk_cur[i];
         me.x = s.x; me.y = s.y; me.vx = s.z; me.vy = s.w;
@@ -638,7 +638,7 @@ __global__ __launch_bounds__(GW * WAVE, 8) void sfm_geometry_kernel(const TickAr
 // pedestrian modes, waypoint queues and gap acceptance on the device
 // ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float2 park_position(uint32_t pid) {      // where a despawned pedestrian waits: a ghost
-    return make_float2(3.0e15f + 1.0e12f * (float)(pid + 1u), -3.0e15f);
+    return make_float2(FAR_AWAY + FAR_STEP * (float)(pid + 1u), -FAR_AWAY);
 }
 
 // PedModeManager._activate_mode (ped_mode_manager.py:49-70): entry action of `m`; returns the new target speed.
@@ -1022,23 +1022,17 @@ __global__ __launch_bounds__(BLOCK) void sfm_tick_kernel(const TickArgs a) {
             }
         }
 
-        // AccelerationForce (forces.py:46-53, stateutils.py:7-15)
+        // (the z lane even in a planar crowd, where vz = 0 makes it exactly +0: with <Z3, false> here and in the cap below,
+        //  sfm_tick_kernel<8, false, false, 4> grows by 92 instructions)
         float fax = 0.f, fay = 0.f, faz = 0.f;
-        if (a.en_acc) {
-            const float tx_ = wx - x, ty_ = wy - y;
-            const float nrm = sqrtf(fmaf(tx_, tx_, ty_ * ty_));
-            const float inv = (nrm == 0.0f) ? 1.0f : 1.0f / nrm;
-            fax = (ts * (tx_ * inv) - vx) * a.inv_tau;
-            fay = (ts * (ty_ * inv) - vy) * a.inv_tau;
-            faz = (0.0f - vz) * a.inv_tau;
-        }
+        if (a.en_acc) acceleration_force<true, false>(a, wx, wy, x, y, vx, vy, vz, ts, fax, fay, faz);
         if (!a.en_ped) { fpx = 0.f; fpy = 0.f; fpz = 0.f; }
         // sum in the dict order acceleration, pedestrian, border, static, dynamic (pedestrian_simulation.py:37-48,81)
         const float Fx = (((fax + fpx) + fbx) + fsx) + fdx;
         const float Fy = (((fay + fpy) + fby) + fsy) + fdy;
         const float Fz = faz + fpz;
 
-        // calculate_new_velocities + cap_velocity (pedestrian_simulation.py:117-124, stateutils.py:18-23)
+        // capped_velocity<true, false> inline: that helper here as well adds 2 s_mov_b32 to sfm_tick_kernel<8, false, true, 4>
         float nvx = fmaf(a.dt, Fx, vx), nvy = fmaf(a.dt, Fy, vy), nvz = fmaf(a.dt, Fz, vz);
         float sp = sqrtf(fmaf(nvx, nvx, fmaf(nvy, nvy, nvz * nvz)));
         sp = (sp == 0.0f) ? 1.0f : sp;
@@ -1061,8 +1055,8 @@ __global__ __launch_bounds__(BLOCK) void sfm_tick_kernel(const TickArgs a) {
             } else if ((a.flags & 2u) && here) {
                 redraw = true;
                 nd = a.draws[i] + 1u;
-                wx = waypoint_coord(a.seed, pid, nd, 0u, a.world_side);
-                wy = waypoint_coord(a.seed, pid, nd, 1u, a.world_side);
+                const float2 w = next_waypoint(a.seed, pid, nd, a.world_side);
+                wx = w.x; wy = w.y;
             }
         }
         float nx = x, ny = y, nz = z;
@@ -1099,18 +1093,13 @@ __global__ __launch_bounds__(WAVE) void sfm_tile_bounds_kernel(const float4* __r
     float x0 = inf, y0 = inf, x1 = -inf, y1 = -inf, v = 0.0f;
     if (i < N) {
         const float4 s = pk[i];
-        if (fabsf(s.x) < 1.0e14f) {                             // despawned pedestrians are parked far away: not in the box
+        if (in_tile_box(s.x)) {
             x0 = x1 = s.x; y0 = y1 = s.y;
             const float vz = zv ? zv[i].y : 0.0f;               // 3-D crowds: |D| is a 3-component norm (forces.py:85-86), so is the speed
-            v = sqrtf(fmaf(s.z, s.z, fmaf(s.w, s.w, vz * vz))) * 1.000001f;  // rounded up: the bound must stay a bound
+            v = speed_bound(fmaf(s.z, s.z, fmaf(s.w, s.w, vz * vz)));
         }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        x0 = fminf(x0, __shfl_xor(x0, m)); y0 = fminf(y0, __shfl_xor(y0, m));
-        x1 = fmaxf(x1, __shfl_xor(x1, m)); y1 = fmaxf(y1, __shfl_xor(y1, m));
-        v = fmaxf(v, __shfl_xor(v, m));
-    }
+    tile_box_reduce(x0, y0, x1, y1, v);
     if (lane == 0) { box[t] = make_float4(x0, y0, x1, y1); vmax[t] = v; }
 }
 
@@ -1130,12 +1119,7 @@ __global__ __launch_bounds__(WAVE) void sfm_strip_bounds_kernel(const float4* __
             v = fmaxf(v, vmax[t]);
         }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        x0 = fminf(x0, __shfl_xor(x0, m)); y0 = fminf(y0, __shfl_xor(y0, m));
-        x1 = fmaxf(x1, __shfl_xor(x1, m)); y1 = fmaxf(y1, __shfl_xor(y1, m));
-        v = fmaxf(v, __shfl_xor(v, m));
-    }
+    tile_box_reduce(x0, y0, x1, y1, v);
     if (lane == 0) { sbox[s] = make_float4(x0, y0, x1, y1); svmax[s] = v; }
 }
 
@@ -1158,7 +1142,7 @@ __global__ __launch_bounds__(TSB_WAVES * WAVE) void sfm_tile_strip_bounds_kernel
 #pragma unroll
     for (int u = 0; u < TSB_AHEAD; ++u) {
         const int t = s * tps + q0 + u * TSB_WAVES, i = t * WAVE + lane;
-        pre[u] = (q0 + u * TSB_WAVES < tps && t < n_t && i < N) ? pk[i] : make_float4(3.0e15f, 0.f, 0.f, 0.f);
+        pre[u] = (q0 + u * TSB_WAVES < tps && t < n_t && i < N) ? pk[i] : make_float4(FAR_AWAY, 0.f, 0.f, 0.f);
     }
 #pragma unroll
     for (int u = 0; u < TSB_AHEAD; ++u) {
@@ -1168,17 +1152,12 @@ __global__ __launch_bounds__(TSB_WAVES * WAVE) void sfm_tile_strip_bounds_kernel
         float x0 = inf, y0 = inf, x1 = -inf, y1 = -inf, v = 0.0f;
         {
             const float4 p = pre[u];
-            if (fabsf(p.x) < 1.0e14f) {
+            if (in_tile_box(p.x)) {
                 x0 = x1 = p.x; y0 = y1 = p.y;
-                v = sqrtf(fmaf(p.z, p.z, p.w * p.w)) * 1.000001f;
+                v = speed_bound(fmaf(p.z, p.z, p.w * p.w));
             }
         }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            x0 = fminf(x0, __shfl_xor(x0, m)); y0 = fminf(y0, __shfl_xor(y0, m));
-            x1 = fmaxf(x1, __shfl_xor(x1, m)); y1 = fmaxf(y1, __shfl_xor(y1, m));
-            v = fmaxf(v, __shfl_xor(v, m));
-        }
+        tile_box_reduce(x0, y0, x1, y1, v);
         if (lane == 0) { box[t] = make_float4(x0, y0, x1, y1); vmax[t] = v; }
         sx0 = fminf(sx0, x0); sy0 = fminf(sy0, y0); sx1 = fmaxf(sx1, x1); sy1 = fmaxf(sy1, y1); sv = fmaxf(sv, v);
     }
@@ -1791,6 +1770,7 @@ __global__ __launch_bounds__(EW * WAVE) void sfm_sym_epilogue_kernel(const TickA
     }
 
     // 2. coincident pairs in this tile: recompute its rows with the exact ordered body (rare)
+    // (the same loop as the fused tick's bad-row pass; shared, it flipped s_cbranch_scc0 / scc1 polarity in both kernels)
     if (exact) {
         for (int p = wave; p < WAVE; p += EW) {
             const int ip = t * WAVE + p;
@@ -1839,6 +1819,7 @@ __global__ __launch_bounds__(EW * WAVE) void sfm_sym_epilogue_kernel(const TickA
     }
     const float fpx = a.en_ped ? a.ped.negA * g.x : 0.f, fpy = a.en_ped ? a.ped.negA * g.y : 0.f;
     const float fpz = (Z3 && a.en_ped) ? a.ped.negA * gz : 0.f;
+    // (the slice sum and the force record below as in sfm_tick_kernel; shared, they cost the 3-D epilogue 4 address instructions)
     float fbx = 0.f, fby = 0.f, fsx = 0.f, fsy = 0.f, fdx = 0.f, fdy = 0.f;
     if (a.geo) {
         const size_t np_ = (size_t)a.N_pad;
@@ -1852,22 +1833,13 @@ __global__ __launch_bounds__(EW * WAVE) void sfm_sym_epilogue_kernel(const TickA
     const float z = stz.x, vz = stz.y;
     float wx = o.x, wy = o.y;
     float fax = 0.f, fay = 0.f, faz = 0.f;
-    if (a.en_acc) {
-        const float tx_ = wx - x, ty_ = wy - y;
-        const float nrm = sqrtf(fmaf(tx_, tx_, ty_ * ty_));
-        const float inv = (nrm == 0.0f) ? 1.0f : 1.0f / nrm;
-        fax = (ts * (tx_ * inv) - vx) * a.inv_tau;
-        fay = (ts * (ty_ * inv) - vy) * a.inv_tau;
-        if (Z3) faz = (0.0f - vz) * a.inv_tau;                     // the desired direction has no z (stateutils.py:12-13)
-    }
+    if (a.en_acc) acceleration_force<Z3, false>(a, wx, wy, x, y, vx, vy, vz, ts, fax, fay, faz);
+    // (the force sum stays in each kernel: its association sets the bits -- this is sfm_tick_kernel's)
     const float Fx = (((fax + fpx) + fbx) + fsx) + fdx;
     const float Fy = (((fay + fpy) + fby) + fsy) + fdy;
     const float Fz = faz + fpz;
-    float nvx = fmaf(a.dt, Fx, vx), nvy = fmaf(a.dt, Fy, vy), nvz = Z3 ? fmaf(a.dt, Fz, vz) : 0.f;
-    float sp = Z3 ? sqrtf(fmaf(nvx, nvx, fmaf(nvy, nvy, nvz * nvz))) : sqrtf(fmaf(nvx, nvx, nvy * nvy));   // cap on the 3-D speed (stateutils.py:18-23)
-    sp = (sp == 0.0f) ? 1.0f : sp;
-    const float fac = fminf(1.0f, (ts * a.max_speed_factor) / sp);
-    nvx *= fac; nvy *= fac; nvz *= fac;
+    float nvx, nvy, nvz;
+    capped_velocity<Z3, false>(a, vx, vy, vz, Fx, Fy, Fz, ts, nvx, nvy, nvz);
     const uint32_t pid = live ? (a.ids ? a.ids[i] : (uint32_t)i) : 0u;
     bool despawn = false;
     const bool gone = live && a.fsm.mode && a.fsm.mode[pid] == MODE_DESPAWNED;
@@ -1880,8 +1852,8 @@ __global__ __launch_bounds__(EW * WAVE) void sfm_sym_epilogue_kernel(const TickA
             if (changed) a.own[i] = make_float4(wx, wy, o.z, o.w);
         } else if ((a.flags & 2u) && here && live) {
             const uint32_t nd = nd0 + 1u;
-            wx = waypoint_coord(a.seed, pid, nd, 0u, a.world_side);
-            wy = waypoint_coord(a.seed, pid, nd, 1u, a.world_side);
+            const float2 w = next_waypoint(a.seed, pid, nd, a.world_side);
+            wx = w.x; wy = w.y;
             a.own[i] = make_float4(wx, wy, o.z, o.w);
             a.draws[i] = nd;
         }
@@ -1894,15 +1866,10 @@ __global__ __launch_bounds__(EW * WAVE) void sfm_sym_epilogue_kernel(const TickA
     if (a.host_pk && live) { a.host_pk[i] = make_float4(nx, ny, nvx, nvy); if (Z3) a.host_zv[i] = make_float2(nz, nvz); }
     if (a.tile_box_out) {                             // whole crowd under the list cutoff: box and largest speed of the tile in the NEXT state
         const float inf = __builtin_inff();
-        const bool in_box = live && fabsf(nx) < 1.0e14f;
+        const bool in_box = live && in_tile_box(nx);
         float x0 = in_box ? nx : inf, y0 = in_box ? ny : inf, x1 = in_box ? nx : -inf, y1 = in_box ? ny : -inf;
-        float v = in_box ? sqrtf(fmaf(nvx, nvx, fmaf(nvy, nvy, nvz * nvz))) * 1.000001f : 0.0f;
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            x0 = fminf(x0, __shfl_xor(x0, m)); y0 = fminf(y0, __shfl_xor(y0, m));
-            x1 = fmaxf(x1, __shfl_xor(x1, m)); y1 = fmaxf(y1, __shfl_xor(y1, m));
-            v = fmaxf(v, __shfl_xor(v, m));
-        }
+        float v = in_box ? speed_bound(fmaf(nvx, nvx, fmaf(nvy, nvy, nvz * nvz))) : 0.0f;
+        tile_box_reduce(x0, y0, x1, y1, v);
         if (lane == 0) { a.tile_box_out[t] = make_float4(x0, y0, x1, y1); a.tile_vmax_out[t] = v; }
     }
     if (a.rec && live) {
@@ -2177,23 +2144,13 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
         const float z = stz.x, vz = stz.y;
         float wx = o.x, wy = o.y;
         float fax = 0.f, fay = 0.f, faz = 0.f;
-        // (round 4: 1 / |.| by v_rsq_f32 -- 1 ulp -- instead of IEEE sqrt + divide, ~35 instructions less in front of every
-        //  workgroup's first systolic step; the zero vector still normalises to zero, stateutils.py:85-92, and a pedestrian at rest
-        //  with target speed 0 still stays at rest, stateutils.py:20-23)
-        if (a.en_acc) {
-            const float tx_ = wx - x, ty_ = wy - y;
-            const float n2 = fmaf(tx_, tx_, ty_ * ty_);
-            const float inv = (n2 > 0.0f) ? rsq(n2) : 1.0f;
-            fax = (ts * (tx_ * inv) - vx) * a.inv_tau;
-            fay = (ts * (ty_ * inv) - vy) * a.inv_tau;
-            if (Z3) faz = (0.0f - vz) * a.inv_tau;
-        }
-        const float Fx = (fax + fpx) + geo_f.x, Fy = (fay + fpy) + geo_f.y;   // forces.py order: acceleration, pedestrian, border + obstacles
+        if (a.en_acc) acceleration_force<Z3, true>(a, wx, wy, x, y, vx, vy, vz, ts, fax, fay, faz);   // RSQ: see acceleration_force
+        // forces.py order: acceleration, pedestrian, border + obstacles -- the last already summed over the slices, so this sum has
+        // its own association (the other kernels add border, static and dynamic one by one)
+        const float Fx = (fax + fpx) + geo_f.x, Fy = (fay + fpy) + geo_f.y;
         const float Fz = faz + fpz;
-        float nvx = fmaf(a.dt, Fx, vx), nvy = fmaf(a.dt, Fy, vy), nvz = Z3 ? fmaf(a.dt, Fz, vz) : 0.f;
-        const float s2 = Z3 ? fmaf(nvx, nvx, fmaf(nvy, nvy, nvz * nvz)) : fmaf(nvx, nvx, nvy * nvy);
-        const float fac = (s2 > 0.0f) ? fminf(1.0f, (ts * a.max_speed_factor) * rsq(s2)) : 0.0f;   // (speed 0: the capped velocity is 0 whatever the factor)
-        nvx *= fac; nvy *= fac; nvz *= fac;
+        float nvx, nvy, nvz;
+        capped_velocity<Z3, true>(a, vx, vy, vz, Fx, Fy, Fz, ts, nvx, nvy, nvz);
         float nx = x, ny = y, nz = z;
         if (a.flags & 1u) { nx = fmaf(a.dt, nvx, x); ny = fmaf(a.dt, nvy, y); if (Z3) nz = fmaf(a.dt, nvz, z); }
         const float4 ns = make_float4(nx, ny, nvx, nvy);
@@ -2203,8 +2160,8 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
                 const float ax_ = wx - x, ay_ = wy - y;
                 if (fmaf(ax_, ax_, ay_ * ay_) < a.arrive_thr2) {
                     const uint32_t nd = nd0 + 1u;
-                    wx = waypoint_coord(a.seed, pid, nd, 0u, a.world_side);
-                    wy = waypoint_coord(a.seed, pid, nd, 1u, a.world_side);
+                    const float2 w = next_waypoint(a.seed, pid, nd, a.world_side);
+                    wx = w.x; wy = w.y;
                     a.draws[i] = nd;
                 }
             }
@@ -2231,7 +2188,7 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
     __syncthreads();
     if (sh.any) {
         // coincident pairs: the rows that caught a NaN are recomputed with the exact ordered body (rare; every workgroup that
-        // holds such a row does it, and they all get the same bits)
+        // holds such a row does it, and they all get the same bits) -- the loop of sfm_sym_epilogue_kernel's step 2, see there
         const int N = a.N;
         for (int q = wave; q < 2 * GROUP; q += NW) {
             if (!sh.badrow[q]) continue;                                  // uniform
@@ -2271,7 +2228,7 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
         const float4 sg = sh.st[(geo_tile & 1) * WAVE + lane];
         GeoLane me;
         me.live = ig < a.N;
-        me.x = 3.0e15f; me.y = 3.0e15f; me.vx = 0.f; me.vy = 0.f; me.r = 0.f;
+        me.x = FAR_AWAY; me.y = FAR_AWAY; me.vx = 0.f; me.vy = 0.f; me.r = 0.f;
         if (me.live) { me.x = sg.x; me.y = sg.y; me.vx = sg.z; me.vy = sg.w; me.r = f.own_cur[ig].w; }
         me.walk = me.live && !(a.crossing && a.crossing[ig]);          // forces.py:140-141,176-177
         __syncthreads();                                               // the geometry body's LDS lies over the prologue's
