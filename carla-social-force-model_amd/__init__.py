@@ -9,7 +9,7 @@ __version__ = "0.1.0"
 
 def __getattr__(name):
     # batched scenes (batch.py), imported on first use so that importing the package stays light
-    if name in ("SfmBatch", "pack_scenes", "split_frames"):
+    if name in ("SfmBatch", "pack_scenes", "pack_boxes", "split_frames"):
         from . import batch
         return getattr(batch, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

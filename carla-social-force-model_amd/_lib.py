@@ -14,13 +14,14 @@ import numpy as np
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFM_LIB_PATH") or os.path.join(PKG_DIR, "libsfm_hip.so")   # (the override is for A/B builds of the kernels)
-ABI_VERSION = 7
+ABI_VERSION = 8
 SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_records": 5,
          **{n: 6 for n in ("sfm_batch_create", "sfm_batch_destroy", "sfm_batch_set_stream", "sfm_batch_set_params",
                            "sfm_batch_upload_state", "sfm_batch_set_borders", "sfm_batch_set_static_obstacles",
                            "sfm_batch_set_dynamic_obstacles", "sfm_batch_tick", "sfm_batch_run", "sfm_batch_download_state",
                            "sfm_batch_last_error")},
-         **{n: 7 for n in ("sfm_batch_set_waypoint_streams", "sfm_batch_download_waypoints", "sfm_batch_run_recorded")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
+         **{n: 7 for n in ("sfm_batch_set_waypoint_streams", "sfm_batch_download_waypoints", "sfm_batch_run_recorded")},
+         **{n: 8 for n in ("sfm_batch_set_dynamic_boxes", "sfm_batch_download_dynamic_obstacles")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
 
 FORCE_NAMES = ("acceleration_force", "pedestrian_force", "border_force",
                "static_obstacle_force", "dynamic_obstacle_force")
@@ -110,6 +111,9 @@ SYMBOLS = {
     "sfm_batch_set_waypoint_streams": (C.c_int, [_H, _U32, _F, _F]),
     "sfm_batch_download_waypoints": (C.c_int, [_H, _F, _F, _U32]),
     "sfm_batch_run_recorded": (C.c_int, [_H, C.c_int, C.c_uint32, C.c_int, _F, _F, C.c_int, C.POINTER(C.c_int)]),
+    # batch device-side vehicles (ABI 8)
+    "sfm_batch_set_dynamic_boxes": (C.c_int, [_H, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F]),
+    "sfm_batch_download_dynamic_obstacles": (C.c_int, [_H, _F, _F, _F, _F]),
 }
 
 _lib = None

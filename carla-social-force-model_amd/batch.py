@@ -16,6 +16,11 @@ Missing geometry keys mean none.  ``vars(scenarios.make_scenario(...))`` is such
 Rollouts longer than one crossing of a scene use per-scene waypoint streams (``set_waypoint_streams`` + ``redraw=True``: on arrival
 a pedestrian takes the next waypoint of its scene's counter-based stream, as a handle does), and ``run_recorded`` returns the
 trajectory of every scene from one launch per tick and one device-to-host copy.
+
+Traffic moves on the device (``set_dynamic_boxes`` or ``upload(..., device_vehicles=True)``, ABI 8): each vehicle is given once as
+an oriented box (the scene keys ``dynamic_obstacles`` centres, ``dynamic_yaw``, ``dynamic_extent``, ``dynamic_vel``), and every
+integrating tick of a scene moves its centres by that scene's step_length * v and regenerates the rings inside the tick's one launch,
+as a handle's ``set_dynamic_boxes`` does.  ``dynamic_obstacles()`` reads them back.
 """
 from __future__ import annotations
 
@@ -156,6 +161,44 @@ def pack_scenes(scenes):
     }
 
 
+def pack_boxes(scenes, resolution=0.1):
+    """Scenes (list of dicts) -> the arguments of sfm_batch_set_dynamic_boxes: (scene_item_off int32 [B+1], offsets int32 [M+1],
+    ux, uy float32 [P], cx, cy, yaw_cos, yaw_sin, vx, vy float32 [M]), concatenated in scene order.  Per scene exactly what
+    ``SfmEngine.set_dynamic_boxes`` passes for it: ring-local offsets from ``scenarios.ring_local_offsets(ex, ey, resolution)``, fp32
+    cos / sin of the float64 yaw.  Uses the centres of ``dynamic_obstacles`` (their rings are ignored), ``dynamic_yaw`` (M,),
+    ``dynamic_extent`` (M,2) half-extents and ``dynamic_vel`` (M,2) or None (at rest).  Pure NumPy; raises ValueError on count
+    mismatches."""
+    from .scenarios import ring_local_offsets
+    scenes = list(scenes)
+    item_off = np.zeros(len(scenes) + 1, dtype=np.int32)
+    locs, cs, yaws, vs = [], [], [], []
+    for k, sc in enumerate(scenes):
+        c, _ = _obstacles(sc.get("dynamic_obstacles"), "dynamic obstacle", k)
+        M = c.shape[0]
+        cols = []
+        for key, width in (("dynamic_yaw", 1), ("dynamic_extent", 2), ("dynamic_vel", 2)):
+            a = sc.get(key)
+            if a is None and (M == 0 or key == "dynamic_vel"):
+                a = np.zeros((M, width))
+            elif a is None:
+                raise ValueError(f"scene {k}: {M} vehicles need {key}")
+            a = np.asarray(a, dtype=np.float64)
+            if a.size != width * M:
+                raise ValueError(f"scene {k}: {M} vehicles need {M} rows of {key} (got {a.size / width:g})")
+            cols.append(a.reshape(M, width))
+        yaw, ext, v = cols
+        locs += [ring_local_offsets(ex, ey, resolution) for ex, ey in ext]
+        cs.append(c)
+        yaws.append(yaw[:, 0])
+        vs.append(v)
+        item_off[k + 1] = item_off[k] + M
+    off, ux, uy = _csr(locs)
+    c = np.concatenate(cs, axis=0) if cs else np.zeros((0, 2))
+    yaw = np.concatenate(yaws) if yaws else np.zeros(0)
+    v = np.concatenate(vs, axis=0) if vs else np.zeros((0, 2))
+    return (item_off, off, ux, uy, f32(c[:, 0]), f32(c[:, 1]), f32(np.cos(yaw)), f32(np.sin(yaw)), f32(v[:, 0]), f32(v[:, 1]))
+
+
 def batch_params(configs, step_lengths, B=None, honour_file_keys=False):
     """One config (dict) or a list of B configs, one step length or B of them -> a ctypes array of B SfmParams
     (``params_from_config`` per scene)."""
@@ -229,6 +272,7 @@ class SfmBatch:
         self.scene_off = None
         self.planar = True
         self._z = None
+        self._dyn = None                  # (scene_item_off, offsets) of the vehicles last set, for dynamic_obstacles()
 
     def _check(self, rc, what):
         if rc != 0:
@@ -254,12 +298,17 @@ class SfmBatch:
         self._check(self._lib.sfm_batch_set_params(self._b, params), "sfm_batch_set_params")
         self.params = params
 
-    def upload(self, scenes, planar=None):
-        """State and geometry of every scene (a list of B scene dicts).  ``planar`` None = pack_scenes' decision."""
+    def upload(self, scenes, planar=None, device_vehicles=False):
+        """State and geometry of every scene (a list of B scene dicts).  ``planar`` None = pack_scenes' decision.
+        ``device_vehicles``: False -- the vehicles' rings as given, which stay where they are (sfm_batch_set_dynamic_obstacles);
+        True -- the vehicles as boxes that move on the device (``set_dynamic_boxes``)."""
         scenes = list(scenes)
         if len(scenes) != self.B:
             raise ValueError(f"{len(scenes)} scenes for a batch of {self.B}")
+        boxes = pack_boxes(scenes) if device_vehicles else None     # (malformed boxes are refused before anything is sent)
         self.upload_packed(pack_scenes(scenes), planar)
+        if boxes is not None:
+            self.set_dynamic_boxes(boxes)
 
     def upload_packed(self, pk, planar=None):
         """``upload`` from the output of ``pack_scenes`` (pack once, upload many times)."""
@@ -274,6 +323,7 @@ class SfmBatch:
                     "sfm_batch_set_static_obstacles")
         self._check(L.sfm_batch_set_dynamic_obstacles(self._b, *(iptr(a) for a in dy[:2]), *(fptr(a) for a in dy[2:])),
                     "sfm_batch_set_dynamic_obstacles")
+        self._dyn = (dy[0].copy(), dy[1].copy())
         z, vz = (None, None) if planar else (pk["z"], pk["vz"])
         self._check(L.sfm_batch_upload_state(self._b, iptr(so), fptr(pk["x"]), fptr(pk["y"]), fptr(z), fptr(pk["vx"]),
                                              fptr(pk["vy"]), fptr(vz), fptr(pk["wx"]), fptr(pk["wy"]), fptr(pk["target_speed"]),
@@ -281,6 +331,30 @@ class SfmBatch:
         self.scene_off = so.copy()
         self.planar = planar
         self._z = pk["z"].copy()          # a planar batch keeps each scene's z on the host (the device holds x / y only)
+
+    def set_dynamic_boxes(self, scenes):
+        """Vehicles of every scene as oriented boxes that move on the device: a list of B scene dicts (see ``pack_boxes``) or the
+        tuple ``pack_boxes`` returns.  Replaces the scenes' vehicles; scenes without vehicles clear them."""
+        boxes = scenes if isinstance(scenes, tuple) else pack_boxes(scenes)
+        if len(boxes[0]) != self.B + 1:
+            raise ValueError(f"boxes of {len(boxes[0]) - 1} scenes for a batch of {self.B}")
+        self._check(self._lib.sfm_batch_set_dynamic_boxes(self._b, *(iptr(a) for a in boxes[:2]), *(fptr(a) for a in boxes[2:])),
+                    "sfm_batch_set_dynamic_boxes")
+        self._dyn = (boxes[0].copy(), boxes[1].copy())
+
+    def dynamic_obstacles(self):
+        """Per scene, its vehicles as the next tick sees them: a list of (center (2,), ring (P,2)) float64 like
+        ``SfmEngine.dynamic_obstacles()``."""
+        if self._dyn is None:
+            return [[] for _ in range(self.B)]
+        item_off, off = self._dyn
+        M, P = int(item_off[-1]), int(off[-1])
+        cx, cy, px, py = (np.zeros(n, np.float32) for n in (M, M, P, P))
+        self._check(self._lib.sfm_batch_download_dynamic_obstacles(self._b, fptr(cx), fptr(cy), fptr(px), fptr(py)),
+                    "sfm_batch_download_dynamic_obstacles")
+        pts = np.stack([px, py], axis=1).astype(np.float64)
+        veh = [(np.array([cx[k], cy[k]], dtype=np.float64), pts[off[k]:off[k + 1]]) for k in range(M)]
+        return [veh[item_off[b]:item_off[b + 1]] for b in range(self.B)]
 
     def set_waypoint_streams(self, seeds, world_sides, arrive_thresholds=2.0):
         """Per-scene waypoint streams for ``redraw=True`` (see ``stream_arrays``; scalars broadcast to every scene).  They stay in

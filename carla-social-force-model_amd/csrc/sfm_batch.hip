@@ -17,6 +17,11 @@
 //      pre-move position and the next waypoint of the scene's counter-based stream (taking effect next tick).
 // A recording tick (frame != null) also stores the pre-tick state of every row while the scene is staged (frame f of a recorded run
 // is the state before tick f*stride).  Redraw and recording are the EXT instantiations; the plain tick is compiled without them.
+// Device-side vehicles (sfm_batch_set_dynamic_boxes, a.veh_on): in the prologue, before the barrier, the waves of workgroup b move
+// scene b's vehicles k0 + wave, k0 + wave + 4, ... by its dt (advance_vehicle, the handle's one vehicle step) from geo[2] -- what
+// this tick's dynamic-force scan reads -- into the other half of a ping-pong (a.veh_*_out), which the host swaps in after the
+// launch.  No launch reads what it writes, so no barrier is added: the one barrier below is followed by `if (slice != 0) return;`,
+// and a later barrier would wait on waves that have left.
 // Planar bodies (moussaid_planar / moussaid_spatial) with the exact body (moussaid<.., EXACT>) recomputing a slice whose sum came out
 // NaN (coincident pair, or two pedestrians above one another in 3-D), as the handle's kernels do.
 // Determinism: no atomics, every order is a function of the scene alone (N_b, its rows, its polylines) -- a scene's result is
@@ -203,6 +208,14 @@ template <bool Z3, bool EXT>
 __global__ __launch_bounds__(BLOCK) void sfm_batch_tick_kernel(const BatchArgs a) {
     __shared__ BatchShared<Z3> sh;
     const int b = blockIdx.x;
+    if (a.veh_on) {                                                     // uniform; also a scene without pedestrians: every vehicle
+        const int k0 = a.geo[2].item_off[b], k1 = a.geo[2].item_off[b + 1];   // must reach the other half
+        const int wave = uniform((int)threadIdx.x >> 6);
+        // (geo[2] is only read here: the moved centres and rings go to veh_*_out, which nothing in this launch reads)
+        const DynAdvance d{const_cast<float4*>(a.geo[2].ctr), a.geo[2].off, a.veh_local, a.veh_rot, const_cast<float2*>(a.geo[2].pts),
+                           0, a.prm[b].dt, 0, a.veh_ctr_out, a.veh_pts_out};
+        for (int k = k0 + wave; k < k1; k += WAVES_PER_BLOCK) advance_vehicle(d, k, threadIdx.x & (WAVE - 1), true);
+    }
     const int s0 = a.scene_off[b], n = a.scene_off[b + 1] - s0;       // 0 <= n <= BATCH_MAX_N (checked on the host)
     if (n <= 0) return;
     const BatchParams& p = a.prm[b];                                    // (read through the pointer: uniform scalar loads)

@@ -2011,6 +2011,7 @@ struct BatchGeoDev {
     float2* pts = nullptr;     // [P]
     float4* ctr = nullptr;     // [K]
     int K = 0;
+    int P = 0;
 };
 
 struct SfmBatch {
@@ -2035,6 +2036,13 @@ struct SfmBatch {
     size_t frames_cap = 0;
     float2* zframes = nullptr;
     size_t zframes_cap = 0;
+    // device-side vehicles (sfm_batch_set_dynamic_boxes): geo[2].ctr / .pts hold the vehicles the next tick sees, veh_ctr_alt /
+    // veh_pts_alt (the same sizes) the half an integrating tick writes; batch_launch swaps them after each such launch
+    bool boxes = false;
+    float2* veh_local = nullptr;       // [P] ring-local offsets
+    float2* veh_rot = nullptr;         // [M] {cos yaw, sin yaw}
+    float4* veh_ctr_alt = nullptr;
+    float2* veh_pts_alt = nullptr;
     std::string err;
 };
 
@@ -2098,7 +2106,15 @@ static void free_batch_geo(BatchGeoDev& g) {
     if (g.off) hipFree(g.off);
     if (g.pts) hipFree(g.pts);
     if (g.ctr) hipFree(g.ctr);
-    g.off = nullptr; g.pts = nullptr; g.ctr = nullptr; g.K = 0;
+    g.off = nullptr; g.pts = nullptr; g.ctr = nullptr; g.K = 0; g.P = 0;
+}
+
+// back to vehicles that stay where they were set (the caller synchronised the stream)
+static void free_batch_boxes(SfmBatch* b) {
+    b->boxes = false;
+    for (void* p : {(void*)b->veh_local, (void*)b->veh_rot, (void*)b->veh_ctr_alt, (void*)b->veh_pts_alt})
+        if (p) hipFree(p);
+    b->veh_local = nullptr; b->veh_rot = nullptr; b->veh_ctr_alt = nullptr; b->veh_pts_alt = nullptr;
 }
 
 // one kind of per-scene CSR polylines; ctr4[K] built by the caller
@@ -2119,6 +2135,7 @@ static int set_batch_geo(SfmBatch* b, int kind, const int32_t* scene_item_off, c
     HIP_TRY(b, hipMemcpy(g.pts, pts.data(), sizeof(float2) * pts.size(), hipMemcpyHostToDevice));
     HIP_TRY(b, hipMemcpy(g.ctr, ctr4.data(), sizeof(float4) * (size_t)K, hipMemcpyHostToDevice));
     g.K = K;
+    g.P = P;
     return SFM_OK;
 }
 
@@ -2162,8 +2179,20 @@ static int batch_launch(SfmBatch* b, uint32_t flags, float4* frame = nullptr, fl
     a.draws = b->draws;
     a.frame = frame;
     a.zframe = b->z3 ? zframe : nullptr;
+    const bool move = b->boxes && (flags & SFM_TICK_INTEGRATE);
+    if (move) {
+        a.veh_ctr_out = b->veh_ctr_alt;
+        a.veh_pts_out = b->veh_pts_alt;
+        a.veh_local = b->veh_local;
+        a.veh_rot = b->veh_rot;
+        a.veh_on = 1;
+    }
     const bool ext = (flags & SFM_TICK_REDRAW_WAYPOINTS) || frame;
     HIP_TRY(b, launch_batch_tick(b->z3, ext, a, b->B, b->stream));
+    if (move) {                                          // the moved half is what the next tick sees
+        std::swap(b->geo[2].ctr, b->veh_ctr_alt);
+        std::swap(b->geo[2].pts, b->veh_pts_alt);
+    }
     return SFM_OK;
 }
 
@@ -2210,6 +2239,7 @@ int sfm_batch_destroy(SfmBatch* b) {
         free_batch_geo(b->geo[k]);
         if (b->geo[k].item_off) hipFree(b->geo[k].item_off);
     }
+    free_batch_boxes(b);
     if (b->d_prm) hipFree(b->d_prm);
     if (b->d_scene_off) hipFree(b->d_scene_off);
     if (b->pk) hipFree(b->pk);
@@ -2329,7 +2359,60 @@ int sfm_batch_set_dynamic_obstacles(SfmBatch* b, const int32_t* scene_item_off, 
     std::vector<float4> c4((size_t)K);
     for (int k = 0; k < K; ++k)       // velocities default to 0 like ObstacleForce (forces.py:212-213)
         c4[k] = make_float4(cx[k], cy[k], vx ? vx[k] : 0.f, vy ? vy[k] : 0.f);
+    HIP_TRY(b, hipStreamSynchronize(b->stream));                 // a tick in flight may still move the boxes
+    free_batch_boxes(b);
     return set_batch_geo(b, 2, scene_item_off, offsets, px, py, c4, K);
+}
+
+// Device-side vehicles (ABI 8), the batch form of sfm_set_dynamic_boxes: geo[2] holds the current half (its pts the world-frame rings),
+// the rings of the given centres are generated by one launch of sfm_dynamic_boxes_kernel over every vehicle of the batch
+int sfm_batch_set_dynamic_boxes(SfmBatch* b, const int32_t* scene_item_off, const int32_t* offsets, const float* ux, const float* uy,
+                                const float* cx, const float* cy, const float* yaw_cos, const float* yaw_sin, const float* vx,
+                                const float* vy) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    int M = 0;
+    rc = check_batch_geo(b, scene_item_off, offsets, ux, uy, cx, cy, &M);
+    if (rc) return rc;
+    if (M > 0 && (!yaw_cos || !yaw_sin)) return bfail(b, SFM_ERR_INVALID, "yaw arrays are NULL");
+    if ((vx == nullptr) != (vy == nullptr)) return bfail(b, SFM_ERR_INVALID, "vx and vy must be given together");
+    std::vector<float4> c4((size_t)M);
+    std::vector<float2> rot((size_t)M);
+    for (int k = 0; k < M; ++k) {     // velocities default to 0 like ObstacleForce (forces.py:212-213)
+        c4[k] = make_float4(cx[k], cy[k], vx ? vx[k] : 0.f, vy ? vy[k] : 0.f);
+        rot[k] = make_float2(yaw_cos[k], yaw_sin[k]);
+    }
+    HIP_TRY(b, hipStreamSynchronize(b->stream));                 // a tick in flight may still move the old boxes
+    free_batch_boxes(b);
+    rc = set_batch_geo(b, 2, scene_item_off, offsets, ux, uy, c4, M);   // pts holds the local offsets until the launch below
+    if (rc || M == 0) return rc;
+    BatchGeoDev& g = b->geo[2];
+    const size_t np = (size_t)(g.P > 0 ? g.P : 1);               // set_batch_geo's sizes: both halves alike
+    HIP_TRY(b, dev_realloc(b->veh_local, np));
+    HIP_TRY(b, dev_realloc(b->veh_rot, (size_t)M));
+    HIP_TRY(b, dev_realloc(b->veh_ctr_alt, (size_t)M));
+    HIP_TRY(b, dev_realloc(b->veh_pts_alt, np));
+    HIP_TRY(b, hipMemcpy(b->veh_local, g.pts, sizeof(float2) * np, hipMemcpyDeviceToDevice));
+    HIP_TRY(b, hipMemcpy(b->veh_rot, rot.data(), sizeof(float2) * (size_t)M, hipMemcpyHostToDevice));
+    HIP_TRY(b, launch_dynamic_boxes(g.ctr, g.off, b->veh_local, b->veh_rot, g.pts, M, 0.f, 0, b->stream));
+    b->boxes = true;
+    return SFM_OK;
+}
+
+int sfm_batch_download_dynamic_obstacles(SfmBatch* b, float* cx, float* cy, float* px, float* py) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    const BatchGeoDev& g = b->geo[2];
+    const int M = g.K, P = g.P;
+    if (M == 0) return SFM_OK;
+    std::vector<float4> c((size_t)M);
+    std::vector<float2> p((size_t)(P > 0 ? P : 1));
+    HIP_TRY(b, hipMemcpy(c.data(), g.ctr, sizeof(float4) * (size_t)M, hipMemcpyDeviceToHost));
+    if (P > 0) HIP_TRY(b, hipMemcpy(p.data(), g.pts, sizeof(float2) * (size_t)P, hipMemcpyDeviceToHost));
+    for (int k = 0; k < M; ++k) { if (cx) cx[k] = c[k].x; if (cy) cy[k] = c[k].y; }
+    for (int q = 0; q < P; ++q) { if (px) px[q] = p[q].x; if (py) py[q] = p[q].y; }
+    return SFM_OK;
 }
 
 int sfm_batch_tick(SfmBatch* b, uint32_t flags) {

@@ -241,6 +241,13 @@ struct BatchArgs {
     uint32_t* draws;          // [N_total] waypoint draw counters
     float4* frame;            // recording tick: the pre-tick {x, y, vx, vy} of every row go here (frame slot of this tick); null: off
     float2* zframe;           // ... and {z, vz} of a 3-D batch (null: off)
+    // device-side vehicles (sfm_batch_set_dynamic_boxes): an integrating tick moves each scene's vehicles from geo[2].ctr / .pts
+    // (what this tick's dynamic-force scan reads) into the other half of a ping-pong, which the host swaps in after the launch
+    float4* veh_ctr_out;      // [M] {cx, cy, vx, vy} one step of the scene's dt later
+    float2* veh_pts_out;      // [P] their rings
+    const float2* veh_local;  // [P] ring points in the vehicle frame
+    const float2* veh_rot;    // [M] {cos yaw, sin yaw}
+    int veh_on;               // 1: boxes are set and the tick integrates; 0: the vehicles stay where they are
 };
 
 // Block-major packing for sharded runs (sfm_set_partition, sfm_reorder.hip): the row order is cut into gx columns by x, each

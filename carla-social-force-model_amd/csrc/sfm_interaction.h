@@ -64,6 +64,24 @@ __device__ __forceinline__ float2 next_waypoint(uint32_t seed, uint32_t key, uin
     return make_float2(waypoint_coord(seed, key, draw, 0u, side), waypoint_coord(seed, key, draw, 1u, side));
 }
 
+// One wave moves vehicle k by dt * v and regenerates its ring p = c + R(yaw) u (obstacles.py:297-329 without the simulator): the one
+// vehicle step of the handle's kernels (sfm_kernels.hip) and the batch kernel (sfm_batch.hip).
+__device__ __forceinline__ void advance_vehicle(const DynAdvance& d, int k, int lane, bool advance) {
+    float4 c = d.ctr[k];
+    if (advance) {
+        c.x = fmaf(d.dt, c.z, c.x);
+        c.y = fmaf(d.dt, c.w, c.y);
+        if (lane == 0) (d.ctr_out ? d.ctr_out : d.ctr)[k] = c;
+    }
+    const float2 r = d.rot[k];                     // {cos yaw, sin yaw}
+    const int o1 = d.off[k + 1];
+    float2* pts = d.pts_out ? d.pts_out : d.pts;
+    for (int p = d.off[k] + lane; p < o1; p += WAVE) {
+        const float2 u = d.local[p];
+        pts[p] = make_float2(fmaf(r.x, u.x, fmaf(-r.y, u.y, c.x)), fmaf(r.y, u.x, fmaf(r.x, u.y, c.y)));
+    }
+}
+
 // The tile-box rule (the operands of tiles_negligible): a row counts unless it is parked far away (a despawned pedestrian or
 // padding), and its speed bound is rounded up so that it stays a bound.  A tile's box and bound are the union over its rows:
 // the callers start from an empty box (+inf / -inf, 0), put in each row that counts, then tile_box_reduce over the wave.

@@ -230,23 +230,6 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
-// One wave moves vehicle k by dt * v and regenerates its ring p = c + R(yaw) u (obstacles.py:297-329 without the simulator).
-__device__ __forceinline__ void advance_vehicle(const DynAdvance& d, int k, int lane, bool advance) {
-    float4 c = d.ctr[k];
-    if (advance) {
-        c.x = fmaf(d.dt, c.z, c.x);
-        c.y = fmaf(d.dt, c.w, c.y);
-        if (lane == 0) (d.ctr_out ? d.ctr_out : d.ctr)[k] = c;
-    }
-    const float2 r = d.rot[k];                     // {cos yaw, sin yaw}
-    const int o1 = d.off[k + 1];
-    float2* pts = d.pts_out ? d.pts_out : d.pts;
-    for (int p = d.off[k] + lane; p < o1; p += WAVE) {
-        const float2 u = d.local[p];
-        pts[p] = make_float2(fmaf(r.x, u.x, fmaf(-r.y, u.y, c.x)), fmaf(r.y, u.x, fmaf(r.x, u.y, c.y)));
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------
 // provably negligible tile pairs
 // ------------------------------------------------------------------------------------------------------

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SFM_ABI_VERSION 7   /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded (additions only) */
+#define SFM_ABI_VERSION 8   /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles (additions only) */
 
 typedef struct SfmHandle SfmHandle;
 
@@ -274,7 +274,7 @@ int sfm_abi_version(void);
  * each, every scene with its own SfmParams (a parameter sweep is one batch) and its own borders / obstacles; each tick is ONE kernel
  * launch for the whole batch (sfm_batch.hip, a workgroup per scene).  A scene's result is bitwise the same whatever else is in the
  * batch and wherever it sits.  Larger crowds belong on a handle.  Waypoint redraw (per-scene streams) and on-device trajectories
- * are ABI 7.  Not supported on a batch: device-side vehicles, the mode state machine, force records, sharding.  Host arrays are fp32 SoA over all scenes concatenated; scene b owns rows
+ * are ABI 7, device-side vehicles ABI 8.  Not supported on a batch: the mode state machine, force records, sharding.  Host arrays are fp32 SoA over all scenes concatenated; scene b owns rows
  * [scene_off[b], scene_off[b+1]).  Geometry is per-scene CSR: scene b owns polylines [scene_item_off[b], scene_item_off[b+1]) of the
  * concatenated set, whose points are offsets[k] .. offsets[k+1]-1 (offsets[0] = 0).  Errors as for a handle: a negative SfmStatus,
  * the message in sfm_batch_last_error(b) (or sfm_batch_last_error(NULL) after a failed sfm_batch_create); nothing is launched on
@@ -298,9 +298,26 @@ int sfm_batch_set_borders(SfmBatch* b, const int32_t* scene_item_off, const int3
                           const float* cx, const float* cy, const float* cull_len);
 int sfm_batch_set_static_obstacles(SfmBatch* b, const int32_t* scene_item_off, const int32_t* offsets, const float* px,
                                    const float* py, const float* cx, const float* cy);
-/* The vehicles as the caller last set them (vx / vy NULL: at rest); a batch does not move them. */
+/* The vehicles as the caller last set them (vx / vy NULL: at rest); the batch does not move them.  Replaces device-side vehicles
+ * (sfm_batch_set_dynamic_boxes): from then on the vehicles stay where they were set. */
 int sfm_batch_set_dynamic_obstacles(SfmBatch* b, const int32_t* scene_item_off, const int32_t* offsets, const float* px,
                                     const float* py, const float* cx, const float* cy, const float* vx, const float* vy);
+/* Device-side vehicles of every scene (ABI 8, the batch form of sfm_set_dynamic_boxes): scene b owns vehicles
+ * [scene_item_off[b], scene_item_off[b+1]); ring-local offsets CSR offsets[M+1], ux, uy; centre, cos/sin yaw, velocity per vehicle
+ * (vx / vy NULL: at rest).  Rings are generated at the given centres when the call returns; after every INTEGRATING tick of a scene
+ * (sfm_batch_tick with SFM_TICK_INTEGRATE, sfm_batch_run, sfm_batch_run_recorded) its centres advance by that scene's
+ * step_length * v and its rings are regenerated, inside the tick's one launch: c' = fma(step_length, v, c), ring point
+ * p = (fma(cos, ux, fma(-sin, uy, cx)), fma(sin, ux, fma(cos, uy, cy))) in fp32, as on a handle.  The vehicles move whether or not
+ * the scene's dynamic obstacle force is on; a tick without SFM_TICK_INTEGRATE leaves them where they are, and so do
+ * sfm_batch_upload_state and sfm_batch_set_params (a new step_length applies from the next integrating tick).
+ * scene_item_off[B] = 0 clears every vehicle.  Refused: the CSR checks of sfm_batch_set_dynamic_obstacles, NULL ux / uy with
+ * ring points, NULL centre or yaw arrays with vehicles, only one of vx / vy. */
+int sfm_batch_set_dynamic_boxes(SfmBatch* b, const int32_t* scene_item_off, const int32_t* offsets, const float* ux,
+                                const float* uy, const float* cx, const float* cy, const float* yaw_cos, const float* yaw_sin,
+                                const float* vx, const float* vy);
+/* Current centres (M) and ring points (P) of every scene's vehicles, concatenated in scene order, as the next tick will see them
+ * (synchronises the batch's stream); NULL skips.  Also the rings of sfm_batch_set_dynamic_obstacles. */
+int sfm_batch_download_dynamic_obstacles(SfmBatch* b, float* cx, float* cy, float* px, float* py);
 /* One tick of every scene: flags 0 or SFM_TICK_INTEGRATE, plus SFM_TICK_REDRAW_WAYPOINTS once sfm_batch_set_waypoint_streams has
  * been called (anything else is an error); v' (and x') in place. */
 int sfm_batch_tick(SfmBatch* b, uint32_t flags);
