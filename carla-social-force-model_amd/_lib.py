@@ -14,14 +14,15 @@ import numpy as np
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFM_LIB_PATH") or os.path.join(PKG_DIR, "libsfm_hip.so")   # (the override is for A/B builds of the kernels)
-ABI_VERSION = 8
+ABI_VERSION = 9
 SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_records": 5,
          **{n: 6 for n in ("sfm_batch_create", "sfm_batch_destroy", "sfm_batch_set_stream", "sfm_batch_set_params",
                            "sfm_batch_upload_state", "sfm_batch_set_borders", "sfm_batch_set_static_obstacles",
                            "sfm_batch_set_dynamic_obstacles", "sfm_batch_tick", "sfm_batch_run", "sfm_batch_download_state",
                            "sfm_batch_last_error")},
          **{n: 7 for n in ("sfm_batch_set_waypoint_streams", "sfm_batch_download_waypoints", "sfm_batch_run_recorded")},
-         **{n: 8 for n in ("sfm_batch_set_dynamic_boxes", "sfm_batch_download_dynamic_obstacles")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
+         **{n: 8 for n in ("sfm_batch_set_dynamic_boxes", "sfm_batch_download_dynamic_obstacles")},
+         **{n: 9 for n in ("sfm_batch_set_mode_fsm", "sfm_batch_download_modes")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
 
 FORCE_NAMES = ("acceleration_force", "pedestrian_force", "border_force",
                "static_obstacle_force", "dynamic_obstacle_force")
@@ -114,6 +115,9 @@ SYMBOLS = {
     # batch device-side vehicles (ABI 8)
     "sfm_batch_set_dynamic_boxes": (C.c_int, [_H, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F]),
     "sfm_batch_download_dynamic_obstacles": (C.c_int, [_H, _F, _F, _F, _F]),
+    # batch mode state machine (ABI 9)
+    "sfm_batch_set_mode_fsm": (C.c_int, [_H, _U8, _F, _F, _F, _F, _F, _I, _F, _F, _U8, _I, _F, _F, _F]),
+    "sfm_batch_download_modes": (C.c_int, [_H, _U8, _F, _I, _F]),
 }
 
 _lib = None

@@ -1,5 +1,5 @@
 """Batched scenes: many small, independent crowds stepped by ONE kernel launch per tick (C ABI: sfm_batch_*, ABI 6; waypoint
-streams and recorded runs, ABI 7).
+streams and recorded runs, ABI 7; device-side vehicles, ABI 8; pedestrian modes, ABI 9).
 
 Social-force models are run in bulk as many small scenes -- scenario sampling, RL environments stepped in lock-step, calibration
 sweeps over A / lambda / gamma / tau.  ``SfmBatch`` holds B scenes of 0 .. 1024 pedestrians, each with its own parameters (its own
@@ -21,6 +21,13 @@ Traffic moves on the device (``set_dynamic_boxes`` or ``upload(..., device_vehic
 an oriented box (the scene keys ``dynamic_obstacles`` centres, ``dynamic_yaw``, ``dynamic_extent``, ``dynamic_vel``), and every
 integrating tick of a scene moves its centres by that scene's step_length * v and regenerates the rings inside the tick's one launch,
 as a handle's ``set_dynamic_boxes`` does.  ``dynamic_obstacles()`` reads them back.
+
+Pedestrian modes run on the device too (``set_modes``, ABI 9): per scene a plan of mode objects (``pack_modes``, or
+``plan_from_managers`` from PedModeManager mirrors) and waypoint queues like the reference's waypoint_dict.  Inside the tick's one
+launch every row applies its mode's target speed, wakes up from IDLE on its scene's clock, waits at the kerb in CHECKING_TRAFFIC
+until gap acceptance against its scene's vehicles lets it cross, walks without the border force on the road, pops its queue on
+arrival and despawns (parked far away) once the queue runs out -- as a handle's ``set_mode_fsm`` does.  ``modes()`` and ``clocks()``
+read them back.  While modes are set, ``redraw=True`` is refused (arrivals pop the queues).
 """
 from __future__ import annotations
 
@@ -238,6 +245,105 @@ def stream_arrays(B, seeds, world_sides, arrive_thresholds=2.0):
     return tuple(out)
 
 
+MODE_KEYS = ("mode", "target_speed", "initial_speed", "crossing_speed", "safety_margin", "next_mode_time")
+
+
+def plan_from_managers(managers, queues):
+    """A scene's mode plan from its PedModeManager mirror objects (the attributes SfmEngine.set_mode_fsm reads: current_mode,
+    target_speed, initial_target_speed, crossing_speed, crossing_safety_margin, next_mode_time) and its waypoint queues
+    (``queues[i]`` = [(waypoint (2|3), crossing_road), ...] like waypoint_dict).  Pure NumPy."""
+    managers = list(managers)
+    f = lambda attr: np.array([float(getattr(m, attr)) for m in managers], dtype=np.float64)
+    return {"mode": np.array([int(m.current_mode) for m in managers], dtype=np.int64),
+            "target_speed": f("target_speed"), "initial_speed": f("initial_target_speed"), "crossing_speed": f("crossing_speed"),
+            "safety_margin": f("crossing_safety_margin"), "next_mode_time": f("next_mode_time"),
+            "queues": [list(q) for q in queues]}
+
+
+def pack_modes(plans, scene_off, scenes=None):
+    """One mode plan per scene (dicts: ``mode``, ``target_speed``, ``initial_speed``, ``crossing_speed``, ``safety_margin``,
+    ``next_mode_time`` (N_b,) each; ``queues`` N_b lists of (waypoint (2|3), crossing_road); optionally ``first_vehicle_extent``
+    (2,), default the scene's ``dynamic_extent[0]`` when ``scenes`` is given and the scene has vehicles, else zeros) -> the
+    per-row arguments of sfm_batch_set_mode_fsm, concatenated in scene order: a dict of ``mode`` uint8, the five float32 columns,
+    ``wp_offsets`` int32 [N_total+1], ``wp_x``, ``wp_y`` float32 [W], ``wp_crossing`` uint8 [W] and ``first_vehicle_extent``
+    float32 [B,2].  Pure NumPy; raises ValueError naming the scene and the key."""
+    so = np.asarray(scene_off)
+    B = len(so) - 1
+    plans = list(plans)
+    if len(plans) != B:
+        raise ValueError(f"{len(plans)} mode plans for {B} scenes")
+    if scenes is not None and len(scenes) != B:
+        raise ValueError(f"{len(scenes)} scenes for {B} mode plans")
+    cols = {k: [] for k in MODE_KEYS}
+    counts, wx, wy, wc = [], [], [], []
+    ext = np.zeros((B, 2))
+    for b, plan in enumerate(plans):
+        n = int(so[b + 1] - so[b])
+        if not isinstance(plan, dict):
+            raise ValueError(f"scene {b}: a mode plan must be a dict")
+        for key in MODE_KEYS + ("queues",):
+            if key not in plan:
+                raise ValueError(f"scene {b}: the mode plan has no {key}")
+        for key in MODE_KEYS:
+            a = np.asarray(plan[key], dtype=np.float64).reshape(-1)
+            if a.shape[0] != n:
+                raise ValueError(f"scene {b}: {key} has {a.shape[0]} rows, expected {n}")
+            if key == "mode" and n and not (np.all(a == np.round(a)) and a.min() >= 0 and a.max() <= 4):
+                raise ValueError(f"scene {b}: mode must hold PedMode values 0..4")
+            cols[key].append(a)
+        queues = list(plan["queues"])
+        if len(queues) != n:
+            raise ValueError(f"scene {b}: queues has {len(queues)} lists, expected {n}")
+        for i, q in enumerate(queues):
+            counts.append(len(q))
+            for e, item in enumerate(q):
+                if len(item) != 2:
+                    raise ValueError(f"scene {b}: queues[{i}][{e}] must be a (waypoint, crossing_road) pair")
+                w = np.asarray(item[0], dtype=np.float64).reshape(-1)
+                if w.size not in (2, 3):
+                    raise ValueError(f"scene {b}: queues[{i}][{e}] has a waypoint of {w.size} coordinates")
+                wx.append(w[0]); wy.append(w[1]); wc.append(1 if item[1] else 0)
+        e0 = plan.get("first_vehicle_extent")
+        if e0 is None and scenes is not None:
+            de = scenes[b].get("dynamic_extent") if isinstance(scenes[b], dict) else getattr(scenes[b], "dynamic_extent", None)
+            if de is not None and len(de):
+                e0 = np.asarray(de, dtype=np.float64).reshape(-1, 2)[0]
+        if e0 is not None:
+            e0 = np.asarray(e0, dtype=np.float64).reshape(-1)
+            if e0.size != 2:
+                raise ValueError(f"scene {b}: first_vehicle_extent must have 2 values, got {e0.size}")
+            ext[b] = e0
+    off = np.zeros(len(counts) + 1, dtype=np.int32)
+    np.cumsum(counts, out=off[1:])
+    cat = lambda key: np.concatenate(cols[key]) if cols[key] else np.zeros(0)
+    out = {"mode": np.ascontiguousarray(cat("mode"), dtype=np.uint8)}
+    out.update({k: f32(cat(k)) for k in MODE_KEYS[1:]})
+    out.update(wp_offsets=off, wp_x=f32(wx), wp_y=f32(wy), wp_crossing=np.ascontiguousarray(wc, dtype=np.uint8),
+               first_vehicle_extent=f32(ext))
+    return out
+
+
+def mode_scene_arrays(B, despawn_on_arrival=True, sim_time0=0.0, arrive_thresholds=2.0):
+    """Per-scene mode arguments -> (despawn_on_arrival int32[B], sim_time0 float32[B], arrive_threshold float32[B]).  Each argument
+    is a scalar (broadcast to every scene) or B values; clocks must be finite, thresholds finite and >= 0.  Pure NumPy; raises
+    ValueError."""
+    def col(v, name):
+        a = np.asarray(v)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] not in (1, B)):
+            raise ValueError(f"{name}: expected a scalar or {B} values, got shape {a.shape}")
+        if a.dtype.kind not in "biuf":
+            raise ValueError(f"{name} must be numbers, got {a.dtype}")
+        return np.broadcast_to(a.reshape(-1), (B,))
+    despawn = np.ascontiguousarray(col(despawn_on_arrival, "despawn_on_arrival").astype(bool), dtype=np.int32)
+    t0 = f32(col(sim_time0, "sim_time0"))
+    if not np.isfinite(t0).all():
+        raise ValueError("sim_time0 must be finite")
+    thr = f32(col(arrive_thresholds, "arrive_thresholds"))
+    if not (np.isfinite(thr).all() and (thr >= 0).all()):
+        raise ValueError("arrive_thresholds must be finite and >= 0")
+    return despawn, t0, thr
+
+
 def split_frames(frames, scene_off):
     """Frames of the concatenated batch, (F, N_total, C), -> a list of B arrays (F, N_b, C), one per scene in scene order (views).
     Pure NumPy."""
@@ -392,6 +498,45 @@ class SfmBatch:
         idx = np.arange(F) * int(stride)
         return (split_frames(frames[:F], self.scene_off), idx,
                 None if zframes is None else split_frames(zframes[:F], self.scene_off))
+
+    def set_modes(self, plans, despawn_on_arrival=True, sim_time0=0.0, arrive_thresholds=2.0, scenes=None):
+        """The pedestrian mode state machine of every scene (sfm_batch_set_mode_fsm): ``plans`` one mode plan per scene (see
+        ``pack_modes``; ``scenes`` supplies each scene's default first-vehicle extent), the per-scene scalars as in
+        ``mode_scene_arrays`` (each a scalar broadcast to every scene, or B values).  ``plans=None`` switches the modes off; so does
+        every ``upload``."""
+        L = self._lib
+        if plans is None:
+            self._check(L.sfm_batch_set_mode_fsm(self._b, *([None] * 14)), "sfm_batch_set_mode_fsm")
+            return
+        if self.scene_off is None:
+            raise SfmLibraryError("SfmBatch.set_modes: upload() has not been called")
+        pm = pack_modes(plans, self.scene_off, scenes)
+        despawn, t0, thr = mode_scene_arrays(self.B, despawn_on_arrival, sim_time0, arrive_thresholds)
+        W = int(pm["wp_offsets"][-1])
+        self._check(L.sfm_batch_set_mode_fsm(self._b, u8ptr(pm["mode"]), *(fptr(pm[k]) for k in MODE_KEYS[1:]),
+                                             iptr(pm["wp_offsets"]), fptr(pm["wp_x"]) if W else None,
+                                             fptr(pm["wp_y"]) if W else None, u8ptr(pm["wp_crossing"]) if W else None,
+                                             iptr(despawn), fptr(t0), fptr(thr), fptr(pm["first_vehicle_extent"])),
+                    "sfm_batch_set_mode_fsm")
+
+    def _modes(self):
+        n = int(self.scene_off[-1]) if self.scene_off is not None else 0
+        m, t, c = np.zeros(n, np.uint8), np.zeros(n, np.float32), np.zeros(n, np.int32)
+        clk = np.zeros(self.B, np.float32)
+        self._check(self._lib.sfm_batch_download_modes(self._b, u8ptr(m) if n else None, fptr(t) if n else None,
+                                                       iptr(c) if n else None, fptr(clk)), "sfm_batch_download_modes")
+        return m, t, c, clk
+
+    def modes(self):
+        """Per scene (mode (N_b,) uint8 with 255 = despawned, mode target speed (N_b,) float32, queue cursor (N_b,) int32), in
+        scene order.  Raises SfmLibraryError while no modes are set."""
+        m, t, c, _ = self._modes()
+        so = self.scene_off
+        return [(m[so[b]:so[b + 1]], t[so[b]:so[b + 1]], c[so[b]:so[b + 1]]) for b in range(self.B)]
+
+    def clocks(self):
+        """Each scene's mode clock (sim_time, float32 [B]): sim_time0 plus one step_length per tick since ``set_modes``."""
+        return self._modes()[3]
 
     def waypoints(self):
         """Per scene (waypoint (N_b,2) float32, draw counter (N_b,) uint32), in scene order."""

@@ -22,6 +22,10 @@
 // this tick's dynamic-force scan reads -- into the other half of a ping-pong (a.veh_*_out), which the host swaps in after the
 // launch.  No launch reads what it writes, so no barrier is added: the one barrier below is followed by `if (slice != 0) return;`,
 // and a later barrier would wait on waves that have left.
+// Pedestrian modes (sfm_batch_set_mode_fsm, the MODES instantiation): the lane that owns a row runs the handle's sfm_mode_kernel for it
+// after the barrier (target of this tick, idle wake-up on the scene's clock, gap acceptance against the scene's geo[2] items), the
+// border mask follows the mode, and after the step an arrival pops the row's queue or despawns it (parked far away, keyed by its index
+// inside the scene).  The scene's clock a.fsm.sim_time[b] is read before the barrier and advanced by thread 0 after it.
 // Planar bodies (moussaid_planar / moussaid_spatial) with the exact body (moussaid<.., EXACT>) recomputing a slice whose sum came out
 // NaN (coincident pair, or two pedestrians above one another in 3-D), as the handle's kernels do.
 // Determinism: no atomics, every order is a function of the scene alone (N_b, its rows, its polylines) -- a scene's result is
@@ -129,8 +133,9 @@ __device__ __forceinline__ void batch_geometry(const BatchArgs& a, const BatchPa
     }
 }
 
-template <bool Z3, bool RAD, bool EXT>
-__device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParams& p, BatchShared<Z3>& sh, int b, int s0, int n) {
+template <bool Z3, bool RAD, bool EXT, bool MODES>
+__device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParams& p, BatchShared<Z3>& sh, int b, int s0, int n,
+                                            float now) {
     const int tid = threadIdx.x;
     const int lane = tid & (WAVE - 1);
     const int wave = uniform(tid >> 6);
@@ -165,7 +170,37 @@ __device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParam
         const float x = s.x, y = s.y, vx = s.z, vy = s.w;
         const float z = Z3 ? sh.zv[ii].x : 0.0f, vz = Z3 ? sh.zv[ii].y : 0.0f;
         const float r = RAD ? sh.r[ii] : 0.0f;
-        const bool walk = live && !(a.crossing && a.crossing[s0 + ii]);   // forces.py:140-141,176-177
+        bool walk = live && !(a.crossing && a.crossing[s0 + ii]);         // forces.py:140-141,176-177
+        // MODES: the batch form of sfm_mode_kernel -- apply_current_mode (this tick's target speed is the mode object's target BEFORE
+        // its tick, pedestrian_state.py:94-95), the idle wake-up (ped_mode_manager.py:30-35) and gap acceptance against the scene's
+        // own vehicles as this tick sees them (pedestrian_simulation.py:63-73); the border mask follows the new mode
+        uint8_t m = MODE_DESPAWNED;
+        float tgt = 0.0f;
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (MODES) {
+            if (live) {
+                m = a.fsm.mode[s0 + i];
+                o = a.own[s0 + i];
+                if (m != MODE_DESPAWNED) {
+                    tgt = a.fsm.target[s0 + i];
+                    const float4 sp = a.fsm.speeds[s0 + i];                  // {initial, crossing, margin, next_mode_time}
+                    o.z = tgt;
+                    if (m == MODE_IDLE && sp.w <= now) { m = MODE_WALKING; tgt = sp.x; }
+                    if (m == MODE_CHECKING) {
+                        const int k0 = a.geo[2].item_off[b], k1 = a.geo[2].item_off[b + 1];
+                        const BatchModeScene ms = a.fsm.scene[b];
+                        if (k0 == k1 || gap_accepted(a.geo[2].ctr, k0, k1, ms.veh_ext_x, ms.veh_ext_y, make_float2(x, y),
+                                                     make_float2(o.x, o.y), sp.y, sp.z)) {
+                            m = MODE_CROSSING;
+                            tgt = sp.y;
+                        }
+                    }
+                } else {
+                    o.z = 0.0f;
+                }
+            }
+            walk = live && m != MODE_CROSSING && m != MODE_ROAD_TO_SIDEWALK && m != MODE_DESPAWNED;   // forces.py:176-177
+        }
         float f[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         batch_geometry<RAD>(a, p, b, x, y, vx, vy, r, live, walk, sh.row[wave], lane, f);
         const float fbx = f[0], fby = f[1];
@@ -173,7 +208,7 @@ __device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParam
         const float fdx = p.dyn.negA * f[4], fdy = p.dyn.negA * f[5];
         if (!live) continue;
 
-        const float4 o = a.own[s0 + i];
+        if (!MODES) o = a.own[s0 + i];
         const float ts = o.z;
         float fax = 0.f, fay = 0.f, faz = 0.f;
         // (the z lane even in a planar scene, where vz = 0 makes it exactly +0: <Z3, false> is shorter but measured 4% slower at 8192
@@ -197,14 +232,45 @@ __device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParam
                 a.draws[s0 + i] = nd;
             }
         }
+        // MODES: arrival on the pre-move position against this tick's waypoint pops the row's queue and requests the new leg's mode,
+        // or despawns the row once its queue is exhausted (run_simulation.py:118-132, pedestrian_state.py:83-92; fsm_arrived)
+        bool park = false;
+        if (MODES) {
+            const BatchModeScene ms = a.fsm.scene[b];
+            const float ax_ = o.x - x, ay_ = o.y - y;
+            park = m == MODE_DESPAWNED;                                 // despawned earlier: stays parked
+            if (!park && fmaf(ax_, ax_, ay_ * ay_) < ms.arrive_thr2) {
+                const int e0 = a.fsm.wp_off[s0 + i], c = a.fsm.cursor[s0 + i];
+                if (c < a.fsm.wp_off[s0 + i + 1] - e0) {
+                    const int e = e0 + c;
+                    const float2 w = a.fsm.wp_xy[e];
+                    const float4 sp = a.fsm.speeds[s0 + i];
+                    o.x = w.x; o.y = w.y;
+                    a.fsm.cursor[s0 + i] = c + 1;
+                    m = fsm_request(m, a.fsm.wp_cross[e] ? MODE_CROSSING : MODE_WALKING);
+                    tgt = fsm_enter(m, tgt, sp.x, sp.y);
+                } else if (ms.despawn_on_arrival) {
+                    park = true;
+                    m = MODE_DESPAWNED;
+                    tgt = 0.0f;
+                }
+            }
+            a.own[s0 + i] = o;                                         // this tick's target in .z (and the popped waypoint)
+            a.fsm.mode[s0 + i] = m;
+            a.fsm.target[s0 + i] = tgt;
+        }
         float nx = x, ny = y, nz = z;
         if (a.flags & 1u) { nx = fmaf(p.dt, nvx, x); ny = fmaf(p.dt, nvy, y); nz = fmaf(p.dt, nvz, z); }
+        if (MODES && park) {                                           // destroy_pedestrian: parked as a ghost, keyed by the
+            const float2 pp = park_position((uint32_t)i);                // scene-local index (a one-scene batch parks where a handle does)
+            nx = pp.x; ny = pp.y; nvx = 0.f; nvy = 0.f; nvz = 0.f;
+        }
         a.pk[s0 + i] = make_float4(nx, ny, nvx, nvy);
         if (Z3) a.zv[s0 + i] = make_float2(nz, nvz);
     }
 }
 
-template <bool Z3, bool EXT>
+template <bool Z3, bool EXT, bool MODES>
 __global__ __launch_bounds__(BLOCK) void sfm_batch_tick_kernel(const BatchArgs a) {
     __shared__ BatchShared<Z3> sh;
     const int b = blockIdx.x;
@@ -217,32 +283,43 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_tick_kernel(const BatchArgs a
         for (int k = k0 + wave; k < k1; k += WAVES_PER_BLOCK) advance_vehicle(d, k, threadIdx.x & (WAVE - 1), true);
     }
     const int s0 = a.scene_off[b], n = a.scene_off[b + 1] - s0;       // 0 <= n <= BATCH_MAX_N (checked on the host)
-    if (n <= 0) return;
+    // MODES: the scene's clock, read by every thread before the barrier and advanced by thread 0 after it (a scene without
+    // pedestrians has no barrier: there only thread 0 reads it), by one step_length per tick like the handle's sim_time
+    float now = 0.0f;
+    if (MODES && (n > 0 || threadIdx.x == 0)) now = a.fsm.sim_time[b];
+    if (n <= 0) {
+        if (MODES && threadIdx.x == 0) a.fsm.sim_time[b] = now + a.prm[b].dt;
+        return;
+    }
     const BatchParams& p = a.prm[b];                                    // (read through the pointer: uniform scalar loads)
     for (int t = threadIdx.x; t < n; t += BLOCK) {
         const float4 q = a.pk[s0 + t];
         sh.pk[t] = q;
-        if (EXT && a.frame) a.frame[s0 + t] = q;                        // recording tick: the pre-tick state, coalesced
+        if ((EXT || MODES) && a.frame) a.frame[s0 + t] = q;             // recording tick: the pre-tick state, coalesced
         if (Z3) {
             const float2 zq = a.zv[s0 + t];
             sh.zv[t] = zq;
-            if (EXT && a.zframe) a.zframe[s0 + t] = zq;
+            if ((EXT || MODES) && a.zframe) a.zframe[s0 + t] = zq;
         }
         sh.r[t] = a.own[s0 + t].w;
     }
     __syncthreads();
-    if (p.rad) batch_scene<Z3, true, EXT>(a, p, sh, b, s0, n);
-    else batch_scene<Z3, false, EXT>(a, p, sh, b, s0, n);
+    if (MODES && threadIdx.x == 0) a.fsm.sim_time[b] = now + p.dt;
+    if (p.rad) batch_scene<Z3, true, EXT, MODES>(a, p, sh, b, s0, n, now);
+    else batch_scene<Z3, false, EXT, MODES>(a, p, sh, b, s0, n, now);
 }
 
-// ext: the tick redraws waypoints or records a frame (a.flags & 2, a.frame); otherwise the plain kernel
-hipError_t launch_batch_tick(bool z3, bool ext, const BatchArgs& a, int B, hipStream_t st) {
+// modes: the mode state machine is on (a.fsm; records frames too, never redraws); else ext: the tick redraws waypoints or records a
+// frame (a.flags & 2, a.frame); otherwise the plain kernel
+hipError_t launch_batch_tick(bool z3, bool ext, bool modes, const BatchArgs& a, int B, hipStream_t st) {
     if (z3) {
-        if (ext) hipLaunchKernelGGL((sfm_batch_tick_kernel<true, true>), dim3(B), dim3(BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((sfm_batch_tick_kernel<true, false>), dim3(B), dim3(BLOCK), 0, st, a);
+        if (modes) hipLaunchKernelGGL((sfm_batch_tick_kernel<true, false, true>), dim3(B), dim3(BLOCK), 0, st, a);
+        else if (ext) hipLaunchKernelGGL((sfm_batch_tick_kernel<true, true, false>), dim3(B), dim3(BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((sfm_batch_tick_kernel<true, false, false>), dim3(B), dim3(BLOCK), 0, st, a);
     } else {
-        if (ext) hipLaunchKernelGGL((sfm_batch_tick_kernel<false, true>), dim3(B), dim3(BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((sfm_batch_tick_kernel<false, false>), dim3(B), dim3(BLOCK), 0, st, a);
+        if (modes) hipLaunchKernelGGL((sfm_batch_tick_kernel<false, false, true>), dim3(B), dim3(BLOCK), 0, st, a);
+        else if (ext) hipLaunchKernelGGL((sfm_batch_tick_kernel<false, true, false>), dim3(B), dim3(BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((sfm_batch_tick_kernel<false, false, false>), dim3(B), dim3(BLOCK), 0, st, a);
     }
     return hipGetLastError();
 }

@@ -45,7 +45,7 @@ hipError_t launch_gather(const uint32_t* src, int N, const float4* pk_in, float4
 hipError_t launch_tile_bounds(const float4* pk, const float2* zv, int N, float4* box, float* vmax, hipStream_t st, int t_lo = 0,
                               int t_hi = -1);
 int probe_dpp_direction(hipStream_t st);
-hipError_t launch_batch_tick(bool z3, bool ext, const BatchArgs& a, int B, hipStream_t st);
+hipError_t launch_batch_tick(bool z3, bool ext, bool modes, const BatchArgs& a, int B, hipStream_t st);
 hipError_t launch_dynamic_boxes(float4* ctr, const int* off, const float2* local, const float2* rot, float2* pts, int M,
                                 float dt, int advance, hipStream_t st);
 }  // namespace sfm
@@ -2043,6 +2043,17 @@ struct SfmBatch {
     float2* veh_rot = nullptr;         // [M] {cos yaw, sin yaw}
     float4* veh_ctr_alt = nullptr;
     float2* veh_pts_alt = nullptr;
+    // the mode state machine (sfm_batch_set_mode_fsm, ABI 9): per row over the concatenated rows, per scene [B]
+    bool fsm_on = false;
+    uint8_t* f_mode = nullptr;
+    float* f_target = nullptr;
+    float4* f_speeds = nullptr;        // {initial_speed, crossing_speed, safety_margin, next_mode_time}
+    int* f_off = nullptr;              // [N_total+1]
+    float2* f_xy = nullptr;
+    uint8_t* f_cross = nullptr;
+    int* f_cursor = nullptr;
+    BatchModeScene* f_scene = nullptr; // [B]
+    float* f_time = nullptr;           // [B] the scenes' clocks
     std::string err;
 };
 
@@ -2102,6 +2113,16 @@ static int check_scene_csr(SfmBatch* b, const int32_t* off, const char* name, in
     return SFM_OK;
 }
 
+// back to a batch without modes (the caller synchronised the stream)
+static void free_batch_modes(SfmBatch* b) {
+    b->fsm_on = false;
+    for (void* p : {(void*)b->f_mode, (void*)b->f_target, (void*)b->f_speeds, (void*)b->f_off, (void*)b->f_xy, (void*)b->f_cross,
+                    (void*)b->f_cursor, (void*)b->f_scene, (void*)b->f_time})
+        if (p) hipFree(p);
+    b->f_mode = nullptr; b->f_target = nullptr; b->f_speeds = nullptr; b->f_off = nullptr; b->f_xy = nullptr; b->f_cross = nullptr;
+    b->f_cursor = nullptr; b->f_scene = nullptr; b->f_time = nullptr;
+}
+
 static void free_batch_geo(BatchGeoDev& g) {
     if (g.off) hipFree(g.off);
     if (g.pts) hipFree(g.pts);
@@ -2154,8 +2175,11 @@ static int check_batch_geo(SfmBatch* b, const int32_t* scene_item_off, const int
     return SFM_OK;
 }
 
-// flags a batch tick takes: SFM_TICK_INTEGRATE, and SFM_TICK_REDRAW_WAYPOINTS once the streams are set
+// flags a batch tick takes: SFM_TICK_INTEGRATE, and SFM_TICK_REDRAW_WAYPOINTS once the streams are set and while no modes are
 static int check_batch_flags(SfmBatch* b, uint32_t flags, const char* what) {
+    if (b->fsm_on && (flags & ~(uint32_t)SFM_TICK_INTEGRATE))
+        return bfail(b, SFM_ERR_INVALID, std::string("a batch ") + what + " with modes set (sfm_batch_set_mode_fsm) takes SFM_TICK_INTEGRATE "
+                                         "only: arrivals pop the waypoint queues, so SFM_TICK_REDRAW_WAYPOINTS does not apply");
     const uint32_t ok = SFM_TICK_INTEGRATE | (b->d_streams ? (uint32_t)SFM_TICK_REDRAW_WAYPOINTS : 0u);
     if (flags & ~ok)
         return bfail(b, SFM_ERR_INVALID, std::string("a batch ") + what + " takes SFM_TICK_INTEGRATE only, and "
@@ -2187,8 +2211,10 @@ static int batch_launch(SfmBatch* b, uint32_t flags, float4* frame = nullptr, fl
         a.veh_rot = b->veh_rot;
         a.veh_on = 1;
     }
+    if (b->fsm_on)
+        a.fsm = BatchModes{b->f_mode, b->f_target, b->f_speeds, b->f_off, b->f_xy, b->f_cross, b->f_cursor, b->f_scene, b->f_time};
     const bool ext = (flags & SFM_TICK_REDRAW_WAYPOINTS) || frame;
-    HIP_TRY(b, launch_batch_tick(b->z3, ext, a, b->B, b->stream));
+    HIP_TRY(b, launch_batch_tick(b->z3, ext, b->fsm_on, a, b->B, b->stream));
     if (move) {                                          // the moved half is what the next tick sees
         std::swap(b->geo[2].ctr, b->veh_ctr_alt);
         std::swap(b->geo[2].pts, b->veh_pts_alt);
@@ -2240,6 +2266,7 @@ int sfm_batch_destroy(SfmBatch* b) {
         if (b->geo[k].item_off) hipFree(b->geo[k].item_off);
     }
     free_batch_boxes(b);
+    free_batch_modes(b);
     if (b->d_prm) hipFree(b->d_prm);
     if (b->d_scene_off) hipFree(b->d_scene_off);
     if (b->pk) hipFree(b->pk);
@@ -2299,6 +2326,7 @@ int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x
         HIP_TRY(b, dev_realloc(b->draws, n));
         b->cap = n;
     }
+    free_batch_modes(b);                                          // a new crowd: its modes are set anew
     b->have_state = false;
     if (n > 0) {
         std::vector<float4> pk(n), own(n);
@@ -2506,6 +2534,85 @@ int sfm_batch_download_waypoints(SfmBatch* b, float* wx, float* wy, uint32_t* dr
         }
     }
     if (draws) HIP_TRY(b, hipMemcpy(draws, b->draws, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    return SFM_OK;
+}
+
+// The mode state machine of every row (ABI 9), the batch form of sfm_set_mode_fsm.  Everything is checked before anything is sent.
+int sfm_batch_set_mode_fsm(SfmBatch* b, const uint8_t* mode, const float* target_speed, const float* initial_speed,
+                           const float* crossing_speed, const float* safety_margin, const float* next_mode_time,
+                           const int32_t* wp_offsets, const float* wp_x, const float* wp_y, const uint8_t* wp_crossing,
+                           const int32_t* despawn_on_arrival, const float* sim_time0, const float* arrive_threshold,
+                           const float* first_vehicle_extent) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!mode) {
+        HIP_TRY(b, hipStreamSynchronize(b->stream));             // a tick in flight may still read the arrays
+        free_batch_modes(b);
+        return SFM_OK;
+    }
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    if (!target_speed || !initial_speed || !crossing_speed || !safety_margin || !next_mode_time || !wp_offsets || !despawn_on_arrival ||
+        !sim_time0 || !arrive_threshold)
+        return bfail(b, SFM_ERR_INVALID, "a required mode array is NULL");
+    const int N = b->n_total, B = b->B;
+    if (wp_offsets[0] != 0) return bfail(b, SFM_ERR_INVALID, "wp_offsets[0] must be 0");
+    for (int i = 0; i < N; ++i) {
+        if (wp_offsets[i + 1] < wp_offsets[i]) return bfail(b, SFM_ERR_INVALID, "wp_offsets must be non-decreasing (row " + std::to_string(i) + ")");
+        if (mode[i] > 4) return bfail(b, SFM_ERR_INVALID, "mode must be a PedMode value 0..4 (row " + std::to_string(i) + ")");
+    }
+    const int W = wp_offsets[N];
+    if (W > 0 && (!wp_x || !wp_y || !wp_crossing)) return bfail(b, SFM_ERR_INVALID, "waypoint arrays are NULL");
+    std::vector<BatchModeScene> sc((size_t)B);
+    std::vector<float> t0((size_t)B);
+    for (int k = 0; k < B; ++k) {
+        const float thr = arrive_threshold[k];
+        if (!std::isfinite(thr) || thr < 0.f || !std::isfinite(sim_time0[k]))
+            return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(k) + ": arrive_threshold must be finite and >= 0, sim_time0 finite");
+        sc[k] = BatchModeScene{(float)((double)thr * (double)thr),             // thr^2 as the handle rounds it
+                               first_vehicle_extent ? first_vehicle_extent[2 * k] : 0.f,
+                               first_vehicle_extent ? first_vehicle_extent[2 * k + 1] : 0.f, despawn_on_arrival[k] ? 1 : 0};
+        t0[k] = sim_time0[k];
+    }
+    const size_t n = (size_t)N;
+    std::vector<float4> speeds(n);
+    for (size_t i = 0; i < n; ++i) speeds[i] = make_float4(initial_speed[i], crossing_speed[i], safety_margin[i], next_mode_time[i]);
+    std::vector<float2> xy((size_t)(W > 0 ? W : 1));
+    for (int e = 0; e < W; ++e) xy[e] = make_float2(wp_x[e], wp_y[e]);
+    HIP_TRY(b, hipStreamSynchronize(b->stream));                 // a tick in flight may still read the old arrays
+    free_batch_modes(b);
+    HIP_TRY(b, dev_realloc(b->f_mode, n)); HIP_TRY(b, dev_realloc(b->f_target, n)); HIP_TRY(b, dev_realloc(b->f_speeds, n));
+    HIP_TRY(b, dev_realloc(b->f_off, n + 1)); HIP_TRY(b, dev_realloc(b->f_cursor, n));
+    HIP_TRY(b, dev_realloc(b->f_xy, xy.size())); HIP_TRY(b, dev_realloc(b->f_cross, xy.size()));
+    HIP_TRY(b, dev_realloc(b->f_scene, (size_t)B)); HIP_TRY(b, dev_realloc(b->f_time, (size_t)B));
+    if (n > 0) {
+        HIP_TRY(b, hipMemcpy(b->f_mode, mode, n, hipMemcpyHostToDevice));
+        HIP_TRY(b, hipMemcpy(b->f_target, target_speed, 4 * n, hipMemcpyHostToDevice));
+        HIP_TRY(b, hipMemcpy(b->f_speeds, speeds.data(), sizeof(float4) * n, hipMemcpyHostToDevice));
+        HIP_TRY(b, hipMemset(b->f_cursor, 0, 4 * n));
+    }
+    HIP_TRY(b, hipMemcpy(b->f_off, wp_offsets, 4 * (n + 1), hipMemcpyHostToDevice));
+    if (W > 0) {
+        HIP_TRY(b, hipMemcpy(b->f_xy, xy.data(), sizeof(float2) * (size_t)W, hipMemcpyHostToDevice));
+        HIP_TRY(b, hipMemcpy(b->f_cross, wp_crossing, (size_t)W, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(b, hipMemcpy(b->f_scene, sc.data(), sizeof(BatchModeScene) * (size_t)B, hipMemcpyHostToDevice));
+    HIP_TRY(b, hipMemcpy(b->f_time, t0.data(), 4 * (size_t)B, hipMemcpyHostToDevice));
+    b->fsm_on = true;
+    return SFM_OK;
+}
+
+int sfm_batch_download_modes(SfmBatch* b, uint8_t* mode, float* target_speed, int32_t* cursor, float* sim_time) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->fsm_on) return bfail(b, SFM_ERR_STATE, "sfm_batch_set_mode_fsm has not been called (or the modes were switched off)");
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    const size_t n = (size_t)b->n_total;
+    if (n > 0) {
+        if (mode) HIP_TRY(b, hipMemcpy(mode, b->f_mode, n, hipMemcpyDeviceToHost));
+        if (target_speed) HIP_TRY(b, hipMemcpy(target_speed, b->f_target, 4 * n, hipMemcpyDeviceToHost));
+        if (cursor) HIP_TRY(b, hipMemcpy(cursor, b->f_cursor, 4 * n, hipMemcpyDeviceToHost));
+    }
+    if (sim_time) HIP_TRY(b, hipMemcpy(sim_time, b->f_time, 4 * (size_t)b->B, hipMemcpyDeviceToHost));
     return SFM_OK;
 }
 

@@ -228,6 +228,22 @@ struct BatchStream {          // one scene's waypoint stream (sfm_batch_set_wayp
     float arrive_thr2;        // arrival threshold^2, rounded once from double like the handle's
     float pad;
 };
+struct BatchModeScene {       // one scene's mode constants (sfm_batch_set_mode_fsm)
+    float arrive_thr2;        // arrival threshold^2, rounded once from double like the handle's
+    float veh_ext_x, veh_ext_y;   // extent of the scene's FIRST vehicle (check_traffic.py:35-36 offsets every vehicle by it)
+    int despawn_on_arrival;
+};
+struct BatchModes {           // the mode state machine of every row (FsmArgs over the concatenated rows); mode == null: off
+    uint8_t* mode;            // [N_total] PedMode (MODE_DESPAWNED once removed)
+    float* target;            // [N_total] the mode object's target_speed (applied to the state one tick later, like the reference)
+    const float4* speeds;     // [N_total] {initial_speed, crossing_speed, safety_margin, next_mode_time}
+    const int* wp_off;        // [N_total+1] CSR of the remaining-waypoint lists
+    const float2* wp_xy;
+    const uint8_t* wp_cross;  // 1: the leg towards this waypoint crosses a road
+    int* cursor;              // [N_total] next unused entry of each list
+    const BatchModeScene* scene;  // [B]
+    float* sim_time;          // [B] each scene's clock: + its step_length per tick (read before the barrier, written by thread 0 after)
+};
 struct BatchArgs {
     const int* scene_off;     // [B+1]
     const BatchParams* prm;   // [B]
@@ -248,6 +264,7 @@ struct BatchArgs {
     const float2* veh_local;  // [P] ring points in the vehicle frame
     const float2* veh_rot;    // [M] {cos yaw, sin yaw}
     int veh_on;               // 1: boxes are set and the tick integrates; 0: the vehicles stay where they are
+    BatchModes fsm;           // the MODES instantiation only (sfm_batch_set_mode_fsm)
 };
 
 // Block-major packing for sharded runs (sfm_set_partition, sfm_reorder.hip): the row order is cut into gx columns by x, each

@@ -358,4 +358,79 @@ __device__ __forceinline__ float2 lane_nearest(const float2* __restrict__ pts, i
     return sp;
 }
 
+// ---- pedestrian modes, waypoint queues and gap acceptance (sfm_mode_kernel / fsm_arrived and the batch kernel's MODES form) ----
+__device__ __forceinline__ float2 park_position(uint32_t pid) {      // where a despawned pedestrian waits: a ghost
+    return make_float2(FAR_AWAY + FAR_STEP * (float)(pid + 1u), -FAR_AWAY);
+}
+
+// PedModeManager._activate_mode (ped_mode_manager.py:49-70): entry action of `m`; returns the new target speed.
+__device__ __forceinline__ float fsm_enter(uint8_t m, float target, float initial, float crossing) {
+    if (m == MODE_IDLE || m == MODE_CHECKING) return 0.0f;
+    if (m == MODE_WALKING) return initial;
+    if (m == MODE_CROSSING) return crossing;
+    return target;                                                    // ROAD_TO_SIDEWALK keeps the speed
+}
+// PedModeManager.set_mode (ped_mode_manager.py:37-47): two requests are diverted through an intermediate mode.
+__device__ __forceinline__ uint8_t fsm_request(uint8_t cur, uint8_t want) {
+    if (cur == MODE_WALKING && want == MODE_CROSSING) return MODE_CHECKING;
+    if (cur == MODE_CROSSING && want == MODE_WALKING) return MODE_ROAD_TO_SIDEWALK;
+    return want;
+}
+
+// Distance from p to the segment a-b (shapely LineString.distance(Point)).
+__device__ __forceinline__ float seg_dist(float2 a, float2 b, float2 p) {
+    const float abx = b.x - a.x, aby = b.y - a.y;
+    const float ab2 = fmaf(abx, abx, aby * aby);
+    float t = ab2 > 0.0f ? (fmaf(p.x - a.x, abx, (p.y - a.y) * aby) / ab2) : 0.0f;
+    t = fminf(fmaxf(t, 0.0f), 1.0f);
+    const float qx = fmaf(t, abx, a.x) - p.x, qy = fmaf(t, aby, a.y) - p.y;
+    return sqrtf(fmaf(qx, qx, qy * qy));
+}
+
+// check_traffic (check_traffic.py:7-61) in closed form: does any vehicle's extrapolated path cross the
+// pedestrian's path while the pedestrian would be there?  true = safe to cross.  The vehicles are ctr[k0 .. k1) ({cx, cy, vx, vy});
+// (ext_x, ext_y) is the extent of the crowd's (the scene's) FIRST vehicle.
+__device__ bool gap_accepted(const float4* ctr, int k0, int k1, float ext_x, float ext_y, float2 loc, float2 goal, float ped_speed,
+                             float margin) {
+    if (margin < 0.0f) return true;                                   // crosses without looking (:24)
+    if (!(ped_speed > 0.0f)) return true;
+    const float rx = goal.x - loc.x, ry = goal.y - loc.y;
+    const float time_ped = sqrtf(fmaf(rx, rx, ry * ry)) / ped_speed;
+    const float rr = fmaf(rx, rx, ry * ry);
+    for (int k = k0; k < k1; ++k) {
+        const float4 c = ctr[k];                           // {cx, cy, vx, vy}
+        const float sp = sqrtf(fmaf(c.z, c.z, c.w * c.w));
+        const float inv = sp == 0.0f ? 1.0f : 1.0f / sp;
+        // (sic) every vehicle is offset by the FIRST vehicle's extent, element-wise (check_traffic.py:35-36)
+        const float ox = c.z * inv * ext_x, oy = c.w * inv * ext_y;
+        const float2 front = make_float2(c.x + ox, c.y + oy), back = make_float2(c.x - ox, c.y - oy);
+        const float T = time_ped + margin;
+        const float2 vgoal = make_float2(fmaf(c.z, T, front.x), fmaf(c.w, T, front.y));
+        // segment loc-goal (p0 + t r) against back-vgoal (q0 + u s)
+        const float sx = vgoal.x - back.x, sy = vgoal.y - back.y;
+        const float qpx = back.x - loc.x, qpy = back.y - loc.y;
+        const float rxs = rx * sy - ry * sx, qpxr = qpx * ry - qpy * rx;
+        bool hit = false, is_seg = false;
+        float2 h0 = make_float2(0.f, 0.f), h1 = h0;
+        if (rxs != 0.0f) {
+            const float t = (qpx * sy - qpy * sx) / rxs, u = qpxr / rxs;
+            if (t >= 0.0f && t <= 1.0f && u >= 0.0f && u <= 1.0f) { hit = true; h0 = make_float2(fmaf(t, rx, loc.x), fmaf(t, ry, loc.y)); }
+        } else if (qpxr == 0.0f && rr > 0.0f) {                       // collinear: overlap interval on the pedestrian's segment
+            const float t0 = fmaf(qpx, rx, qpy * ry) / rr, t1 = t0 + fmaf(sx, rx, sy * ry) / rr;
+            const float lo = fmaxf(0.0f, fminf(t0, t1)), hi = fminf(1.0f, fmaxf(t0, t1));
+            if (lo <= hi) {
+                hit = true; is_seg = lo < hi;
+                h0 = make_float2(fmaf(lo, rx, loc.x), fmaf(lo, ry, loc.y));
+                h1 = make_float2(fmaf(hi, rx, loc.x), fmaf(hi, ry, loc.y));
+            }
+        }
+        if (!hit || sp == 0.0f) continue;
+        if (!is_seg) h1 = h0;
+        const float tti_ped = seg_dist(h0, h1, loc) / ped_speed;
+        const float tti_front = seg_dist(h0, h1, front) / sp, tti_back = seg_dist(h0, h1, back) / sp;
+        if (tti_front - margin < tti_ped && tti_ped < tti_back + margin) return false;
+    }
+    return true;
+}
+
 }  // namespace sfm

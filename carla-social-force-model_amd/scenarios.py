@@ -185,6 +185,39 @@ def advance_dynamic(sc: Scenario, dt):
     return sc
 
 
+def make_mode_plan(sc, seed, queue_len=3, idle_every=11, reckless_every=5):
+    """A synthetic mode plan for one scene (a Scenario or a scene dict), the recipe of the device mode tests: every pedestrian a
+    PedModeManager mirror walking the sidewalk (crossing speed 1.5 x target speed, safety margin 1 s), every ``reckless_every``-th
+    (i % reckless_every == 0) crossing without looking (margin -1), every ``idle_every``-th (i % idle_every == 3) IDLE at t = 0
+    (wakes up after 5 s); ``queue_len`` more waypoints each, steps of up to 4 m apart from the current one, every other leg crossing a
+    road.  The scene's first waypoints are REWRITTEN in place to within 3 m of each pedestrian, so arrivals come early.  Returns
+    (plan, managers): the plan as ``batch.plan_from_managers`` builds it, and the mirror objects themselves (for a host loop)."""
+    from .batch import plan_from_managers
+    from .host_state import PedMode, PedModeManager
+    get = (lambda k: sc[k]) if isinstance(sc, dict) else (lambda k: getattr(sc, k))
+    loc, wp, ts = get("loc"), get("waypoint"), get("target_speed")
+    n = len(loc)
+    rng = np.random.default_rng(seed)
+    managers = []
+    for i in range(n):
+        m = PedModeManager(f"ped_{i}", float(ts[i]), PedMode.WALKING_SIDEWALK, 1.5,
+                           -1.0 if reckless_every and i % reckless_every == 0 else 1.0)
+        if idle_every and i % idle_every == 3:
+            m.set_mode(PedMode.IDLE)
+        managers.append(m)
+    queues = []
+    for i in range(n):
+        p = np.asarray(wp[i], dtype=np.float64)[:2].copy()
+        lst = []
+        for k in range(queue_len):
+            p = _f32(p + rng.uniform(-4.0, 4.0, 2))
+            lst.append((np.array([p[0], p[1], 0.0]), bool((i + k) % 2)))
+        queues.append(lst)
+    if n:
+        wp[:, :2] = _f32(np.asarray(loc, dtype=np.float64)[:, :2] + rng.uniform(-3.0, 3.0, (n, 2)))
+    return plan_from_managers(managers, queues), managers
+
+
 # BASELINE.json configs (SURVEY.md section 8d): name -> (kwargs for make_scenario, enabled forces)
 ALL_FORCES = ("acceleration_force", "pedestrian_force", "border_force",
               "static_obstacle_force", "dynamic_obstacle_force")

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SFM_ABI_VERSION 8   /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles (additions only) */
+#define SFM_ABI_VERSION 9   /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles; 9: + sfm_batch_set_mode_fsm, sfm_batch_download_modes (additions only) */
 
 typedef struct SfmHandle SfmHandle;
 
@@ -274,7 +274,8 @@ int sfm_abi_version(void);
  * each, every scene with its own SfmParams (a parameter sweep is one batch) and its own borders / obstacles; each tick is ONE kernel
  * launch for the whole batch (sfm_batch.hip, a workgroup per scene).  A scene's result is bitwise the same whatever else is in the
  * batch and wherever it sits.  Larger crowds belong on a handle.  Waypoint redraw (per-scene streams) and on-device trajectories
- * are ABI 7, device-side vehicles ABI 8.  Not supported on a batch: the mode state machine, force records, sharding.  Host arrays are fp32 SoA over all scenes concatenated; scene b owns rows
+ * are ABI 7, device-side vehicles ABI 8, the mode state machine (sfm_batch_set_mode_fsm) ABI 9.  Not supported on a batch: force
+ * records, sharding.  Host arrays are fp32 SoA over all scenes concatenated; scene b owns rows
  * [scene_off[b], scene_off[b+1]).  Geometry is per-scene CSR: scene b owns polylines [scene_item_off[b], scene_item_off[b+1]) of the
  * concatenated set, whose points are offsets[k] .. offsets[k+1]-1 (offsets[0] = 0).  Errors as for a handle: a negative SfmStatus,
  * the message in sfm_batch_last_error(b) (or sfm_batch_last_error(NULL) after a failed sfm_batch_create); nothing is launched on
@@ -319,7 +320,7 @@ int sfm_batch_set_dynamic_boxes(SfmBatch* b, const int32_t* scene_item_off, cons
  * (synchronises the batch's stream); NULL skips.  Also the rings of sfm_batch_set_dynamic_obstacles. */
 int sfm_batch_download_dynamic_obstacles(SfmBatch* b, float* cx, float* cy, float* px, float* py);
 /* One tick of every scene: flags 0 or SFM_TICK_INTEGRATE, plus SFM_TICK_REDRAW_WAYPOINTS once sfm_batch_set_waypoint_streams has
- * been called (anything else is an error); v' (and x') in place. */
+ * been called and while no modes are set (anything else is an error); v' (and x') in place. */
 int sfm_batch_tick(SfmBatch* b, uint32_t flags);
 /* `ticks` integrating ticks, one launch each (SFM_TICK_INTEGRATE implied; SFM_TICK_REDRAW_WAYPOINTS as for sfm_batch_tick; other
  * flags are an error). */
@@ -340,6 +341,31 @@ int sfm_batch_download_waypoints(SfmBatch* b, float* wx, float* wy, uint32_t* dr
  * max_frames < 0, NULL frames with F > 0, NULL n_frames, zframes on a planar batch, other flags, and more than
  * SFM_BATCH_MAX_RECORD_BYTES of frames in one call (split the run). */
 #define SFM_BATCH_MAX_RECORD_BYTES (1ull << 30)
+/* The pedestrian mode state machine of every row (ABI 9), the batch form of sfm_set_mode_fsm, run inside each tick's one launch.
+ * Per-row arrays over the concatenated rows (N_total of the last sfm_batch_upload_state): mode (PedMode 0..4), the mode objects'
+ * target_speed, initial_speed, crossing_speed, safety_margin (< 0: crosses without looking), next_mode_time; each row's remaining
+ * waypoints as CSR (wp_offsets [N_total+1], wp_offsets[0] = 0, non-decreasing; wp_x, wp_y, wp_crossing [W], W = wp_offsets[N_total],
+ * may be NULL when W = 0; wp_crossing 1: the leg towards that waypoint crosses a road).  Per scene [B]: despawn_on_arrival, sim_time0
+ * (the scene's clock, finite), arrive_threshold (finite, >= 0), first_vehicle_extent [B][2] (NULL: zeros; every vehicle of the scene
+ * is offset by it in gap acceptance, like check_traffic.py:35-36).  Cursors start at 0.  Every tick, per row, in the handle's order:
+ * the mode pass (target speed of this tick = the mode object's target before its tick; IDLE wakes up once next_mode_time <= the
+ * scene's clock; CHECKING crosses once gap acceptance against the scene's vehicles, as this tick sees them, says so -- at once
+ * without vehicles; the border force is off in CROSSING and ROAD_TO_SIDEWALK), the forces and the step, then the arrival test on the
+ * pre-move position (strict <, every tick): an arrival takes the next waypoint of the row's list with the mode request of its leg,
+ * or, with the list exhausted and despawn_on_arrival, despawns the row: mode 255, target 0, parked far away keyed by its index
+ * inside the scene, velocity 0.  Each scene's clock advances by its step_length per tick.  While modes are set, sfm_batch_tick,
+ * sfm_batch_run and sfm_batch_run_recorded take SFM_TICK_INTEGRATE only (SFM_TICK_REDRAW_WAYPOINTS is refused: arrivals pop the
+ * queues).  mode = NULL switches the modes off; so does every sfm_batch_upload_state.  Refused before anything is sent: no state
+ * uploaded (SFM_ERR_STATE), a NULL required array, a mode > 4, bad wp_offsets, NULL waypoint arrays with W > 0, a threshold that is
+ * not finite or < 0, a sim_time0 that is not finite. */
+int sfm_batch_set_mode_fsm(SfmBatch* b, const uint8_t* mode, const float* target_speed, const float* initial_speed,
+                           const float* crossing_speed, const float* safety_margin, const float* next_mode_time,
+                           const int32_t* wp_offsets, const float* wp_x, const float* wp_y, const uint8_t* wp_crossing,
+                           const int32_t* despawn_on_arrival, const float* sim_time0, const float* arrive_threshold,
+                           const float* first_vehicle_extent);
+/* Modes (255 = despawned), mode target speeds and queue cursors of every row [N_total], and each scene's clock [B] (synchronises the
+ * batch's stream); NULL skips a column.  SFM_ERR_STATE while no modes are set. */
+int sfm_batch_download_modes(SfmBatch* b, uint8_t* mode, float* target_speed, int32_t* cursor, float* sim_time);
 int sfm_batch_run_recorded(SfmBatch* b, int ticks, uint32_t flags, int stride, float* frames, float* zframes, int max_frames,
                            int* n_frames);
 /* Current state of every scene (synchronises the batch's stream); NULL skips a column.  A planar batch leaves z alone and
