@@ -14,7 +14,7 @@ import numpy as np
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFM_LIB_PATH") or os.path.join(PKG_DIR, "libsfm_hip.so")   # (the override is for A/B builds of the kernels)
-ABI_VERSION = 9
+ABI_VERSION = 10
 SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_records": 5,
          **{n: 6 for n in ("sfm_batch_create", "sfm_batch_destroy", "sfm_batch_set_stream", "sfm_batch_set_params",
                            "sfm_batch_upload_state", "sfm_batch_set_borders", "sfm_batch_set_static_obstacles",
@@ -22,7 +22,8 @@ SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_
                            "sfm_batch_last_error")},
          **{n: 7 for n in ("sfm_batch_set_waypoint_streams", "sfm_batch_download_waypoints", "sfm_batch_run_recorded")},
          **{n: 8 for n in ("sfm_batch_set_dynamic_boxes", "sfm_batch_download_dynamic_obstacles")},
-         **{n: 9 for n in ("sfm_batch_set_mode_fsm", "sfm_batch_download_modes")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
+         **{n: 9 for n in ("sfm_batch_set_mode_fsm", "sfm_batch_download_modes")},
+         **{n: 10 for n in ("sfm_batch_tick_forces", "sfm_batch_run_recorded_forces")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
 
 FORCE_NAMES = ("acceleration_force", "pedestrian_force", "border_force",
                "static_obstacle_force", "dynamic_obstacle_force")
@@ -118,6 +119,10 @@ SYMBOLS = {
     # batch mode state machine (ABI 9)
     "sfm_batch_set_mode_fsm": (C.c_int, [_H, _U8, _F, _F, _F, _F, _F, _I, _F, _F, _U8, _I, _F, _F, _F]),
     "sfm_batch_download_modes": (C.c_int, [_H, _U8, _F, _I, _F]),
+    # batch force records (ABI 10)
+    "sfm_batch_tick_forces": (C.c_int, [_H, C.c_uint32, C.c_uint32, _F]),
+    "sfm_batch_run_recorded_forces": (C.c_int, [_H, C.c_int, C.c_uint32, C.c_int, C.c_uint32, _F, _F, _F, C.c_int,
+                                                C.POINTER(C.c_int)]),
 }
 
 _lib = None

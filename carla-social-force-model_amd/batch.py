@@ -1,5 +1,5 @@
 """Batched scenes: many small, independent crowds stepped by ONE kernel launch per tick (C ABI: sfm_batch_*, ABI 6; waypoint
-streams and recorded runs, ABI 7; device-side vehicles, ABI 8; pedestrian modes, ABI 9).
+streams and recorded runs, ABI 7; device-side vehicles, ABI 8; pedestrian modes, ABI 9; force records, ABI 10).
 
 Social-force models are run in bulk as many small scenes -- scenario sampling, RL environments stepped in lock-step, calibration
 sweeps over A / lambda / gamma / tau.  ``SfmBatch`` holds B scenes of 0 .. 1024 pedestrians, each with its own parameters (its own
@@ -28,6 +28,10 @@ launch every row applies its mode's target speed, wakes up from IDLE on its scen
 until gap acceptance against its scene's vehicles lets it cross, walks without the border force on the road, pops its queue on
 arrival and despawns (parked far away) once the queue runs out -- as a handle's ``set_mode_fsm`` does.  ``modes()`` and ``clocks()``
 read them back.  While modes are set, ``redraw=True`` is refused (arrivals pop the queues).
+
+Force records (ABI 10): ``tick_forces`` returns what ``Force.get_force`` gives for every scene (each force of the reference's dict
+and the total the velocity update takes) from the tick's one launch, and ``run_recorded_forces`` records them beside every frame
+of a recorded run -- for datasets of (state, force) pairs, calibration against observed accelerations, or rewards on single forces.
 """
 from __future__ import annotations
 
@@ -42,6 +46,9 @@ MAX_RECORD_BYTES = 1 << 30       # SFM_BATCH_MAX_RECORD_BYTES: frames one run_re
 from .engine import _csr, params_from_config
 
 MAX_SCENE_PEDESTRIANS = 1024     # SFM_BATCH_MAX_N
+
+# the forces a batch records, in SFM_FORCE_* index order: the reference's force-dict keys and the total (SfmEngine.forces' names)
+FORCE_RECORD_NAMES = tuple(_lib.FORCE_NAMES) + ("total",)
 
 
 def _rows(a, n, width, name, k):
@@ -353,6 +360,42 @@ def split_frames(frames, scene_off):
     return [frames[:, so[b]:so[b + 1]] for b in range(len(so) - 1)]
 
 
+def _record_names(names):
+    """Force names (None = all six) -> the selected names in index order; ValueError on an unknown or empty selection."""
+    if names is None:
+        return FORCE_RECORD_NAMES
+    names = [names] if isinstance(names, str) else list(names)
+    bad = [n for n in names if n not in FORCE_RECORD_NAMES]
+    if bad or not names:
+        raise ValueError(f"forces must be a non-empty selection of {FORCE_RECORD_NAMES}, got {names}")
+    return tuple(n for n in FORCE_RECORD_NAMES if n in names)
+
+
+def force_mask(names=None):
+    """Force names (an iterable of FORCE_RECORD_NAMES, or one name; None = all six) -> the force_mask of sfm_batch_tick_forces /
+    sfm_batch_run_recorded_forces: bit k for FORCE_RECORD_NAMES[k].  Pure NumPy; raises ValueError."""
+    return sum(1 << FORCE_RECORD_NAMES.index(n) for n in _record_names(names))
+
+
+def split_forces(buf, scene_off, names=None):
+    """A force record of the concatenated batch, (..., K, N_total, C) with the K forces of ``names`` in index order, -> a list of B
+    dicts name -> (..., N_b, C), one per scene in scene order (views).  Pure NumPy."""
+    names = _record_names(names)
+    so = np.asarray(scene_off)
+    buf = np.asarray(buf)
+    if buf.ndim < 3 or buf.shape[-3] != len(names) or buf.shape[-2] != int(so[-1]):
+        raise ValueError(f"a force record of shape {buf.shape} for {len(names)} forces of {int(so[-1])} pedestrians")
+    return [{n: buf[..., k, so[b]:so[b + 1], :] for k, n in enumerate(names)} for b in range(len(so) - 1)]
+
+
+def record_bytes(n_total, frames, planar, forces=None, zframes=False):
+    """Bytes one run_recorded_forces call records (frames, zframes and forces together; the library refuses more than
+    MAX_RECORD_BYTES).  ``forces`` as for force_mask."""
+    C_ = 2 if planar else 3
+    per_row = 16 + (8 if zframes else 0) + 4 * C_ * len(_record_names(forces))
+    return int(n_total) * int(frames) * per_row
+
+
 def n_frames(ticks, stride, max_frames=None):
     """Frames a recorded run of ``ticks`` ticks keeps: min(max_frames, ceil(ticks / stride)) (0 for invalid arguments, which the
     library refuses)."""
@@ -498,6 +541,48 @@ class SfmBatch:
         idx = np.arange(F) * int(stride)
         return (split_frames(frames[:F], self.scene_off), idx,
                 None if zframes is None else split_frames(zframes[:F], self.scene_off))
+
+    def _force_cols(self):
+        return 2 if self.planar else 3
+
+    def tick_forces(self, integrate=False, redraw=False, forces=None):
+        """One tick exactly as ``tick`` that also returns its forces: a list of B dicts name -> (N_b, C) float32, C = 2 {fx, fy}
+        for a planar batch, 3 for a 3-D one; ``forces`` a selection of FORCE_RECORD_NAMES (None: all six).  With
+        ``integrate=False`` it is Force.get_force of every scene, with nothing moved."""
+        if self.scene_off is None:
+            raise SfmLibraryError("SfmBatch.tick_forces: upload() has not been called")
+        names = _record_names(forces)
+        buf = np.zeros((len(names), int(self.scene_off[-1]), self._force_cols()), np.float32)
+        self._check(self._lib.sfm_batch_tick_forces(self._b, self._flags(integrate, redraw), force_mask(names), fptr(buf)),
+                    "sfm_batch_tick_forces")
+        return split_forces(buf, self.scene_off, names)
+
+    def run_recorded_forces(self, ticks, stride=1, redraw=False, max_frames=None, forces=None):
+        """``run_recorded`` that also records, for every recorded tick f*stride, the forces that tick computed from frame f's
+        state.  Returns (frames, ticks_idx, zframes, forces): the first three exactly as ``run_recorded``; forces a list of B dicts
+        name -> (F, N_b, C) float32."""
+        if self.scene_off is None:
+            raise SfmLibraryError("SfmBatch.run_recorded_forces: upload() has not been called")
+        names = _record_names(forces)
+        n = int(self.scene_off[-1])
+        F = n_frames(int(ticks), int(stride), None if max_frames is None else int(max_frames))
+        need = record_bytes(n, F, self.planar, names, zframes=not self.planar)
+        if need > MAX_RECORD_BYTES:                   # the library's refusal, before the host buffers are allocated
+            raise SfmLibraryError(f"sfm_batch_run_recorded_forces: the frames and forces of this call need {need} bytes, more "
+                                  f"than the {MAX_RECORD_BYTES} one call may record: split the run")
+        frames = np.zeros((F, n, 4), np.float32)
+        zframes = None if self.planar else np.zeros((F, n, 2), np.float32)
+        buf = np.zeros((F, len(names), n, self._force_cols()), np.float32)
+        got = C.c_int(0)
+        self._check(self._lib.sfm_batch_run_recorded_forces(self._b, int(ticks), self._flags(True, redraw), int(stride),
+                                                            force_mask(names), fptr(frames) if F else None,
+                                                            fptr(zframes) if F and zframes is not None else None,
+                                                            fptr(buf) if F else None, F if max_frames is None else int(max_frames),
+                                                            C.byref(got)), "sfm_batch_run_recorded_forces")
+        F = got.value
+        idx = np.arange(F) * int(stride)
+        return (split_frames(frames[:F], self.scene_off), idx,
+                None if zframes is None else split_frames(zframes[:F], self.scene_off), split_forces(buf[:F], self.scene_off, names))
 
     def set_modes(self, plans, despawn_on_arrival=True, sim_time0=0.0, arrive_thresholds=2.0, scenes=None):
         """The pedestrian mode state machine of every scene (sfm_batch_set_mode_fsm): ``plans`` one mode plan per scene (see

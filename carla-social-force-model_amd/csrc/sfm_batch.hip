@@ -17,6 +17,8 @@
 //      pre-move position and the next waypoint of the scene's counter-based stream (taking effect next tick).
 // A recording tick (frame != null) also stores the pre-tick state of every row while the scene is staged (frame f of a recorded run
 // is the state before tick f*stride).  Redraw and recording are the EXT instantiations; the plain tick is compiled without them.
+// A force-recording tick (force_rec != null, EXT or MODES) also stores each selected force of a row, and the total F, from the
+// epilogue's registers in the lane that owns the row.
 // Device-side vehicles (sfm_batch_set_dynamic_boxes, a.veh_on): in the prologue, before the barrier, the waves of workgroup b move
 // scene b's vehicles k0 + wave, k0 + wave + 4, ... by its dt (advance_vehicle, the handle's one vehicle step) from geo[2] -- what
 // this tick's dynamic-force scan reads -- into the other half of a ping-pong (a.veh_*_out), which the host swaps in after the
@@ -218,6 +220,24 @@ __device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParam
         const float Fx = (((fax + fpx) + fbx) + fsx) + fdx;
         const float Fy = (((fay + fpy) + fby) + fsy) + fdy;
         const float Fz = faz + fpz;
+        // force record: what get_force returns, from the values above (the total is F exactly); the lane owns the row, so a
+        // planar wave stores 64 consecutive float2 per force -- no barrier, no atomics, nothing read back in this launch
+        if ((EXT || MODES) && a.force_rec) {
+            const float vx6[6] = {fax, fpx, fbx, fsx, fdx, Fx}, vy6[6] = {fay, fpy, fby, fsy, fdy, Fy};
+            const float vz6[6] = {faz, fpz, 0.0f, 0.0f, 0.0f, Fz};
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                const uint32_t sl = (a.force_slots >> (4 * k)) & 15u;  // uniform
+                if (sl == 15u) continue;
+                const size_t row = (size_t)sl * (size_t)a.force_n + (size_t)(s0 + i);
+                if (Z3) {
+                    float* q = a.force_rec + 3 * row;
+                    q[0] = vx6[k]; q[1] = vy6[k]; q[2] = vz6[k];
+                } else {
+                    reinterpret_cast<float2*>(a.force_rec)[row] = make_float2(vx6[k], vy6[k]);
+                }
+            }
+        }
         float nvx, nvy, nvz;
         capped_velocity<true, false>(p, vx, vy, vz, Fx, Fy, Fz, ts, nvx, nvy, nvz);
         // arrival on the pre-move position against this tick's waypoint -> next draw of the scene's stream, keyed by the
@@ -309,8 +329,8 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_tick_kernel(const BatchArgs a
     else batch_scene<Z3, false, EXT, MODES>(a, p, sh, b, s0, n, now);
 }
 
-// modes: the mode state machine is on (a.fsm; records frames too, never redraws); else ext: the tick redraws waypoints or records a
-// frame (a.flags & 2, a.frame); otherwise the plain kernel
+// modes: the mode state machine is on (a.fsm; records frames and forces too, never redraws); else ext: the tick redraws waypoints or
+// records a frame or forces (a.flags & 2, a.frame, a.force_rec); otherwise the plain kernel
 hipError_t launch_batch_tick(bool z3, bool ext, bool modes, const BatchArgs& a, int B, hipStream_t st) {
     if (z3) {
         if (modes) hipLaunchKernelGGL((sfm_batch_tick_kernel<true, false, true>), dim3(B), dim3(BLOCK), 0, st, a);

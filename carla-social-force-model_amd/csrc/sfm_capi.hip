@@ -2036,6 +2036,8 @@ struct SfmBatch {
     size_t frames_cap = 0;
     float2* zframes = nullptr;
     size_t zframes_cap = 0;
+    float* forces = nullptr;           // sfm_batch_tick_forces / sfm_batch_run_recorded_forces: grow-only device force record
+    size_t forces_cap = 0;
     // device-side vehicles (sfm_batch_set_dynamic_boxes): geo[2].ctr / .pts hold the vehicles the next tick sees, veh_ctr_alt /
     // veh_pts_alt (the same sizes) the half an integrating tick writes; batch_launch swaps them after each such launch
     bool boxes = false;
@@ -2187,8 +2189,24 @@ static int check_batch_flags(SfmBatch* b, uint32_t flags, const char* what) {
     return SFM_OK;
 }
 
-// one tick of the whole batch; frame / zframe: this tick's frame slot of a recorded run (null: not recorded)
-static int batch_launch(SfmBatch* b, uint32_t flags, float4* frame = nullptr, float2* zframe = nullptr) {
+// force mask -> the kernel's packed slot word (nibble k: slot of force k in index order, 15: not recorded) and K = popcount(mask)
+static int batch_force_slots(SfmBatch* b, uint32_t force_mask, uint32_t* slots, int* K) {
+    if (force_mask == 0 || (force_mask & ~0x3Fu))
+        return bfail(b, SFM_ERR_INVALID, "force_mask must select forces 0..5 (bit k = SFM_FORCE_* index k, bit 5 = SFM_FORCE_TOTAL) "
+                                         "and at least one of them");
+    uint32_t w = 0xFFFFFFFFu;
+    int k = 0;
+    for (int f = 0; f <= SFM_FORCE_TOTAL; ++f)
+        if (force_mask & (1u << f)) w = (w & ~(15u << (4 * f))) | ((uint32_t)k++ << (4 * f));
+    *slots = w;
+    *K = k;
+    return SFM_OK;
+}
+
+// one tick of the whole batch; frame / zframe: this tick's frame slot of a recorded run (null: not recorded); force_rec: this
+// tick's [K][N_total][C] force record with force_slots from batch_force_slots (null: not recorded)
+static int batch_launch(SfmBatch* b, uint32_t flags, float4* frame = nullptr, float2* zframe = nullptr, float* force_rec = nullptr,
+                        uint32_t force_slots = 0xFFFFFFFFu) {
     BatchArgs a;
     memset(&a, 0, sizeof(a));
     a.scene_off = b->d_scene_off;
@@ -2213,12 +2231,71 @@ static int batch_launch(SfmBatch* b, uint32_t flags, float4* frame = nullptr, fl
     }
     if (b->fsm_on)
         a.fsm = BatchModes{b->f_mode, b->f_target, b->f_speeds, b->f_off, b->f_xy, b->f_cross, b->f_cursor, b->f_scene, b->f_time};
-    const bool ext = (flags & SFM_TICK_REDRAW_WAYPOINTS) || frame;
+    a.force_rec = force_rec;
+    a.force_n = b->n_total;
+    a.force_slots = force_slots;
+    const bool ext = (flags & SFM_TICK_REDRAW_WAYPOINTS) || frame || force_rec;
     HIP_TRY(b, launch_batch_tick(b->z3, ext, b->fsm_on, a, b->B, b->stream));
     if (move) {                                          // the moved half is what the next tick sees
         std::swap(b->geo[2].ctr, b->veh_ctr_alt);
         std::swap(b->geo[2].pts, b->veh_pts_alt);
     }
+    return SFM_OK;
+}
+
+// sfm_batch_run_recorded, and with want_forces also the [F][K][N_total][C] force record of every recorded tick
+static int batch_run_recorded(SfmBatch* b, int ticks, uint32_t flags, int stride, float* frames, float* zframes, int max_frames,
+                              int* n_frames, bool want_forces, uint32_t force_mask, float* forces) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (ticks < 0 || stride <= 0 || max_frames < 0) return bfail(b, SFM_ERR_INVALID, "ticks < 0, stride <= 0 or max_frames < 0");
+    if (!n_frames) return bfail(b, SFM_ERR_INVALID, "n_frames is NULL");
+    *n_frames = 0;
+    uint32_t slots = 0xFFFFFFFFu;
+    int K = 0;
+    if (want_forces) {
+        rc = batch_force_slots(b, force_mask, &slots, &K);
+        if (rc) return rc;
+    }
+    rc = check_batch_flags(b, flags, "recorded run");
+    if (rc) return rc;
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    if (zframes && !b->z3) return bfail(b, SFM_ERR_INVALID, "zframes on a planar batch (it has no z / vz to record)");
+    const int F = (int)std::min<long long>(max_frames, ((long long)ticks + stride - 1) / stride);
+    if (F > 0 && !frames) return bfail(b, SFM_ERR_INVALID, "frames is NULL");
+    if (F > 0 && want_forces && !forces) return bfail(b, SFM_ERR_INVALID, "forces is NULL");
+    const size_t n = (size_t)b->n_total;
+    const size_t recs = n * (size_t)F;
+    const size_t fvals = recs * (size_t)K * (b->z3 ? 3 : 2);          // per frame [K][N_total][C]
+    const size_t bytes = recs * (sizeof(float4) + (zframes ? sizeof(float2) : 0)) + fvals * sizeof(float);
+    if (bytes > SFM_BATCH_MAX_RECORD_BYTES)
+        return bfail(b, SFM_ERR_INVALID, std::string("the frames ") + (want_forces ? "and forces " : "") + "of this call need " +
+                                         std::to_string(bytes) + " bytes, more than the " +
+                                         std::to_string((unsigned long long)SFM_BATCH_MAX_RECORD_BYTES) +
+                                         " one call may record: split the run into several " +
+                                         (want_forces ? "sfm_batch_run_recorded_forces" : "sfm_batch_run_recorded") + " calls");
+    if (recs > 0) {
+        HIP_TRY(b, hipStreamSynchronize(b->stream));             // a tick in flight may still write the old buffers
+        HIP_TRY(b, dev_reserve(b->frames, b->frames_cap, recs));
+        if (zframes) HIP_TRY(b, dev_reserve(b->zframes, b->zframes_cap, recs));
+        if (fvals > 0) HIP_TRY(b, dev_reserve(b->forces, b->forces_cap, fvals));
+    }
+    const size_t fstride = fvals / (F > 0 ? (size_t)F : 1);
+    for (int t = 0, f = 0; t < ticks; ++t) {
+        const bool rec = t % stride == 0 && f < F && recs > 0;
+        rc = batch_launch(b, flags | SFM_TICK_INTEGRATE, rec ? b->frames + n * (size_t)f : nullptr,
+                          rec && zframes ? b->zframes + n * (size_t)f : nullptr,
+                          rec && fvals > 0 ? b->forces + fstride * (size_t)f : nullptr, slots);
+        if (rc) return rc;
+        if (t % stride == 0) ++f;
+    }
+    if (recs > 0) {
+        HIP_TRY(b, hipMemcpyAsync(frames, b->frames, sizeof(float4) * recs, hipMemcpyDeviceToHost, b->stream));
+        if (zframes) HIP_TRY(b, hipMemcpyAsync(zframes, b->zframes, sizeof(float2) * recs, hipMemcpyDeviceToHost, b->stream));
+        if (fvals > 0) HIP_TRY(b, hipMemcpyAsync(forces, b->forces, sizeof(float) * fvals, hipMemcpyDeviceToHost, b->stream));
+    }
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    *n_frames = F;
     return SFM_OK;
 }
 
@@ -2277,6 +2354,7 @@ int sfm_batch_destroy(SfmBatch* b) {
     if (b->d_streams) hipFree(b->d_streams);
     if (b->frames) hipFree(b->frames);
     if (b->zframes) hipFree(b->zframes);
+    if (b->forces) hipFree(b->forces);
     delete b;
     return SFM_OK;
 }
@@ -2452,6 +2530,29 @@ int sfm_batch_tick(SfmBatch* b, uint32_t flags) {
     return batch_launch(b, flags);
 }
 
+int sfm_batch_tick_forces(SfmBatch* b, uint32_t flags, uint32_t force_mask, float* forces) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    uint32_t slots = 0;
+    int K = 0;
+    rc = batch_force_slots(b, force_mask, &slots, &K);
+    if (rc) return rc;
+    if (!forces) return bfail(b, SFM_ERR_INVALID, "forces is NULL");
+    rc = check_batch_flags(b, flags, "tick");
+    if (rc) return rc;
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    const size_t vals = (size_t)K * (size_t)b->n_total * (b->z3 ? 3 : 2);
+    if (vals > 0) {
+        HIP_TRY(b, hipStreamSynchronize(b->stream));             // a tick in flight may still write the old buffer
+        HIP_TRY(b, dev_reserve(b->forces, b->forces_cap, vals));
+    }
+    rc = batch_launch(b, flags, nullptr, nullptr, vals > 0 ? b->forces : nullptr, slots);
+    if (rc) return rc;
+    if (vals > 0) HIP_TRY(b, hipMemcpyAsync(forces, b->forces, sizeof(float) * vals, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    return SFM_OK;
+}
+
 int sfm_batch_run(SfmBatch* b, int ticks, uint32_t flags) {
     int rc = bbind(b);
     if (rc) return rc;
@@ -2618,43 +2719,12 @@ int sfm_batch_download_modes(SfmBatch* b, uint8_t* mode, float* target_speed, in
 
 int sfm_batch_run_recorded(SfmBatch* b, int ticks, uint32_t flags, int stride, float* frames, float* zframes, int max_frames,
                            int* n_frames) {
-    int rc = bbind(b);
-    if (rc) return rc;
-    if (ticks < 0 || stride <= 0 || max_frames < 0) return bfail(b, SFM_ERR_INVALID, "ticks < 0, stride <= 0 or max_frames < 0");
-    if (!n_frames) return bfail(b, SFM_ERR_INVALID, "n_frames is NULL");
-    *n_frames = 0;
-    rc = check_batch_flags(b, flags, "recorded run");
-    if (rc) return rc;
-    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
-    if (zframes && !b->z3) return bfail(b, SFM_ERR_INVALID, "zframes on a planar batch (it has no z / vz to record)");
-    const int F = (int)std::min<long long>(max_frames, ((long long)ticks + stride - 1) / stride);
-    if (F > 0 && !frames) return bfail(b, SFM_ERR_INVALID, "frames is NULL");
-    const size_t n = (size_t)b->n_total;
-    const size_t recs = n * (size_t)F;
-    const size_t bytes = recs * (sizeof(float4) + (zframes ? sizeof(float2) : 0));
-    if (bytes > SFM_BATCH_MAX_RECORD_BYTES)
-        return bfail(b, SFM_ERR_INVALID, "the frames of this call need " + std::to_string(bytes) + " bytes, more than the " +
-                                         std::to_string((unsigned long long)SFM_BATCH_MAX_RECORD_BYTES) +
-                                         " one call may record: split the run into several sfm_batch_run_recorded calls");
-    if (recs > 0) {
-        HIP_TRY(b, hipStreamSynchronize(b->stream));             // a tick in flight may still write the old buffers
-        HIP_TRY(b, dev_reserve(b->frames, b->frames_cap, recs));
-        if (zframes) HIP_TRY(b, dev_reserve(b->zframes, b->zframes_cap, recs));
-    }
-    for (int t = 0, f = 0; t < ticks; ++t) {
-        const bool rec = t % stride == 0 && f < F && recs > 0;
-        rc = batch_launch(b, flags | SFM_TICK_INTEGRATE, rec ? b->frames + n * (size_t)f : nullptr,
-                          rec && zframes ? b->zframes + n * (size_t)f : nullptr);
-        if (rc) return rc;
-        if (t % stride == 0) ++f;
-    }
-    if (recs > 0) {
-        HIP_TRY(b, hipMemcpyAsync(frames, b->frames, sizeof(float4) * recs, hipMemcpyDeviceToHost, b->stream));
-        if (zframes) HIP_TRY(b, hipMemcpyAsync(zframes, b->zframes, sizeof(float2) * recs, hipMemcpyDeviceToHost, b->stream));
-    }
-    HIP_TRY(b, hipStreamSynchronize(b->stream));
-    *n_frames = F;
-    return SFM_OK;
+    return batch_run_recorded(b, ticks, flags, stride, frames, zframes, max_frames, n_frames, false, 0, nullptr);
+}
+
+int sfm_batch_run_recorded_forces(SfmBatch* b, int ticks, uint32_t flags, int stride, uint32_t force_mask, float* frames,
+                                  float* zframes, float* forces, int max_frames, int* n_frames) {
+    return batch_run_recorded(b, ticks, flags, stride, frames, zframes, max_frames, n_frames, true, force_mask, forces);
 }
 
 const char* sfm_batch_last_error(const SfmBatch* b) { return b ? b->err.c_str() : g_create_error.c_str(); }

@@ -265,6 +265,13 @@ struct BatchArgs {
     const float2* veh_rot;    // [M] {cos yaw, sin yaw}
     int veh_on;               // 1: boxes are set and the tick integrates; 0: the vehicles stay where they are
     BatchModes fsm;           // the MODES instantiation only (sfm_batch_set_mode_fsm)
+    // per-force record (sfm_batch_tick_forces, sfm_batch_run_recorded_forces; EXT and MODES instantiations only): force k (the
+    // SFM_FORCE_* index, 5 the total) of row r goes to force_rec[(slot_k * force_n + r) * C + c], C = 2 planar / 3 in 3-D, where
+    // slot_k = (force_slots >> 4k) & 15 (filled on the host; 15: not recorded).  One packed word keeps the table in one SGPR.
+    // Appended last, so the plain instantiations read every other field where they did.
+    float* force_rec;         // null: off
+    int force_n;              // N_total
+    uint32_t force_slots;
 };
 
 // Block-major packing for sharded runs (sfm_set_partition, sfm_reorder.hip): the row order is cut into gx columns by x, each

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SFM_ABI_VERSION 9   /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles; 9: + sfm_batch_set_mode_fsm, sfm_batch_download_modes (additions only) */
+#define SFM_ABI_VERSION 10  /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles; 9: + sfm_batch_set_mode_fsm, sfm_batch_download_modes; 10: + sfm_batch_tick_forces, sfm_batch_run_recorded_forces (additions only) */
 
 typedef struct SfmHandle SfmHandle;
 
@@ -274,8 +274,8 @@ int sfm_abi_version(void);
  * each, every scene with its own SfmParams (a parameter sweep is one batch) and its own borders / obstacles; each tick is ONE kernel
  * launch for the whole batch (sfm_batch.hip, a workgroup per scene).  A scene's result is bitwise the same whatever else is in the
  * batch and wherever it sits.  Larger crowds belong on a handle.  Waypoint redraw (per-scene streams) and on-device trajectories
- * are ABI 7, device-side vehicles ABI 8, the mode state machine (sfm_batch_set_mode_fsm) ABI 9.  Not supported on a batch: force
- * records, sharding.  Host arrays are fp32 SoA over all scenes concatenated; scene b owns rows
+ * are ABI 7, device-side vehicles ABI 8, the mode state machine (sfm_batch_set_mode_fsm) ABI 9, force records ABI 10.  Not
+ * supported on a batch: sharding.  Host arrays are fp32 SoA over all scenes concatenated; scene b owns rows
  * [scene_off[b], scene_off[b+1]).  Geometry is per-scene CSR: scene b owns polylines [scene_item_off[b], scene_item_off[b+1]) of the
  * concatenated set, whose points are offsets[k] .. offsets[k+1]-1 (offsets[0] = 0).  Errors as for a handle: a negative SfmStatus,
  * the message in sfm_batch_last_error(b) (or sfm_batch_last_error(NULL) after a failed sfm_batch_create); nothing is launched on
@@ -368,6 +368,26 @@ int sfm_batch_set_mode_fsm(SfmBatch* b, const uint8_t* mode, const float* target
 int sfm_batch_download_modes(SfmBatch* b, uint8_t* mode, float* target_speed, int32_t* cursor, float* sim_time);
 int sfm_batch_run_recorded(SfmBatch* b, int ticks, uint32_t flags, int stride, float* frames, float* zframes, int max_frames,
                            int* n_frames);
+/* Force records of a batch (ABI 10): Force.get_force (forces.py:28-32) of every scene, from the tick's one launch.  force_mask
+ * selects the forces: bit k = SFM_FORCE_* index k, bit 5 = SFM_FORCE_TOTAL; the K = popcount(force_mask) selected forces are stored
+ * in index order, each as [N_total][C] over the concatenated rows, C = 2 {fx, fy} for a planar batch, 3 {fx, fy, fz} for a 3-D one.
+ * Each force is what get_force returns: acceleration, the pedestrian force (-A times the pair sum), border, static, dynamic
+ * obstacle force; the total is the exact fp32 F the tick passes to the velocity update, summed in the dict order acceleration,
+ * pedestrian, border, static, dynamic (the -A products fused into their additions as the tick computes them: bitwise the float
+ * sum of the recorded parts whenever those products are exact, e.g. for A a power of two).  A force that is switched off in a
+ * scene records zeros; border, static and dynamic forces record z = 0; a planar batch has no z column for any force.  With
+ * modes set the forces are those of the tick's mode pass (its target speed; no border force in CROSSING and ROAD_TO_SIDEWALK),
+ * and a row despawned before the tick records zeros for every force.  SFM_TICK_RECORD_FORCES stays refused by sfm_batch_tick,
+ * sfm_batch_run and sfm_batch_run_recorded.  Refused before any launch, the batch staying usable: force_mask 0 or a bit above 5,
+ * NULL forces while K * F > 0, and every refusal of the call it extends. */
+/* One tick exactly as sfm_batch_tick(b, flags) (the same flags), which also writes that tick's forces into forces
+ * [K][N_total][C]; synchronises the batch's stream.  flags = 0: the forces of every scene with nothing moved. */
+int sfm_batch_tick_forces(SfmBatch* b, uint32_t flags, uint32_t force_mask, float* forces);
+/* sfm_batch_run_recorded (the same frames, F and refusals) that also stores, for every recorded tick f*stride, the forces that tick
+ * computed from the state in frame f: forces [F][K][N_total][C], copied to the host once after the last tick.
+ * SFM_BATCH_MAX_RECORD_BYTES applies to the frames and the forces together. */
+int sfm_batch_run_recorded_forces(SfmBatch* b, int ticks, uint32_t flags, int stride, uint32_t force_mask, float* frames,
+                                  float* zframes, float* forces, int max_frames, int* n_frames);
 /* Current state of every scene (synchronises the batch's stream); NULL skips a column.  A planar batch leaves z alone and
  * writes vz = 0. */
 int sfm_batch_download_state(SfmBatch* b, float* x, float* y, float* z, float* vx, float* vy, float* vz);
