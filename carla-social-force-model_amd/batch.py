@@ -1,5 +1,5 @@
 """Batched scenes: many small, independent crowds stepped by ONE kernel launch per tick (C ABI: sfm_batch_*, ABI 6; waypoint
-streams and recorded runs, ABI 7; device-side vehicles, ABI 8; pedestrian modes, ABI 9; force records, ABI 10).
+streams and recorded runs, ABI 7; device-side vehicles, ABI 8; pedestrian modes, ABI 9; force records, ABI 10; spawn schedules, ABI 11).
 
 Social-force models are run in bulk as many small scenes -- scenario sampling, RL environments stepped in lock-step, calibration
 sweeps over A / lambda / gamma / tau.  ``SfmBatch`` holds B scenes of 0 .. 1024 pedestrians, each with its own parameters (its own
@@ -32,6 +32,13 @@ read them back.  While modes are set, ``redraw=True`` is refused (arrivals pop t
 Force records (ABI 10): ``tick_forces`` returns what ``Force.get_force`` gives for every scene (each force of the reference's dict
 and the total the velocity update takes) from the tick's one launch, and ``run_recorded_forces`` records them beside every frame
 of a recorded run -- for datasets of (state, force) pairs, calibration against observed accelerations, or rewards on single forces.
+
+Spawn schedules (ABI 11): pedestrians enter a scene on the device as they leave it.  A scene keeps a fixed set of rows -- everyone
+who will ever walk in it -- and ``set_spawns`` says when each enters (``spawn_time`` on the scene's clock, ``chain`` for the
+reference's one release per spawner per tick; ``spawner.scene_from_spawners`` builds rows, mode plan and schedule from PedSpawner
+mirrors).  Until its birth tick a row is a ghost like a despawned one (``modes()`` reports 254); in that tick it is staged at its
+spawn state before anyone's forces are summed, so it pushes and is pushed from its first tick on.  ``spawns()`` reads back who
+is born and on which clock value.
 """
 from __future__ import annotations
 
@@ -330,6 +337,43 @@ def pack_modes(plans, scene_off, scenes=None):
     return out
 
 
+def pack_spawns(schedules, scene_off):
+    """One spawn schedule per scene (``None``: everyone is there from the start; or a dict ``spawn_time`` (N_b,) -- seconds on the
+    scene's clock, -inf: there from the start, +inf: never -- and ``chain`` (N_b,) 0 / 1, default zeros: 1 = the row waits for row
+    i - 1 of its scene to be born in an earlier tick) -> the per-row arguments of sfm_batch_set_spawn_schedule, concatenated in
+    scene order: (spawn_time float32 [N_total], chain uint8 [N_total]).  Pure NumPy; raises ValueError naming the scene."""
+    so = np.asarray(scene_off)
+    B = len(so) - 1
+    schedules = list(schedules)
+    if len(schedules) != B:
+        raise ValueError(f"{len(schedules)} spawn schedules for {B} scenes")
+    times, chains = [], []
+    for b, sch in enumerate(schedules):
+        n = int(so[b + 1] - so[b])
+        if sch is None:
+            times.append(np.full(n, -np.inf)); chains.append(np.zeros(n))
+            continue
+        if not isinstance(sch, dict):
+            raise ValueError(f"scene {b}: a spawn schedule must be a dict or None")
+        if "spawn_time" not in sch:
+            raise ValueError(f"scene {b}: the spawn schedule has no spawn_time")
+        t = np.asarray(sch["spawn_time"], dtype=np.float64).reshape(-1)
+        c = np.zeros(n) if sch.get("chain") is None else np.asarray(sch["chain"], dtype=np.float64).reshape(-1)
+        for key, a in (("spawn_time", t), ("chain", c)):
+            if a.shape[0] != n:
+                raise ValueError(f"scene {b}: {key} has {a.shape[0]} rows, expected {n}")
+        if np.isnan(t).any():
+            raise ValueError(f"scene {b}: spawn_time must not be NaN (-inf: there from the start, +inf: never)")
+        if n and not np.isin(c, (0.0, 1.0)).all():
+            raise ValueError(f"scene {b}: chain must hold 0 or 1")
+        if n and c[0] != 0:
+            raise ValueError(f"scene {b}: chain must be 0 on the scene's first row (it has no row to wait for)")
+        times.append(t); chains.append(c)
+    cat = lambda xs: np.concatenate(xs) if xs else np.zeros(0)
+    with np.errstate(over="ignore"):
+        return f32(cat(times)), np.ascontiguousarray(cat(chains), dtype=np.uint8)
+
+
 def mode_scene_arrays(B, despawn_on_arrival=True, sim_time0=0.0, arrive_thresholds=2.0):
     """Per-scene mode arguments -> (despawn_on_arrival int32[B], sim_time0 float32[B], arrive_threshold float32[B]).  Each argument
     is a scalar (broadcast to every scene) or B values; clocks must be finite, thresholds finite and >= 0.  Pure NumPy; raises
@@ -604,6 +648,33 @@ class SfmBatch:
                                              iptr(despawn), fptr(t0), fptr(thr), fptr(pm["first_vehicle_extent"])),
                     "sfm_batch_set_mode_fsm")
 
+    def set_spawns(self, schedules):
+        """The spawn schedule of every scene (sfm_batch_set_spawn_schedule): ``schedules`` one per scene (see ``pack_spawns``;
+        ``None`` for a scene whose rows are all there).  Needs ``set_modes`` first.  Rows that are not due on their scene's clock
+        (or wait for their predecessor) leave the live state until their birth tick.  ``upload`` and ``set_modes`` drop the
+        schedule, ``set_params`` keeps it; a second schedule without an ``upload`` + ``set_modes`` in between is refused.
+        ``schedules=None`` switches the schedule off, refused while a row is unborn."""
+        L = self._lib
+        if schedules is None:
+            self._check(L.sfm_batch_set_spawn_schedule(self._b, None, None), "sfm_batch_set_spawn_schedule")
+            return
+        if self.scene_off is None:
+            raise SfmLibraryError("SfmBatch.set_spawns: upload() has not been called")
+        t, c = pack_spawns(schedules, self.scene_off)
+        if t.shape[0] == 0:                                            # (no rows: still a call, so that the refusals are the library's)
+            t, c = np.zeros(1, np.float32), np.zeros(1, np.uint8)
+        self._check(L.sfm_batch_set_spawn_schedule(self._b, fptr(t), u8ptr(c)), "sfm_batch_set_spawn_schedule")
+
+    def spawns(self):
+        """Per scene (born (N_b,) bool, birth_time (N_b,) float32: the scene's clock before the row's birth tick -- the clock
+        at ``set_spawns`` for rows live from the start -- NaN while unborn), in scene order.  Raises SfmLibraryError while no
+        schedule is set."""
+        n = int(self.scene_off[-1]) if self.scene_off is not None else 0
+        born, when = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.float32)
+        self._check(self._lib.sfm_batch_download_spawns(self._b, u8ptr(born), fptr(when)), "sfm_batch_download_spawns")
+        so = self.scene_off if self.scene_off is not None else np.zeros(self.B + 1, np.int32)
+        return [(born[so[b]:so[b + 1]].astype(bool), when[so[b]:so[b + 1]]) for b in range(self.B)]
+
     def _modes(self):
         n = int(self.scene_off[-1]) if self.scene_off is not None else 0
         m, t, c = np.zeros(n, np.uint8), np.zeros(n, np.float32), np.zeros(n, np.int32)
@@ -613,7 +684,7 @@ class SfmBatch:
         return m, t, c, clk
 
     def modes(self):
-        """Per scene (mode (N_b,) uint8 with 255 = despawned, mode target speed (N_b,) float32, queue cursor (N_b,) int32), in
+        """Per scene (mode (N_b,) uint8 with 255 = despawned and 254 = not yet spawned, mode target speed (N_b,) float32, queue cursor (N_b,) int32), in
         scene order.  Raises SfmLibraryError while no modes are set."""
         m, t, c, _ = self._modes()
         so = self.scene_off

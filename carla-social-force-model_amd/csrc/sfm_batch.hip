@@ -28,6 +28,14 @@
 // after the barrier (target of this tick, idle wake-up on the scene's clock, gap acceptance against the scene's geo[2] items), the
 // border mask follows the mode, and after the step an arrival pops the row's queue or despawns it (parked far away, keyed by its index
 // inside the scene).  The scene's clock a.fsm.sim_time[b] is read before the barrier and advanced by thread 0 after it.
+// Spawn schedule (sfm_batch_set_spawn_schedule, the SPAWN instantiation of MODES): a row may wait off the map as a ghost (parked like a
+// despawned row, a.spn.born = 0) until the scene's clock reaches its spawn time.  The thread that stages row t decides its birth from
+// values read before the barrier (born[t], born[t - 1] of a chained row, spawn_time[t], now), stages a newborn at its spawn state --
+// so every row's pair sum of this tick sees it -- and leaves the decision in LDS (sh.st); the lane that owns the row reads it there
+// after the barrier, starts the mode machine from the row's initial mode and stores born / birth_time.  born[] is never read after
+// the barrier, so a chained row cannot see its predecessor's store of the same tick: one release per chain per tick.  A row that was
+// due when the schedule was set never left the live state (born = BORN_AT_SET); the first tick after that is its birth tick as far
+// as the row chained to it is concerned (the reference's spawn manager would release it at the top of that tick), and sets BORN_YES.
 // Planar bodies (moussaid_planar / moussaid_spatial) with the exact body (moussaid<.., EXACT>) recomputing a slice whose sum came out
 // NaN (coincident pair, or two pedestrians above one another in 3-D), as the handle's kernels do.
 // Determinism: no atomics, every order is a function of the scene alone (N_b, its rows, its polylines) -- a scene's result is
@@ -39,8 +47,16 @@
 
 namespace sfm {
 
-template <bool Z3>
-struct BatchShared {
+template <bool SPAWN>
+struct BatchSpawnShared {};                        // (empty base: the other instantiations keep their LDS size)
+template <>
+struct BatchSpawnShared<true> {
+    uint8_t st[BATCH_MAX_N];                       // SPAWN_GHOST / _LIVE / _NEWBORN / _SETTLED, decided while staging
+};
+constexpr uint8_t SPAWN_GHOST = 0, SPAWN_LIVE = 1, SPAWN_NEWBORN = 2, SPAWN_SETTLED = 3;   // (SETTLED: live, born[] still BORN_AT_SET)
+
+template <bool Z3, bool SPAWN = false>
+struct BatchShared : BatchSpawnShared<SPAWN> {
     float4 pk[BATCH_MAX_N];                        // {x, y, vx, vy}
     float2 zv[Z3 ? BATCH_MAX_N : 1];               // {z, vz}
     float r[BATCH_MAX_N];                          // radius
@@ -49,8 +65,8 @@ struct BatchShared {
 };
 
 // Pedestrian force on row i from rows [j0, j1) of the scene, without the factor -A; j == i is dropped (stateutils.py:41-49)
-template <bool Z3, bool RAD>
-__device__ __forceinline__ void batch_pair_sum(const IxConst& c, const BatchShared<Z3>& sh, int i, int j0, int j1,
+template <bool Z3, bool RAD, typename SH>
+__device__ __forceinline__ void batch_pair_sum(const IxConst& c, const SH& sh, int i, int j0, int j1,
                                                float& gx, float& gy, float& gz) {
     const float4 si = sh.pk[i];
     const float zi = Z3 ? sh.zv[i].x : 0.0f, vzi = Z3 ? sh.zv[i].y : 0.0f;
@@ -135,8 +151,8 @@ __device__ __forceinline__ void batch_geometry(const BatchArgs& a, const BatchPa
     }
 }
 
-template <bool Z3, bool RAD, bool EXT, bool MODES>
-__device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParams& p, BatchShared<Z3>& sh, int b, int s0, int n,
+template <bool Z3, bool RAD, bool EXT, bool MODES, bool SPAWN>
+__device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParams& p, BatchShared<Z3, SPAWN>& sh, int b, int s0, int n,
                                             float now) {
     const int tid = threadIdx.x;
     const int lane = tid & (WAVE - 1);
@@ -179,9 +195,12 @@ __device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParam
         uint8_t m = MODE_DESPAWNED;
         float tgt = 0.0f;
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        uint8_t born = SPAWN_LIVE;                                     // SPAWN: the staging thread's decision for this row
+        if constexpr (SPAWN) born = sh.st[ii];
         if (MODES) {
             if (live) {
-                m = a.fsm.mode[s0 + i];
+                // (an unborn row keeps its initial mode and target in a.fsm until its birth tick; here it is a ghost like a despawned row)
+                m = SPAWN && born == SPAWN_GHOST ? MODE_DESPAWNED : a.fsm.mode[s0 + i];
                 o = a.own[s0 + i];
                 if (m != MODE_DESPAWNED) {
                     tgt = a.fsm.target[s0 + i];
@@ -275,9 +294,16 @@ __device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParam
                     tgt = 0.0f;
                 }
             }
-            a.own[s0 + i] = o;                                         // this tick's target in .z (and the popped waypoint)
-            a.fsm.mode[s0 + i] = m;
-            a.fsm.target[s0 + i] = tgt;
+            if (!SPAWN || born != SPAWN_GHOST) {                       // (an unborn row's waypoint, mode and target wait as they were set)
+                a.own[s0 + i] = o;                                     // this tick's target in .z (and the popped waypoint)
+                a.fsm.mode[s0 + i] = m;
+                a.fsm.target[s0 + i] = tgt;
+            }
+            if (SPAWN && born == SPAWN_NEWBORN) {                      // born in this tick, on the clock the tick started with
+                a.spn.born[s0 + i] = BORN_YES;
+                a.spn.birth_time[s0 + i] = now;
+            }
+            if (SPAWN && born == SPAWN_SETTLED) a.spn.born[s0 + i] = BORN_YES;
         }
         float nx = x, ny = y, nz = z;
         if (a.flags & 1u) { nx = fmaf(p.dt, nvx, x); ny = fmaf(p.dt, nvy, y); nz = fmaf(p.dt, nvz, z); }
@@ -290,9 +316,10 @@ __device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParam
     }
 }
 
-template <bool Z3, bool EXT, bool MODES>
+template <bool Z3, bool EXT, bool MODES, bool SPAWN = false>
 __global__ __launch_bounds__(BLOCK) void sfm_batch_tick_kernel(const BatchArgs a) {
-    __shared__ BatchShared<Z3> sh;
+    static_assert(!SPAWN || MODES, "a spawn schedule runs on the mode state machine");
+    __shared__ BatchShared<Z3, SPAWN> sh;
     const int b = blockIdx.x;
     if (a.veh_on) {                                                     // uniform; also a scene without pedestrians: every vehicle
         const int k0 = a.geo[2].item_off[b], k1 = a.geo[2].item_off[b + 1];   // must reach the other half
@@ -313,26 +340,62 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_tick_kernel(const BatchArgs a
     }
     const BatchParams& p = a.prm[b];                                    // (read through the pointer: uniform scalar loads)
     for (int t = threadIdx.x; t < n; t += BLOCK) {
-        const float4 q = a.pk[s0 + t];
-        sh.pk[t] = q;
+        float4 q = a.pk[s0 + t];
         if ((EXT || MODES) && a.frame) a.frame[s0 + t] = q;             // recording tick: the pre-tick state, coalesced
+        // SPAWN: the birth rule, on values this launch has not written yet (born[] is stored after the barrier only); row t - 1 of
+        // a chained row is in the same scene (the host refuses chain = 1 on a scene's first row)
+        uint8_t st = SPAWN_LIVE;
+        if constexpr (SPAWN) {
+            const uint8_t bn = a.spn.born[s0 + t];
+            if (bn == BORN_NO) {
+                const bool due = a.spn.spawn_time[s0 + t] <= now && (!a.spn.chain[s0 + t] || a.spn.born[s0 + t - 1] == BORN_YES);
+                st = due ? SPAWN_NEWBORN : SPAWN_GHOST;
+                if (due) q = a.spn.pk0[s0 + t];                        // the spawn state: every row's pair sum of this tick sees it
+            } else if (bn == BORN_AT_SET) {                            // live since the schedule was set: this tick is its birth tick
+                st = SPAWN_SETTLED;                                    // for the row chained to it, which waits one tick more
+            }
+            sh.st[t] = st;
+        }
+        sh.pk[t] = q;
         if (Z3) {
-            const float2 zq = a.zv[s0 + t];
-            sh.zv[t] = zq;
+            float2 zq = a.zv[s0 + t];
             if ((EXT || MODES) && a.zframe) a.zframe[s0 + t] = zq;
+            if (SPAWN && st == SPAWN_NEWBORN) zq = a.spn.zv0[s0 + t];
+            sh.zv[t] = zq;
         }
         sh.r[t] = a.own[s0 + t].w;
     }
     __syncthreads();
     if (MODES && threadIdx.x == 0) a.fsm.sim_time[b] = now + p.dt;
-    if (p.rad) batch_scene<Z3, true, EXT, MODES>(a, p, sh, b, s0, n, now);
-    else batch_scene<Z3, false, EXT, MODES>(a, p, sh, b, s0, n, now);
+    if (p.rad) batch_scene<Z3, true, EXT, MODES, SPAWN>(a, p, sh, b, s0, n, now);
+    else batch_scene<Z3, false, EXT, MODES, SPAWN>(a, p, sh, b, s0, n, now);
+}
+
+// sfm_batch_set_spawn_schedule: the rows that are unborn when the schedule is set leave the live state -- parked where a despawned
+// row of the same scene-local index would be, velocity 0 (not hot: once per schedule).  A workgroup per scene, as the tick.
+__global__ __launch_bounds__(BLOCK) void sfm_batch_park_unborn_kernel(const int* scene_off, const uint8_t* born, float4* pk, float2* zv) {
+    const int s0 = scene_off[blockIdx.x], n = scene_off[blockIdx.x + 1] - s0;
+    for (int t = threadIdx.x; t < n; t += BLOCK) {
+        if (born[s0 + t] != BORN_NO) continue;
+        const float2 pp = park_position((uint32_t)t);
+        pk[s0 + t] = make_float4(pp.x, pp.y, 0.f, 0.f);
+        if (zv) zv[s0 + t].y = 0.f;
+    }
+}
+
+hipError_t launch_batch_park_unborn(const int* scene_off, const uint8_t* born, float4* pk, float2* zv, int B, hipStream_t st) {
+    hipLaunchKernelGGL(sfm_batch_park_unborn_kernel, dim3(B), dim3(BLOCK), 0, st, scene_off, born, pk, zv);
+    return hipGetLastError();
 }
 
 // modes: the mode state machine is on (a.fsm; records frames and forces too, never redraws); else ext: the tick redraws waypoints or
-// records a frame or forces (a.flags & 2, a.frame, a.force_rec); otherwise the plain kernel
-hipError_t launch_batch_tick(bool z3, bool ext, bool modes, const BatchArgs& a, int B, hipStream_t st) {
-    if (z3) {
+// records a frame or forces (a.flags & 2, a.frame, a.force_rec); otherwise the plain kernel.  spawn (modes only): a spawn schedule
+// is set (a.spn) -- its own instantiation, so a batch without one launches the kernel it always did
+hipError_t launch_batch_tick(bool z3, bool ext, bool modes, bool spawn, const BatchArgs& a, int B, hipStream_t st) {
+    if (modes && spawn) {
+        if (z3) hipLaunchKernelGGL((sfm_batch_tick_kernel<true, false, true, true>), dim3(B), dim3(BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((sfm_batch_tick_kernel<false, false, true, true>), dim3(B), dim3(BLOCK), 0, st, a);
+    } else if (z3) {
         if (modes) hipLaunchKernelGGL((sfm_batch_tick_kernel<true, false, true>), dim3(B), dim3(BLOCK), 0, st, a);
         else if (ext) hipLaunchKernelGGL((sfm_batch_tick_kernel<true, true, false>), dim3(B), dim3(BLOCK), 0, st, a);
         else hipLaunchKernelGGL((sfm_batch_tick_kernel<true, false, false>), dim3(B), dim3(BLOCK), 0, st, a);

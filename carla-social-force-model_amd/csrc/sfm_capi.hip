@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -45,7 +46,8 @@ hipError_t launch_gather(const uint32_t* src, int N, const float4* pk_in, float4
 hipError_t launch_tile_bounds(const float4* pk, const float2* zv, int N, float4* box, float* vmax, hipStream_t st, int t_lo = 0,
                               int t_hi = -1);
 int probe_dpp_direction(hipStream_t st);
-hipError_t launch_batch_tick(bool z3, bool ext, bool modes, const BatchArgs& a, int B, hipStream_t st);
+hipError_t launch_batch_tick(bool z3, bool ext, bool modes, bool spawn, const BatchArgs& a, int B, hipStream_t st);
+hipError_t launch_batch_park_unborn(const int* scene_off, const uint8_t* born, float4* pk, float2* zv, int B, hipStream_t st);
 hipError_t launch_dynamic_boxes(float4* ctr, const int* off, const float2* local, const float2* rot, float2* pts, int M,
                                 float dt, int advance, hipStream_t st);
 }  // namespace sfm
@@ -2056,6 +2058,15 @@ struct SfmBatch {
     int* f_cursor = nullptr;
     BatchModeScene* f_scene = nullptr; // [B]
     float* f_time = nullptr;           // [B] the scenes' clocks
+    // the spawn schedule (sfm_batch_set_spawn_schedule, ABI 11): per row; dropped with the modes it refers to
+    bool spawn_on = false;
+    bool spawn_used = false;           // a schedule was set since the last sfm_batch_set_mode_fsm: a second one is refused
+    float* s_time = nullptr;
+    uint8_t* s_chain = nullptr;
+    uint8_t* s_born = nullptr;
+    float* s_birth = nullptr;
+    float4* s_pk0 = nullptr;           // the spawn state: the rows as they were when the schedule was set
+    float2* s_zv0 = nullptr;
     std::string err;
 };
 
@@ -2115,8 +2126,18 @@ static int check_scene_csr(SfmBatch* b, const int32_t* off, const char* name, in
     return SFM_OK;
 }
 
-// back to a batch without modes (the caller synchronised the stream)
+// back to a batch without a spawn schedule (the caller synchronised the stream)
+static void free_batch_spawns(SfmBatch* b) {
+    b->spawn_on = false;
+    for (void* p : {(void*)b->s_time, (void*)b->s_chain, (void*)b->s_born, (void*)b->s_birth, (void*)b->s_pk0, (void*)b->s_zv0})
+        if (p) hipFree(p);
+    b->s_time = nullptr; b->s_chain = nullptr; b->s_born = nullptr; b->s_birth = nullptr; b->s_pk0 = nullptr; b->s_zv0 = nullptr;
+}
+
+// back to a batch without modes, and without the spawn schedule that refers to them (the caller synchronised the stream)
 static void free_batch_modes(SfmBatch* b) {
+    free_batch_spawns(b);
+    b->spawn_used = false;
     b->fsm_on = false;
     for (void* p : {(void*)b->f_mode, (void*)b->f_target, (void*)b->f_speeds, (void*)b->f_off, (void*)b->f_xy, (void*)b->f_cross,
                     (void*)b->f_cursor, (void*)b->f_scene, (void*)b->f_time})
@@ -2234,8 +2255,9 @@ static int batch_launch(SfmBatch* b, uint32_t flags, float4* frame = nullptr, fl
     a.force_rec = force_rec;
     a.force_n = b->n_total;
     a.force_slots = force_slots;
+    if (b->spawn_on) a.spn = BatchSpawn{b->s_time, b->s_chain, b->s_born, b->s_birth, b->s_pk0, b->s_zv0};
     const bool ext = (flags & SFM_TICK_REDRAW_WAYPOINTS) || frame || force_rec;
-    HIP_TRY(b, launch_batch_tick(b->z3, ext, b->fsm_on, a, b->B, b->stream));
+    HIP_TRY(b, launch_batch_tick(b->z3, ext, b->fsm_on, b->fsm_on && b->spawn_on, a, b->B, b->stream));
     if (move) {                                          // the moved half is what the next tick sees
         std::swap(b->geo[2].ctr, b->veh_ctr_alt);
         std::swap(b->geo[2].pts, b->veh_pts_alt);
@@ -2714,6 +2736,99 @@ int sfm_batch_download_modes(SfmBatch* b, uint8_t* mode, float* target_speed, in
         if (cursor) HIP_TRY(b, hipMemcpy(cursor, b->f_cursor, 4 * n, hipMemcpyDeviceToHost));
     }
     if (sim_time) HIP_TRY(b, hipMemcpy(sim_time, b->f_time, 4 * (size_t)b->B, hipMemcpyDeviceToHost));
+    if (b->spawn_on && n > 0 && (mode || target_speed || cursor)) {      // an unborn row: SFM_MODE_UNBORN, target 0, cursor 0
+        std::vector<uint8_t> born(n);
+        HIP_TRY(b, hipMemcpy(born.data(), b->s_born, n, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) {
+            if (born[i]) continue;
+            if (mode) mode[i] = MODE_UNBORN;
+            if (target_speed) target_speed[i] = 0.f;
+            if (cursor) cursor[i] = 0;
+        }
+    }
+    return SFM_OK;
+}
+
+// The spawn schedule of every row (ABI 11).  Everything is checked before anything is sent.
+int sfm_batch_set_spawn_schedule(SfmBatch* b, const float* spawn_time, const uint8_t* chain) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    const size_t n = b->have_state ? (size_t)b->n_total : 0;
+    if (!spawn_time) {
+        if (!b->spawn_on) return SFM_OK;
+        HIP_TRY(b, hipStreamSynchronize(b->stream));             // a tick in flight may still write born[]
+        std::vector<uint8_t> born(n);
+        if (n > 0) HIP_TRY(b, hipMemcpy(born.data(), b->s_born, n, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i)
+            if (!born[i])
+                return bfail(b, SFM_ERR_STATE, "the spawn schedule cannot be switched off while a row is unborn (row " + std::to_string(i) +
+                                               "): a ghost without a schedule could never enter");
+        free_batch_spawns(b);
+        return SFM_OK;
+    }
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    if (!b->fsm_on)
+        return bfail(b, SFM_ERR_STATE, "a spawn schedule needs modes: call sfm_batch_set_mode_fsm first (a newborn starts from its initial mode)");
+    if (b->spawn_used)
+        return bfail(b, SFM_ERR_STATE, "a spawn schedule has already been set on these rows: upload the state and set the modes again "
+                                       "before a second one");
+    if (n > 0 && !chain) return bfail(b, SFM_ERR_INVALID, "chain is NULL");
+    for (size_t i = 0; i < n; ++i) {
+        if (std::isnan(spawn_time[i]))
+            return bfail(b, SFM_ERR_INVALID, "spawn_time must not be NaN (row " + std::to_string(i) + "; -inf: there from the start, +inf: never)");
+        if (chain[i] > 1) return bfail(b, SFM_ERR_INVALID, "chain must be 0 or 1 (row " + std::to_string(i) + ")");
+    }
+    HIP_TRY(b, hipStreamSynchronize(b->stream));                 // the clocks and the state as the last tick left them
+    std::vector<int> off((size_t)b->B + 1);
+    std::vector<float> clk((size_t)b->B);
+    HIP_TRY(b, hipMemcpy(off.data(), b->d_scene_off, sizeof(int) * off.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(b, hipMemcpy(clk.data(), b->f_time, 4 * clk.size(), hipMemcpyDeviceToHost));
+    for (int k = 0; k < b->B; ++k)
+        if (off[k + 1] > off[k] && chain[off[k]])
+            return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(k) + ": chain must be 0 on a scene's first row (it has no row to wait for)");
+    // who is there already: spawn_time <= the scene's clock and nobody to wait for; the others wait as ghosts
+    std::vector<uint8_t> born(n);
+    std::vector<float> birth(n);
+    bool any_unborn = false;
+    for (int k = 0; k < b->B; ++k)
+        for (int i = off[k]; i < off[k + 1]; ++i) {
+            born[i] = spawn_time[i] <= clk[k] && !chain[i] ? BORN_AT_SET : BORN_NO;
+            birth[i] = born[i] ? clk[k] : std::numeric_limits<float>::quiet_NaN();
+            any_unborn = any_unborn || !born[i];
+        }
+    const size_t m = n > 0 ? n : 1;
+    HIP_TRY(b, dev_realloc(b->s_time, m)); HIP_TRY(b, dev_realloc(b->s_chain, m)); HIP_TRY(b, dev_realloc(b->s_born, m));
+    HIP_TRY(b, dev_realloc(b->s_birth, m)); HIP_TRY(b, dev_realloc(b->s_pk0, m)); HIP_TRY(b, dev_realloc(b->s_zv0, m));
+    if (n > 0) {
+        HIP_TRY(b, hipMemcpy(b->s_time, spawn_time, 4 * n, hipMemcpyHostToDevice));
+        HIP_TRY(b, hipMemcpy(b->s_chain, chain, n, hipMemcpyHostToDevice));
+        HIP_TRY(b, hipMemcpy(b->s_born, born.data(), n, hipMemcpyHostToDevice));
+        HIP_TRY(b, hipMemcpy(b->s_birth, birth.data(), 4 * n, hipMemcpyHostToDevice));
+        HIP_TRY(b, hipMemcpy(b->s_pk0, b->pk, sizeof(float4) * n, hipMemcpyDeviceToDevice));
+        if (b->z3) HIP_TRY(b, hipMemcpy(b->s_zv0, b->zv, sizeof(float2) * n, hipMemcpyDeviceToDevice));
+        if (any_unborn) {                                        // the unborn rows leave the live state (parked by the device's own rule)
+            HIP_TRY(b, launch_batch_park_unborn(b->d_scene_off, b->s_born, b->pk, b->z3 ? b->zv : nullptr, b->B, b->stream));
+            HIP_TRY(b, hipStreamSynchronize(b->stream));
+        }
+    }
+    b->spawn_on = true;
+    b->spawn_used = true;
+    return SFM_OK;
+}
+
+int sfm_batch_download_spawns(SfmBatch* b, uint8_t* born, float* birth_time) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->spawn_on) return bfail(b, SFM_ERR_STATE, "sfm_batch_set_spawn_schedule has not been called (or the schedule was dropped)");
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    const size_t n = (size_t)b->n_total;
+    if (n > 0) {
+        if (born) {
+            HIP_TRY(b, hipMemcpy(born, b->s_born, n, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < n; ++i) born[i] = born[i] != BORN_NO;
+        }
+        if (birth_time) HIP_TRY(b, hipMemcpy(birth_time, b->s_birth, 4 * n, hipMemcpyDeviceToHost));
+    }
     return SFM_OK;
 }
 

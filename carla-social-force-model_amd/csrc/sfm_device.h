@@ -59,6 +59,7 @@ struct Geo {                  // CSR polylines / rings
 // run_simulation.py:118-132 for device-resident runs.  mode == null: off.
 constexpr uint8_t MODE_IDLE = 0, MODE_WALKING = 1, MODE_CROSSING = 2, MODE_ROAD_TO_SIDEWALK = 3, MODE_CHECKING = 4,
                   MODE_DESPAWNED = 255;
+constexpr uint8_t MODE_UNBORN = 254;   // what sfm_batch_download_modes reports for a row that waits for its spawn time (SFM_MODE_UNBORN)
 struct FsmArgs {
     uint8_t* mode;            // PedMode per pedestrian (MODE_DESPAWNED once removed)
     float* target;            // the mode object's target_speed (applied to the state one tick later, like the reference)
@@ -244,6 +245,15 @@ struct BatchModes {           // the mode state machine of every row (FsmArgs ov
     const BatchModeScene* scene;  // [B]
     float* sim_time;          // [B] each scene's clock: + its step_length per tick (read before the barrier, written by thread 0 after)
 };
+constexpr uint8_t BORN_NO = 0, BORN_YES = 1, BORN_AT_SET = 2;   // AT_SET: live since the schedule was set, no tick has run on it yet
+struct BatchSpawn {           // the spawn schedule of every row (sfm_batch_set_spawn_schedule); the SPAWN instantiation only
+    const float* spawn_time;  // [N_total] on the scene's clock
+    const uint8_t* chain;     // [N_total] 1: the row waits for row - 1 of its scene to be born in an earlier tick
+    uint8_t* born;            // [N_total] BORN_*; read while staging (before the barrier), set by the lane that owns the row (after it)
+    float* birth_time;        // [N_total] the scene's clock before the birth tick; NaN while unborn
+    const float4* pk0;        // [N_total] the spawn state {x, y, vx, vy}: what the upload gave the row
+    const float2* zv0;        // [N_total] ... and {z, vz} of a 3-D batch
+};
 struct BatchArgs {
     const int* scene_off;     // [B+1]
     const BatchParams* prm;   // [B]
@@ -272,6 +282,7 @@ struct BatchArgs {
     float* force_rec;         // null: off
     int force_n;              // N_total
     uint32_t force_slots;
+    BatchSpawn spn;           // the SPAWN instantiation only (appended last for the same reason)
 };
 
 // Block-major packing for sharded runs (sfm_set_partition, sfm_reorder.hip): the row order is cut into gx columns by x, each

@@ -218,6 +218,43 @@ def make_mode_plan(sc, seed, queue_len=3, idle_every=11, reckless_every=5):
     return plan_from_managers(managers, queues), managers
 
 
+def make_spawn_plan(sc, seed, dt=0.05, t0=0.0, present=0.35, n_spawners=4, horizon=4.0):
+    """A synthetic spawn schedule for one scene (a Scenario or a scene dict), the recipe of the batch spawn tests: the first
+    ``present`` fraction of the rows is there from the start (``spawn_time = -inf``), the others are dealt in row order to
+    ``n_spawners`` spawners of consecutive rows (``chain = 1`` on all but a spawner's first row).  Spawner 0 starts two steps
+    BEHIND the clock ``t0`` with an interval of 0.4 steps (a backlog: one release per tick), spawner 1 has an interval of 0.4 steps
+    too but starts inside the run, the others intervals of 2.5 to 6 steps; starts lie within ``horizon`` / 2 seconds of ``t0`` and
+    intervals are scaled so that every spawner is done inside about ``horizon`` seconds.  Release times accumulate in float64 and are rounded to float32
+    once, as ``spawner.scene_from_spawners`` does.  ``present = 0`` gives a scene in which everybody is unborn at first (spawner 0
+    then starts inside the run as well).  The rows themselves (positions, waypoints, modes) are the scene's.  Returns the dict
+    ``SfmBatch.set_spawns`` takes: ``spawn_time`` float32 (N,), ``chain`` uint8 (N,)."""
+    get = (lambda k: sc[k]) if isinstance(sc, dict) else (lambda k: getattr(sc, k))
+    n = len(get("loc"))
+    rng = np.random.default_rng(seed)
+    times = np.full(n, -np.inf)
+    chain = np.zeros(n, dtype=np.uint8)
+    n0 = min(n, int(round(present * n)))
+    rest = n - n0
+    groups = min(n_spawners, rest)
+    bounds = n0 + (np.arange(groups + 1) * rest) // max(groups, 1)
+    for g in range(groups):
+        lo, hi = int(bounds[g]), int(bounds[g + 1])
+        q = hi - lo
+        if g == 0 and present > 0:
+            start, interval = t0 - 2.0 * dt, 0.4 * dt
+        else:
+            start = t0 + float(rng.uniform(0.5 * dt, 0.5 * horizon))
+            interval = 0.4 * dt if g == 1 else float(rng.uniform(2.5, 6.0)) * dt
+            interval = min(interval, max(0.4 * dt, 0.5 * horizon / max(q, 1)))
+        t = float(start)
+        for i in range(lo, hi):
+            times[i] = t
+            t += interval
+            chain[i] = 1 if i > lo else 0
+    with np.errstate(over="ignore"):
+        return {"spawn_time": times.astype(np.float32), "chain": chain}
+
+
 # BASELINE.json configs (SURVEY.md section 8d): name -> (kwargs for make_scenario, enabled forces)
 ALL_FORCES = ("acceleration_force", "pedestrian_force", "border_force",
               "static_obstacle_force", "dynamic_obstacle_force")

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SFM_ABI_VERSION 10  /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles; 9: + sfm_batch_set_mode_fsm, sfm_batch_download_modes; 10: + sfm_batch_tick_forces, sfm_batch_run_recorded_forces (additions only) */
+#define SFM_ABI_VERSION 11  /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles; 9: + sfm_batch_set_mode_fsm, sfm_batch_download_modes; 10: + sfm_batch_tick_forces, sfm_batch_run_recorded_forces; 11: + sfm_batch_set_spawn_schedule, sfm_batch_download_spawns, SFM_MODE_UNBORN (additions only) */
 
 typedef struct SfmHandle SfmHandle;
 
@@ -274,7 +274,7 @@ int sfm_abi_version(void);
  * each, every scene with its own SfmParams (a parameter sweep is one batch) and its own borders / obstacles; each tick is ONE kernel
  * launch for the whole batch (sfm_batch.hip, a workgroup per scene).  A scene's result is bitwise the same whatever else is in the
  * batch and wherever it sits.  Larger crowds belong on a handle.  Waypoint redraw (per-scene streams) and on-device trajectories
- * are ABI 7, device-side vehicles ABI 8, the mode state machine (sfm_batch_set_mode_fsm) ABI 9, force records ABI 10.  Not
+ * are ABI 7, device-side vehicles ABI 8, the mode state machine (sfm_batch_set_mode_fsm) ABI 9, force records ABI 10, spawn schedules ABI 11.  Not
  * supported on a batch: sharding.  Host arrays are fp32 SoA over all scenes concatenated; scene b owns rows
  * [scene_off[b], scene_off[b+1]).  Geometry is per-scene CSR: scene b owns polylines [scene_item_off[b], scene_item_off[b+1]) of the
  * concatenated set, whose points are offsets[k] .. offsets[k+1]-1 (offsets[0] = 0).  Errors as for a handle: a negative SfmStatus,
@@ -363,9 +363,37 @@ int sfm_batch_set_mode_fsm(SfmBatch* b, const uint8_t* mode, const float* target
                            const int32_t* wp_offsets, const float* wp_x, const float* wp_y, const uint8_t* wp_crossing,
                            const int32_t* despawn_on_arrival, const float* sim_time0, const float* arrive_threshold,
                            const float* first_vehicle_extent);
-/* Modes (255 = despawned), mode target speeds and queue cursors of every row [N_total], and each scene's clock [B] (synchronises the
- * batch's stream); NULL skips a column.  SFM_ERR_STATE while no modes are set. */
+/* Modes (255 = despawned, 254 = SFM_MODE_UNBORN: waiting for its spawn time, with target 0 and cursor 0), mode target speeds and
+ * queue cursors of every row [N_total], and each scene's clock [B] (synchronises the batch's stream); NULL skips a column.
+ * SFM_ERR_STATE while no modes are set. */
 int sfm_batch_download_modes(SfmBatch* b, uint8_t* mode, float* target_speed, int32_t* cursor, float* sim_time);
+/* Pedestrian spawners on the device (ABI 11): the other half of the reference's life cycle (PedSpawnManager.tick at the top of every
+ * tick, pedestrian_spawner.py:46-59, 219-229), inside each tick's one launch.  A scene keeps its N_b rows -- everyone who will ever
+ * walk in it -- and the schedule says when each enters: spawn_time [N_total] on the scene's clock (-inf: there from the start, +inf:
+ * never; NaN refused) and chain [N_total] (1: the row waits for row - 1 of its scene, which must have been born in an EARLIER tick:
+ * one release per spawner per tick; 0 on every scene's first row; a row that is live when the schedule is set counts as born in the
+ * first tick after that, as the reference's spawn manager would release it at the top of that tick).  Birth rule, in every tick form (integrating or not), with `now`
+ * the scene's clock before the tick (what sfm_batch_download_modes returns before it): an unborn row i is born iff spawn_time[i] <= now
+ * (fp32) and, if chain[i], row i - 1 was born before this tick.  A newborn takes part in its birth tick: it is staged at its spawn
+ * state, so every row's pedestrian force of that tick includes it, its own v' (and x') come from that tick, and its mode machine
+ * runs from its initial mode.  The spawn state is what sfm_batch_upload_state gave the row (position, velocity, z / vz, radius) and
+ * what sfm_batch_set_mode_fsm gave it (waypoint, mode, speeds, margin, queue).  Setting the schedule decides who is there already
+ * (spawn_time <= the scene's clock now and chain = 0: live, birth time = that clock; a schedule of such rows only leaves the batch
+ * bit for bit what it is without one) and moves the others out of the live state: until birth they are ghosts like despawned rows
+ * (parked far away keyed by the index inside the scene, velocity 0, no force on anyone, skipped by the mode pass; waypoint, queue
+ * and cursor untouched).  While a row is unborn sfm_batch_download_state gives the parked ghost, sfm_batch_download_modes mode 254 /
+ * target 0 / cursor 0, recorded frames the ghost (the frame of the birth tick too: frames hold the state before their tick) and
+ * force records zeros.  Needs modes (SFM_ERR_STATE otherwise); sfm_batch_upload_state and sfm_batch_set_mode_fsm (mode = NULL
+ * included) drop the schedule, sfm_batch_set_params keeps it.  A second schedule on the same rows is refused (SFM_ERR_STATE): upload
+ * and set the modes again first.  spawn_time = NULL switches the schedule off, refused (SFM_ERR_STATE) while a row is unborn.
+ * Refused before anything is sent, the batch staying as it was: NULL chain, a NaN spawn_time, a chain value > 1, chain = 1 on a
+ * scene's first row. */
+#define SFM_MODE_UNBORN 254
+int sfm_batch_set_spawn_schedule(SfmBatch* b, const float* spawn_time, const uint8_t* chain);
+/* Who has been born [N_total] (1 / 0) and the scene clock before each row's birth tick (the clock at which the schedule was set for
+ * rows live from the start; NaN while unborn); synchronises the batch's stream; NULL skips a column.  SFM_ERR_STATE while no
+ * schedule is set. */
+int sfm_batch_download_spawns(SfmBatch* b, uint8_t* born, float* birth_time);
 int sfm_batch_run_recorded(SfmBatch* b, int ticks, uint32_t flags, int stride, float* frames, float* zframes, int max_frames,
                            int* n_frames);
 /* Force records of a batch (ABI 10): Force.get_force (forces.py:28-32) of every scene, from the tick's one launch.  force_mask
