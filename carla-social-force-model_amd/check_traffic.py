@@ -2,9 +2,9 @@
 
 Closed-form restatement of the reference's check_traffic (check_traffic.py:7-61), which leans on
 shapely's LineString.intersection / distance.  Scalar host logic on the handful of pedestrians in
-CHECKING_TRAFFIC mode; it is not on the device path.  Parity status: *unpinned* -- shapely is absent from
-this image, so no golden vectors could be produced from the reference for this function; the tests pin it
-against hand-derived cases instead.
+CHECKING_TRAFFIC mode; the device twin is gap_accepted in csrc/sfm_interaction.h.  Parity status: pinned by tests/golden/traffic/gap_*.npz,
+decisions the reference's own function returned with an exact-rational stand-in for shapely's two primitives
+(tests/golden/_standins/); that stand-in's definition of segment intersection / distance is what is still taken on trust.
 
 Kept bug-compatible: the reference offsets every vehicle's front/back by ``vehicle_extents[:][0]``
 (check_traffic.py:35-36), i.e. by the *first* vehicle's (x,y) extent, element-wise on the direction.
@@ -33,6 +33,8 @@ def _segment_intersection(p0, p1, q0, q1):
         ss = float(s @ s)
         if ss == 0.0:
             return p0 if np.array_equal(p0, q0) else None
+        if (p0[0] - q0[0]) * s[1] - (p0[1] - q0[1]) * s[0] != 0.0:   # (r = 0 makes qpxr vacuous: the point is off q's line)
+            return None
         u = float((p0 - q0) @ s) / ss
         return p0 if 0.0 <= u <= 1.0 else None
     t0 = float(qp @ r) / rr

@@ -423,6 +423,9 @@ __device__ bool gap_accepted(const float4* ctr, int k0, int k1, float ext_x, flo
                 h0 = make_float2(fmaf(lo, rx, loc.x), fmaf(lo, ry, loc.y));
                 h1 = make_float2(fmaf(hi, rx, loc.x), fmaf(hi, ry, loc.y));
             }
+        } else if (rr == 0.0f) {                                      // the pedestrian stands on its waypoint: a point against the path
+            const float ss = fmaf(sx, sx, sy * sy), w = -fmaf(qpx, sx, qpy * sy);      // w = (loc - back) . s
+            if (ss > 0.0f ? (qpx * sy - qpy * sx == 0.0f && w >= 0.0f && w <= ss) : (qpx == 0.0f && qpy == 0.0f)) { hit = true; h0 = loc; }
         }
         if (!hit || sp == 0.0f) continue;
         if (!is_seg) h1 = h0;

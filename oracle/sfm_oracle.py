@@ -485,8 +485,9 @@ def free_step(loc, vel, waypoint, target_speed, radius, crossing, draws, geom, p
 
 # --------------------------------------------------------------------------------------------------
 # independent float64 restatements used as checkers of the product's host twins and
-# device code.  PARITY UNPINNED: obstacles.py needs carla and check_traffic.py needs shapely, neither is installable here, and
-# the reference holds no fixtures for them -- these follow the source text and the documented semantics of the two libraries.
+# device code.  Pinned by tests/golden/traffic/*.npz: outputs of the reference's own generate_ellipse_border and check_traffic, run by
+# tests/golden/make_golden_traffic.py with stand-ins for carla and shapely (neither is installable here).  Still taken on trust: the
+# stand-ins' definition of two library primitives -- two-segment intersection / distance, and a yaw rotation.
 # --------------------------------------------------------------------------------------------------
 def ellipse_ring(center, yaw, extent_x, extent_y, resolution=0.1, size_factor=np.sqrt(2.0)):
     """generate_ellipse_border (obstacles.py:269-281): ``samples = max(6, int((2 ex + 2 ey) / resolution))`` points
@@ -522,6 +523,8 @@ def _segments_meet(p0, p1, q0, q1):
         M = float(d2 @ d2)
         if M == 0.0:
             return [p0] if (p0 == q0).all() else []
+        if _cross2(p0 - q0, d2) != 0.0:                      # (r = 0 makes the test above vacuous: the point is off q's line)
+            return []
         u = float((p0 - q0) @ d2) / M
         return [p0] if 0.0 <= u <= 1.0 else []
     a, b = sorted((float((q0 - p0) @ d1) / L, float((q1 - p0) @ d1) / L))   # q's extent along p's parameter
@@ -565,3 +568,53 @@ def gap_accepted(ped_loc, ped_goal, ped_speed, safety_margin, vehicle_locs, vehi
             if _dist_to(meet, front) / speed - safety_margin < tti_ped < _dist_to(meet, back) / speed + safety_margin:
                 return False
     return True
+
+
+def gap_slack(ped_loc, ped_goal, ped_speed, safety_margin, vehicle_locs, vehicle_velocities, vehicle_extents):
+    """How far ``gap_accepted``'s decision for this case is from flipping: the smallest normalised distance of a comparison that
+    would change the outcome from its boundary.  Per vehicle, with s = sin of the angle between the two paths (|r x s| / (|r||s|)):
+    the hit test contributes min(|t|, |1-t|, |u|, |1-u|) * s when the paths meet, the largest violation * s when they do not (every
+    violated bound has to give way), and s itself (t and u are conditioned like 1 / s); a hit of a moving vehicle contributes the two
+    inequalities of :58 divided by the largest time involved, again * s (the meeting point moves like 1 / s) -- the smaller of
+    the two when the vehicle refuses, the violated one(s) when it does not.  A vehicle that cannot refuse whatever is perturbed
+    (at rest with a zero-length path) contributes inf; exactly parallel paths of a moving vehicle contribute 0: no perturbation
+    bound exists for them, they belong to hand-built exact cases.  An accepted case takes the minimum over its vehicles, a refused
+    one the maximum over the vehicles that refuse; a negative margin gives inf."""
+    ped_loc, ped_goal = np.asarray(ped_loc, dtype=np.float64)[:2], np.asarray(ped_goal, dtype=np.float64)[:2]
+    if not safety_margin >= 0:
+        return np.inf
+    r = ped_goal - ped_loc
+    time_ped = np.linalg.norm(r) / ped_speed
+    locs = np.asarray(vehicle_locs, dtype=np.float64).reshape(-1, 2)
+    vels = np.asarray(vehicle_velocities, dtype=np.float64).reshape(-1, 2)
+    dirs, _ = unit_and_norm(vels)
+    first_extent = np.asarray(vehicle_extents, dtype=np.float64).reshape(-1, 2)[0]
+    accept, refuse = [np.inf], []
+    for loc, vel, d in zip(locs, vels, dirs):
+        front, back = loc + d * first_extent, loc - d * first_extent
+        s = front + vel * (time_ped + safety_margin) - back
+        speed = np.linalg.norm(vel)
+        den = _cross2(r, s)
+        if den == 0.0:
+            accept.append(np.inf if speed == 0 and not s.any() else 0.0)
+            continue
+        sin = abs(den) / (np.linalg.norm(r) * np.linalg.norm(s))
+        t, u = _cross2(back - ped_loc, s) / den, _cross2(back - ped_loc, r) / den
+        out = max(-t, t - 1.0, -u, u - 1.0)
+        if out > 0.0:                                                            # no hit: all violated bounds must give way
+            accept.append(min(sin, out * sin))
+            continue
+        hit_slack = min(sin, -out * sin)
+        if speed == 0:
+            accept.append(np.inf)
+            continue
+        x = ped_loc + t * r
+        tti_ped = np.hypot(*(x - ped_loc)) / ped_speed
+        tti_front, tti_back = np.hypot(*(x - front)) / speed, np.hypot(*(x - back)) / speed
+        a, b = tti_ped - (tti_front - safety_margin), (tti_back + safety_margin) - tti_ped
+        scale = max(tti_ped, tti_front, tti_back, safety_margin, 1e-300)
+        if a > 0 and b > 0:
+            refuse.append(min(hit_slack, min(a, b) / scale * sin))
+        else:
+            accept.append(max(-a, -b) / scale * sin)
+    return float(max(refuse)) if refuse else float(min(accept))

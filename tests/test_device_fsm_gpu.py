@@ -3,8 +3,9 @@ inside sfm_run, against the host loop of the reference (its order, run_simulatio
 pedestrian_simulation.py:57-83) built from the host-side mirror classes and the float64 oracle.  The host
 state is re-synchronised to the device's fp32 state every tick, so each tick's decisions are compared from
 identical inputs; decisions within fp32 noise of their threshold are excluded.  The gap-acceptance decisions the device is
-held to are the oracle's (oracle.sfm_oracle.gap_accepted); the reference holds no fixtures for check_traffic.py and shapely
-is absent here, so that oracle leg -- and with it row f3 -- stays PARITY UNPINNED."""
+held to are the oracle's (oracle.sfm_oracle.gap_accepted); that oracle, and the device directly, are held to decisions of the reference's
+own check_traffic in tests/test_traffic_golden.py and tests/test_gap_acceptance_gpu.py (what stays assumed there: a stand-in's definition
+of shapely's segment intersection / distance)."""
 import numpy as np
 import pytest
 

@@ -218,7 +218,7 @@ def test_interior_shard_bounds_are_whole_tiles_for_any_size():
 def test_gap_acceptance_and_vehicle_rings_agree_with_the_oracles_restatement():
     """SURVEY.md section 8f rows 2 and 3.  Neither obstacles.py (carla) nor check_traffic.py (shapely) can run here and the
     reference holds no fixtures for them, so the product's host code is checked against an independent float64 restatement in
-    oracle/ written from the reference source (parity unpinned, stated in both places): 4000 random crossings incl. axis-aligned
+    oracle/ written from the reference source (the restatement itself is held to the reference's outputs in test_traffic_golden.py): 4000 random crossings incl. axis-aligned
     and collinear ones, and the ellipse rings of random vehicles."""
     from types import SimpleNamespace
     from carla_social_force_model_amd import scenarios
