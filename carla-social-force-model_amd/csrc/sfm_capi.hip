@@ -297,10 +297,15 @@ static IxConst fold(const SfmInteraction& s) {
 
 static int check_params(const SfmParams* p, const char** why) {
     if (!p) { *why = "params is NULL"; return 0; }
-    if (!(p->step_length > 0.f)) { *why = "step_length must be > 0"; return 0; }
-    if (!(p->tau > 0.f)) { *why = "tau must be > 0"; return 0; }
-    if (p->enabled[SFM_FORCE_PEDESTRIAN] && !(p->pedestrian.gamma != 0.f)) { *why = "pedestrian.gamma is 0"; return 0; }
-    if (p->enabled[SFM_FORCE_BORDER] && !(p->border_b != 0.f)) { *why = "border_force.b is 0"; return 0; }
+    // ("Parameters the library refuses": a decay length gamma or b <= 0 turns exp(-d / B) into a growth that overflows
+    //  fp32 within a few metres, where the float64 reference still holds a number; nothing the kernels return there can match it)
+    if (!(p->step_length > 0.f) || std::isinf(p->step_length)) { *why = "step_length must be > 0 and finite"; return 0; }
+    if (!(p->tau > 0.f) || std::isinf(p->tau)) { *why = "tau must be > 0 and finite"; return 0; }
+    if (!std::isfinite(p->max_speed_factor)) { *why = "max_speed_factor must be finite"; return 0; }
+    if (p->enabled[SFM_FORCE_PEDESTRIAN] && !(p->pedestrian.gamma > 0.f)) { *why = "pedestrian_force.gamma must be > 0"; return 0; }
+    if (p->enabled[SFM_FORCE_BORDER] && !(p->border_b > 0.f)) { *why = "border_force.b must be > 0"; return 0; }
+    if (p->enabled[SFM_FORCE_STATIC_OBSTACLE] && !(p->static_obstacle.gamma > 0.f)) { *why = "static_obstacle_force.gamma must be > 0"; return 0; }
+    if (p->enabled[SFM_FORCE_DYNAMIC_OBSTACLE] && !(p->dynamic_obstacle.gamma > 0.f)) { *why = "dynamic_obstacle_force.gamma must be > 0"; return 0; }
     return 1;
 }
 

@@ -13,7 +13,8 @@ import numpy as np
 
 import _golden_io as gio
 
-CASES = ["all_s0_n16", "all_s1_n64", "modes_n32", "c1_n64", "coincident_n8", "zspread_n64"]
+CASES = ["all_s0_n16", "all_s1_n64", "modes_n32", "c1_n64", "coincident_n8", "zspread_n64", "ps_shortrange_rad_n48",
+         "ps_integrate_fine_n32"]
 
 
 def _is_reference_output(key):

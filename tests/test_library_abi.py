@@ -53,3 +53,32 @@ def test_product_never_imports_oracle():
             if f.endswith((".py", ".hip", ".h", ".cpp")):
                 txt = open(os.path.join(dirpath, f)).read()
                 assert "import oracle" not in txt and "from oracle" not in txt and "sfm_oracle" not in txt, f
+
+
+def test_parameters_the_formulas_cannot_honour_are_refused():
+    """a decay length <= 0 of an enabled force and non-finite integration constants are refused by
+    sfm_create with a message that names the parameter -- before any device is touched, so this runs without a GPU."""
+    from carla_social_force_model_amd.engine import params_from_config
+    lib = _lib.load()
+    for mutate, word in ((lambda p: setattr(p.pedestrian, "gamma", -0.35), "pedestrian_force.gamma"),
+                         (lambda p: setattr(p.pedestrian, "gamma", 0.0), "pedestrian_force.gamma"),
+                         (lambda p: setattr(p, "border_b", -0.3), "border_force.b"),
+                         (lambda p: setattr(p.static_obstacle, "gamma", -0.4), "static_obstacle_force.gamma"),
+                         (lambda p: setattr(p.dynamic_obstacle, "gamma", float("nan")), "dynamic_obstacle_force.gamma"),
+                         (lambda p: setattr(p, "tau", float("inf")), "tau"),
+                         (lambda p: setattr(p, "tau", 0.0), "tau"),
+                         (lambda p: setattr(p, "max_speed_factor", float("nan")), "max_speed_factor"),
+                         (lambda p: setattr(p, "step_length", float("inf")), "step_length")):
+        p = params_from_config(default_sfm_config(), 0.05)
+        mutate(p)
+        h = ctypes.c_void_p()
+        assert lib.sfm_create(ctypes.byref(p), 0, ctypes.byref(h)) == -1 and not h.value, word
+        assert word in lib.sfm_last_error(None).decode(), (word, lib.sfm_last_error(None))
+    # ... and a force that is switched off is not looked at: the refusal then comes from the missing device, not the parameter
+    p = params_from_config(default_sfm_config(("acceleration_force", "pedestrian_force")), 0.05)
+    p.border_b = -1.0
+    h = ctypes.c_void_p()
+    rc = lib.sfm_create(ctypes.byref(p), 0, ctypes.byref(h))
+    assert rc == 0 or "border_force" not in lib.sfm_last_error(None).decode()
+    if rc == 0:
+        lib.sfm_destroy(h)
