@@ -1,5 +1,6 @@
 """Batched scenes: many small, independent crowds stepped by ONE kernel launch per tick (C ABI: sfm_batch_*, ABI 6; waypoint
-streams and recorded runs, ABI 7; device-side vehicles, ABI 8; pedestrian modes, ABI 9; force records, ABI 10; spawn schedules, ABI 11).
+streams and recorded runs, ABI 7; device-side vehicles, ABI 8; pedestrian modes, ABI 9; force records, ABI 10; spawn schedules, ABI 11;
+vehicle tracks, ABI 12).
 
 Social-force models are run in bulk as many small scenes -- scenario sampling, RL environments stepped in lock-step, calibration
 sweeps over A / lambda / gamma / tau.  ``SfmBatch`` holds B scenes of 0 .. 1024 pedestrians, each with its own parameters (its own
@@ -39,6 +40,12 @@ reference's one release per spawner per tick; ``spawner.scene_from_spawners`` bu
 mirrors).  Until its birth tick a row is a ghost like a despawned one (``modes()`` reports 254); in that tick it is staged at its
 spawn state before anyone's forces are summed, so it pushes and is pushed from its first tick on.  ``spawns()`` reads back who
 is born and on which clock value.
+
+Vehicle tracks (ABI 12): the reference's scripted traffic.  ``set_vehicle_tracks`` gives a device-side vehicle a list of keyframes
+(centre, yaw, speed) and a first tick; every integrating tick teleports it to the keyframe of that tick inside the tick's one launch
+-- it can turn, brake, stop and pull away -- and outside its list it is absent: centre and ring at +inf, velocity 0, no force on
+anyone and no say in gap acceptance.  ``vehicle_tracks()`` reads back the tick counter and who is present;
+``scenarios.place_tracked`` is the host twin and ``vehicle_spawner.tracks_from_spawners`` builds tracks from VehicleSpawner mirrors.
 """
 from __future__ import annotations
 
@@ -53,6 +60,7 @@ MAX_RECORD_BYTES = 1 << 30       # SFM_BATCH_MAX_RECORD_BYTES: frames one run_re
 from .engine import _csr, params_from_config
 
 MAX_SCENE_PEDESTRIANS = 1024     # SFM_BATCH_MAX_N
+MAX_TRACK_KEYS = 1 << 22         # SFM_BATCH_MAX_TRACK_KEYS: keyframes one set_vehicle_tracks call may hold
 
 # the forces a batch records, in SFM_FORCE_* index order: the reference's force-dict keys and the total (SfmEngine.forces' names)
 FORCE_RECORD_NAMES = tuple(_lib.FORCE_NAMES) + ("total",)
@@ -374,6 +382,85 @@ def pack_spawns(schedules, scene_off):
         return f32(cat(times)), np.ascontiguousarray(cat(chains), dtype=np.uint8)
 
 
+TRACK_KEYS = ("xy", "yaw", "speed", "first_tick")
+
+
+def _vehicle_counts(scenes):
+    """``scenes`` as pack_tracks takes it -> vehicles per scene: a list of scene dicts / Scenario objects (their
+    ``dynamic_obstacles``), or the vehicles' scene_item_off [B+1] (what ``pack_boxes`` returns first)."""
+    if isinstance(scenes, np.ndarray):
+        off = scenes.reshape(-1)
+        if off.dtype.kind not in "iu" or off.size < 2 or off[0] != 0 or (np.diff(off) < 0).any():
+            raise ValueError("scenes given as an array must be the vehicles' scene_item_off: integers from 0, non-decreasing")
+        return [int(c) for c in np.diff(off)]
+    counts = []
+    for sc in scenes:
+        dyn = sc.get("dynamic_obstacles") if isinstance(sc, dict) else getattr(sc, "dynamic_obstacles", None)
+        counts.append(0 if dyn is None else len(dyn))
+    return counts
+
+
+def pack_tracks(tracks, scenes):
+    """Vehicle tracks -> the arguments of sfm_batch_set_vehicle_tracks.  ``tracks``: per scene ``None`` (no vehicle of the scene is
+    tracked) or a list with one entry per vehicle, each ``None`` (free-running) or a dict ``xy`` (L,2), ``yaw`` (L,) radians,
+    ``speed`` (L,), L >= 1, and ``first_tick`` (an integer, may be negative): keyframe j is what integrating tick first_tick + j
+    after the call sees.  ``scenes``: what says how many vehicles each scene has (see ``_vehicle_counts``).
+
+    Returns a dict: ``trk_off`` int32 [M+1], ``first_tick`` int32 [M] (0 for untracked vehicles), ``kx ky kvx kvy kcos ksin``
+    float32 [T], concatenated in scene order.  Velocity is (speed cos yaw, speed sin yaw), each product formed in float64 and
+    rounded to float32 once; ``kcos`` / ``ksin`` are the float32 cos / sin of the float64 yaw, as ``scenarios.place_ring_f32``
+    rounds them.  Pure NumPy; raises ValueError naming the scene and the vehicle."""
+    counts = _vehicle_counts(scenes)
+    tracks = list(tracks)
+    if len(tracks) != len(counts):
+        raise ValueError(f"{len(tracks)} track lists for {len(counts)} scenes")
+    lens, first, cols = [], [], {k: [] for k in ("x", "y", "vx", "vy", "cos", "sin")}
+    for b, (per, M) in enumerate(zip(tracks, counts)):
+        per = [None] * M if per is None else list(per)
+        if len(per) != M:
+            raise ValueError(f"scene {b}: {len(per)} tracks for {M} vehicles")
+        for k, tr in enumerate(per):
+            if tr is None:
+                lens.append(0); first.append(0)
+                continue
+            if not isinstance(tr, dict):
+                raise ValueError(f"scene {b}, vehicle {k}: a track must be a dict or None")
+            for key in TRACK_KEYS:
+                if key not in tr:
+                    raise ValueError(f"scene {b}, vehicle {k}: the track has no {key}")
+            xy = np.asarray(tr["xy"], dtype=np.float64)
+            yaw = np.asarray(tr["yaw"], dtype=np.float64).reshape(-1)
+            sp = np.asarray(tr["speed"], dtype=np.float64).reshape(-1)
+            if xy.ndim != 2 or xy.shape[1] != 2:
+                raise ValueError(f"scene {b}, vehicle {k}: xy must be (L,2), got shape {xy.shape}")
+            L = xy.shape[0]
+            if L < 1:
+                raise ValueError(f"scene {b}, vehicle {k}: a track needs at least one keyframe (None: free-running)")
+            if yaw.shape[0] != L or sp.shape[0] != L:
+                raise ValueError(f"scene {b}, vehicle {k}: {L} keyframes need {L} yaw and speed values "
+                                 f"(got {yaw.shape[0]} and {sp.shape[0]})")
+            ft = tr["first_tick"]
+            if isinstance(ft, (bool, np.bool_)) or not isinstance(ft, (int, np.integer)) or not -2**31 <= int(ft) < 2**31:
+                raise ValueError(f"scene {b}, vehicle {k}: first_tick must be an integer that fits int32, got {ft!r}")
+            with np.errstate(over="ignore", invalid="ignore"):
+                vx, vy = sp * np.cos(yaw), sp * np.sin(yaw)
+                vals = [f32(xy[:, 0]), f32(xy[:, 1]), f32(vx), f32(vy), f32(np.cos(yaw)), f32(np.sin(yaw))]
+            if not all(np.isfinite(v).all() for v in vals):
+                raise ValueError(f"scene {b}, vehicle {k}: keyframes must be finite in float32")
+            for key, v in zip(cols, vals):
+                cols[key].append(v)
+            lens.append(L); first.append(int(ft))
+    off = np.zeros(len(lens) + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    if off[-1] > MAX_TRACK_KEYS:
+        raise ValueError(f"the tracks hold {int(off[-1])} keyframes, more than the {MAX_TRACK_KEYS} one call may set: "
+                         "set shorter tracks and set them again later")
+    cat = lambda key: np.concatenate(cols[key]) if cols[key] else np.zeros(0, np.float32)
+    out = {"trk_off": off.astype(np.int32), "first_tick": np.asarray(first, dtype=np.int32).reshape(-1)}
+    out.update({"k" + key: f32(cat(key)) for key in cols})
+    return out
+
+
 def mode_scene_arrays(B, despawn_on_arrival=True, sim_time0=0.0, arrive_thresholds=2.0):
     """Per-scene mode arguments -> (despawn_on_arrival int32[B], sim_time0 float32[B], arrive_threshold float32[B]).  Each argument
     is a scalar (broadcast to every scene) or B values; clocks must be finite, thresholds finite and >= 0.  Pure NumPy; raises
@@ -548,6 +635,37 @@ class SfmBatch:
         pts = np.stack([px, py], axis=1).astype(np.float64)
         veh = [(np.array([cx[k], cy[k]], dtype=np.float64), pts[off[k]:off[k + 1]]) for k in range(M)]
         return [veh[item_off[b]:item_off[b + 1]] for b in range(self.B)]
+
+    def set_vehicle_tracks(self, tracks):
+        """Scripted tracks for the device-side vehicles (sfm_batch_set_vehicle_tracks): ``tracks`` per scene ``None`` or one entry
+        per vehicle (see ``pack_tracks``), or the dict ``pack_tracks`` returns.  Needs ``upload(..., device_vehicles=True)`` or
+        ``set_dynamic_boxes`` first.  The tracked vehicles are placed for tick 0 at once; ``upload``, ``set_dynamic_boxes`` and
+        ``sfm_batch_set_dynamic_obstacles`` drop the tracks, ``set_params``, ``set_modes`` and ``set_spawns`` keep them, setting
+        them again restarts the tick counter.  ``tracks=None`` switches them off (the vehicles run free from where they are)."""
+        L = self._lib
+        if tracks is None:
+            self._check(L.sfm_batch_set_vehicle_tracks(self._b, *([None] * 8)), "sfm_batch_set_vehicle_tracks")
+            return
+        if self._dyn is None:
+            raise SfmLibraryError("SfmBatch.set_vehicle_tracks: upload() has not been called")
+        pt = tracks if isinstance(tracks, dict) else pack_tracks(tracks, self._dyn[0])
+        if len(pt["trk_off"]) != int(self._dyn[0][-1]) + 1:
+            raise ValueError(f"tracks of {len(pt['trk_off']) - 1} vehicles for a batch of {int(self._dyn[0][-1])}")
+        T = int(pt["trk_off"][-1])
+        keys = [fptr(pt[k]) if T else None for k in ("kx", "ky", "kvx", "kvy", "kcos", "ksin")]
+        self._check(L.sfm_batch_set_vehicle_tracks(self._b, iptr(pt["trk_off"]),
+                                                   iptr(pt["first_tick"]) if len(pt["first_tick"]) else None, *keys),
+                    "sfm_batch_set_vehicle_tracks")
+
+    def vehicle_tracks(self):
+        """(tick, present): the integrating ticks since ``set_vehicle_tracks`` and, per scene, a bool array (M_b,) -- does the next
+        integrating tick see the vehicle (an untracked one is always there)?  Raises SfmLibraryError while no tracks are set."""
+        item_off = self._dyn[0] if self._dyn is not None else np.zeros(self.B + 1, np.int32)
+        pres = np.zeros(max(int(item_off[-1]), 1), np.uint8)
+        tick = C.c_int64(0)
+        self._check(self._lib.sfm_batch_download_vehicle_tracks(self._b, C.byref(tick), u8ptr(pres)),
+                    "sfm_batch_download_vehicle_tracks")
+        return int(tick.value), [pres[item_off[b]:item_off[b + 1]].astype(bool) for b in range(self.B)]
 
     def set_waypoint_streams(self, seeds, world_sides, arrive_thresholds=2.0):
         """Per-scene waypoint streams for ``redraw=True`` (see ``stream_arrays``; scalars broadcast to every scene).  They stay in

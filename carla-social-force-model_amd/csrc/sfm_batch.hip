@@ -22,7 +22,9 @@
 // Device-side vehicles (sfm_batch_set_dynamic_boxes, a.veh_on): in the prologue, before the barrier, the waves of workgroup b move
 // scene b's vehicles k0 + wave, k0 + wave + 4, ... by its dt (advance_vehicle, the handle's one vehicle step) from geo[2] -- what
 // this tick's dynamic-force scan reads -- into the other half of a ping-pong (a.veh_*_out), which the host swaps in after the
-// launch.  No launch reads what it writes, so no barrier is added: the one barrier below is followed by `if (slice != 0) return;`,
+// launch.  With vehicle tracks set (sfm_batch_set_vehicle_tracks, a.trk.off) a vehicle that has keyframes is not moved but
+// teleported: the same waves write the keyframe the NEXT tick sees (or the absent state) from the read-only track arrays.
+// No launch reads what it writes, so no barrier is added: the one barrier below is followed by `if (slice != 0) return;`,
 // and a later barrier would wait on waves that have left.
 // Pedestrian modes (sfm_batch_set_mode_fsm, the MODES instantiation): the lane that owns a row runs the handle's sfm_mode_kernel for it
 // after the barrier (target of this tick, idle wake-up on the scene's clock, gap acceptance against the scene's geo[2] items), the
@@ -327,7 +329,16 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_tick_kernel(const BatchArgs a
         // (geo[2] is only read here: the moved centres and rings go to veh_*_out, which nothing in this launch reads)
         const DynAdvance d{const_cast<float4*>(a.geo[2].ctr), a.geo[2].off, a.veh_local, a.veh_rot, const_cast<float2*>(a.geo[2].pts),
                            0, a.prm[b].dt, 0, a.veh_ctr_out, a.veh_pts_out};
-        for (int k = k0 + wave; k < k1; k += WAVES_PER_BLOCK) advance_vehicle(d, k, threadIdx.x & (WAVE - 1), true);
+        if (a.trk.off) {                                                // uniform: tracks are set -- a vehicle with keyframes is teleported
+            for (int k = k0 + wave; k < k1; k += WAVES_PER_BLOCK) {       // to the one the next tick sees, the others run free as ever
+                if (a.trk.off[k + 1] > a.trk.off[k])
+                    track_vehicle(a.trk, k, threadIdx.x & (WAVE - 1), a.geo[2].off, a.veh_local, a.veh_ctr_out, a.veh_pts_out);
+                else
+                    advance_vehicle(d, k, threadIdx.x & (WAVE - 1), true);
+            }
+        } else {
+            for (int k = k0 + wave; k < k1; k += WAVES_PER_BLOCK) advance_vehicle(d, k, threadIdx.x & (WAVE - 1), true);
+        }
     }
     const int s0 = a.scene_off[b], n = a.scene_off[b + 1] - s0;       // 0 <= n <= BATCH_MAX_N (checked on the host)
     // MODES: the scene's clock, read by every thread before the barrier and advanced by thread 0 after it (a scene without
@@ -385,6 +396,22 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_park_unborn_kernel(const int*
 
 hipError_t launch_batch_park_unborn(const int* scene_off, const uint8_t* born, float4* pk, float2* zv, int B, hipStream_t st) {
     hipLaunchKernelGGL(sfm_batch_park_unborn_kernel, dim3(B), dim3(BLOCK), 0, st, scene_off, born, pk, zv);
+    return hipGetLastError();
+}
+
+// sfm_batch_set_vehicle_tracks: the tracked vehicles as tick t.tick (0 when the tracks are set) sees them, in place -- no tick is in
+// flight (not hot: once per call).  A wave per vehicle, like sfm_dynamic_boxes_kernel; a vehicle without keyframes is left alone.
+__global__ __launch_bounds__(BLOCK) void sfm_batch_place_tracks_kernel(const BatchTracks t, const int* off, const float2* local, float4* ctr,
+                                                                        float2* pts, int M) {
+    const int k = uniform((int)(blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6)));
+    if (k >= M || t.off[k + 1] == t.off[k]) return;
+    track_vehicle(t, k, threadIdx.x & (WAVE - 1), off, local, ctr, pts);
+}
+
+hipError_t launch_batch_place_tracks(const BatchTracks& t, const int* off, const float2* local, float4* ctr, float2* pts, int M,
+                                     hipStream_t st) {
+    hipLaunchKernelGGL(sfm_batch_place_tracks_kernel, dim3((M + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), dim3(BLOCK), 0, st, t, off, local,
+                       ctr, pts, M);
     return hipGetLastError();
 }
 

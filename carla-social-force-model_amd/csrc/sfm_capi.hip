@@ -48,6 +48,8 @@ hipError_t launch_tile_bounds(const float4* pk, const float2* zv, int N, float4*
 int probe_dpp_direction(hipStream_t st);
 hipError_t launch_batch_tick(bool z3, bool ext, bool modes, bool spawn, const BatchArgs& a, int B, hipStream_t st);
 hipError_t launch_batch_park_unborn(const int* scene_off, const uint8_t* born, float4* pk, float2* zv, int B, hipStream_t st);
+hipError_t launch_batch_place_tracks(const BatchTracks& t, const int* off, const float2* local, float4* ctr, float2* pts, int M,
+                                     hipStream_t st);
 hipError_t launch_dynamic_boxes(float4* ctr, const int* off, const float2* local, const float2* rot, float2* pts, int M,
                                 float dt, int advance, hipStream_t st);
 }  // namespace sfm
@@ -2052,6 +2054,14 @@ struct SfmBatch {
     float2* veh_rot = nullptr;         // [M] {cos yaw, sin yaw}
     float4* veh_ctr_alt = nullptr;
     float2* veh_pts_alt = nullptr;
+    // scripted vehicle tracks (sfm_batch_set_vehicle_tracks, ABI 12): read-only on the device; dropped with the boxes they refer to
+    bool tracks = false;
+    int* t_off = nullptr;              // [M+1]
+    int* t_first = nullptr;            // [M]
+    float4* t_key = nullptr;           // [T] {x, y, vx, vy}
+    float2* t_rot = nullptr;           // [T] {cos yaw, sin yaw}
+    long long t_tick = 0;              // tau: integrating ticks since the tracks were set (a kernel argument, not device state)
+    std::vector<int32_t> t_off_h, t_first_h;   // host copies: sfm_batch_download_vehicle_tracks answers without the device
     // the mode state machine (sfm_batch_set_mode_fsm, ABI 9): per row over the concatenated rows, per scene [B]
     bool fsm_on = false;
     uint8_t* f_mode = nullptr;
@@ -2158,8 +2168,19 @@ static void free_batch_geo(BatchGeoDev& g) {
     g.off = nullptr; g.pts = nullptr; g.ctr = nullptr; g.K = 0; g.P = 0;
 }
 
-// back to vehicles that stay where they were set (the caller synchronised the stream)
+// back to vehicles without tracks (the caller synchronised the stream)
+static void free_batch_tracks(SfmBatch* b) {
+    b->tracks = false;
+    b->t_tick = 0;
+    for (void* p : {(void*)b->t_off, (void*)b->t_first, (void*)b->t_key, (void*)b->t_rot})
+        if (p) hipFree(p);
+    b->t_off = nullptr; b->t_first = nullptr; b->t_key = nullptr; b->t_rot = nullptr;
+    b->t_off_h.clear(); b->t_first_h.clear();
+}
+
+// back to vehicles that stay where they were set, and without the tracks that refer to the boxes (the caller synchronised the stream)
 static void free_batch_boxes(SfmBatch* b) {
+    free_batch_tracks(b);
     b->boxes = false;
     for (void* p : {(void*)b->veh_local, (void*)b->veh_rot, (void*)b->veh_ctr_alt, (void*)b->veh_pts_alt})
         if (p) hipFree(p);
@@ -2254,6 +2275,7 @@ static int batch_launch(SfmBatch* b, uint32_t flags, float4* frame = nullptr, fl
         a.veh_local = b->veh_local;
         a.veh_rot = b->veh_rot;
         a.veh_on = 1;
+        if (b->tracks) a.trk = BatchTracks{b->t_off, b->t_first, b->t_key, b->t_rot, b->t_tick + 1};   // this launch writes tick tau + 1
     }
     if (b->fsm_on)
         a.fsm = BatchModes{b->f_mode, b->f_target, b->f_speeds, b->f_off, b->f_xy, b->f_cross, b->f_cursor, b->f_scene, b->f_time};
@@ -2266,6 +2288,7 @@ static int batch_launch(SfmBatch* b, uint32_t flags, float4* frame = nullptr, fl
     if (move) {                                          // the moved half is what the next tick sees
         std::swap(b->geo[2].ctr, b->veh_ctr_alt);
         std::swap(b->geo[2].pts, b->veh_pts_alt);
+        if (b->tracks) ++b->t_tick;
     }
     return SFM_OK;
 }
@@ -2529,6 +2552,75 @@ int sfm_batch_set_dynamic_boxes(SfmBatch* b, const int32_t* scene_item_off, cons
     HIP_TRY(b, hipMemcpy(b->veh_rot, rot.data(), sizeof(float2) * (size_t)M, hipMemcpyHostToDevice));
     HIP_TRY(b, launch_dynamic_boxes(g.ctr, g.off, b->veh_local, b->veh_rot, g.pts, M, 0.f, 0, b->stream));
     b->boxes = true;
+    return SFM_OK;
+}
+
+// Scripted vehicle tracks (ABI 12): everything is checked before anything is sent; the tracked vehicles are placed for tau = 0 by
+// one launch of sfm_batch_place_tracks_kernel into the current half, in place
+int sfm_batch_set_vehicle_tracks(SfmBatch* b, const int32_t* trk_off, const int32_t* first_tick, const float* kx, const float* ky,
+                                 const float* kvx, const float* kvy, const float* kcos, const float* ksin) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->boxes)
+        return bfail(b, SFM_ERR_STATE, "vehicle tracks need device-side vehicles: call sfm_batch_set_dynamic_boxes first");
+    if (!trk_off) {                                              // tracks off: the vehicles run free from where they are
+        HIP_TRY(b, hipStreamSynchronize(b->stream));
+        free_batch_tracks(b);
+        return SFM_OK;
+    }
+    const int M = b->geo[2].K;
+    if (trk_off[0] != 0) return bfail(b, SFM_ERR_INVALID, "trk_off[0] must be 0");
+    for (int k = 0; k < M; ++k) {
+        if (trk_off[k + 1] < trk_off[k]) return bfail(b, SFM_ERR_INVALID, "trk_off must be non-decreasing (vehicle " + std::to_string(k) + ")");
+        if (trk_off[k + 1] > SFM_BATCH_MAX_TRACK_KEYS)
+            return bfail(b, SFM_ERR_INVALID, "the tracks hold more than " + std::to_string(SFM_BATCH_MAX_TRACK_KEYS) +
+                                             " keyframes (SFM_BATCH_MAX_TRACK_KEYS): set shorter tracks and set them again later");
+    }
+    const int T = trk_off[M];
+    if (T > 0 && (!first_tick || !kx || !ky || !kvx || !kvy || !kcos || !ksin))
+        return bfail(b, SFM_ERR_INVALID, "first_tick or a keyframe array is NULL while a track has keyframes");
+    for (const float* col : {kx, ky, kvx, kvy, kcos, ksin})
+        for (int e = 0; e < T; ++e)
+            if (!std::isfinite(col[e])) return bfail(b, SFM_ERR_INVALID, "keyframe " + std::to_string(e) + " holds a value that is not finite");
+    std::vector<float4> key((size_t)(T > 0 ? T : 1));
+    std::vector<float2> rot(key.size());
+    for (int e = 0; e < T; ++e) {
+        key[e] = make_float4(kx[e], ky[e], kvx[e], kvy[e]);
+        rot[e] = make_float2(kcos[e], ksin[e]);
+    }
+    std::vector<int32_t> first((size_t)M, 0);
+    if (first_tick) first.assign(first_tick, first_tick + M);
+    HIP_TRY(b, hipStreamSynchronize(b->stream));                 // a tick in flight may still read the old tracks
+    free_batch_tracks(b);
+    HIP_TRY(b, dev_realloc(b->t_off, (size_t)M + 1));
+    HIP_TRY(b, dev_realloc(b->t_first, (size_t)M));
+    HIP_TRY(b, dev_realloc(b->t_key, key.size()));
+    HIP_TRY(b, dev_realloc(b->t_rot, rot.size()));
+    HIP_TRY(b, hipMemcpy(b->t_off, trk_off, sizeof(int) * ((size_t)M + 1), hipMemcpyHostToDevice));
+    HIP_TRY(b, hipMemcpy(b->t_first, first.data(), sizeof(int) * (size_t)M, hipMemcpyHostToDevice));
+    HIP_TRY(b, hipMemcpy(b->t_key, key.data(), sizeof(float4) * key.size(), hipMemcpyHostToDevice));
+    HIP_TRY(b, hipMemcpy(b->t_rot, rot.data(), sizeof(float2) * rot.size(), hipMemcpyHostToDevice));
+    b->t_off_h.assign(trk_off, trk_off + M + 1);
+    b->t_first_h = first;
+    b->t_tick = 0;
+    const BatchGeoDev& g = b->geo[2];
+    if (T > 0)
+        HIP_TRY(b, launch_batch_place_tracks(BatchTracks{b->t_off, b->t_first, b->t_key, b->t_rot, 0}, g.off, b->veh_local, g.ctr, g.pts, M,
+                                             b->stream));
+    b->tracks = true;
+    return SFM_OK;
+}
+
+int sfm_batch_download_vehicle_tracks(SfmBatch* b, int64_t* tick, uint8_t* present) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->tracks) return bfail(b, SFM_ERR_STATE, "no vehicle tracks are set (sfm_batch_set_vehicle_tracks)");
+    if (tick) *tick = (int64_t)b->t_tick;
+    const int M = b->geo[2].K;
+    for (int k = 0; present && k < M; ++k) {
+        const long long L = b->t_off_h[k + 1] - b->t_off_h[k], j = b->t_tick - (long long)b->t_first_h[k];
+        present[k] = L == 0 || (j >= 0 && j < L);                // (a vehicle without keyframes runs free: always there)
+    }
     return SFM_OK;
 }
 

@@ -254,6 +254,13 @@ struct BatchSpawn {           // the spawn schedule of every row (sfm_batch_set_
     const float4* pk0;        // [N_total] the spawn state {x, y, vx, vy}: what the upload gave the row
     const float2* zv0;        // [N_total] ... and {z, vz} of a 3-D batch
 };
+struct BatchTracks {          // scripted vehicle tracks (sfm_batch_set_vehicle_tracks); off == null: every vehicle runs free
+    const int* off;           // [M+1] CSR of the keyframes of each vehicle; an empty list: that vehicle runs free
+    const int* first;         // [M] first_tick: keyframe j of vehicle k is what tick first[k] + j sees
+    const float4* key;        // [T] {x, y, vx, vy}
+    const float2* rot;        // [T] {cos yaw, sin yaw}
+    long long tick;           // the tick whose vehicle state this launch writes (tau + 1): kept by the host, the same for every scene
+};
 struct BatchArgs {
     const int* scene_off;     // [B+1]
     const BatchParams* prm;   // [B]
@@ -283,6 +290,7 @@ struct BatchArgs {
     int force_n;              // N_total
     uint32_t force_slots;
     BatchSpawn spn;           // the SPAWN instantiation only (appended last for the same reason)
+    BatchTracks trk;          // vehicle tracks, read in the vehicle prologue only (appended last for the same reason)
 };
 
 // Block-major packing for sharded runs (sfm_set_partition, sfm_reorder.hip): the row order is cut into gx columns by x, each

@@ -82,6 +82,28 @@ __device__ __forceinline__ void advance_vehicle(const DynAdvance& d, int k, int 
     }
 }
 
+// One wave writes vehicle k as tick t.tick of its track sees it (sfm_batch_set_vehicle_tracks): a teleport to keyframe
+// j = t.tick - first[k] with that keyframe's velocity and yaw (run_simulation.py:56-67, carla_simulation.py:107-111), the ring
+// p = c + R(yaw_j) u as advance_vehicle forms it.  Outside 0 <= j < L the vehicle is ABSENT: centre and ring points at +inf, velocity 0
+// -- its squared distance to anyone is +inf, which fails every strict-< cull (even against an infinite threshold), and speed 0 never
+// makes gap_accepted refuse.  k is wave-uniform, so the track reads are scalar loads.
+__device__ __forceinline__ void track_vehicle(const BatchTracks& t, int k, int lane, const int* off, const float2* local, float4* ctr_out,
+                                              float2* pts_out) {
+    const int e0 = t.off[k];
+    const long long j = t.tick - (long long)t.first[k];
+    const bool present = j >= 0 && j < (long long)(t.off[k + 1] - e0);
+    const float inf = __builtin_inff();
+    float4 c = make_float4(inf, inf, 0.0f, 0.0f);
+    float2 r = make_float2(1.0f, 0.0f);
+    if (present) { c = t.key[e0 + (int)j]; r = t.rot[e0 + (int)j]; }
+    if (lane == 0) ctr_out[k] = c;
+    const int o1 = off[k + 1];
+    for (int p = off[k] + lane; p < o1; p += WAVE) {
+        const float2 u = local[p];
+        pts_out[p] = present ? make_float2(fmaf(r.x, u.x, fmaf(-r.y, u.y, c.x)), fmaf(r.y, u.x, fmaf(r.x, u.y, c.y))) : make_float2(inf, inf);
+    }
+}
+
 // The tile-box rule (the operands of tiles_negligible): a row counts unless it is parked far away (a despawned pedestrian or
 // padding), and its speed bound is rounded up so that it stays a bound.  A tile's box and bound are the union over its rows:
 // the callers start from an empty box (+inf / -inf, 0), put in each row that counts, then tile_box_reduce over the wave.

@@ -185,6 +185,106 @@ def advance_dynamic(sc: Scenario, dt):
     return sc
 
 
+def _accessors(sc):
+    if isinstance(sc, dict):
+        return sc.get, sc.__setitem__
+    return (lambda k, d=None: getattr(sc, k, d)), (lambda k, v: setattr(sc, k, v))
+
+
+def track_present(track, tau):
+    """Does tick ``tau`` see the vehicle of ``track`` (None: untracked, always there)?  0 <= tau - first_tick < L."""
+    if track is None:
+        return True
+    return 0 <= int(tau) - int(track["first_tick"]) < len(np.asarray(track["yaw"]).reshape(-1))
+
+
+def place_tracked(sc, tracks, tau, dt=None):
+    """The host twin of the batch's vehicle tracks for ONE scene (a Scenario or a scene dict; ``tracks``: None or one entry per
+    vehicle, each None or a track dict as ``batch.pack_tracks`` takes it): sets ``dynamic_obstacles``, ``dynamic_vel`` and
+    ``dynamic_yaw`` to what integrating tick ``tau`` after ``set_vehicle_tracks`` sees, bit for bit what the device holds, and
+    ``dynamic_present`` (M,) bool.
+
+    A tracked vehicle that is present (0 <= tau - first_tick < L) is AT keyframe j = tau - first_tick: centre the float32 of
+    ``xy[j]``, velocity the float32 of the float64 products ``speed[j] * (cos, sin)(yaw[j])``, ring ``place_ring_f32`` at
+    ``yaw[j]`` -- a teleport, the step length plays no part.  Otherwise it is absent: centre and every ring point +inf, velocity 0
+    (its squared distance to anyone is +inf, which fails every strict-< cull; speed 0 never makes gap acceptance refuse).  An
+    untracked vehicle follows ``advance_dynamic``'s rule: with ``dt`` given it moves one step of ``dt`` (the call that goes from
+    tick tau - 1 to tick tau), without it stays (tau = 0, or a tick that did not integrate).  Returns ``sc``."""
+    get, put = _accessors(sc)
+    dyn = list(get("dynamic_obstacles") or [])
+    M = len(dyn)
+    tracks = [None] * M if tracks is None else list(tracks)
+    if len(tracks) != M:
+        raise ValueError(f"{len(tracks)} tracks for {M} vehicles")
+    vel = get("dynamic_vel")
+    vel = np.zeros((M, 2)) if vel is None else np.array(vel, dtype=np.float64).reshape(M, 2)
+    yaws = np.array(get("dynamic_yaw"), dtype=np.float64).reshape(M)
+    ext = np.asarray(get("dynamic_extent"), dtype=np.float64).reshape(M, 2)
+    present = np.ones(M, dtype=bool)
+    new = []
+    for k, (c, ring) in enumerate(dyn):
+        tr = tracks[k]
+        local = ring_local_offsets(*ext[k])
+        if tr is None:
+            if dt is not None:
+                c = advance_center_f32(c, vel[k], dt)
+            new.append((np.asarray(c, dtype=np.float64), place_ring_f32(c, yaws[k], local)))
+            continue
+        j = int(tau) - int(tr["first_tick"])
+        if track_present(tr, tau):
+            yaw = float(np.asarray(tr["yaw"], dtype=np.float64).reshape(-1)[j])
+            sp = float(np.asarray(tr["speed"], dtype=np.float64).reshape(-1)[j])
+            c = _f32(np.asarray(tr["xy"], dtype=np.float64).reshape(-1, 2)[j])
+            vel[k] = _f32([sp * np.cos(yaw), sp * np.sin(yaw)])
+            yaws[k] = yaw
+            new.append((c, place_ring_f32(c, yaw, local)))
+        else:
+            present[k] = False
+            vel[k] = 0.0
+            new.append((np.full(2, np.inf), np.full((len(local), 2), np.inf)))
+    put("dynamic_obstacles", new)
+    put("dynamic_vel", vel)
+    put("dynamic_yaw", yaws)
+    put("dynamic_present", present)
+    return sc
+
+
+def make_track_plan(sc, seed, ticks, dt=0.05, max_speed=1.4):
+    """A synthetic track plan for one scene (a Scenario or a scene dict), the recipe of the batch track tests: every vehicle drives
+    a gentle arc (constant turn rate, up to +-0.6 rad over the run) that passes through the crowd's centre of mass half-way; the
+    keyframes are dt apart at the keyframe speeds, so position and speed agree.  Vehicle 0 brakes linearly to speed 0, stands for
+    about a tenth of the run and pulls away again; vehicle k enters at tick 3 k (staggered entries; vehicle 0 at tick -2, already
+    under way); the last vehicle's list ends at about two thirds of the run (an exit inside ``ticks``), the others' at ``ticks``
+    or later.  Speeds stay <= ``max_speed``.  Returns the list ``SfmBatch.set_vehicle_tracks`` takes for the scene."""
+    get, _ = _accessors(sc)
+    M = len(get("dynamic_obstacles") or [])
+    loc = np.asarray(get("loc"), dtype=np.float64).reshape(-1, 3)
+    mid = loc[:, :2].mean(axis=0) if len(loc) else np.zeros(2)
+    rng = np.random.default_rng(seed)
+    ticks = int(ticks)
+    tracks = []
+    for k in range(M):
+        first = -2 if k == 0 else 3 * k
+        last = ticks + 2 if k < M - 1 or M == 1 else max(first + 1, (2 * ticks) // 3)
+        if M == 1:
+            last = max(first + 1, (2 * ticks) // 3)
+        L = max(1, last - first)
+        speed = np.full(L, rng.uniform(0.6, 1.0) * max_speed)
+        if k == 0 and L >= 8:
+            a, b = L // 4, L // 4 + max(1, L // 10)
+            ramp = max(2, L // 8)
+            speed[a - ramp:a] = speed[0] * np.linspace(1.0, 0.0, ramp, endpoint=False)
+            speed[a:b] = 0.0
+            speed[b:b + ramp] = speed[0] * np.linspace(0.0, 1.0, ramp, endpoint=False)
+        yaw0 = rng.uniform(-np.pi, np.pi)
+        yaw = yaw0 + rng.uniform(-0.6, 0.6) * (np.arange(L) / max(L - 1, 1) - 0.5)
+        step = speed[:, None] * dt * np.column_stack((np.cos(yaw), np.sin(yaw)))
+        xy = np.cumsum(step, axis=0) - step
+        xy += mid + rng.uniform(-1.0, 1.0, 2) - xy[L // 2]
+        tracks.append({"xy": _f32(xy), "yaw": yaw, "speed": _f32(speed), "first_tick": int(first)})
+    return tracks
+
+
 def make_mode_plan(sc, seed, queue_len=3, idle_every=11, reckless_every=5):
     """A synthetic mode plan for one scene (a Scenario or a scene dict), the recipe of the device mode tests: every pedestrian a
     PedModeManager mirror walking the sidewalk (crossing speed 1.5 x target speed, safety margin 1 s), every ``reckless_every``-th

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SFM_ABI_VERSION 11  /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles; 9: + sfm_batch_set_mode_fsm, sfm_batch_download_modes; 10: + sfm_batch_tick_forces, sfm_batch_run_recorded_forces; 11: + sfm_batch_set_spawn_schedule, sfm_batch_download_spawns, SFM_MODE_UNBORN (additions only) */
+#define SFM_ABI_VERSION 12  /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles; 9: + sfm_batch_set_mode_fsm, sfm_batch_download_modes; 10: + sfm_batch_tick_forces, sfm_batch_run_recorded_forces; 11: + sfm_batch_set_spawn_schedule, sfm_batch_download_spawns, SFM_MODE_UNBORN; 12: + sfm_batch_set_vehicle_tracks, sfm_batch_download_vehicle_tracks (additions only) */
 
 typedef struct SfmHandle SfmHandle;
 
@@ -274,7 +274,7 @@ int sfm_abi_version(void);
  * each, every scene with its own SfmParams (a parameter sweep is one batch) and its own borders / obstacles; each tick is ONE kernel
  * launch for the whole batch (sfm_batch.hip, a workgroup per scene).  A scene's result is bitwise the same whatever else is in the
  * batch and wherever it sits.  Larger crowds belong on a handle.  Waypoint redraw (per-scene streams) and on-device trajectories
- * are ABI 7, device-side vehicles ABI 8, the mode state machine (sfm_batch_set_mode_fsm) ABI 9, force records ABI 10, spawn schedules ABI 11.  Not
+ * are ABI 7, device-side vehicles ABI 8, the mode state machine (sfm_batch_set_mode_fsm) ABI 9, force records ABI 10, spawn schedules ABI 11, vehicle tracks ABI 12.  Not
  * supported on a batch: sharding.  Host arrays are fp32 SoA over all scenes concatenated; scene b owns rows
  * [scene_off[b], scene_off[b+1]).  Geometry is per-scene CSR: scene b owns polylines [scene_item_off[b], scene_item_off[b+1]) of the
  * concatenated set, whose points are offsets[k] .. offsets[k+1]-1 (offsets[0] = 0).  Errors as for a handle: a negative SfmStatus,
@@ -319,6 +319,32 @@ int sfm_batch_set_dynamic_boxes(SfmBatch* b, const int32_t* scene_item_off, cons
 /* Current centres (M) and ring points (P) of every scene's vehicles, concatenated in scene order, as the next tick will see them
  * (synchronises the batch's stream); NULL skips.  Also the rings of sfm_batch_set_dynamic_obstacles. */
 int sfm_batch_download_dynamic_obstacles(SfmBatch* b, float* cx, float* cy, float* px, float* py);
+/* Scripted vehicle tracks (ABI 12): the reference's trajectory vehicles (vehicle_spawner.py:140-144, run_simulation.py:56-67) inside
+ * each tick's one launch.  Needs device-side vehicles (sfm_batch_set_dynamic_boxes, M of them over all scenes; SFM_ERR_STATE
+ * otherwise).  Vehicle k owns keyframes [trk_off[k], trk_off[k+1]) (trk_off [M+1], trk_off[0] = 0, non-decreasing); an empty list
+ * leaves the vehicle free-running exactly as without tracks.  Keyframe e is {kx, ky} the centre, {kvx, kvy} the velocity the
+ * dynamic obstacle force and gap acceptance see, {kcos, ksin} the yaw of the ring; first_tick[M] may be negative.  Let tau count
+ * the INTEGRATING ticks of the batch since this call (0 when it returns; ticks without SFM_TICK_INTEGRATE move no vehicle and do
+ * not count).  In tick tau a tracked vehicle is present iff 0 <= tau - first_tick[k] < L_k and is then AT keyframe
+ * j = tau - first_tick[k]: a teleport, the step length plays no part; ring point p = (fma(cos, ux, fma(-sin, uy, x)),
+ * fma(sin, ux, fma(cos, uy, y))) with the ring-local offsets of sfm_batch_set_dynamic_boxes.  Otherwise it is ABSENT: centre and
+ * every ring point (+inf, +inf), velocity 0 -- which is what sfm_batch_download_dynamic_obstacles returns for it.  Its squared
+ * distance to any pedestrian is +inf, so it fails the strict-< perception cull for every threshold, and with speed 0 it never makes
+ * gap acceptance refuse; a scene whose vehicles are all absent lets a CHECKING pedestrian cross.  Gap acceptance keeps the
+ * first_vehicle_extent of sfm_batch_set_mode_fsm.  The call places the tracked vehicles for tau = 0 with one launch; every
+ * integrating tick then writes the state of tick tau + 1 into the other half of the vehicles' ping-pong from the read-only track
+ * arrays: no extra launch, copy or barrier per tick.  sfm_batch_set_dynamic_boxes and sfm_batch_set_dynamic_obstacles drop the
+ * tracks; sfm_batch_upload_state, sfm_batch_set_params, sfm_batch_set_mode_fsm and sfm_batch_set_spawn_schedule keep them; setting
+ * them again restarts tau at 0.  trk_off = NULL switches the tracks off: every vehicle runs free from where it is (an absent one
+ * stays absent).  Refused before anything is sent or launched, the batch staying as it was: no device-side vehicles, trk_off[0] != 0
+ * or decreasing, more than SFM_BATCH_MAX_TRACK_KEYS keyframes in all, a NULL first_tick or keyframe array while any track has
+ * keyframes, a keyframe value that is not finite. */
+#define SFM_BATCH_MAX_TRACK_KEYS (1 << 22)
+int sfm_batch_set_vehicle_tracks(SfmBatch* b, const int32_t* trk_off, const int32_t* first_tick, const float* kx, const float* ky,
+                                 const float* kvx, const float* kvy, const float* kcos, const float* ksin);
+/* tau (*tick) and, per vehicle [M], whether the next integrating tick sees it (1; a vehicle without keyframes is always there) or
+ * it is absent (0); NULL skips.  SFM_ERR_STATE while no tracks are set. */
+int sfm_batch_download_vehicle_tracks(SfmBatch* b, int64_t* tick, uint8_t* present);
 /* One tick of every scene: flags 0 or SFM_TICK_INTEGRATE, plus SFM_TICK_REDRAW_WAYPOINTS once sfm_batch_set_waypoint_streams has
  * been called and while no modes are set (anything else is an error); v' (and x') in place. */
 int sfm_batch_tick(SfmBatch* b, uint32_t flags);
