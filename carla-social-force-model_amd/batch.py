@@ -1,6 +1,6 @@
 """Batched scenes: many small, independent crowds stepped by ONE kernel launch per tick (C ABI: sfm_batch_*, ABI 6; waypoint
 streams and recorded runs, ABI 7; device-side vehicles, ABI 8; pedestrian modes, ABI 9; force records, ABI 10; spawn schedules, ABI 11;
-vehicle tracks, ABI 12).
+vehicle tracks, ABI 12; snapshot and restart, ABI 13).
 
 Social-force models are run in bulk as many small scenes -- scenario sampling, RL environments stepped in lock-step, calibration
 sweeps over A / lambda / gamma / tau.  ``SfmBatch`` holds B scenes of 0 .. 1024 pedestrians, each with its own parameters (its own
@@ -46,6 +46,14 @@ Vehicle tracks (ABI 12): the reference's scripted traffic.  ``set_vehicle_tracks
 -- it can turn, brake, stop and pull away -- and outside its list it is absent: centre and ring at +inf, velocity 0, no force on
 anyone and no say in gap acceptance.  ``vehicle_tracks()`` reads back the tick counter and who is present;
 ``scenarios.place_tracked`` is the host twin and ``vehicle_spawner.tracks_from_spawners`` builds tracks from VehicleSpawner mirrors.
+
+Starting over (ABI 13): ``snapshot()`` copies, on the device, everything a tick can change -- state, waypoints, draw counters,
+vehicles, modes, clocks, births, track time -- and ``restart(scenes)`` puts the chosen scenes back to it with one launch, leaving the
+others alone bit for bit: episodes of an RL loop that end at different times, or a calibration sweep (``snapshot()`` once, then per
+candidate ``set_params``, ``restart()``, ``run``: a restarted scene runs under the parameters, waypoint streams, borders and static
+obstacles of the moment).  ``upload`` and the calls that set vehicles, modes, spawn schedules or tracks drop the snapshot
+(``has_snapshot``).  Scripted traffic restarts per scene as well: a restarted scene's tracked vehicles are where they were at the
+snapshot, while ``vehicle_tracks()`` goes on counting the batch's ticks.
 """
 from __future__ import annotations
 
@@ -482,6 +490,28 @@ def mode_scene_arrays(B, despawn_on_arrival=True, sim_time0=0.0, arrive_threshol
     return despawn, t0, thr
 
 
+def restart_mask(B, scenes=None):
+    """Which scenes ``SfmBatch.restart`` restarts -> the mask of sfm_batch_restart, uint8 [B] of 0 / 1.  ``scenes``: None (every
+    scene), a bool array (B,), or a sequence of scene indices 0 .. B-1 (duplicates are fine, an empty one chooses nobody).  Pure
+    NumPy; raises ValueError on a bool array of another length, an index outside 0 .. B-1, or an index that is not an integer."""
+    B = int(B)
+    if scenes is None:
+        return np.ones(B, dtype=np.uint8)
+    a = np.asarray(scenes)
+    if a.dtype == np.bool_:
+        if a.shape != (B,):
+            raise ValueError(f"a bool mask of shape {a.shape} for a batch of {B} scenes")
+        return np.ascontiguousarray(a, dtype=np.uint8)
+    a = a.reshape(-1)
+    if a.size and a.dtype.kind not in "iu":
+        raise ValueError(f"scene indices must be integers, got {a.dtype}")
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= B):
+        raise ValueError(f"scene indices must lie in 0 .. {B - 1}, got {int(a.min())} .. {int(a.max())}")
+    mask = np.zeros(B, dtype=np.uint8)
+    mask[a.astype(np.int64)] = 1
+    return mask
+
+
 def split_frames(frames, scene_off):
     """Frames of the concatenated batch, (F, N_total, C), -> a list of B arrays (F, N_b, C), one per scene in scene order (views).
     Pure NumPy."""
@@ -553,11 +583,17 @@ class SfmBatch:
         self.planar = True
         self._z = None
         self._dyn = None                  # (scene_item_off, offsets) of the vehicles last set, for dynamic_obstacles()
+        self.has_snapshot = False         # snapshot() has been taken and no later call has dropped it
 
     def _check(self, rc, what):
         if rc != 0:
             msg = self._lib.sfm_batch_last_error(self._b)
             raise SfmLibraryError(f"{what} failed ({rc}): {msg.decode() if msg else '?'}")
+
+    def _check_drops(self, rc, what):
+        """``_check`` for the calls that drop the snapshot once they succeed (a refused call drops nothing)."""
+        self._check(rc, what)
+        self.has_snapshot = False
 
     def close(self):
         if getattr(self, "_b", None) is not None and self._b:
@@ -601,13 +637,14 @@ class SfmBatch:
         self._check(L.sfm_batch_set_borders(self._b, *(iptr(a) for a in bo[:2]), *(fptr(a) for a in bo[2:])), "sfm_batch_set_borders")
         self._check(L.sfm_batch_set_static_obstacles(self._b, *(iptr(a) for a in st[:2]), *(fptr(a) for a in st[2:])),
                     "sfm_batch_set_static_obstacles")
-        self._check(L.sfm_batch_set_dynamic_obstacles(self._b, *(iptr(a) for a in dy[:2]), *(fptr(a) for a in dy[2:])),
-                    "sfm_batch_set_dynamic_obstacles")
+        self._check_drops(L.sfm_batch_set_dynamic_obstacles(self._b, *(iptr(a) for a in dy[:2]), *(fptr(a) for a in dy[2:])),
+                          "sfm_batch_set_dynamic_obstacles")
         self._dyn = (dy[0].copy(), dy[1].copy())
         z, vz = (None, None) if planar else (pk["z"], pk["vz"])
-        self._check(L.sfm_batch_upload_state(self._b, iptr(so), fptr(pk["x"]), fptr(pk["y"]), fptr(z), fptr(pk["vx"]),
-                                             fptr(pk["vy"]), fptr(vz), fptr(pk["wx"]), fptr(pk["wy"]), fptr(pk["target_speed"]),
-                                             fptr(pk["radius"]), u8ptr(pk["crossing"])), "sfm_batch_upload_state")
+        self._check_drops(L.sfm_batch_upload_state(self._b, iptr(so), fptr(pk["x"]), fptr(pk["y"]), fptr(z), fptr(pk["vx"]),
+                                                   fptr(pk["vy"]), fptr(vz), fptr(pk["wx"]), fptr(pk["wy"]),
+                                                   fptr(pk["target_speed"]), fptr(pk["radius"]), u8ptr(pk["crossing"])),
+                          "sfm_batch_upload_state")
         self.scene_off = so.copy()
         self.planar = planar
         self._z = pk["z"].copy()          # a planar batch keeps each scene's z on the host (the device holds x / y only)
@@ -618,8 +655,8 @@ class SfmBatch:
         boxes = scenes if isinstance(scenes, tuple) else pack_boxes(scenes)
         if len(boxes[0]) != self.B + 1:
             raise ValueError(f"boxes of {len(boxes[0]) - 1} scenes for a batch of {self.B}")
-        self._check(self._lib.sfm_batch_set_dynamic_boxes(self._b, *(iptr(a) for a in boxes[:2]), *(fptr(a) for a in boxes[2:])),
-                    "sfm_batch_set_dynamic_boxes")
+        self._check_drops(self._lib.sfm_batch_set_dynamic_boxes(self._b, *(iptr(a) for a in boxes[:2]),
+                                                                *(fptr(a) for a in boxes[2:])), "sfm_batch_set_dynamic_boxes")
         self._dyn = (boxes[0].copy(), boxes[1].copy())
 
     def dynamic_obstacles(self):
@@ -644,7 +681,7 @@ class SfmBatch:
         them again restarts the tick counter.  ``tracks=None`` switches them off (the vehicles run free from where they are)."""
         L = self._lib
         if tracks is None:
-            self._check(L.sfm_batch_set_vehicle_tracks(self._b, *([None] * 8)), "sfm_batch_set_vehicle_tracks")
+            self._check_drops(L.sfm_batch_set_vehicle_tracks(self._b, *([None] * 8)), "sfm_batch_set_vehicle_tracks")
             return
         if self._dyn is None:
             raise SfmLibraryError("SfmBatch.set_vehicle_tracks: upload() has not been called")
@@ -653,9 +690,9 @@ class SfmBatch:
             raise ValueError(f"tracks of {len(pt['trk_off']) - 1} vehicles for a batch of {int(self._dyn[0][-1])}")
         T = int(pt["trk_off"][-1])
         keys = [fptr(pt[k]) if T else None for k in ("kx", "ky", "kvx", "kvy", "kcos", "ksin")]
-        self._check(L.sfm_batch_set_vehicle_tracks(self._b, iptr(pt["trk_off"]),
-                                                   iptr(pt["first_tick"]) if len(pt["first_tick"]) else None, *keys),
-                    "sfm_batch_set_vehicle_tracks")
+        self._check_drops(L.sfm_batch_set_vehicle_tracks(self._b, iptr(pt["trk_off"]),
+                                                         iptr(pt["first_tick"]) if len(pt["first_tick"]) else None, *keys),
+                          "sfm_batch_set_vehicle_tracks")
 
     def vehicle_tracks(self):
         """(tick, present): the integrating ticks since ``set_vehicle_tracks`` and, per scene, a bool array (M_b,) -- does the next
@@ -666,6 +703,22 @@ class SfmBatch:
         self._check(self._lib.sfm_batch_download_vehicle_tracks(self._b, C.byref(tick), u8ptr(pres)),
                     "sfm_batch_download_vehicle_tracks")
         return int(tick.value), [pres[item_off[b]:item_off[b + 1]].astype(bool) for b in range(self.B)]
+
+    def snapshot(self):
+        """Record every scene as it is now (sfm_batch_snapshot): device-to-device copies on the batch's stream of everything a tick
+        can change; the host does not wait.  A second snapshot replaces the first.  ``upload``, ``set_dynamic_boxes``,
+        ``set_modes``, ``set_spawns`` and ``set_vehicle_tracks`` (``None`` included) drop it; ``set_params`` and
+        ``set_waypoint_streams`` keep it."""
+        self.has_snapshot = False
+        self._check(self._lib.sfm_batch_snapshot(self._b), "sfm_batch_snapshot")
+        self.has_snapshot = True
+
+    def restart(self, scenes=None):
+        """Put the chosen scenes back to the snapshot with one launch (sfm_batch_restart); the others are not touched.  ``scenes``
+        as for ``restart_mask``: None (every scene), a bool array (B,), or scene indices.  A restarted scene runs under the
+        parameters and static geometry of the moment; its tracked vehicles are where they were at the snapshot."""
+        mask = None if scenes is None else restart_mask(self.B, scenes)
+        self._check(self._lib.sfm_batch_restart(self._b, u8ptr(mask)), "sfm_batch_restart")
 
     def set_waypoint_streams(self, seeds, world_sides, arrive_thresholds=2.0):
         """Per-scene waypoint streams for ``redraw=True`` (see ``stream_arrays``; scalars broadcast to every scene).  They stay in
@@ -753,18 +806,18 @@ class SfmBatch:
         every ``upload``."""
         L = self._lib
         if plans is None:
-            self._check(L.sfm_batch_set_mode_fsm(self._b, *([None] * 14)), "sfm_batch_set_mode_fsm")
+            self._check_drops(L.sfm_batch_set_mode_fsm(self._b, *([None] * 14)), "sfm_batch_set_mode_fsm")
             return
         if self.scene_off is None:
             raise SfmLibraryError("SfmBatch.set_modes: upload() has not been called")
         pm = pack_modes(plans, self.scene_off, scenes)
         despawn, t0, thr = mode_scene_arrays(self.B, despawn_on_arrival, sim_time0, arrive_thresholds)
         W = int(pm["wp_offsets"][-1])
-        self._check(L.sfm_batch_set_mode_fsm(self._b, u8ptr(pm["mode"]), *(fptr(pm[k]) for k in MODE_KEYS[1:]),
-                                             iptr(pm["wp_offsets"]), fptr(pm["wp_x"]) if W else None,
-                                             fptr(pm["wp_y"]) if W else None, u8ptr(pm["wp_crossing"]) if W else None,
-                                             iptr(despawn), fptr(t0), fptr(thr), fptr(pm["first_vehicle_extent"])),
-                    "sfm_batch_set_mode_fsm")
+        self._check_drops(L.sfm_batch_set_mode_fsm(self._b, u8ptr(pm["mode"]), *(fptr(pm[k]) for k in MODE_KEYS[1:]),
+                                                   iptr(pm["wp_offsets"]), fptr(pm["wp_x"]) if W else None,
+                                                   fptr(pm["wp_y"]) if W else None, u8ptr(pm["wp_crossing"]) if W else None,
+                                                   iptr(despawn), fptr(t0), fptr(thr), fptr(pm["first_vehicle_extent"])),
+                          "sfm_batch_set_mode_fsm")
 
     def set_spawns(self, schedules):
         """The spawn schedule of every scene (sfm_batch_set_spawn_schedule): ``schedules`` one per scene (see ``pack_spawns``;
@@ -774,14 +827,14 @@ class SfmBatch:
         ``schedules=None`` switches the schedule off, refused while a row is unborn."""
         L = self._lib
         if schedules is None:
-            self._check(L.sfm_batch_set_spawn_schedule(self._b, None, None), "sfm_batch_set_spawn_schedule")
+            self._check_drops(L.sfm_batch_set_spawn_schedule(self._b, None, None), "sfm_batch_set_spawn_schedule")
             return
         if self.scene_off is None:
             raise SfmLibraryError("SfmBatch.set_spawns: upload() has not been called")
         t, c = pack_spawns(schedules, self.scene_off)
         if t.shape[0] == 0:                                            # (no rows: still a call, so that the refusals are the library's)
             t, c = np.zeros(1, np.float32), np.zeros(1, np.uint8)
-        self._check(L.sfm_batch_set_spawn_schedule(self._b, fptr(t), u8ptr(c)), "sfm_batch_set_spawn_schedule")
+        self._check_drops(L.sfm_batch_set_spawn_schedule(self._b, fptr(t), u8ptr(c)), "sfm_batch_set_spawn_schedule")
 
     def spawns(self):
         """Per scene (born (N_b,) bool, birth_time (N_b,) float32: the scene's clock before the row's birth tick -- the clock

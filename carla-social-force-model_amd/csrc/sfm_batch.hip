@@ -434,4 +434,43 @@ hipError_t launch_batch_tick(bool z3, bool ext, bool modes, bool spawn, const Ba
     return hipGetLastError();
 }
 
+// sfm_batch_restart: the chosen scenes go back to the batch's snapshot (sfm_batch_snapshot) -- every array a tick can change, and
+// nothing else.  A workgroup per chosen scene, as the tick: it copies the scene's rows of every per-row array, its vehicles (the half
+// of the ping-pong the next tick reads) with their ring points, and its clock.  Plain loads and stores, no LDS, no atomics: a scene
+// is written by its own workgroup only, and the scenes that are not chosen are not touched.  A tracked vehicle's first tick moves
+// by r.shift (the batch's ticks since the snapshot), so that the batch-wide tick counter tau finds it at the keyframe it was at.
+template <typename T>
+__device__ __forceinline__ void restart_copy(T* dst, const T* src, int i0, int i1) {
+    if (!dst) return;                                                   // uniform: the batch has no such array
+    for (int i = i0 + (int)threadIdx.x; i < i1; i += BLOCK) dst[i] = src[i];
+}
+
+__global__ __launch_bounds__(BLOCK) void sfm_batch_restart_kernel(const BatchRestart r) {
+    const int b = r.list ? r.list[blockIdx.x] : (int)blockIdx.x;
+    const int s0 = r.scene_off[b], s1 = r.scene_off[b + 1];
+    restart_copy(r.pk, r.s_pk, s0, s1);
+    restart_copy(r.zv, r.s_zv, s0, s1);
+    restart_copy(r.own, r.s_own, s0, s1);
+    restart_copy(r.draws, r.s_draws, s0, s1);
+    restart_copy(r.mode, r.s_mode, s0, s1);
+    restart_copy(r.target, r.s_target, s0, s1);
+    restart_copy(r.cursor, r.s_cursor, s0, s1);
+    restart_copy(r.born, r.s_born, s0, s1);
+    restart_copy(r.birth_time, r.s_birth_time, s0, s1);
+    if (r.ctr) {                                                        // uniform: device-side vehicles
+        const int k0 = r.item_off[b], k1 = r.item_off[b + 1];
+        restart_copy(r.ctr, r.s_ctr, k0, k1);
+        restart_copy(r.pts, r.s_pts, r.veh_off[k0], r.veh_off[k1]);
+        if (r.first)
+            for (int k = k0 + (int)threadIdx.x; k < k1; k += BLOCK)
+                r.first[k] = r.trk_off[k + 1] > r.trk_off[k] ? (int)((long long)r.s_first[k] + r.shift) : r.s_first[k];
+    }
+    if (r.sim_time && threadIdx.x == 0) r.sim_time[b] = r.s_sim_time[b];
+}
+
+hipError_t launch_batch_restart(const BatchRestart& r, int scenes, hipStream_t st) {
+    hipLaunchKernelGGL(sfm_batch_restart_kernel, dim3(scenes), dim3(BLOCK), 0, st, r);
+    return hipGetLastError();
+}
+
 }  // namespace sfm

@@ -50,6 +50,7 @@ hipError_t launch_batch_tick(bool z3, bool ext, bool modes, bool spawn, const Ba
 hipError_t launch_batch_park_unborn(const int* scene_off, const uint8_t* born, float4* pk, float2* zv, int B, hipStream_t st);
 hipError_t launch_batch_place_tracks(const BatchTracks& t, const int* off, const float2* local, float4* ctr, float2* pts, int M,
                                      hipStream_t st);
+hipError_t launch_batch_restart(const BatchRestart& r, int scenes, hipStream_t st);
 hipError_t launch_dynamic_boxes(float4* ctr, const int* off, const float2* local, const float2* rot, float2* pts, int M,
                                 float dt, int advance, hipStream_t st);
 }  // namespace sfm
@@ -2023,6 +2024,12 @@ struct BatchGeoDev {
     int P = 0;
 };
 
+template <typename T>
+struct SnapBuf {               // one grow-only snapshot array of a batch (sfm_batch_snapshot)
+    T* p = nullptr;
+    size_t cap = 0;
+};
+
 struct SfmBatch {
     int device = 0;
     int B = 0;
@@ -2082,6 +2089,24 @@ struct SfmBatch {
     float* s_birth = nullptr;
     float4* s_pk0 = nullptr;           // the spawn state: the rows as they were when the schedule was set
     float2* s_zv0 = nullptr;
+    // the snapshot (sfm_batch_snapshot / sfm_batch_restart, ABI 13): a copy of every array a tick can change, grow-only; what it
+    // holds follows boxes / fsm_on / spawn_on / tracks, which cannot change while it is valid (every call that changes them drops it)
+    bool snap = false;
+    SnapBuf<float4> n_pk, n_own, n_ctr;
+    SnapBuf<float2> n_zv, n_pts;
+    SnapBuf<uint32_t> n_draws;
+    SnapBuf<uint8_t> n_mode, n_born;
+    SnapBuf<float> n_target, n_time, n_birth;
+    SnapBuf<int> n_cursor, n_first;
+    long long n_tick = 0;              // t_tick when the snapshot was taken
+    std::vector<int32_t> n_first_h;    // t_first_h when the snapshot was taken
+    std::vector<int32_t> box_item_off_h;   // the vehicles' scene_item_off [B+1] on the host, while boxes are set
+    // sfm_batch_restart's list of chosen scenes: pinned on the host, copied to r_list on the stream; r_done is recorded behind the
+    // launch that reads it, and the next masked restart waits for it before it refills the pinned list
+    int* r_list = nullptr;
+    int* r_list_h = nullptr;
+    hipEvent_t r_done = nullptr;
+    bool r_pending = false;
     std::string err;
 };
 
@@ -2182,6 +2207,7 @@ static void free_batch_tracks(SfmBatch* b) {
 static void free_batch_boxes(SfmBatch* b) {
     free_batch_tracks(b);
     b->boxes = false;
+    b->box_item_off_h.clear();
     for (void* p : {(void*)b->veh_local, (void*)b->veh_rot, (void*)b->veh_ctr_alt, (void*)b->veh_pts_alt})
         if (p) hipFree(p);
     b->veh_local = nullptr; b->veh_rot = nullptr; b->veh_ctr_alt = nullptr; b->veh_pts_alt = nullptr;
@@ -2290,6 +2316,19 @@ static int batch_launch(SfmBatch* b, uint32_t flags, float4* frame = nullptr, fl
         std::swap(b->geo[2].pts, b->veh_pts_alt);
         if (b->tracks) ++b->t_tick;
     }
+    return SFM_OK;
+}
+
+// One array into its snapshot copy, on the batch's stream.  The copy only grows, and only then does the host wait: a restart in
+// flight may still read the buffer that is replaced.
+template <typename T>
+static int snap_copy(SfmBatch* b, SnapBuf<T>& s, const T* src, size_t count) {
+    if (count == 0) return SFM_OK;
+    if (!s.p || count > s.cap) {
+        HIP_TRY(b, hipStreamSynchronize(b->stream));
+        HIP_TRY(b, dev_reserve(s.p, s.cap, count));
+    }
+    HIP_TRY(b, hipMemcpyAsync(s.p, src, sizeof(T) * count, hipMemcpyDeviceToDevice, b->stream));
     return SFM_OK;
 }
 
@@ -2405,6 +2444,12 @@ int sfm_batch_destroy(SfmBatch* b) {
     if (b->frames) hipFree(b->frames);
     if (b->zframes) hipFree(b->zframes);
     if (b->forces) hipFree(b->forces);
+    for (void* p : {(void*)b->n_pk.p, (void*)b->n_own.p, (void*)b->n_ctr.p, (void*)b->n_zv.p, (void*)b->n_pts.p, (void*)b->n_draws.p,
+                    (void*)b->n_mode.p, (void*)b->n_born.p, (void*)b->n_target.p, (void*)b->n_time.p, (void*)b->n_birth.p,
+                    (void*)b->n_cursor.p, (void*)b->n_first.p, (void*)b->r_list})
+        if (p) hipFree(p);
+    if (b->r_list_h) hipHostFree(b->r_list_h);
+    if (b->r_done) hipEventDestroy(b->r_done);
     delete b;
     return SFM_OK;
 }
@@ -2455,6 +2500,7 @@ int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x
         b->cap = n;
     }
     free_batch_modes(b);                                          // a new crowd: its modes are set anew
+    b->snap = false;                                              // ... and so is its snapshot
     b->have_state = false;
     if (n > 0) {
         std::vector<float4> pk(n), own(n);
@@ -2517,6 +2563,7 @@ int sfm_batch_set_dynamic_obstacles(SfmBatch* b, const int32_t* scene_item_off, 
         c4[k] = make_float4(cx[k], cy[k], vx ? vx[k] : 0.f, vy ? vy[k] : 0.f);
     HIP_TRY(b, hipStreamSynchronize(b->stream));                 // a tick in flight may still move the boxes
     free_batch_boxes(b);
+    b->snap = false;
     return set_batch_geo(b, 2, scene_item_off, offsets, px, py, c4, K);
 }
 
@@ -2540,6 +2587,7 @@ int sfm_batch_set_dynamic_boxes(SfmBatch* b, const int32_t* scene_item_off, cons
     }
     HIP_TRY(b, hipStreamSynchronize(b->stream));                 // a tick in flight may still move the old boxes
     free_batch_boxes(b);
+    b->snap = false;
     rc = set_batch_geo(b, 2, scene_item_off, offsets, ux, uy, c4, M);   // pts holds the local offsets until the launch below
     if (rc || M == 0) return rc;
     BatchGeoDev& g = b->geo[2];
@@ -2551,6 +2599,7 @@ int sfm_batch_set_dynamic_boxes(SfmBatch* b, const int32_t* scene_item_off, cons
     HIP_TRY(b, hipMemcpy(b->veh_local, g.pts, sizeof(float2) * np, hipMemcpyDeviceToDevice));
     HIP_TRY(b, hipMemcpy(b->veh_rot, rot.data(), sizeof(float2) * (size_t)M, hipMemcpyHostToDevice));
     HIP_TRY(b, launch_dynamic_boxes(g.ctr, g.off, b->veh_local, b->veh_rot, g.pts, M, 0.f, 0, b->stream));
+    b->box_item_off_h.assign(scene_item_off, scene_item_off + b->B + 1);
     b->boxes = true;
     return SFM_OK;
 }
@@ -2566,6 +2615,7 @@ int sfm_batch_set_vehicle_tracks(SfmBatch* b, const int32_t* trk_off, const int3
     if (!trk_off) {                                              // tracks off: the vehicles run free from where they are
         HIP_TRY(b, hipStreamSynchronize(b->stream));
         free_batch_tracks(b);
+        b->snap = false;
         return SFM_OK;
     }
     const int M = b->geo[2].K;
@@ -2592,6 +2642,7 @@ int sfm_batch_set_vehicle_tracks(SfmBatch* b, const int32_t* trk_off, const int3
     if (first_tick) first.assign(first_tick, first_tick + M);
     HIP_TRY(b, hipStreamSynchronize(b->stream));                 // a tick in flight may still read the old tracks
     free_batch_tracks(b);
+    b->snap = false;
     HIP_TRY(b, dev_realloc(b->t_off, (size_t)M + 1));
     HIP_TRY(b, dev_realloc(b->t_first, (size_t)M));
     HIP_TRY(b, dev_realloc(b->t_key, key.size()));
@@ -2768,6 +2819,7 @@ int sfm_batch_set_mode_fsm(SfmBatch* b, const uint8_t* mode, const float* target
     if (!mode) {
         HIP_TRY(b, hipStreamSynchronize(b->stream));             // a tick in flight may still read the arrays
         free_batch_modes(b);
+        b->snap = false;
         return SFM_OK;
     }
     if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
@@ -2800,6 +2852,7 @@ int sfm_batch_set_mode_fsm(SfmBatch* b, const uint8_t* mode, const float* target
     for (int e = 0; e < W; ++e) xy[e] = make_float2(wp_x[e], wp_y[e]);
     HIP_TRY(b, hipStreamSynchronize(b->stream));                 // a tick in flight may still read the old arrays
     free_batch_modes(b);
+    b->snap = false;
     HIP_TRY(b, dev_realloc(b->f_mode, n)); HIP_TRY(b, dev_realloc(b->f_target, n)); HIP_TRY(b, dev_realloc(b->f_speeds, n));
     HIP_TRY(b, dev_realloc(b->f_off, n + 1)); HIP_TRY(b, dev_realloc(b->f_cursor, n));
     HIP_TRY(b, dev_realloc(b->f_xy, xy.size())); HIP_TRY(b, dev_realloc(b->f_cross, xy.size()));
@@ -2852,7 +2905,7 @@ int sfm_batch_set_spawn_schedule(SfmBatch* b, const float* spawn_time, const uin
     if (rc) return rc;
     const size_t n = b->have_state ? (size_t)b->n_total : 0;
     if (!spawn_time) {
-        if (!b->spawn_on) return SFM_OK;
+        if (!b->spawn_on) { b->snap = false; return SFM_OK; }
         HIP_TRY(b, hipStreamSynchronize(b->stream));             // a tick in flight may still write born[]
         std::vector<uint8_t> born(n);
         if (n > 0) HIP_TRY(b, hipMemcpy(born.data(), b->s_born, n, hipMemcpyDeviceToHost));
@@ -2861,6 +2914,7 @@ int sfm_batch_set_spawn_schedule(SfmBatch* b, const float* spawn_time, const uin
                 return bfail(b, SFM_ERR_STATE, "the spawn schedule cannot be switched off while a row is unborn (row " + std::to_string(i) +
                                                "): a ghost without a schedule could never enter");
         free_batch_spawns(b);
+        b->snap = false;
         return SFM_OK;
     }
     if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
@@ -2894,6 +2948,7 @@ int sfm_batch_set_spawn_schedule(SfmBatch* b, const float* spawn_time, const uin
             any_unborn = any_unborn || !born[i];
         }
     const size_t m = n > 0 ? n : 1;
+    b->snap = false;
     HIP_TRY(b, dev_realloc(b->s_time, m)); HIP_TRY(b, dev_realloc(b->s_chain, m)); HIP_TRY(b, dev_realloc(b->s_born, m));
     HIP_TRY(b, dev_realloc(b->s_birth, m)); HIP_TRY(b, dev_realloc(b->s_pk0, m)); HIP_TRY(b, dev_realloc(b->s_zv0, m));
     if (n > 0) {
@@ -2926,6 +2981,131 @@ int sfm_batch_download_spawns(SfmBatch* b, uint8_t* born, float* birth_time) {
         }
         if (birth_time) HIP_TRY(b, hipMemcpy(birth_time, b->s_birth, 4 * n, hipMemcpyDeviceToHost));
     }
+    return SFM_OK;
+}
+
+// The snapshot (ABI 13): every array a tick can change, device to device on the batch's stream; the host does not wait.
+int sfm_batch_snapshot(SfmBatch* b) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    b->snap = false;                                             // (a failure below leaves the batch without a snapshot)
+    const size_t n = (size_t)b->n_total, B = (size_t)b->B;
+    if ((rc = snap_copy(b, b->n_pk, b->pk, n))) return rc;
+    if (b->z3 && (rc = snap_copy(b, b->n_zv, b->zv, n))) return rc;
+    if ((rc = snap_copy(b, b->n_own, b->own, n))) return rc;
+    if ((rc = snap_copy(b, b->n_draws, b->draws, n))) return rc;
+    if (b->boxes) {                                              // the half of the ping-pong the next tick reads
+        const BatchGeoDev& g = b->geo[2];
+        if ((rc = snap_copy(b, b->n_ctr, g.ctr, (size_t)g.K))) return rc;
+        if ((rc = snap_copy(b, b->n_pts, g.pts, (size_t)g.P))) return rc;
+    }
+    if (b->fsm_on) {
+        if ((rc = snap_copy(b, b->n_mode, b->f_mode, n))) return rc;
+        if ((rc = snap_copy(b, b->n_target, b->f_target, n))) return rc;
+        if ((rc = snap_copy(b, b->n_cursor, b->f_cursor, n))) return rc;
+        if ((rc = snap_copy(b, b->n_time, b->f_time, B))) return rc;
+    }
+    if (b->spawn_on) {
+        if ((rc = snap_copy(b, b->n_born, b->s_born, n))) return rc;
+        if ((rc = snap_copy(b, b->n_birth, b->s_birth, n))) return rc;
+    }
+    if (b->tracks) {
+        if ((rc = snap_copy(b, b->n_first, b->t_first, (size_t)b->geo[2].K))) return rc;
+        b->n_first_h = b->t_first_h;
+        b->n_tick = b->t_tick;
+    }
+    b->snap = true;
+    return SFM_OK;
+}
+
+// The chosen scenes back to the snapshot: ONE launch of sfm_batch_restart_kernel, a workgroup per chosen scene.  Everything is
+// checked before anything is sent or launched.
+int sfm_batch_restart(SfmBatch* b, const uint8_t* mask) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->snap)
+        return bfail(b, SFM_ERR_STATE, "the batch has no snapshot: call sfm_batch_snapshot first (sfm_batch_upload_state and the calls "
+                                       "that set vehicles, modes, a spawn schedule or tracks drop it)");
+    const int B = b->B;
+    int chosen = B;
+    if (mask) {
+        chosen = 0;
+        for (int k = 0; k < B; ++k) {
+            if (mask[k] > 1) return bfail(b, SFM_ERR_INVALID, "mask must hold 0 or 1 (scene " + std::to_string(k) + ")");
+            chosen += mask[k];
+        }
+    }
+    // track time per scene: the chosen scenes' tracked vehicles are found by tau at the keyframe the snapshot had them at
+    const long long shift = b->tracks ? b->t_tick - b->n_tick : 0;
+    if (b->tracks)
+        for (int k = 0; k < B; ++k) {
+            if (mask && !mask[k]) continue;
+            for (int v = b->box_item_off_h[k]; v < b->box_item_off_h[k + 1]; ++v) {
+                const long long first = (long long)b->n_first_h[v] + shift;
+                if (b->t_off_h[v + 1] > b->t_off_h[v] && (first < INT32_MIN || first > INT32_MAX))
+                    return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(k) + ", vehicle " + std::to_string(v) + ": its first tick moved by the " +
+                                                     std::to_string(shift) + " ticks since the snapshot does not fit int32: set the tracks "
+                                                     "again (sfm_batch_set_vehicle_tracks restarts the tick counter)");
+            }
+        }
+    if (chosen == 0) return SFM_OK;
+    if (mask) {
+        if (!b->r_list) {
+            HIP_TRY(b, hipMalloc(reinterpret_cast<void**>(&b->r_list), sizeof(int) * (size_t)B));
+            HIP_TRY(b, hipHostMalloc(reinterpret_cast<void**>(&b->r_list_h), sizeof(int) * (size_t)B, 0));
+            HIP_TRY(b, hipEventCreateWithFlags(&b->r_done, hipEventDisableTiming));
+        }
+        if (b->r_pending) {                                      // the restart before this one may still read the pinned list
+            HIP_TRY(b, hipEventSynchronize(b->r_done));
+            b->r_pending = false;
+        }
+        for (int k = 0, q = 0; k < B; ++k)
+            if (mask[k]) b->r_list_h[q++] = k;
+        HIP_TRY(b, hipMemcpyAsync(b->r_list, b->r_list_h, sizeof(int) * (size_t)chosen, hipMemcpyHostToDevice, b->stream));
+    }
+    BatchRestart r;
+    memset(&r, 0, sizeof(r));
+    r.list = mask ? b->r_list : nullptr;
+    r.scene_off = b->d_scene_off;
+    r.pk = b->pk; r.s_pk = b->n_pk.p;
+    if (b->z3) { r.zv = b->zv; r.s_zv = b->n_zv.p; }
+    r.own = b->own; r.s_own = b->n_own.p;
+    r.draws = b->draws; r.s_draws = b->n_draws.p;
+    if (b->boxes) {
+        const BatchGeoDev& g = b->geo[2];
+        r.item_off = g.item_off; r.veh_off = g.off;
+        r.ctr = g.ctr; r.s_ctr = b->n_ctr.p;
+        r.pts = g.P > 0 ? g.pts : nullptr; r.s_pts = b->n_pts.p;
+    }
+    if (b->fsm_on) {
+        r.mode = b->f_mode; r.s_mode = b->n_mode.p;
+        r.target = b->f_target; r.s_target = b->n_target.p;
+        r.cursor = b->f_cursor; r.s_cursor = b->n_cursor.p;
+        r.sim_time = b->f_time; r.s_sim_time = b->n_time.p;
+    }
+    if (b->spawn_on) {
+        r.born = b->s_born; r.s_born = b->n_born.p;
+        r.birth_time = b->s_birth; r.s_birth_time = b->n_birth.p;
+    }
+    if (b->tracks) {
+        r.first = b->t_first; r.s_first = b->n_first.p;
+        r.trk_off = b->t_off;
+        r.shift = shift;
+    }
+    if (b->n_total == 0) { r.pk = nullptr; r.own = nullptr; r.draws = nullptr; r.zv = nullptr; r.mode = nullptr; r.target = nullptr;
+                           r.cursor = nullptr; r.born = nullptr; r.birth_time = nullptr; }      // (no rows: no snapshot arrays either)
+    HIP_TRY(b, launch_batch_restart(r, chosen, b->stream));
+    if (mask) {
+        HIP_TRY(b, hipEventRecord(b->r_done, b->stream));
+        b->r_pending = true;
+    }
+    if (b->tracks)                                               // the host's copy, which sfm_batch_download_vehicle_tracks answers from
+        for (int k = 0; k < B; ++k) {
+            if (mask && !mask[k]) continue;
+            for (int v = b->box_item_off_h[k]; v < b->box_item_off_h[k + 1]; ++v)
+                b->t_first_h[v] = b->t_off_h[v + 1] > b->t_off_h[v] ? (int32_t)((long long)b->n_first_h[v] + shift) : b->n_first_h[v];
+        }
     return SFM_OK;
 }
 

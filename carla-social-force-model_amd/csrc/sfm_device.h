@@ -293,6 +293,34 @@ struct BatchArgs {
     BatchTracks trk;          // vehicle tracks, read in the vehicle prologue only (appended last for the same reason)
 };
 
+// Restart of chosen scenes from the batch's snapshot (sfm_batch_restart, sfm_batch_restart_kernel): every array a tick can change,
+// the live one and its snapshot copy (s_*) side by side; a null live pointer: the batch has no such array.
+struct BatchRestart {
+    const int* list;          // [grid] the chosen scenes, ascending; null: workgroup g restarts scene g
+    const int* scene_off;     // [B+1]
+    float4* pk;         const float4* s_pk;
+    float2* zv;         const float2* s_zv;       // 3-D batches only
+    float4* own;        const float4* s_own;
+    uint32_t* draws;    const uint32_t* s_draws;
+    // device-side vehicles: the half of the ping-pong the next tick reads
+    const int* item_off;      // [B+1] geo[2].item_off
+    const int* veh_off;       // [M+1] geo[2].off
+    float4* ctr;        const float4* s_ctr;
+    float2* pts;        const float2* s_pts;
+    // modes
+    uint8_t* mode;      const uint8_t* s_mode;
+    float* target;      const float* s_target;
+    int* cursor;        const int* s_cursor;
+    float* sim_time;    const float* s_sim_time;  // [B]
+    // spawn schedule
+    uint8_t* born;      const uint8_t* s_born;
+    float* birth_time;  const float* s_birth_time;
+    // vehicle tracks: a tracked vehicle's first tick moves with the scene, first = s_first + shift (checked on the host to fit)
+    int* first;         const int* s_first;
+    const int* trk_off;       // [M+1]
+    long long shift;          // tau now - tau of the snapshot
+};
+
 // Block-major packing for sharded runs (sfm_set_partition, sfm_reorder.hip): the row order is cut into gx columns by x, each
 // column into gy blocks by y -- block b = column * gy + position holds rows [bound[b], bound[b+1]) -- and every block is
 // strip-packed on its own, so a rank's contiguous row range is a compact rectangle of the map instead of a slab across it.

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SFM_ABI_VERSION 12  /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles; 9: + sfm_batch_set_mode_fsm, sfm_batch_download_modes; 10: + sfm_batch_tick_forces, sfm_batch_run_recorded_forces; 11: + sfm_batch_set_spawn_schedule, sfm_batch_download_spawns, SFM_MODE_UNBORN; 12: + sfm_batch_set_vehicle_tracks, sfm_batch_download_vehicle_tracks (additions only) */
+#define SFM_ABI_VERSION 13  /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles; 9: + sfm_batch_set_mode_fsm, sfm_batch_download_modes; 10: + sfm_batch_tick_forces, sfm_batch_run_recorded_forces; 11: + sfm_batch_set_spawn_schedule, sfm_batch_download_spawns, SFM_MODE_UNBORN; 12: + sfm_batch_set_vehicle_tracks, sfm_batch_download_vehicle_tracks; 13: + sfm_batch_snapshot, sfm_batch_restart (additions only) */
 
 typedef struct SfmHandle SfmHandle;
 
@@ -442,6 +442,30 @@ int sfm_batch_tick_forces(SfmBatch* b, uint32_t flags, uint32_t force_mask, floa
  * SFM_BATCH_MAX_RECORD_BYTES applies to the frames and the forces together. */
 int sfm_batch_run_recorded_forces(SfmBatch* b, int ticks, uint32_t flags, int stride, uint32_t force_mask, float* frames,
                                   float* zframes, float* forces, int max_frames, int* n_frames);
+/* Restart from a device snapshot (ABI 13): episodes that end and start over -- RL environments, scenario sampling, calibration
+ * sweeps -- without the host in the loop.  sfm_batch_snapshot records, on the batch's stream, every piece of state a tick can
+ * change, for all scenes: positions and velocities (z / vz of a 3-D batch), waypoints and target speeds, the draw counters; with
+ * device-side vehicles the centres, velocities and rings the next tick reads; with modes each row's mode, mode target speed and
+ * queue cursor and each scene's clock; with a spawn schedule who is born and when; with tracks every vehicle's first tick and tau.
+ * The copies are device to device into grow-only buffers of the batch; the host does not wait for them.  A second snapshot
+ * replaces the first.  SFM_ERR_STATE before sfm_batch_upload_state. */
+int sfm_batch_snapshot(SfmBatch* b);
+/* Puts the chosen scenes back to the snapshot: mask [B] on the host, 1 = restart the scene, 0 = leave it alone (bit for bit);
+ * NULL = every scene.  ONE launch (sfm_batch_restart_kernel, a workgroup per chosen scene) ordered on the batch's stream with the
+ * ticks around it; the only copy is the list of chosen scenes (none with mask = NULL), and an all-zero mask launches nothing.
+ * A restarted scene then computes what it computed after the snapshot, whatever the other scenes do -- under the parameters, waypoint
+ * streams, borders and static obstacles of the moment, which may be set anew in between (the sweep: snapshot once, then per
+ * candidate sfm_batch_set_params, sfm_batch_restart(b, NULL), sfm_batch_run).  Track time is per scene: tau stays the batch's one
+ * counter (sfm_batch_download_vehicle_tracks goes on returning it), and a restart at tau_r of a snapshot taken at tau_s sets
+ * first_tick[k] = first_tick_snapshot[k] + (tau_r - tau_s) for the tracked vehicles of the chosen scenes, so that their keyframe
+ * index tau - first_tick[k], and with it their presence, is what it was at the snapshot.  sfm_batch_set_params,
+ * sfm_batch_set_waypoint_streams, sfm_batch_set_borders and sfm_batch_set_static_obstacles keep the snapshot;
+ * sfm_batch_upload_state, sfm_batch_set_dynamic_obstacles, sfm_batch_set_dynamic_boxes, sfm_batch_set_mode_fsm,
+ * sfm_batch_set_spawn_schedule and sfm_batch_set_vehicle_tracks drop it, each also in its "off" form (they change which arrays
+ * exist, or their sizes); a call that is refused drops nothing.  Refused with nothing sent or launched, the batch staying usable:
+ * no snapshot (SFM_ERR_STATE), a mask value above 1, a moved first tick that does not fit int32 (SFM_ERR_INVALID: set the tracks
+ * again, which restarts tau). */
+int sfm_batch_restart(SfmBatch* b, const uint8_t* mask);
 /* Current state of every scene (synchronises the batch's stream); NULL skips a column.  A planar batch leaves z alone and
  * writes vz = 0. */
 int sfm_batch_download_state(SfmBatch* b, float* x, float* y, float* z, float* vx, float* vy, float* vz);
