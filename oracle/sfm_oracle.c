@@ -64,7 +64,16 @@ static double moussaid(const OIx* p, const double* e, double dist, const double*
               + fabs(ft) * (1.0 + (2.0 * (p->n * B) * (p->n * B) * at + xt) * res);
         *plain += fabs(fv) + fabs(ft);                  /* the same sum without the conditioning weights */
     }
-    if (theta_tol > 0.0 && (fabs(theta) < theta_tol || fabs(fabs(raw) - M_PI) < theta_tol) && !isnan(ft)) return 2.0 * fabs(ft);
+    if (theta_tol > 0.0 && (fabs(theta) < theta_tol || fabs(fabs(raw) - M_PI) < theta_tol) && !isnan(ft)) {
+        double ex = 2.0 * fabs(ft);
+        if (fabs(fabs(raw) - M_PI) < theta_tol) {   /* the other side of the wrap: theta moves by 2 pi, so |theta| by 2 epsilon B (sfm_oracle.py) */
+            const double th2 = ang - copysign(2.0 * M_PI, ang) + B * (-p->epsilon);
+            const double fv2 = -1.0 * p->A * exp(a - (p->n_prime * B * th2) * (p->n_prime * B * th2));
+            const double ft2 = -1.0 * p->A * exp(a - (p->n * B * th2) * (p->n * B * th2));
+            if (!isnan(fv2) && !isnan(ft2)) ex += fabs(fv - fv2) + fabs(fabs(ft) - fabs(ft2));
+        }
+        return ex;
+    }
     return 0.0;
 }
 

@@ -114,7 +114,8 @@ def moussaid_term(e, dist, dv, p: Interaction, theta_tol=0.0, diagnostics=True):
     forces.py:241-270 (ped-obstacle).  ``e`` unit direction towards the other body (k components),
     ``dist`` the (possibly radius-reduced) distance, ``dv`` = v_self - v_other.
     Returns (force[..., k], exposure[...], magnitude[...]): exposure is the jump of the lateral term if
-    the sign of theta (or the +-pi wrap) flipped and |theta| (or |raw|-pi) is within ``theta_tol``;
+    the sign of theta (or the +-pi wrap) flipped and |theta| (or |raw|-pi) is within ``theta_tol`` -- at the wrap plus what
+    both terms change in size, since |theta| itself moves by 2 |epsilon| B there;
     magnitude = |f_v| + |f_theta| is the size of the term, the natural scale for the rounding error of a
     sum of such terms."""
     D = p.lam * dv + e                                       # :85
@@ -132,9 +133,18 @@ def moussaid_term(e, dist, dv, p: Interaction, theta_tol=0.0, diagnostics=True):
     if not diagnostics:                                      # plain forces only (the CPU timing leg of bench.py)
         return F, None, None
     if theta_tol > 0.0:
-        near = (np.abs(theta) < theta_tol) | (np.abs(np.abs(raw) - np.pi) < theta_tol)
-        with np.errstate(invalid="ignore"):
+        wrap = np.abs(np.abs(raw) - np.pi) < theta_tol
+        near = (np.abs(theta) < theta_tol) | wrap
+        with np.errstate(all="ignore"):
             expo = np.where(near, 2.0 * np.abs(f_th), 0.0)
+            # At the wrap the angle lands on the other side of +-pi: theta moves by 2 pi, and since theta = angle - epsilon B is not
+            # re-wrapped, |theta| moves by 2 |epsilon| B -- both exponentials change size as well as f_theta its sign.  The jump is at
+            # most 2 |f_theta| + |f_v - f_v'| + ||f_theta| - |f_theta'||, primes on the other side.
+            th2 = ang - np.copysign(TWO_PI, ang) - p.epsilon * B
+            fv2 = -p.A * np.exp(a - np.square(p.n_prime * B * th2))
+            ft2 = -p.A * np.exp(a - np.square(p.n * B * th2))
+            extra = np.abs(f_v - fv2) + np.abs(np.abs(f_th) - np.abs(ft2))
+            expo = expo + np.where(wrap & ~np.isnan(extra), extra, 0.0)
     else:
         expo = np.zeros_like(dist)
     # Conditioning: d f/d theta = -2 (n B)^2 theta f.  fp32 cannot resolve theta finer than ~2^-22 rad (theta is
