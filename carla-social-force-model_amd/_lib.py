@@ -14,7 +14,7 @@ import numpy as np
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFM_LIB_PATH") or os.path.join(PKG_DIR, "libsfm_hip.so")   # (the override is for A/B builds of the kernels)
-ABI_VERSION = 13
+ABI_VERSION = 14
 SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_records": 5,
          **{n: 6 for n in ("sfm_batch_create", "sfm_batch_destroy", "sfm_batch_set_stream", "sfm_batch_set_params",
                            "sfm_batch_upload_state", "sfm_batch_set_borders", "sfm_batch_set_static_obstacles",
@@ -26,7 +26,9 @@ SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_
          **{n: 10 for n in ("sfm_batch_tick_forces", "sfm_batch_run_recorded_forces")},
          **{n: 11 for n in ("sfm_batch_set_spawn_schedule", "sfm_batch_download_spawns")},
          **{n: 12 for n in ("sfm_batch_set_vehicle_tracks", "sfm_batch_download_vehicle_tracks")},
-         **{n: 13 for n in ("sfm_batch_snapshot", "sfm_batch_restart")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
+         **{n: 13 for n in ("sfm_batch_snapshot", "sfm_batch_restart")},
+         **{n: 14 for n in ("sfm_batch_set_steering", "sfm_batch_set_commands", "sfm_batch_download_steering",
+                            "sfm_batch_device_ptr")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
 
 FORCE_NAMES = ("acceleration_force", "pedestrian_force", "border_force",
                "static_obstacle_force", "dynamic_obstacle_force")
@@ -135,6 +137,11 @@ SYMBOLS = {
     # batch snapshot and restart (ABI 13)
     "sfm_batch_snapshot": (C.c_int, [_H]),
     "sfm_batch_restart": (C.c_int, [_H, _U8]),
+    # batch steering (ABI 14)
+    "sfm_batch_set_steering": (C.c_int, [_H, _U8, _F, _F, _F]),
+    "sfm_batch_set_commands": (C.c_int, [_H, _F, _F, _F]),
+    "sfm_batch_download_steering": (C.c_int, [_H, _U8, _F, _F, _F]),
+    "sfm_batch_device_ptr": (C.c_void_p, [_H, C.c_int, C.POINTER(C.c_int64)]),
 }
 
 _lib = None

@@ -1,6 +1,6 @@
 """Batched scenes: many small, independent crowds stepped by ONE kernel launch per tick (C ABI: sfm_batch_*, ABI 6; waypoint
 streams and recorded runs, ABI 7; device-side vehicles, ABI 8; pedestrian modes, ABI 9; force records, ABI 10; spawn schedules, ABI 11;
-vehicle tracks, ABI 12; snapshot and restart, ABI 13).
+vehicle tracks, ABI 12; snapshot and restart, ABI 13; steered pedestrians, ABI 14).
 
 Social-force models are run in bulk as many small scenes -- scenario sampling, RL environments stepped in lock-step, calibration
 sweeps over A / lambda / gamma / tau.  ``SfmBatch`` holds B scenes of 0 .. 1024 pedestrians, each with its own parameters (its own
@@ -54,6 +54,14 @@ candidate ``set_params``, ``restart()``, ``run``: a restarted scene runs under t
 obstacles of the moment).  ``upload`` and the calls that set vehicles, modes, spawn schedules or tracks drop the snapshot
 (``has_snapshot``).  Scripted traffic restarts per scene as well: a restarted scene's tracked vehicles are where they were at the
 snapshot, while ``vehicle_tracks()`` goes on counting the batch's ticks.
+
+Steered pedestrians (ABI 14): rows whose motion the caller decides -- the ego agent of an RL policy, observed pedestrians replayed
+along their recorded motion, the reference's ``update_ped_info``.  ``set_steering(kinds, commands)`` gives every row a kind (0 not
+steered, 1 velocity command: v' is the command bit for bit; 2 preferred velocity: the command replaces v0 * e_wp in the
+acceleration term) and a command; the tick's one launch reads them, everyone else sees a steered row as an ordinary pedestrian,
+and arrivals, modes, despawn and birth go on for it.  ``set_commands`` sends new velocities with one copy per step;
+``command_tensor()`` is the command buffer as a torch tensor a policy writes on the device, ``state_tensor()`` / ``zstate_tensor()``
+the state it reads.  Steering is an input like the parameters: only ``upload`` drops it, and a snapshot neither holds nor loses it.
 """
 from __future__ import annotations
 
@@ -512,6 +520,73 @@ def restart_mask(B, scenes=None):
     return mask
 
 
+STEER_OFF, STEER_VELOCITY, STEER_PREFERRED = 0, 1, 2   # the kinds of a steered row (held as floats in the command buffer)
+PTR_COMMANDS, PTR_STATE, PTR_ZSTATE = 0, 1, 2          # SFM_BATCH_PTR_*: what sfm_batch_device_ptr / SfmBatch.device_ptr select
+
+
+def _per_scene(v, so, width, name):
+    """A list / tuple with one entry per scene, or one ndarray over the concatenated rows -> a float64 array of N_total rows
+    (``width`` 0: flat values; else 2 or 3 columns, padded with zeros to 3).  One value (flat) or one (2|3,) vector stands for every
+    row of its scene, or of the batch."""
+    B, n = len(so) - 1, int(so[-1])
+
+    def rows(e, nb, where):
+        a = np.asarray(e, dtype=np.float64)
+        if not width:
+            a = np.broadcast_to(a, (nb,)) if a.ndim == 0 else a
+            ok = a.ndim == 1 and a.shape[0] == nb
+        else:
+            if a.ndim == 1 and a.shape[0] in (2, 3):
+                a = np.broadcast_to(a, (nb, a.shape[0]))
+            if a.size == 0 and nb == 0:
+                a = np.zeros((0, 3))
+            ok = a.ndim == 2 and a.shape[0] == nb and a.shape[1] in (2, 3)
+            if ok and a.shape[1] == 2:
+                a = np.concatenate([a, np.zeros((nb, 1))], axis=1)
+        if not ok:
+            raise ValueError(f"{where}{name} of shape {a.shape} for {nb} rows")
+        return a
+
+    if isinstance(v, (list, tuple)):
+        if len(v) != B:
+            raise ValueError(f"{len(v)} entries of {name} for {B} scenes (a list is per scene; pass an ndarray for concatenated rows)")
+        parts = [rows(np.zeros(3 if width else ()) if e is None else e, int(so[b + 1] - so[b]), f"scene {b}: ") for b, e in enumerate(v)]
+        return np.concatenate(parts, axis=0)
+    return rows(v, n, "")
+
+
+def pack_steering(kinds, commands, scene_off):
+    """Steering -> the arguments of sfm_batch_set_steering: (kind uint8 [N_total], ux, uy, uz float32 [N_total]).  ``kinds``: a list
+    with one entry per scene (each (N_b,), or one value for the whole scene), or an ndarray (N_total,) over the concatenated rows, or
+    one value for every row; 0 not steered, 1 velocity command, 2 preferred velocity.  ``commands``: a list with one entry per
+    scene (each (N_b,2|3), one (2|3,) command for the whole scene, or None: zeros), or an ndarray (N_total,2|3), or None (zeros);
+    two columns leave uz = 0.  ``kinds=None``: (None, ux, uy, uz), the commands alone.  Pure NumPy; raises ValueError on a shape that
+    does not fit, a kind that is not 0, 1 or 2, and a command that is not finite in float32 on a steered row (with ``kinds=None``:
+    on any row)."""
+    so = np.asarray(scene_off)
+    n = int(so[-1])
+    kd = None
+    if kinds is not None:
+        k = _per_scene(kinds, so, 0, "kinds")
+        if n and not np.isin(k, (0.0, 1.0, 2.0)).all():
+            raise ValueError("kinds must hold 0 (not steered), 1 (velocity command) or 2 (preferred velocity)")
+        kd = np.ascontiguousarray(k, dtype=np.uint8)
+    c = np.zeros((n, 3)) if commands is None else _per_scene(commands, so, 3, "commands")
+    with np.errstate(over="ignore", invalid="ignore"):
+        u = np.ascontiguousarray(c, dtype=np.float32)
+    bad = ~np.isfinite(u).all(axis=1) & (np.ones(n, bool) if kd is None else kd != 0)
+    if bad.any():
+        raise ValueError(f"row {int(np.flatnonzero(bad)[0])}: the command of a steered row must be finite in float32")
+    return kd, f32(u[:, 0]), f32(u[:, 1]), f32(u[:, 2])
+
+
+class _DeviceSpan:
+    """Minimal __cuda_array_interface__ carrier so torch can alias a raw device pointer (no copy), as stepper._DevSpan."""
+
+    def __init__(self, ptr, shape):
+        self.__cuda_array_interface__ = {"shape": tuple(int(d) for d in shape), "typestr": "<f4", "data": (int(ptr), False), "version": 2}
+
+
 def split_frames(frames, scene_off):
     """Frames of the concatenated batch, (F, N_total, C), -> a list of B arrays (F, N_b, C), one per scene in scene order (views).
     Pure NumPy."""
@@ -719,6 +794,86 @@ class SfmBatch:
         parameters and static geometry of the moment; its tracked vehicles are where they were at the snapshot."""
         mask = None if scenes is None else restart_mask(self.B, scenes)
         self._check(self._lib.sfm_batch_restart(self._b, u8ptr(mask)), "sfm_batch_restart")
+
+    def set_steering(self, kinds, commands=None):
+        """Which rows the caller steers, and their first commands (sfm_batch_set_steering; see ``pack_steering``): kind 1 rows take
+        the command as their new velocity, kind 2 rows as their preferred velocity.  ``kinds=None`` switches steering off.  Needs
+        ``upload`` first, which also drops it; every other call keeps it, and it keeps the snapshot.  Reallocates the command buffer
+        (``command_tensor()`` must be taken again)."""
+        L = self._lib
+        if kinds is None:
+            self._check(L.sfm_batch_set_steering(self._b, None, None, None, None), "sfm_batch_set_steering")
+            return
+        if self.scene_off is None:
+            raise SfmLibraryError("SfmBatch.set_steering: upload() has not been called")
+        kd, ux, uy, uz = pack_steering(kinds, commands, self.scene_off)
+        if kd.shape[0] == 0:                                           # (no rows: still a call, so that steering is on)
+            kd, ux, uy, uz = np.zeros(1, np.uint8), np.zeros(1, np.float32), np.zeros(1, np.float32), np.zeros(1, np.float32)
+        self._check(L.sfm_batch_set_steering(self._b, u8ptr(kd), fptr(ux), fptr(uy), fptr(uz)), "sfm_batch_set_steering")
+
+    def set_commands(self, commands):
+        """New commands for every row, kinds as ``set_steering`` set them (sfm_batch_set_commands): one host-to-device copy on the
+        batch's stream, no wait.  ``commands`` as for ``pack_steering``; rows that are not steered may hold anything finite or
+        not -- they are validated by the library against the kinds it knows."""
+        if self.scene_off is None:
+            raise SfmLibraryError("SfmBatch.set_commands: upload() has not been called")
+        so = self.scene_off
+        c = np.zeros((int(so[-1]), 3)) if commands is None else _per_scene(commands, so, 3, "commands")
+        with np.errstate(over="ignore", invalid="ignore"):
+            u = np.ascontiguousarray(c, dtype=np.float32)
+        ux, uy, uz = f32(u[:, 0]), f32(u[:, 1]), f32(u[:, 2])
+        if ux.shape[0] == 0:
+            ux = uy = uz = np.zeros(1, np.float32)
+        self._check(self._lib.sfm_batch_set_commands(self._b, fptr(ux), fptr(uy), fptr(uz)), "sfm_batch_set_commands")
+
+    def steering(self):
+        """Per scene (kind (N_b,) uint8, command (N_b,3) float32) as the next tick reads them, in scene order (synchronises the
+        batch's stream).  Raises SfmLibraryError while steering is off."""
+        n = int(self.scene_off[-1]) if self.scene_off is not None else 0
+        kd = np.zeros(max(n, 1), np.uint8)
+        u = [np.zeros(max(n, 1), np.float32) for _ in range(3)]
+        self._check(self._lib.sfm_batch_download_steering(self._b, u8ptr(kd), *(fptr(a) for a in u)), "sfm_batch_download_steering")
+        so = self.scene_off if self.scene_off is not None else np.zeros(self.B + 1, np.int32)
+        cmd = np.stack(u, axis=1)
+        return [(kd[so[b]:so[b + 1]], cmd[so[b]:so[b + 1]]) for b in range(self.B)]
+
+    def device_ptr(self, which):
+        """(address, bytes) of a device buffer of the batch (sfm_batch_device_ptr): ``PTR_COMMANDS``, ``PTR_STATE`` or
+        ``PTR_ZSTATE`` ((0, 0) for a planar batch).  Valid until the next ``upload`` (the command buffer: or ``set_steering``)."""
+        nbytes = C.c_int64(0)
+        if self.scene_off is None:
+            raise SfmLibraryError("SfmBatch.device_ptr: upload() has not been called")
+        ptr = self._lib.sfm_batch_device_ptr(self._b, int(which), C.byref(nbytes))
+        if not ptr and int(self.scene_off[-1]) > 0 and not (which == PTR_ZSTATE and self.planar):
+            self._check(-1, "sfm_batch_device_ptr")                    # (without rows, and {z, vz} of a planar batch: no buffer)
+        return int(ptr or 0), int(nbytes.value)
+
+    def _tensor(self, which, width, device):
+        import torch
+        ptr, nbytes = self.device_ptr(which)
+        dev = f"cuda:{torch.cuda.current_device() if device is None else int(device)}"
+        if not ptr:
+            return torch.zeros((0, width), dtype=torch.float32, device=dev)
+        return torch.as_tensor(_DeviceSpan(ptr, (nbytes // (4 * width), width)), device=dev)
+
+    def command_tensor(self, device=None):
+        """The command buffer as a torch tensor (N_total, 4) float32 {ux, uy, uz, kind} that aliases device memory (no copy): what a
+        policy writes.  Put torch and the batch on one stream (``set_stream(torch.cuda.current_stream().cuda_stream)``) so that
+        writes and ticks are ordered.  What is written here is not validated: a kind other than 1 or 2 counts as 0, and a
+        command that is not finite goes into the state.  ``set_commands`` sends the kinds of ``set_steering`` and so overwrites
+        kinds changed here.  Take it again after ``upload`` or ``set_steering``."""
+        return self._tensor(PTR_COMMANDS, 4, device)
+
+    def state_tensor(self, device=None):
+        """The state as a torch tensor (N_total, 4) float32 {x, y, vx, vy} that aliases device memory: what a policy reads, current
+        once the batch's stream has run the ticks issued.  Take it again after ``upload``."""
+        return self._tensor(PTR_STATE, 4, device)
+
+    def zstate_tensor(self, device=None):
+        """{z, vz} of a 3-D batch as a torch tensor (N_total, 2) float32 aliasing device memory; None for a planar batch."""
+        if self.planar:
+            return None
+        return self._tensor(PTR_ZSTATE, 2, device)
 
     def set_waypoint_streams(self, seeds, world_sides, arrive_thresholds=2.0):
         """Per-scene waypoint streams for ``redraw=True`` (see ``stream_arrays``; scalars broadcast to every scene).  They stay in

@@ -38,6 +38,10 @@
 // the barrier, so a chained row cannot see its predecessor's store of the same tick: one release per chain per tick.  A row that was
 // due when the schedule was set never left the live state (born = BORN_AT_SET); the first tick after that is its birth tick as far
 // as the row chained to it is concerned (the reference's spawn manager would release it at the top of that tick), and sets BORN_YES.
+// Steered rows (sfm_batch_set_steering, the STEER instantiations of EXT, MODES and MODES + SPAWN): the lane that owns a row loads its
+// command {ux, uy, uz, kind} from a.cmd in the epilogue -- an input like the parameters, never written here.  Kind 1: v' is the
+// command bit for bit; kind 2: the command stands where v0 e_wp stands in the acceleration term; both by select, so any other row
+// computes what it computes without STEER.  Everyone else sees the row as staged: nothing is ordered inside a launch.
 // Planar bodies (moussaid_planar / moussaid_spatial) with the exact body (moussaid<.., EXACT>) recomputing a slice whose sum came out
 // NaN (coincident pair, or two pedestrians above one another in 3-D), as the handle's kernels do.
 // Determinism: no atomics, every order is a function of the scene alone (N_b, its rows, its polylines) -- a scene's result is
@@ -153,7 +157,20 @@ __device__ __forceinline__ void batch_geometry(const BatchArgs& a, const BatchPa
     }
 }
 
-template <bool Z3, bool RAD, bool EXT, bool MODES, bool SPAWN>
+// acceleration_force<true, false> of a row that may be steered: for a kind 2 row (k2) the command u stands where v0 e_wp stands,
+// F_acc = (u - v) / tau in every component.  The unsteered term is acceleration_force's own; the steered one is written as
+// fma(-v, 1/tau, u * 1/tau), an expression of another shape, so that the compiler cannot merge the two sides of the select into
+// shared operations and fuse them differently: a row that is not steered gets, bit for bit, what it gets without STEER.
+template <bool Z3, class P>
+__device__ __forceinline__ void steered_acceleration_force(const P& p, float wx, float wy, float x, float y, float vx, float vy, float vz,
+                                                           float ts, bool k2, const float4& u, float& fax, float& fay, float& faz) {
+    acceleration_force<true, false>(p, wx, wy, x, y, vx, vy, vz, ts, fax, fay, faz);
+    fax = k2 ? __builtin_fmaf(-vx, p.inv_tau, u.x * p.inv_tau) : fax;
+    fay = k2 ? __builtin_fmaf(-vy, p.inv_tau, u.y * p.inv_tau) : fay;
+    if (Z3) faz = k2 ? __builtin_fmaf(-vz, p.inv_tau, u.z * p.inv_tau) : faz;   // (planar: uz = 0 is the term it has)
+}
+
+template <bool Z3, bool RAD, bool EXT, bool MODES, bool SPAWN, bool STEER>
 __device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParams& p, BatchShared<Z3, SPAWN>& sh, int b, int s0, int n,
                                             float now) {
     const int tid = threadIdx.x;
@@ -233,10 +250,25 @@ __device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParam
 
         if (!MODES) o = a.own[s0 + i];
         const float ts = o.z;
+        // STEER: the row's command {ux, uy, uz, kind}, one 16-byte load by the lane that owns the row; the kernel never writes it.
+        // kind 1: v' is the command; kind 2: the command replaces v0 e_wp in the acceleration term; anything else: not steered.  A
+        // ghost (despawned earlier, or unborn) ignores its command.  Selects, so a row with kind 0 runs the arithmetic it always ran
+        bool k1 = false, k2 = false;
+        float4 u = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (STEER) {
+            u = a.cmd[s0 + i];
+            const bool there = !MODES || m != MODE_DESPAWNED;
+            k1 = there && u.w == 1.0f;
+            k2 = there && u.w == 2.0f;
+            if (!Z3) u.z = 0.0f;                                       // a planar batch ignores uz
+        }
         float fax = 0.f, fay = 0.f, faz = 0.f;
         // (the z lane even in a planar scene, where vz = 0 makes it exactly +0: <Z3, false> is shorter but measured 4% slower at 8192
         //  scenes, profiles/r07_batch_planar_z_lane.txt)
-        if (p.en_acc) acceleration_force<true, false>(p, o.x, o.y, x, y, vx, vy, vz, ts, fax, fay, faz);
+        if (p.en_acc) {
+            if constexpr (STEER) steered_acceleration_force<Z3>(p, o.x, o.y, x, y, vx, vy, vz, ts, k2, u, fax, fay, faz);
+            else acceleration_force<true, false>(p, o.x, o.y, x, y, vx, vy, vz, ts, fax, fay, faz);
+        }
         // sum in the dict order acceleration, pedestrian, border, static, dynamic (pedestrian_simulation.py:37-48,81), as sfm_tick_kernel
         const float Fx = (((fax + fpx) + fbx) + fsx) + fdx;
         const float Fy = (((fay + fpy) + fby) + fsy) + fdy;
@@ -307,6 +339,12 @@ __device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParam
             }
             if (SPAWN && born == SPAWN_SETTLED) a.spn.born[s0 + i] = BORN_YES;
         }
+        if constexpr (STEER) {                                         // kind 1: the command bit for bit, no cap; it moves below as
+            const bool go = k1 && !park;                               // every row does.  A row that parks in this tick is not
+            nvx = go ? u.x : nvx;                                      // steered: parking overrides the command altogether, so its
+            nvy = go ? u.y : nvy;                                      // z (all that is left of the move) is the unsteered row's
+            nvz = go ? u.z : nvz;
+        }
         float nx = x, ny = y, nz = z;
         if (a.flags & 1u) { nx = fmaf(p.dt, nvx, x); ny = fmaf(p.dt, nvy, y); nz = fmaf(p.dt, nvz, z); }
         if (MODES && park) {                                           // destroy_pedestrian: parked as a ghost, keyed by the
@@ -318,9 +356,10 @@ __device__ __forceinline__ void batch_scene(const BatchArgs& a, const BatchParam
     }
 }
 
-template <bool Z3, bool EXT, bool MODES, bool SPAWN = false>
+template <bool Z3, bool EXT, bool MODES, bool SPAWN = false, bool STEER = false>
 __global__ __launch_bounds__(BLOCK) void sfm_batch_tick_kernel(const BatchArgs a) {
     static_assert(!SPAWN || MODES, "a spawn schedule runs on the mode state machine");
+    static_assert(!STEER || EXT || MODES, "steered rows ride the EXT and MODES forms");
     __shared__ BatchShared<Z3, SPAWN> sh;
     const int b = blockIdx.x;
     if (a.veh_on) {                                                     // uniform; also a scene without pedestrians: every vehicle
@@ -378,8 +417,8 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_tick_kernel(const BatchArgs a
     }
     __syncthreads();
     if (MODES && threadIdx.x == 0) a.fsm.sim_time[b] = now + p.dt;
-    if (p.rad) batch_scene<Z3, true, EXT, MODES, SPAWN>(a, p, sh, b, s0, n, now);
-    else batch_scene<Z3, false, EXT, MODES, SPAWN>(a, p, sh, b, s0, n, now);
+    if (p.rad) batch_scene<Z3, true, EXT, MODES, SPAWN, STEER>(a, p, sh, b, s0, n, now);
+    else batch_scene<Z3, false, EXT, MODES, SPAWN, STEER>(a, p, sh, b, s0, n, now);
 }
 
 // sfm_batch_set_spawn_schedule: the rows that are unborn when the schedule is set leave the live state -- parked where a despawned
@@ -417,9 +456,20 @@ hipError_t launch_batch_place_tracks(const BatchTracks& t, const int* off, const
 
 // modes: the mode state machine is on (a.fsm; records frames and forces too, never redraws); else ext: the tick redraws waypoints or
 // records a frame or forces (a.flags & 2, a.frame, a.force_rec); otherwise the plain kernel.  spawn (modes only): a spawn schedule
-// is set (a.spn) -- its own instantiation, so a batch without one launches the kernel it always did
-hipError_t launch_batch_tick(bool z3, bool ext, bool modes, bool spawn, const BatchArgs& a, int B, hipStream_t st) {
-    if (modes && spawn) {
+// is set (a.spn) -- its own instantiation, so a batch without one launches the kernel it always did.  steer: commands are set
+// (a.cmd) -- instantiations of their own again: of the EXT form (a plain steered tick takes it), of MODES and of MODES + SPAWN
+template <bool Z3>
+static void launch_batch_tick_steered(bool modes, bool spawn, const BatchArgs& a, int B, hipStream_t st) {
+    if (modes && spawn) hipLaunchKernelGGL((sfm_batch_tick_kernel<Z3, false, true, true, true>), dim3(B), dim3(BLOCK), 0, st, a);
+    else if (modes) hipLaunchKernelGGL((sfm_batch_tick_kernel<Z3, false, true, false, true>), dim3(B), dim3(BLOCK), 0, st, a);
+    else hipLaunchKernelGGL((sfm_batch_tick_kernel<Z3, true, false, false, true>), dim3(B), dim3(BLOCK), 0, st, a);
+}
+
+hipError_t launch_batch_tick(bool z3, bool ext, bool modes, bool spawn, bool steer, const BatchArgs& a, int B, hipStream_t st) {
+    if (steer) {
+        if (z3) launch_batch_tick_steered<true>(modes, spawn, a, B, st);
+        else launch_batch_tick_steered<false>(modes, spawn, a, B, st);
+    } else if (modes && spawn) {
         if (z3) hipLaunchKernelGGL((sfm_batch_tick_kernel<true, false, true, true>), dim3(B), dim3(BLOCK), 0, st, a);
         else hipLaunchKernelGGL((sfm_batch_tick_kernel<false, false, true, true>), dim3(B), dim3(BLOCK), 0, st, a);
     } else if (z3) {

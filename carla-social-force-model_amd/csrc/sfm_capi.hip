@@ -46,7 +46,7 @@ hipError_t launch_gather(const uint32_t* src, int N, const float4* pk_in, float4
 hipError_t launch_tile_bounds(const float4* pk, const float2* zv, int N, float4* box, float* vmax, hipStream_t st, int t_lo = 0,
                               int t_hi = -1);
 int probe_dpp_direction(hipStream_t st);
-hipError_t launch_batch_tick(bool z3, bool ext, bool modes, bool spawn, const BatchArgs& a, int B, hipStream_t st);
+hipError_t launch_batch_tick(bool z3, bool ext, bool modes, bool spawn, bool steer, const BatchArgs& a, int B, hipStream_t st);
 hipError_t launch_batch_park_unborn(const int* scene_off, const uint8_t* born, float4* pk, float2* zv, int B, hipStream_t st);
 hipError_t launch_batch_place_tracks(const BatchTracks& t, const int* off, const float2* local, float4* ctr, float2* pts, int M,
                                      hipStream_t st);
@@ -2107,6 +2107,15 @@ struct SfmBatch {
     int* r_list_h = nullptr;
     hipEvent_t r_done = nullptr;
     bool r_pending = false;
+    // steering (sfm_batch_set_steering, ABI 14): the command of every row {ux, uy, uz, kind}, an input the ticks only read.  c_cmd_h
+    // is its pinned host copy (the kinds of the last sfm_batch_set_steering, the velocities of the last call that sent any):
+    // sfm_batch_set_commands refills it and sends it with one copy on the stream; c_done is recorded behind that copy, and the
+    // next call waits for it before it refills
+    bool steer_on = false;
+    float4* c_cmd = nullptr;           // [N_total] on the device
+    float4* c_cmd_h = nullptr;
+    hipEvent_t c_done = nullptr;
+    bool c_pending = false;
     std::string err;
 };
 
@@ -2163,6 +2172,26 @@ static int check_scene_csr(SfmBatch* b, const int32_t* off, const char* name, in
                                              " pedestrians; a batch takes up to " + std::to_string(max_per_scene) + " per scene (larger crowds belong on a handle)");
     }
     *total = off[b->B];
+    return SFM_OK;
+}
+
+// back to a batch without steering (the caller synchronised the stream)
+static void free_batch_steering(SfmBatch* b) {
+    b->steer_on = false;
+    b->c_pending = false;
+    if (b->c_cmd) hipFree(b->c_cmd);
+    if (b->c_cmd_h) hipHostFree(b->c_cmd_h);
+    b->c_cmd = nullptr; b->c_cmd_h = nullptr;
+}
+
+// the velocities of a steering call: every array that is needed is there, and a steered row's command is finite
+static int check_batch_commands(SfmBatch* b, const float4* kinds, const uint8_t* kind, const float* ux, const float* uy, const float* uz) {
+    if (b->n_total > 0 && (!ux || !uy)) return bfail(b, SFM_ERR_INVALID, "ux or uy is NULL");
+    for (int i = 0; i < b->n_total; ++i) {
+        const bool steered = kind ? kind[i] != 0 : kinds[i].w != 0.0f;
+        if (steered && !(std::isfinite(ux[i]) && std::isfinite(uy[i]) && (!uz || std::isfinite(uz[i]))))
+            return bfail(b, SFM_ERR_INVALID, "row " + std::to_string(i) + ": the command of a steered row is not finite");
+    }
     return SFM_OK;
 }
 
@@ -2309,8 +2338,10 @@ static int batch_launch(SfmBatch* b, uint32_t flags, float4* frame = nullptr, fl
     a.force_n = b->n_total;
     a.force_slots = force_slots;
     if (b->spawn_on) a.spn = BatchSpawn{b->s_time, b->s_chain, b->s_born, b->s_birth, b->s_pk0, b->s_zv0};
+    const bool steer = b->steer_on && b->n_total > 0;            // (no rows: no command buffer, and nobody to steer)
+    if (steer) a.cmd = b->c_cmd;
     const bool ext = (flags & SFM_TICK_REDRAW_WAYPOINTS) || frame || force_rec;
-    HIP_TRY(b, launch_batch_tick(b->z3, ext, b->fsm_on, b->fsm_on && b->spawn_on, a, b->B, b->stream));
+    HIP_TRY(b, launch_batch_tick(b->z3, ext, b->fsm_on, b->fsm_on && b->spawn_on, steer, a, b->B, b->stream));
     if (move) {                                          // the moved half is what the next tick sees
         std::swap(b->geo[2].ctr, b->veh_ctr_alt);
         std::swap(b->geo[2].pts, b->veh_pts_alt);
@@ -2433,6 +2464,8 @@ int sfm_batch_destroy(SfmBatch* b) {
     }
     free_batch_boxes(b);
     free_batch_modes(b);
+    free_batch_steering(b);
+    if (b->c_done) hipEventDestroy(b->c_done);
     if (b->d_prm) hipFree(b->d_prm);
     if (b->d_scene_off) hipFree(b->d_scene_off);
     if (b->pk) hipFree(b->pk);
@@ -2500,6 +2533,7 @@ int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x
         b->cap = n;
     }
     free_batch_modes(b);                                          // a new crowd: its modes are set anew
+    free_batch_steering(b);                                       // ... and so are its commands (the rows may differ)
     b->snap = false;                                              // ... and so is its snapshot
     b->have_state = false;
     if (n > 0) {
@@ -3117,6 +3151,92 @@ int sfm_batch_run_recorded(SfmBatch* b, int ticks, uint32_t flags, int stride, f
 int sfm_batch_run_recorded_forces(SfmBatch* b, int ticks, uint32_t flags, int stride, uint32_t force_mask, float* frames,
                                   float* zframes, float* forces, int max_frames, int* n_frames) {
     return batch_run_recorded(b, ticks, flags, stride, frames, zframes, max_frames, n_frames, true, force_mask, forces);
+}
+
+// Steering (ABI 14): per-row commands the ticks read.  Everything is checked before anything is sent or freed.
+int sfm_batch_set_steering(SfmBatch* b, const uint8_t* kind, const float* ux, const float* uy, const float* uz) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    const size_t n = (size_t)b->n_total;
+    if (kind) {
+        for (size_t i = 0; i < n; ++i)
+            if (kind[i] > 2)
+                return bfail(b, SFM_ERR_INVALID, "row " + std::to_string(i) + ": kind must be 0 (not steered), 1 (velocity command) or 2 "
+                                                 "(preferred velocity)");
+        rc = check_batch_commands(b, nullptr, kind, ux, uy, uz);
+        if (rc) return rc;
+    }
+    HIP_TRY(b, hipStreamSynchronize(b->stream));                 // a tick or a copy in flight may still read the buffers
+    free_batch_steering(b);
+    if (!kind) return SFM_OK;
+    if (n > 0) {
+        HIP_TRY(b, hipMalloc(reinterpret_cast<void**>(&b->c_cmd), sizeof(float4) * n));
+        HIP_TRY(b, hipHostMalloc(reinterpret_cast<void**>(&b->c_cmd_h), sizeof(float4) * n, 0));
+        if (!b->c_done) HIP_TRY(b, hipEventCreateWithFlags(&b->c_done, hipEventDisableTiming));
+        for (size_t i = 0; i < n; ++i) b->c_cmd_h[i] = make_float4(ux[i], uy[i], uz ? uz[i] : 0.f, (float)kind[i]);
+        HIP_TRY(b, hipMemcpy(b->c_cmd, b->c_cmd_h, sizeof(float4) * n, hipMemcpyHostToDevice));
+    }
+    b->steer_on = true;
+    return SFM_OK;
+}
+
+int sfm_batch_set_commands(SfmBatch* b, const float* ux, const float* uy, const float* uz) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->steer_on) return bfail(b, SFM_ERR_STATE, "steering is off: call sfm_batch_set_steering first (sfm_batch_upload_state drops it)");
+    rc = check_batch_commands(b, b->c_cmd_h, nullptr, ux, uy, uz);
+    if (rc) return rc;
+    const size_t n = (size_t)b->n_total;
+    if (n == 0) return SFM_OK;
+    if (b->c_pending) {                                          // the copy before this one may still read the pinned block
+        HIP_TRY(b, hipEventSynchronize(b->c_done));
+        b->c_pending = false;
+    }
+    for (size_t i = 0; i < n; ++i) { b->c_cmd_h[i].x = ux[i]; b->c_cmd_h[i].y = uy[i]; b->c_cmd_h[i].z = uz ? uz[i] : 0.f; }
+    HIP_TRY(b, hipMemcpyAsync(b->c_cmd, b->c_cmd_h, sizeof(float4) * n, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(b, hipEventRecord(b->c_done, b->stream));
+    b->c_pending = true;
+    return SFM_OK;
+}
+
+int sfm_batch_download_steering(SfmBatch* b, uint8_t* kind, float* ux, float* uy, float* uz) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->steer_on) return bfail(b, SFM_ERR_STATE, "steering is off: call sfm_batch_set_steering first (sfm_batch_upload_state drops it)");
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    const size_t n = (size_t)b->n_total;
+    if (n == 0) return SFM_OK;
+    std::vector<float4> c(n);
+    HIP_TRY(b, hipMemcpy(c.data(), b->c_cmd, sizeof(float4) * n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        if (kind) kind[i] = c[i].w == 1.0f ? 1 : c[i].w == 2.0f ? 2 : 0;   // (what the tick makes of it)
+        if (ux) ux[i] = c[i].x;
+        if (uy) uy[i] = c[i].y;
+        if (uz) uz[i] = c[i].z;
+    }
+    return SFM_OK;
+}
+
+void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes) {
+    if (bytes) *bytes = 0;
+    if (!b) return nullptr;
+    if (which < SFM_BATCH_PTR_COMMANDS || which > SFM_BATCH_PTR_ZSTATE) { bfail(b, SFM_ERR_INVALID, "which must be SFM_BATCH_PTR_COMMANDS, _STATE or _ZSTATE"); return nullptr; }
+    if (!b->have_state) { bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called"); return nullptr; }
+    const size_t n = (size_t)b->n_total;
+    if (which == SFM_BATCH_PTR_COMMANDS) {
+        if (!b->steer_on) { bfail(b, SFM_ERR_STATE, "steering is off: call sfm_batch_set_steering first (sfm_batch_upload_state drops it)"); return nullptr; }
+        if (bytes) *bytes = (int64_t)(sizeof(float4) * n);
+        return b->c_cmd;
+    }
+    if (which == SFM_BATCH_PTR_ZSTATE) {
+        if (!b->z3 || n == 0) return nullptr;                    // a planar batch has no {z, vz}
+        if (bytes) *bytes = (int64_t)(sizeof(float2) * n);
+        return b->zv;
+    }
+    if (n == 0) return nullptr;
+    if (bytes) *bytes = (int64_t)(sizeof(float4) * n);
+    return b->pk;
 }
 
 const char* sfm_batch_last_error(const SfmBatch* b) { return b ? b->err.c_str() : g_create_error.c_str(); }

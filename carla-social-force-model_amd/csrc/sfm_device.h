@@ -291,6 +291,10 @@ struct BatchArgs {
     uint32_t force_slots;
     BatchSpawn spn;           // the SPAWN instantiation only (appended last for the same reason)
     BatchTracks trk;          // vehicle tracks, read in the vehicle prologue only (appended last for the same reason)
+    // steering (sfm_batch_set_steering; the STEER instantiations only, appended last for the same reason): the command of every row,
+    // {ux, uy, uz, kind} with kind 0 not steered, 1 velocity command, 2 preferred velocity (held as a float; any other value: 0).
+    // Read by the lane that owns the row, never written by a tick -- the caller may write it on the batch's stream
+    const float4* cmd;        // [N_total]
 };
 
 // Restart of chosen scenes from the batch's snapshot (sfm_batch_restart, sfm_batch_restart_kernel): every array a tick can change,

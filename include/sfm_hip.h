@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SFM_ABI_VERSION 13  /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles; 9: + sfm_batch_set_mode_fsm, sfm_batch_download_modes; 10: + sfm_batch_tick_forces, sfm_batch_run_recorded_forces; 11: + sfm_batch_set_spawn_schedule, sfm_batch_download_spawns, SFM_MODE_UNBORN; 12: + sfm_batch_set_vehicle_tracks, sfm_batch_download_vehicle_tracks; 13: + sfm_batch_snapshot, sfm_batch_restart (additions only) */
+#define SFM_ABI_VERSION 14  /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles; 9: + sfm_batch_set_mode_fsm, sfm_batch_download_modes; 10: + sfm_batch_tick_forces, sfm_batch_run_recorded_forces; 11: + sfm_batch_set_spawn_schedule, sfm_batch_download_spawns, SFM_MODE_UNBORN; 12: + sfm_batch_set_vehicle_tracks, sfm_batch_download_vehicle_tracks; 13: + sfm_batch_snapshot, sfm_batch_restart; 14: + sfm_batch_set_steering, sfm_batch_set_commands, sfm_batch_download_steering, sfm_batch_device_ptr (additions only) */
 
 typedef struct SfmHandle SfmHandle;
 
@@ -274,7 +274,7 @@ int sfm_abi_version(void);
  * each, every scene with its own SfmParams (a parameter sweep is one batch) and its own borders / obstacles; each tick is ONE kernel
  * launch for the whole batch (sfm_batch.hip, a workgroup per scene).  A scene's result is bitwise the same whatever else is in the
  * batch and wherever it sits.  Larger crowds belong on a handle.  Waypoint redraw (per-scene streams) and on-device trajectories
- * are ABI 7, device-side vehicles ABI 8, the mode state machine (sfm_batch_set_mode_fsm) ABI 9, force records ABI 10, spawn schedules ABI 11, vehicle tracks ABI 12.  Not
+ * are ABI 7, device-side vehicles ABI 8, the mode state machine (sfm_batch_set_mode_fsm) ABI 9, force records ABI 10, spawn schedules ABI 11, vehicle tracks ABI 12, restart ABI 13, steered pedestrians ABI 14.  Not
  * supported on a batch: sharding.  Host arrays are fp32 SoA over all scenes concatenated; scene b owns rows
  * [scene_off[b], scene_off[b+1]).  Geometry is per-scene CSR: scene b owns polylines [scene_item_off[b], scene_item_off[b+1]) of the
  * concatenated set, whose points are offsets[k] .. offsets[k+1]-1 (offsets[0] = 0).  Errors as for a handle: a negative SfmStatus,
@@ -466,6 +466,50 @@ int sfm_batch_snapshot(SfmBatch* b);
  * no snapshot (SFM_ERR_STATE), a mask value above 1, a moved first tick that does not fit int32 (SFM_ERR_INVALID: set the tracks
  * again, which restarts tau). */
 int sfm_batch_restart(SfmBatch* b, const uint8_t* mask);
+/* Pedestrians steered from outside (ABI 14): the reference's update_ped_info (run_simulation.py:79-87), where the simulator -- a
+ * policy, a recording -- decides a walker's motion, inside each tick's one launch.  Every row has a command {ux, uy, uz, kind} in a
+ * device buffer [N_total][4] of floats that the ticks read and never write; kind is held as a float: 0 not steered, 1 velocity
+ * command, 2 preferred velocity, any other value counts as 0.  The lane that owns a row reads its command in the epilogue.
+ * Kind 1: the row's new velocity IS the command, bit for bit, v' = (ux, uy[, uz]) -- no cap, no force applied -- and with
+ * SFM_TICK_INTEGRATE it moves as every row does, x' = fma(step_length, v', x).  Its forces are computed and recorded as ever (what
+ * Force.get_force returns for it); only the velocity update ignores them.  Kind 2: the row's acceleration term is (u - v) / tau
+ * in every component instead of (v0 e_wp - v) / tau, summed only where the scene's acceleration force is on; everything else is
+ * unchanged, the cap at max_speed_factor times this tick's target speed included; a force record holds the replaced term in
+ * the acceleration slot and the F that was used in the total.  To everyone else a steered row is an ordinary pedestrian at its
+ * staged position and velocity.  A planar batch ignores uz (it computes for uz = 0).  Nothing else about a steered row changes:
+ * arrival tests on the pre-move position, waypoint redraws, the mode machine, gap acceptance, queue pops, despawn and birth go
+ * on.  A despawned or unborn row ignores its command, parking overrides it (velocity 0; a kind 1 row that despawns
+ * in a tick is parked exactly as if it were not steered, its z of a 3-D batch included), and a row born in a tick is steered in
+ * that tick.  sfm_batch_run, sfm_batch_run_recorded and sfm_batch_run_recorded_forces hold the commands for all their ticks
+ * (action repeat); a tick without SFM_TICK_INTEGRATE writes v' only.  Steering is an input like the parameters:
+ * sfm_batch_set_params, sfm_batch_set_waypoint_streams, the geometry calls, sfm_batch_set_mode_fsm, sfm_batch_set_spawn_schedule,
+ * sfm_batch_set_vehicle_tracks, sfm_batch_snapshot and sfm_batch_restart keep it (a snapshot does not contain commands, and the
+ * steering calls keep the snapshot); sfm_batch_upload_state drops it, because the rows may differ.  A batch without steering
+ * launches exactly the kernels it launched before.
+ * sfm_batch_set_steering: kind [N_total] (0, 1, 2), ux, uy, uz [N_total] (uz NULL: zeros); kind = NULL switches steering off.
+ * It (re)allocates the command buffer and waits for the batch's stream.  Refused with nothing sent or freed: no state uploaded
+ * (SFM_ERR_STATE), a kind above 2, NULL ux / uy, a command that is not finite on a row with kind != 0. */
+int sfm_batch_set_steering(SfmBatch* b, const uint8_t* kind, const float* ux, const float* uy, const float* uz);
+/* New velocities for every row, the kinds staying those of the last sfm_batch_set_steering: ONE copy of the whole buffer from
+ * pinned memory, ordered on the batch's stream (the host waits only for the copy before, if it is still in flight).  Since it
+ * sends the kinds it knows, it overwrites kinds the caller changed on the device.  Refused: steering off (SFM_ERR_STATE), NULL
+ * ux / uy, a value that is not finite on a steered row. */
+int sfm_batch_set_commands(SfmBatch* b, const float* ux, const float* uy, const float* uz);
+/* The commands as the next tick will read them (synchronises the batch's stream): kind as the tick understands it (0, 1, 2);
+ * NULL skips a column.  SFM_ERR_STATE while steering is off. */
+int sfm_batch_download_steering(SfmBatch* b, uint8_t* kind, float* ux, float* uy, float* uz);
+/* Device pointers of a batch, the counterpart of sfm_row_data_ptr for a handle: which = SFM_BATCH_PTR_COMMANDS, the command buffer
+ * ([N_total][4] float {ux, uy, uz, kind}; the caller may write it, on the batch's stream or ordered with it -- a policy's output
+ * needs no host copy); SFM_BATCH_PTR_STATE, the state ([N_total][4] float {x, y, vx, vy}, as the last tick left it);
+ * SFM_BATCH_PTR_ZSTATE, {z, vz} ([N_total][2] float; NULL for a planar batch).  *bytes (may be NULL) receives the size.  The pointers
+ * stay valid until the next call that reallocates: sfm_batch_upload_state (all three) and sfm_batch_set_steering (the command
+ * buffer).  What the caller writes into the command buffer on the device is NOT validated: a kind other than 1 or 2 counts as
+ * 0, and a non-finite command of a steered row goes into the state as it is.  NULL (and the message in sfm_batch_last_error) for an
+ * unknown `which`, before sfm_batch_upload_state, and for the command buffer while steering is off; NULL without rows. */
+#define SFM_BATCH_PTR_COMMANDS 0
+#define SFM_BATCH_PTR_STATE 1
+#define SFM_BATCH_PTR_ZSTATE 2
+void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes);
 /* Current state of every scene (synchronises the batch's stream); NULL skips a column.  A planar batch leaves z alone and
  * writes vz = 0. */
 int sfm_batch_download_state(SfmBatch* b, float* x, float* y, float* z, float* vx, float* vy, float* vz);
