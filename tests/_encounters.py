@@ -546,7 +546,7 @@ def slots_symmetric(n, i, j):
 
 
 def fused_waves(n, geo):
-    """Waves per workgroup of the fused tick: csrc/sfm_capi.hip:1138-1148 (16, or 8 when pair + geometry workgroups exceed 512)."""
+    """Waves per workgroup of the fused tick: ``fused_launch`` in csrc/sfm_capi.hip (16, or 8 when pair + geometry workgroups exceed 512)."""
     n_t = (n + 63) // 64
     n_g = (n_t + 1) // 2
     n_pair = (n_g + 1) // 2 + n_g * ((n_g - 1) // 2) + (0 if n_g & 1 else n_g // 2)      # sfm_kernels.hip:2497
