@@ -14,7 +14,7 @@ import numpy as np
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFM_LIB_PATH") or os.path.join(PKG_DIR, "libsfm_hip.so")   # (the override is for A/B builds of the kernels)
-ABI_VERSION = 14
+ABI_VERSION = 15
 SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_records": 5,
          **{n: 6 for n in ("sfm_batch_create", "sfm_batch_destroy", "sfm_batch_set_stream", "sfm_batch_set_params",
                            "sfm_batch_upload_state", "sfm_batch_set_borders", "sfm_batch_set_static_obstacles",
@@ -28,7 +28,9 @@ SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_
          **{n: 12 for n in ("sfm_batch_set_vehicle_tracks", "sfm_batch_download_vehicle_tracks")},
          **{n: 13 for n in ("sfm_batch_snapshot", "sfm_batch_restart")},
          **{n: 14 for n in ("sfm_batch_set_steering", "sfm_batch_set_commands", "sfm_batch_download_steering",
-                            "sfm_batch_device_ptr")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
+                            "sfm_batch_device_ptr")},
+         **{n: 15 for n in ("sfm_batch_set_observation", "sfm_batch_observe", "sfm_batch_download_observations",
+                            "sfm_batch_observation_ptr")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
 
 FORCE_NAMES = ("acceleration_force", "pedestrian_force", "border_force",
                "static_obstacle_force", "dynamic_obstacle_force")
@@ -142,6 +144,11 @@ SYMBOLS = {
     "sfm_batch_set_commands": (C.c_int, [_H, _F, _F, _F]),
     "sfm_batch_download_steering": (C.c_int, [_H, _U8, _F, _F, _F]),
     "sfm_batch_device_ptr": (C.c_void_p, [_H, C.c_int, C.POINTER(C.c_int64)]),
+    # batch observations (ABI 15)
+    "sfm_batch_set_observation": (C.c_int, [_H, C.c_int, _F, C.c_int]),
+    "sfm_batch_observe": (C.c_int, [_H]),
+    "sfm_batch_download_observations": (C.c_int, [_H, _F]),
+    "sfm_batch_observation_ptr": (C.c_void_p, [_H, C.POINTER(C.c_int64)]),
 }
 
 _lib = None

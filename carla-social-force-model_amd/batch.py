@@ -1,6 +1,6 @@
 """Batched scenes: many small, independent crowds stepped by ONE kernel launch per tick (C ABI: sfm_batch_*, ABI 6; waypoint
 streams and recorded runs, ABI 7; device-side vehicles, ABI 8; pedestrian modes, ABI 9; force records, ABI 10; spawn schedules, ABI 11;
-vehicle tracks, ABI 12; snapshot and restart, ABI 13; steered pedestrians, ABI 14).
+vehicle tracks, ABI 12; snapshot and restart, ABI 13; steered pedestrians, ABI 14; observations, ABI 15).
 
 Social-force models are run in bulk as many small scenes -- scenario sampling, RL environments stepped in lock-step, calibration
 sweeps over A / lambda / gamma / tau.  ``SfmBatch`` holds B scenes of 0 .. 1024 pedestrians, each with its own parameters (its own
@@ -62,6 +62,16 @@ acceleration term) and a command; the tick's one launch reads them, everyone els
 and arrivals, modes, despawn and birth go on for it.  ``set_commands`` sends new velocities with one copy per step;
 ``command_tensor()`` is the command buffer as a torch tensor a policy writes on the device, ``state_tensor()`` / ``zstate_tensor()``
 the state it reads.  Steering is an input like the parameters: only ``upload`` drops it, and a snapshot neither holds nor loses it.
+
+Observations (ABI 15): what a policy or a reward reads per agent, computed on the device by one launch per call.
+``set_observation(k, sense_range, frame)`` chooses k neighbour slots, a sense range per scene and world axes or the row's heading
+frame; ``observe()`` fills, per row, ``16 + 4k`` floats -- goal, own velocity, target speed, a live flag, the number of neighbours
+found, which kinds of geometry are in range, the nearest vehicle ring point with the vehicle's relative velocity, the nearest border
+and static-obstacle points, and the k nearest neighbours in ascending (distance, index) order as relative positions and velocities
+(the record and its exact rules: include/sfm_hip.h).  ``observations()`` downloads them per scene, ``observation_tensor()`` is the
+buffer as a torch tensor a policy reads on the device, and ``observe.observe_scene`` is the host twin, bit for bit in frame 0.
+Observing changes nothing a tick reads.  With ``snapshot`` / ``restart`` (the reset) and steering (the action) this closes an RL
+loop with no host in it: examples/batch_rl_loop.py.
 """
 from __future__ import annotations
 
@@ -580,6 +590,49 @@ def pack_steering(kinds, commands, scene_off):
     return kd, f32(u[:, 0]), f32(u[:, 1]), f32(u[:, 2])
 
 
+OBS_HEADER = 16                  # SFM_BATCH_OBS_HEADER: floats of a row's record in front of its neighbour slots
+MAX_OBS_NEIGHBOURS = 16          # SFM_BATCH_MAX_OBS_NEIGHBOURS
+MAX_SENSE_RANGE = 1.0e6          # SFM_BATCH_MAX_SENSE_RANGE, metres
+FRAME_WORLD, FRAME_HEADING = 0, 1
+
+
+def obs_width(k):
+    """Floats of one row's observation record with ``k`` neighbour slots: OBS_HEADER + 4 k.  Raises ValueError outside 1 .. 16."""
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_OBS_NEIGHBOURS:
+        raise ValueError(f"k must be an integer 1 .. {MAX_OBS_NEIGHBOURS} (neighbour slots per row), got {k!r}")
+    return OBS_HEADER + 4 * int(k)
+
+
+def observation_arrays(B, k, sense_range, frame=0):
+    """Observation settings -> the arguments of sfm_batch_set_observation: (k int, sense_range float32 [B], frame int).
+    ``sense_range`` is a scalar (broadcast to every scene, like ``stream_arrays``) or B values, in metres: finite, > 0 and <= 1e6
+    in float32.  Pure NumPy; raises ValueError on a k outside 1 .. 16, a frame other than 0 or 1, and a range the library would
+    refuse."""
+    obs_width(k)
+    if isinstance(frame, (bool, np.bool_)) or not isinstance(frame, (int, np.integer)) or int(frame) not in (FRAME_WORLD, FRAME_HEADING):
+        raise ValueError(f"frame must be 0 (world axes) or 1 (the row's heading frame), got {frame!r}")
+    a = np.asarray(sense_range)
+    if a.dtype.kind not in "iuf":
+        raise ValueError(f"sense_range must be numbers, got {a.dtype}")
+    if a.ndim > 1 or (a.ndim == 1 and a.shape[0] not in (1, int(B))):
+        raise ValueError(f"sense_range: expected a scalar or {int(B)} values, got shape {a.shape}")
+    with np.errstate(over="ignore"):
+        r = f32(np.broadcast_to(a.reshape(-1), (int(B),)))
+    if not (np.isfinite(r).all() and (r > 0).all() and (r <= np.float32(MAX_SENSE_RANGE)).all()):
+        raise ValueError(f"sense_range must be finite, > 0 and <= {MAX_SENSE_RANGE:g} metres")
+    return int(k), r, int(frame)
+
+
+def split_observations(buf, scene_off):
+    """Observations of the concatenated batch, (N_total, W), -> a list of B arrays (N_b, W), one per scene in scene order
+    (views).  Pure NumPy."""
+    so = np.asarray(scene_off)
+    buf = np.asarray(buf)
+    if buf.ndim != 2 or buf.shape[0] != int(so[-1]):
+        raise ValueError(f"observations of shape {buf.shape} for {int(so[-1])} pedestrians")
+    return [buf[so[b]:so[b + 1]] for b in range(len(so) - 1)]
+
+
 class _DeviceSpan:
     """Minimal __cuda_array_interface__ carrier so torch can alias a raw device pointer (no copy), as stepper._DevSpan."""
 
@@ -659,6 +712,7 @@ class SfmBatch:
         self._z = None
         self._dyn = None                  # (scene_item_off, offsets) of the vehicles last set, for dynamic_obstacles()
         self.has_snapshot = False         # snapshot() has been taken and no later call has dropped it
+        self.obs_k = None                 # neighbour slots of set_observation (None: observations are off)
 
     def _check(self, rc, what):
         if rc != 0:
@@ -721,6 +775,7 @@ class SfmBatch:
                                                    fptr(pk["target_speed"]), fptr(pk["radius"]), u8ptr(pk["crossing"])),
                           "sfm_batch_upload_state")
         self.scene_off = so.copy()
+        self.obs_k = None                 # (the upload dropped the observations with the rows)
         self.planar = planar
         self._z = pk["z"].copy()          # a planar batch keeps each scene's z on the host (the device holds x / y only)
 
@@ -874,6 +929,55 @@ class SfmBatch:
         if self.planar:
             return None
         return self._tensor(PTR_ZSTATE, 2, device)
+
+    def set_observation(self, k, sense_range=None, frame=0):
+        """What ``observe`` computes (sfm_batch_set_observation; see ``observation_arrays`` and the module docstring): ``k``
+        neighbour slots per row, a sense range in metres (one value, or one per scene), world axes (``frame=0``) or the row's
+        heading frame (``frame=1``).  ``k=None`` switches observations off and frees the buffer.  Needs ``upload`` first, which
+        also drops them; every other call keeps them, and they keep the snapshot.  Allocates and zero-fills the buffer
+        (``observation_tensor()`` must be taken again)."""
+        L = self._lib
+        if k is None:
+            self._check(L.sfm_batch_set_observation(self._b, 0, None, 0), "sfm_batch_set_observation")
+            self.obs_k = None
+            return
+        if self.scene_off is None:
+            raise SfmLibraryError("SfmBatch.set_observation: upload() has not been called")
+        if sense_range is None:
+            raise ValueError("set_observation needs a sense_range (metres)")
+        k, r, frame = observation_arrays(self.B, k, sense_range, frame)
+        self._check(L.sfm_batch_set_observation(self._b, k, fptr(r), frame), "sfm_batch_set_observation")
+        self.obs_k = k
+
+    def observe(self):
+        """Compute every row's observation as the state is now (sfm_batch_observe): one launch on the batch's stream, ordered
+        with the ticks and restarts around it; the host does not wait.  Raises SfmLibraryError while observations are off."""
+        self._check(self._lib.sfm_batch_observe(self._b), "sfm_batch_observe")
+
+    def observations(self):
+        """``observe()`` and a download: a list of B float32 arrays (N_b, 16 + 4k) in scene order (synchronises the batch's
+        stream)."""
+        self.observe()
+        n = int(self.scene_off[-1])
+        buf = np.zeros((n, obs_width(self.obs_k)), np.float32)
+        self._check(self._lib.sfm_batch_download_observations(self._b, fptr(buf) if n else None), "sfm_batch_download_observations")
+        return split_observations(buf, self.scene_off)
+
+    def observation_tensor(self, device=None):
+        """The observation buffer as a torch tensor (N_total, 16 + 4k) float32 that aliases device memory (no copy): what a
+        policy reads after ``observe()``.  Put torch and the batch on one stream
+        (``set_stream(torch.cuda.current_stream().cuda_stream)``) so that the launch and the reads are ordered.  Take it again
+        after ``upload`` or ``set_observation``.  Raises SfmLibraryError while observations are off."""
+        import torch
+        nbytes = C.c_int64(0)
+        ptr = self._lib.sfm_batch_observation_ptr(self._b, C.byref(nbytes))
+        if not ptr and (self.obs_k is None or self.scene_off is None or int(self.scene_off[-1]) > 0):
+            self._check(-1, "sfm_batch_observation_ptr")
+        w = obs_width(self.obs_k)
+        dev = f"cuda:{torch.cuda.current_device() if device is None else int(device)}"
+        if not ptr:                                                    # (without rows: no buffer)
+            return torch.zeros((0, w), dtype=torch.float32, device=dev)
+        return torch.as_tensor(_DeviceSpan(ptr, (int(nbytes.value) // (4 * w), w)), device=dev)
 
     def set_waypoint_streams(self, seeds, world_sides, arrive_thresholds=2.0):
         """Per-scene waypoint streams for ``redraw=True`` (see ``stream_arrays``; scalars broadcast to every scene).  They stay in

@@ -97,6 +97,15 @@ struct BatchSteerDev {
     bool pending = false;
 };
 
+// observations (sfm_batch_set_observation, ABI 15): the settings and the buffer sfm_batch_observe fills; nothing a tick reads or writes
+struct BatchObsDev {
+    bool on = false;           // (not "buf is allocated": a batch without rows can be observed and has no buffer)
+    int k = 0;
+    int frame = 0;
+    DevBuf<float> range2;      // [B] sense_range^2
+    DevBuf<float> buf;         // [N_total][16 + 4 k]
+};
+
 struct BatchRecordDev {        // grow-only device buffers of the recording calls
     DevBuf<float4> frames;     // sfm_batch_run_recorded
     DevBuf<float2> zframes;
@@ -130,6 +139,7 @@ struct SfmBatch {
     BatchSnapDev snap;
     BatchRestartDev restart;
     BatchSteerDev steer;
+    BatchObsDev obs;
     Event c_done;                      // created by the first sfm_batch_set_steering with rows; outlives every drop of the steering
     std::string err;
 };
@@ -479,6 +489,7 @@ int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x
     }
     drop_batch_modes(b);                                          // a new crowd: its modes are set anew
     b->steer = {};                                                // ... and so are its commands (the rows may differ)
+    b->obs = {};                                                  // ... and its observations
     b->snap.on = false;                                           // ... and so is its snapshot
     b->have_state = false;
     if (n > 0) {
@@ -1182,6 +1193,83 @@ void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes) {
     if (n == 0) return nullptr;
     if (bytes) *bytes = (int64_t)(sizeof(float4) * n);
     return b->pk;
+}
+
+// Observations (ABI 15).  Everything is checked before anything is allocated or freed.
+int sfm_batch_set_observation(SfmBatch* b, int k, const float* sense_range, int frame) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!sense_range) {
+        HIP_TRY(b, hipStreamSynchronize(b->stream));             // an observe in flight may still write the buffer
+        b->obs = {};
+        return SFM_OK;
+    }
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    if (k < 1 || k > SFM_BATCH_MAX_OBS_NEIGHBOURS)
+        return bfail(b, SFM_ERR_INVALID, "k must be 1 .. " + std::to_string(SFM_BATCH_MAX_OBS_NEIGHBOURS) + " neighbour slots, got " + std::to_string(k));
+    if (frame != SFM_OBS_FRAME_WORLD && frame != SFM_OBS_FRAME_HEADING)
+        return bfail(b, SFM_ERR_INVALID, "frame must be 0 (world axes) or 1 (the row's heading frame), got " + std::to_string(frame));
+    std::vector<float> r2((size_t)b->B);
+    for (int s = 0; s < b->B; ++s) {
+        const float r = sense_range[s];
+        if (!std::isfinite(r) || !(r > 0.f) || r > SFM_BATCH_MAX_SENSE_RANGE)
+            return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(s) + ": sense_range must be finite, > 0 and <= 1e6 metres");
+        r2[s] = (float)((double)r * (double)r);                      // R^2 rounded once, like thr2
+    }
+    const size_t vals = (size_t)b->n_total * (size_t)(SFM_BATCH_OBS_HEADER + 4 * k);
+    BatchObsDev o;
+    HIP_TRY(b, o.range2.alloc((size_t)b->B));
+    HIP_TRY(b, hipMemcpy(o.range2, r2.data(), sizeof(float) * r2.size(), hipMemcpyHostToDevice));
+    if (vals > 0) {
+        HIP_TRY(b, o.buf.alloc(vals));
+        HIP_TRY(b, hipMemsetAsync(o.buf, 0, sizeof(float) * vals, b->stream));
+    }
+    o.k = k;
+    o.frame = frame;
+    o.on = true;
+    HIP_TRY(b, hipStreamSynchronize(b->stream));                 // the zero fill; and an observe in flight may still write the old buffer
+    b->obs = std::move(o);
+    return SFM_OK;
+}
+
+int sfm_batch_observe(SfmBatch* b) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->obs.on) return bfail(b, SFM_ERR_STATE, "observations are off: call sfm_batch_set_observation first (sfm_batch_upload_state drops them)");
+    if (b->n_total == 0) return SFM_OK;
+    ObserveArgs a;
+    memset(&a, 0, sizeof(a));
+    a.scene_off = b->d_scene_off;
+    a.pk = b->pk;
+    a.own = b->own;
+    for (int k = 0; k < 3; ++k) a.geo[k] = BatchGeo{b->geo_item_off[k], b->geo[k].off, b->geo[k].pts, b->geo[k].ctr};
+    a.range2 = b->obs.range2;
+    a.obs = b->obs.buf;
+    a.k = b->obs.k;
+    a.frame = b->obs.frame;
+    HIP_TRY(b, launch_batch_observe(a, b->B, b->stream));
+    return SFM_OK;
+}
+
+int sfm_batch_download_observations(SfmBatch* b, float* out) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->obs.on) return bfail(b, SFM_ERR_STATE, "observations are off: call sfm_batch_set_observation first (sfm_batch_upload_state drops them)");
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    const size_t vals = (size_t)b->n_total * (size_t)(SFM_BATCH_OBS_HEADER + 4 * b->obs.k);
+    if (vals == 0) return SFM_OK;
+    if (!out) return bfail(b, SFM_ERR_INVALID, "out is NULL");
+    HIP_TRY(b, hipMemcpy(out, b->obs.buf, sizeof(float) * vals, hipMemcpyDeviceToHost));
+    return SFM_OK;
+}
+
+void* sfm_batch_observation_ptr(SfmBatch* b, int64_t* bytes) {
+    if (bytes) *bytes = 0;
+    if (!b) return nullptr;
+    if (!b->obs.on) { bfail(b, SFM_ERR_STATE, "observations are off: call sfm_batch_set_observation first (sfm_batch_upload_state drops them)"); return nullptr; }
+    if (b->n_total == 0) return nullptr;
+    if (bytes) *bytes = (int64_t)(sizeof(float) * (size_t)b->n_total * (size_t)(SFM_BATCH_OBS_HEADER + 4 * b->obs.k));
+    return b->obs.buf;
 }
 
 const char* sfm_batch_last_error(const SfmBatch* b) { return b ? b->err.c_str() : g_create_error.c_str(); }

@@ -325,6 +325,18 @@ struct BatchRestart {
     long long shift;          // tau now - tau of the snapshot
 };
 
+// Observations of a batch (sfm_batch_observe, sfm_batch_observe_kernel in sfm_batch_observe.hip): everything but obs is read only.
+struct ObserveArgs {
+    const int* scene_off;     // [B+1]
+    const float4* pk;         // {x, y, vx, vy}
+    const float4* own;        // {wx, wy, target_speed, radius}
+    BatchGeo geo[3];          // borders, static obstacles, dynamic obstacles (the half of the ping-pong the next tick reads)
+    const float* range2;      // [B] sense_range^2, formed in double and rounded once
+    float* obs;               // [N_total][16 + 4 k]
+    int k;                    // neighbour slots per row, 1 .. SFM_BATCH_MAX_OBS_NEIGHBOURS
+    int frame;                // 0 world axes, 1 the row's heading frame
+};
+
 // Block-major packing for sharded runs (sfm_set_partition, sfm_reorder.hip): the row order is cut into gx columns by x, each
 // column into gy blocks by y -- block b = column * gy + position holds rows [bound[b], bound[b+1]) -- and every block is
 // strip-packed on its own, so a rank's contiguous row range is a compact rectangle of the map instead of a slab across it.

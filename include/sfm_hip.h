@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SFM_ABI_VERSION 14  /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles; 9: + sfm_batch_set_mode_fsm, sfm_batch_download_modes; 10: + sfm_batch_tick_forces, sfm_batch_run_recorded_forces; 11: + sfm_batch_set_spawn_schedule, sfm_batch_download_spawns, SFM_MODE_UNBORN; 12: + sfm_batch_set_vehicle_tracks, sfm_batch_download_vehicle_tracks; 13: + sfm_batch_snapshot, sfm_batch_restart; 14: + sfm_batch_set_steering, sfm_batch_set_commands, sfm_batch_download_steering, sfm_batch_device_ptr (additions only) */
+#define SFM_ABI_VERSION 15  /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles; 9: + sfm_batch_set_mode_fsm, sfm_batch_download_modes; 10: + sfm_batch_tick_forces, sfm_batch_run_recorded_forces; 11: + sfm_batch_set_spawn_schedule, sfm_batch_download_spawns, SFM_MODE_UNBORN; 12: + sfm_batch_set_vehicle_tracks, sfm_batch_download_vehicle_tracks; 13: + sfm_batch_snapshot, sfm_batch_restart; 14: + sfm_batch_set_steering, sfm_batch_set_commands, sfm_batch_download_steering, sfm_batch_device_ptr; 15: + sfm_batch_set_observation, sfm_batch_observe, sfm_batch_download_observations, sfm_batch_observation_ptr (additions only) */
 
 typedef struct SfmHandle SfmHandle;
 
@@ -510,6 +510,77 @@ int sfm_batch_download_steering(SfmBatch* b, uint8_t* kind, float* ux, float* uy
 #define SFM_BATCH_PTR_STATE 1
 #define SFM_BATCH_PTR_ZSTATE 2
 void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes);
+/* Per-pedestrian observations computed on the device (ABI 15): what a policy or a reward reads per agent -- who is near it and how
+ * they move relative to it, where the kerb, the nearest obstacle and the nearest vehicle are, where its goal is -- by ONE launch of
+ * sfm_batch_observe_kernel (a workgroup per scene) straight from the buffers the tick reads, into a device buffer the caller reads
+ * with no copy.  With sfm_batch_snapshot / sfm_batch_restart (the reset) and sfm_batch_set_steering (the action) it closes a
+ * reinforcement-learning loop with no host in it.
+ *
+ * Settings.  k: neighbour slots per row, 1 .. SFM_BATCH_MAX_OBS_NEIGHBOURS, one value for the batch.  sense_range[b]: metres, per
+ * scene, finite, 0 < R <= SFM_BATCH_MAX_SENSE_RANGE; the kernel uses R2 = float32(R * R), formed in double and rounded once, like
+ * thr2.  frame: SFM_OBS_FRAME_WORLD (0, world axes) or SFM_OBS_FRAME_HEADING (1, the row's heading frame), one value for the batch.
+ *
+ * Inputs.  Only {x, y, vx, vy} of the state is used, for planar and 3-D batches alike; z and vz play no part, so a 3-D batch gives,
+ * bit for bit, the record of the planar batch with the same x, y, vx, vy.
+ *
+ * Record.  Row i owns W = SFM_BATCH_OBS_HEADER + 4 k floats, row-major [N_total][W], in concatenated scene order:
+ *     0-1      goal (wx - x, wy - y)
+ *     2-3      own velocity (vx, vy)
+ *     4        target speed (the value the next tick would read from `own`)
+ *     5        live: 1.0 or 0.0
+ *     6        m = number of filled neighbour slots, 0 .. k, as a float
+ *     7        geometry flags as a float: 1 (border point present) + 2 (static point present) + 4 (vehicle point present)
+ *     8-11     nearest vehicle ring point (px - x, py - y, ovx - vx, ovy - vy)
+ *     12-13    nearest border point (px - x, py - y)
+ *     14-15    nearest static-obstacle point (px - x, py - y)
+ *     16+4s .. neighbour slot s: (x_j - x_i, y_j - y_i, vx_j - vx_i, vy_j - vy_i)
+ *
+ * Rules, all exact.
+ * Live rows: row i is live iff |x_i| < NEAR_LIMIT and |y_i| < NEAR_LIMIT (1e12, sfm_device.h).  Despawned and unborn rows are parked
+ * beyond that limit, so they are not live; a NaN position fails the test, so such a row is not live.  A row that is not live has an
+ * all-zero record.
+ * Neighbours: a candidate of row i is a row j != i of the same scene with d2 = fmaf(dx, dx, dy * dy) < R2 (dx = x_j - x_i; strict
+ * `<`).  Ghosts sit at least FAR_STEP apart, far from anyone, so the range bound excludes them without a test of their own.  The
+ * slots hold the first k candidates in ascending (d2, j) order -- among equal d2 the lower index inside the scene comes first --
+ * and slots m .. k-1 are zeros.  A coincident pair (d2 == 0) is a candidate like any other.
+ * Nearest points, per kind (border, static, vehicle): the nearest point over ALL points of ALL the scene's polylines of that kind,
+ * with the tick's own distance d2 = fmaf(ax, ax, ay * ay), ax = x - px; the first minimum wins (polylines in order, points in
+ * order: np.argmin's rule).  A point is present iff its d2 < R2; a point that is absent is zeros.  There is no cull by
+ * section_length or by perception threshold, and no force switch and no crossing mask is consulted: this is what the row can see,
+ * not what pushes it.
+ * Vehicles are read as the next tick would read them (the current half of the ping-pong for device-side vehicles and tracks); a
+ * tracked vehicle that is absent has its ring at +inf, so d2 = +inf and it fails the test.  A vehicle's velocity is that of its
+ * item.
+ * Frame 0: every value is a single fp32 subtraction or a copy, so the whole record is defined bit for bit.
+ * Frame 1: the selection, order, m and flags are those of frame 0 -- they are decided before any rotation.  The heading is
+ * h = v / |v| when fmaf(vx, vx, vy * vy) > 0; otherwise g / |g| of the goal entry g = (wx - x, wy - y) when fmaf(gx, gx, gy * gy) > 0;
+ * otherwise (1, 0).  Every 2-vector (a, b) of the record -- the goal, the own velocity, both halves of the vehicle entry, the border
+ * and static entries, both halves of every slot -- is replaced by (h_x a + h_y b, -h_y a + h_x b).
+ * The kernel writes nothing but the observation buffer; it reads the state, `own`, the scene offsets, the three geometry CSRs and
+ * the per-scene ranges.  No atomics, every order a function of the scene alone: a scene's record is bitwise the same alone or
+ * anywhere in any batch.
+ *
+ * sfm_batch_set_observation: sense_range [B]; sense_range = NULL switches observations off and frees the buffer.  Otherwise it
+ * allocates and zero-fills [N_total][SFM_BATCH_OBS_HEADER + 4 k] and waits for the batch's stream.  Refused with nothing changed:
+ * before sfm_batch_upload_state (SFM_ERR_STATE), k outside 1 .. 16, frame outside {0, 1}, a sense_range that is NaN, infinite,
+ * <= 0 or > 1e6.  sfm_batch_upload_state drops the observations because the rows may differ, as it drops steering; every other call
+ * keeps them, and they keep the snapshot.  A snapshot neither holds nor restores observations. */
+#define SFM_BATCH_OBS_HEADER 16
+#define SFM_BATCH_MAX_OBS_NEIGHBOURS 16
+#define SFM_BATCH_MAX_SENSE_RANGE 1.0e6f
+#define SFM_OBS_FRAME_WORLD 0
+#define SFM_OBS_FRAME_HEADING 1
+int sfm_batch_set_observation(SfmBatch* b, int k, const float* sense_range, int frame);
+/* ONE launch on the batch's stream, ordered with the ticks and restarts around it; the host does not wait.  SFM_ERR_STATE while
+ * observations are off.  With no rows it launches nothing and succeeds. */
+int sfm_batch_observe(SfmBatch* b);
+/* Synchronises the batch's stream, then copies the buffer ([N_total][SFM_BATCH_OBS_HEADER + 4 k] floats) as the last
+ * sfm_batch_observe left it; before the first observe that is zeros.  SFM_ERR_STATE while observations are off. */
+int sfm_batch_download_observations(SfmBatch* b, float* out);
+/* The observation buffer on the device; *bytes (may be NULL) receives N_total * (SFM_BATCH_OBS_HEADER + 4 k) * 4.  Valid until the
+ * next sfm_batch_upload_state or sfm_batch_set_observation.  NULL (and the message in sfm_batch_last_error) while observations are
+ * off; NULL without rows. */
+void* sfm_batch_observation_ptr(SfmBatch* b, int64_t* bytes);
 /* Current state of every scene (synchronises the batch's stream); NULL skips a column.  A planar batch leaves z alone and
  * writes vz = 0. */
 int sfm_batch_download_state(SfmBatch* b, float* x, float* y, float* z, float* vx, float* vy, float* vz);
