@@ -14,7 +14,7 @@ import numpy as np
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFM_LIB_PATH") or os.path.join(PKG_DIR, "libsfm_hip.so")   # (the override is for A/B builds of the kernels)
-ABI_VERSION = 15
+ABI_VERSION = 16
 SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_records": 5,
          **{n: 6 for n in ("sfm_batch_create", "sfm_batch_destroy", "sfm_batch_set_stream", "sfm_batch_set_params",
                            "sfm_batch_upload_state", "sfm_batch_set_borders", "sfm_batch_set_static_obstacles",
@@ -30,7 +30,9 @@ SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_
          **{n: 14 for n in ("sfm_batch_set_steering", "sfm_batch_set_commands", "sfm_batch_download_steering",
                             "sfm_batch_device_ptr")},
          **{n: 15 for n in ("sfm_batch_set_observation", "sfm_batch_observe", "sfm_batch_download_observations",
-                            "sfm_batch_observation_ptr")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
+                            "sfm_batch_observation_ptr")},
+         **{n: 16 for n in ("sfm_batch_set_episodes", "sfm_batch_end_step", "sfm_batch_download_episodes",
+                            "sfm_batch_restart_device")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
 
 FORCE_NAMES = ("acceleration_force", "pedestrian_force", "border_force",
                "static_obstacle_force", "dynamic_obstacle_force")
@@ -149,6 +151,11 @@ SYMBOLS = {
     "sfm_batch_observe": (C.c_int, [_H]),
     "sfm_batch_download_observations": (C.c_int, [_H, _F]),
     "sfm_batch_observation_ptr": (C.c_void_p, [_H, C.POINTER(C.c_int64)]),
+    # batch episodes and the restart by device mask (ABI 16)
+    "sfm_batch_set_episodes": (C.c_int, [_H, _I, _F, _F, _F, _I]),
+    "sfm_batch_end_step": (C.c_int, [_H, C.c_uint32]),
+    "sfm_batch_download_episodes": (C.c_int, [_H, _F, _U8]),
+    "sfm_batch_restart_device": (C.c_int, [_H, C.c_void_p]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 """Batched scenes: many small, independent crowds stepped by ONE kernel launch per tick (C ABI: sfm_batch_*, ABI 6; waypoint
 streams and recorded runs, ABI 7; device-side vehicles, ABI 8; pedestrian modes, ABI 9; force records, ABI 10; spawn schedules, ABI 11;
-vehicle tracks, ABI 12; snapshot and restart, ABI 13; steered pedestrians, ABI 14; observations, ABI 15).
+vehicle tracks, ABI 12; snapshot and restart, ABI 13; steered pedestrians, ABI 14; observations, ABI 15; episode ends and the restart
+by device mask, ABI 16).
 
 Social-force models are run in bulk as many small scenes -- scenario sampling, RL environments stepped in lock-step, calibration
 sweeps over A / lambda / gamma / tau.  ``SfmBatch`` holds B scenes of 0 .. 1024 pedestrians, each with its own parameters (its own
@@ -72,6 +73,15 @@ and static-obstacle points, and the k nearest neighbours in ascending (distance,
 buffer as a torch tensor a policy reads on the device, and ``observe.observe_scene`` is the host twin, bit for bit in frame 0.
 Observing changes nothing a tick reads.  With ``snapshot`` / ``restart`` (the reset) and steering (the action) this closes an RL
 loop with no host in it: examples/batch_rl_loop.py.
+
+Episode ends (ABI 16): who is done, decided on the device.  ``set_episodes(agent, goal_radius, ped_radius, veh_radius, max_steps)``
+names one agent row per scene, three radii and a time limit; ``end_step()`` is one launch that writes, per scene, a record of 8
+floats (``EP_*``: done, the reason bits ``REASON_*``, the episode's age, the squared distances to the goal now and one evaluation
+ago, to the nearest live pedestrian, vehicle ring point and border / static-obstacle point -- what a reward is made of) and a byte
+mask ``done``; ``end_step(auto_restart=True)`` follows it with ``restart_device()``, the restart whose mask stays on the device, so
+a step of the loop copies nothing and waits for nothing: examples/batch_rl_loop_device.py.  Every restart of a scene starts its
+episode clock over.  ``episodes()`` downloads record and mask, ``episode_tensor()`` / ``done_tensor()`` alias them, and
+``episode.episode_scene`` is the host twin, bit for bit.
 """
 from __future__ import annotations
 
@@ -532,6 +542,7 @@ def restart_mask(B, scenes=None):
 
 STEER_OFF, STEER_VELOCITY, STEER_PREFERRED = 0, 1, 2   # the kinds of a steered row (held as floats in the command buffer)
 PTR_COMMANDS, PTR_STATE, PTR_ZSTATE = 0, 1, 2          # SFM_BATCH_PTR_*: what sfm_batch_device_ptr / SfmBatch.device_ptr select
+PTR_EPISODES, PTR_DONE = 3, 4                          # ... the episode record [B][8] and the mask done[B] (while episodes are on)
 
 
 def _per_scene(v, so, width, name):
@@ -633,11 +644,49 @@ def split_observations(buf, scene_off):
     return [buf[so[b]:so[b + 1]] for b in range(len(so) - 1)]
 
 
+EPISODE_WIDTH = 8                # SFM_BATCH_EPISODE_WIDTH: floats of a scene's episode record
+EP_DONE, EP_REASON, EP_AGE, EP_GOAL_D2, EP_PREV_GOAL_D2, EP_PED_D2, EP_VEH_D2, EP_WALL_D2 = range(8)     # its slots
+REASON_ARRIVED, REASON_TIME_LIMIT, REASON_PED_HIT, REASON_VEH_HIT, REASON_NOT_LIVE = 1, 2, 4, 8, 16     # SFM_EPISODE_*: bits of slot 1
+END_STEP_AUTO_RESTART = 1        # SFM_END_STEP_AUTO_RESTART
+
+
+def episode_arrays(B, agent, goal_radius=0.0, ped_radius=0.0, veh_radius=0.0, max_steps=0):
+    """Episode settings -> the arguments of sfm_batch_set_episodes: (agent int32 [B], goal_radius, ped_radius, veh_radius float32
+    [B], max_steps int32 [B]).  Each argument is a scalar (broadcast to every scene, like ``stream_arrays``) or B values.  ``agent``:
+    integers >= -1 (-1: the scene has no agent; the upper bound N_b is the library's to check, or ``SfmBatch.set_episodes``');
+    radii in metres, finite, >= 0 and <= 1e6 in float32 (0: the test is off); ``max_steps`` integers >= 0 (0: no time limit).  Pure
+    NumPy; raises ValueError on a shape that does not fit and on every value the library would refuse."""
+    B = int(B)
+
+    def col(v, name, kinds):
+        a = np.asarray(v)
+        if a.dtype.kind not in kinds:
+            raise ValueError(f"{name} must be {'integers' if kinds == 'iu' else 'numbers'}, got {a.dtype}")
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] not in (1, B)):
+            raise ValueError(f"{name}: expected a scalar or {B} values, got shape {a.shape}")
+        return np.broadcast_to(a.reshape(-1), (B,))
+
+    ag = col(agent, "agent", "iu").astype(np.int64)
+    if (ag < -1).any() or (ag >= MAX_SCENE_PEDESTRIANS).any():
+        raise ValueError(f"agent must be -1 (no agent) or a row 0 .. N_b-1 of its scene, got {int(ag.min())} .. {int(ag.max())}")
+    radii = []
+    for v, name in ((goal_radius, "goal_radius"), (ped_radius, "ped_radius"), (veh_radius, "veh_radius")):
+        with np.errstate(over="ignore"):
+            r = f32(col(v, name, "iuf"))
+        if not (np.isfinite(r).all() and (r >= 0).all() and (r <= np.float32(MAX_SENSE_RANGE)).all()):
+            raise ValueError(f"{name} must be finite, >= 0 and <= {MAX_SENSE_RANGE:g} metres")
+        radii.append(r)
+    ms = col(max_steps, "max_steps", "iu").astype(np.int64)
+    if (ms < 0).any() or (ms >= 2**31).any():
+        raise ValueError("max_steps must be >= 0 (0: no time limit) and fit int32")
+    return (np.ascontiguousarray(ag, dtype=np.int32), *radii, np.ascontiguousarray(ms, dtype=np.int32))
+
+
 class _DeviceSpan:
     """Minimal __cuda_array_interface__ carrier so torch can alias a raw device pointer (no copy), as stepper._DevSpan."""
 
-    def __init__(self, ptr, shape):
-        self.__cuda_array_interface__ = {"shape": tuple(int(d) for d in shape), "typestr": "<f4", "data": (int(ptr), False), "version": 2}
+    def __init__(self, ptr, shape, typestr="<f4"):
+        self.__cuda_array_interface__ = {"shape": tuple(int(d) for d in shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
 
 
 def split_frames(frames, scene_off):
@@ -713,6 +762,7 @@ class SfmBatch:
         self._dyn = None                  # (scene_item_off, offsets) of the vehicles last set, for dynamic_obstacles()
         self.has_snapshot = False         # snapshot() has been taken and no later call has dropped it
         self.obs_k = None                 # neighbour slots of set_observation (None: observations are off)
+        self.has_episodes = False         # set_episodes has been called and no later call has dropped it
 
     def _check(self, rc, what):
         if rc != 0:
@@ -776,6 +826,7 @@ class SfmBatch:
                           "sfm_batch_upload_state")
         self.scene_off = so.copy()
         self.obs_k = None                 # (the upload dropped the observations with the rows)
+        self.has_episodes = False         # ... and the episodes
         self.planar = planar
         self._z = pk["z"].copy()          # a planar batch keeps each scene's z on the host (the device holds x / y only)
 
@@ -850,6 +901,76 @@ class SfmBatch:
         mask = None if scenes is None else restart_mask(self.B, scenes)
         self._check(self._lib.sfm_batch_restart(self._b, u8ptr(mask)), "sfm_batch_restart")
 
+    def restart_device(self, mask=None):
+        """``restart`` with its mask on the device (sfm_batch_restart_device): one launch, no copy, no wait.  ``mask``: None -- the
+        batch's own ``done`` as the last ``end_step`` left it; or a torch tensor of B one-byte elements (bool, uint8 or int8) on the
+        batch's device, contiguous, nonzero = restart.  Put torch and the batch on one stream so that the mask's writer and the
+        launch are ordered; keep the tensor alive until the launch has run."""
+        if mask is None:
+            ptr, _ = self.device_ptr(PTR_DONE)
+        else:
+            import torch
+            if not isinstance(mask, torch.Tensor):
+                raise ValueError("restart_device takes a torch tensor on the device (or None: the batch's done); a host mask goes to restart()")
+            if not mask.is_cuda:
+                raise ValueError("the mask of restart_device must be on the device (a host mask goes to restart())")
+            if mask.element_size() != 1 or mask.dtype not in (torch.bool, torch.uint8, torch.int8):
+                raise ValueError(f"the mask of restart_device must be bool, uint8 or int8, got {mask.dtype}")
+            if mask.numel() != self.B or not mask.is_contiguous():
+                raise ValueError(f"the mask of restart_device must hold {self.B} contiguous elements, got shape {tuple(mask.shape)}"
+                                 f"{'' if mask.is_contiguous() else ' (not contiguous)'}")
+            ptr = mask.data_ptr()
+        self._check(self._lib.sfm_batch_restart_device(self._b, C.c_void_p(ptr or None)), "sfm_batch_restart_device")
+
+    def set_episodes(self, agent, goal_radius=0.0, ped_radius=0.0, veh_radius=0.0, max_steps=0):
+        """Which row of every scene is its agent and what ends its episode (sfm_batch_set_episodes; see ``episode_arrays`` and the
+        module docstring).  ``agent=None`` switches episodes off and frees the buffers.  Needs ``upload`` first, which also drops
+        them; every other call keeps them, and they keep the snapshot.  Allocates and fills the record, the mask and the episode
+        state (``episode_tensor()`` / ``done_tensor()`` must be taken again)."""
+        L = self._lib
+        if agent is None:
+            self._check(L.sfm_batch_set_episodes(self._b, None, None, None, None, None), "sfm_batch_set_episodes")
+            self.has_episodes = False
+            return
+        if self.scene_off is None:
+            raise SfmLibraryError("SfmBatch.set_episodes: upload() has not been called")
+        ag, rg, rp, rv, ms = episode_arrays(self.B, agent, goal_radius, ped_radius, veh_radius, max_steps)
+        n = np.diff(self.scene_off)
+        if (ag >= n).any():
+            k = int(np.flatnonzero(ag >= n)[0])
+            raise ValueError(f"scene {k}: agent {int(ag[k])} is no row of a scene of {int(n[k])} pedestrians")
+        self._check(L.sfm_batch_set_episodes(self._b, iptr(ag), fptr(rg), fptr(rp), fptr(rv), iptr(ms)), "sfm_batch_set_episodes")
+        self.has_episodes = True
+
+    def end_step(self, auto_restart=False):
+        """Decide whose episode is over (sfm_batch_end_step): one launch on the batch's stream fills the record and ``done``; the
+        host does not wait.  ``auto_restart=True``: a second launch restarts the scenes that are done from the snapshot
+        (``restart_device()``), the record keeping the terminal values.  Raises SfmLibraryError while episodes are off and, with
+        ``auto_restart``, while there is no snapshot."""
+        self._check(self._lib.sfm_batch_end_step(self._b, END_STEP_AUTO_RESTART if auto_restart else 0), "sfm_batch_end_step")
+
+    def episodes(self):
+        """(record (B, 8) float32, done (B,) bool) as the last ``end_step`` left them (synchronises the batch's stream)."""
+        rec, done = np.zeros((self.B, EPISODE_WIDTH), np.float32), np.zeros(self.B, np.uint8)
+        self._check(self._lib.sfm_batch_download_episodes(self._b, fptr(rec), u8ptr(done)), "sfm_batch_download_episodes")
+        return rec, done.astype(bool)
+
+    def _episode_span(self, which, shape, typestr, device):
+        import torch
+        ptr, _ = self.device_ptr(which)
+        dev = f"cuda:{torch.cuda.current_device() if device is None else int(device)}"
+        return torch.as_tensor(_DeviceSpan(ptr, shape, typestr), device=dev)
+
+    def episode_tensor(self, device=None):
+        """The episode record as a torch tensor (B, 8) float32 that aliases device memory (no copy): what a reward reads after
+        ``end_step()``.  Put torch and the batch on one stream.  Take it again after ``upload`` or ``set_episodes``.  Raises
+        SfmLibraryError while episodes are off."""
+        return self._episode_span(PTR_EPISODES, (self.B, EPISODE_WIDTH), "<f4", device)
+
+    def done_tensor(self, device=None):
+        """The mask ``done`` as a torch tensor (B,) uint8 (0 / 1) that aliases device memory: what ``restart_device`` takes."""
+        return self._episode_span(PTR_DONE, (self.B,), "|u1", device)
+
     def set_steering(self, kinds, commands=None):
         """Which rows the caller steers, and their first commands (sfm_batch_set_steering; see ``pack_steering``): kind 1 rows take
         the command as their new velocity, kind 2 rows as their preferred velocity.  ``kinds=None`` switches steering off.  Needs
@@ -893,12 +1014,15 @@ class SfmBatch:
         return [(kd[so[b]:so[b + 1]], cmd[so[b]:so[b + 1]]) for b in range(self.B)]
 
     def device_ptr(self, which):
-        """(address, bytes) of a device buffer of the batch (sfm_batch_device_ptr): ``PTR_COMMANDS``, ``PTR_STATE`` or
-        ``PTR_ZSTATE`` ((0, 0) for a planar batch).  Valid until the next ``upload`` (the command buffer: or ``set_steering``)."""
+        """(address, bytes) of a device buffer of the batch (sfm_batch_device_ptr): ``PTR_COMMANDS``, ``PTR_STATE``,
+        ``PTR_ZSTATE`` ((0, 0) for a planar batch), ``PTR_EPISODES`` or ``PTR_DONE``.  Valid until the next ``upload`` (the
+        command buffer: or ``set_steering``; the episode buffers: or ``set_episodes``)."""
         nbytes = C.c_int64(0)
         if self.scene_off is None:
             raise SfmLibraryError("SfmBatch.device_ptr: upload() has not been called")
         ptr = self._lib.sfm_batch_device_ptr(self._b, int(which), C.byref(nbytes))
+        if not ptr and which in (PTR_EPISODES, PTR_DONE):
+            self._check(-1, "sfm_batch_device_ptr")                    # (episodes are off: the library's message)
         if not ptr and int(self.scene_off[-1]) > 0 and not (which == PTR_ZSTATE and self.planar):
             self._check(-1, "sfm_batch_device_ptr")                    # (without rows, and {z, vz} of a planar batch: no buffer)
         return int(ptr or 0), int(nbytes.value)

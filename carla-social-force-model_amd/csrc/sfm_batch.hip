@@ -489,6 +489,9 @@ hipError_t launch_batch_tick(bool z3, bool ext, bool modes, bool spawn, bool ste
 // of the ping-pong the next tick reads) with their ring points, and its clock.  Plain loads and stores, no LDS, no atomics: a scene
 // is written by its own workgroup only, and the scenes that are not chosen are not touched.  A tracked vehicle's first tick moves
 // by r.shift (the batch's ticks since the snapshot), so that the batch-wide tick counter tau finds it at the keyframe it was at.
+// With r.mask (sfm_batch_restart_device) the grid is all B scenes and the choice is made here: workgroup b reads mask[b] from device
+// memory and leaves at once while it is 0 -- a uniform branch, no list, no copy.  With episodes on, a restarted scene's episode
+// state starts over.
 template <typename T>
 __device__ __forceinline__ void restart_copy(T* dst, const T* src, int i0, int i1) {
     if (!dst) return;                                                   // uniform: the batch has no such array
@@ -497,6 +500,7 @@ __device__ __forceinline__ void restart_copy(T* dst, const T* src, int i0, int i
 
 __global__ __launch_bounds__(BLOCK) void sfm_batch_restart_kernel(const BatchRestart r) {
     const int b = r.list ? r.list[blockIdx.x] : (int)blockIdx.x;
+    if (r.mask && r.mask[b] == 0) return;                               // uniform: the scene is not chosen
     const int s0 = r.scene_off[b], s1 = r.scene_off[b + 1];
     restart_copy(r.pk, r.s_pk, s0, s1);
     restart_copy(r.zv, r.s_zv, s0, s1);
@@ -516,6 +520,10 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_restart_kernel(const BatchRes
                 r.first[k] = r.trk_off[k + 1] > r.trk_off[k] ? (int)((long long)r.s_first[k] + r.shift) : r.s_first[k];
     }
     if (r.sim_time && threadIdx.x == 0) r.sim_time[b] = r.s_sim_time[b];
+    if (r.age && threadIdx.x == 0) {                                    // the episode starts over
+        r.age[b] = 0;
+        r.prev_goal_d2[b] = __builtin_nanf("");
+    }
 }
 
 hipError_t launch_batch_restart(const BatchRestart& r, int scenes, hipStream_t st) {

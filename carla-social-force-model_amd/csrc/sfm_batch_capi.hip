@@ -35,6 +35,8 @@ struct BatchTracksDev {
     DevBuf<float2> rot;        // [T] {cos yaw, sin yaw}
     long long tick = 0;        // tau: integrating ticks since the tracks were set (a kernel argument, not device state)
     std::vector<int32_t> off_h, first_h;   // host copies: sfm_batch_download_vehicle_tracks answers without the device
+    bool first_stale = false;  // a restart by device mask moved `first` of scenes the host cannot know: first_h is refreshed from
+                               // the device before it is read (refresh_track_first)
 };
 
 // the mode state machine (sfm_batch_set_mode_fsm, ABI 9): per row over the concatenated rows, per scene [B]
@@ -106,6 +108,17 @@ struct BatchObsDev {
     DevBuf<float> buf;         // [N_total][16 + 4 k]
 };
 
+// episodes (sfm_batch_set_episodes, ABI 16): the settings, the per-scene episode state, and the record and mask sfm_batch_end_step
+// fills; nothing a tick reads or writes
+struct BatchEpisodeDev {
+    bool on = false;
+    DevBuf<BatchEpisodeScene> set;     // [B]
+    DevBuf<int> age;                   // [B]
+    DevBuf<float> prev;                // [B] prev_goal_d2
+    DevBuf<float> record;              // [B][8]
+    DevBuf<uint8_t> done;              // [B]
+};
+
 struct BatchRecordDev {        // grow-only device buffers of the recording calls
     DevBuf<float4> frames;     // sfm_batch_run_recorded
     DevBuf<float2> zframes;
@@ -140,6 +153,7 @@ struct SfmBatch {
     BatchRestartDev restart;
     BatchSteerDev steer;
     BatchObsDev obs;
+    BatchEpisodeDev ep;
     Event c_done;                      // created by the first sfm_batch_set_steering with rows; outlives every drop of the steering
     std::string err;
 };
@@ -344,6 +358,82 @@ static int snap_copy(SfmBatch* b, DevBuf<T>& s, const DevBuf<T>& src, size_t cou
     return SFM_OK;
 }
 
+// The host's copy of the tracks' first ticks, current: after a restart by device mask it is read back from the device (the
+// callers synchronise anyway).
+static int refresh_track_first(SfmBatch* b) {
+    if (!b->tracks.on || !b->tracks.first_stale) return SFM_OK;
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    const size_t M = (size_t)b->geo[2].K;
+    if (M > 0) HIP_TRY(b, hipMemcpy(b->tracks.first_h.data(), b->tracks.first, sizeof(int) * M, hipMemcpyDeviceToHost));
+    b->tracks.first_stale = false;
+    return SFM_OK;
+}
+
+// The restart kernel's arguments but for the choice of scenes (list / mask): every live array beside its snapshot copy.
+static BatchRestart restart_args(SfmBatch* b, long long shift) {
+    BatchRestart r;
+    memset(&r, 0, sizeof(r));
+    r.scene_off = b->d_scene_off;
+    r.pk = b->pk; r.s_pk = b->snap.pk;
+    if (b->z3) { r.zv = b->zv; r.s_zv = b->snap.zv; }
+    r.own = b->own; r.s_own = b->snap.own;
+    r.draws = b->draws; r.s_draws = b->snap.draws;
+    if (b->boxes.on) {
+        const BatchGeoDev& g = b->geo[2];
+        r.item_off = b->geo_item_off[2]; r.veh_off = g.off;
+        r.ctr = g.ctr; r.s_ctr = b->snap.ctr;
+        r.pts = g.P > 0 ? g.pts : nullptr; r.s_pts = b->snap.pts;
+    }
+    if (b->modes.on) {
+        r.mode = b->modes.mode; r.s_mode = b->snap.mode;
+        r.target = b->modes.target; r.s_target = b->snap.target;
+        r.cursor = b->modes.cursor; r.s_cursor = b->snap.cursor;
+        r.sim_time = b->modes.time; r.s_sim_time = b->snap.time;
+    }
+    if (b->spawns.on) {
+        r.born = b->spawns.born; r.s_born = b->snap.born;
+        r.birth_time = b->spawns.birth; r.s_birth_time = b->snap.birth;
+    }
+    if (b->tracks.on) {
+        r.first = b->tracks.first; r.s_first = b->snap.first;
+        r.trk_off = b->tracks.off;
+        r.shift = shift;
+    }
+    if (b->n_total == 0) { r.pk = nullptr; r.own = nullptr; r.draws = nullptr; r.zv = nullptr; r.mode = nullptr; r.target = nullptr;
+                           r.cursor = nullptr; r.born = nullptr; r.birth_time = nullptr; }      // (no rows: no snapshot arrays either)
+    if (b->ep.on) { r.age = b->ep.age; r.prev_goal_d2 = b->ep.prev; }  // a restarted scene's episode starts over
+    return r;
+}
+
+// A tracked vehicle's first tick moved by `shift` must fit int32: scene k's vehicles (mask null or mask[k]), else SFM_ERR_INVALID
+static int check_restart_shift(SfmBatch* b, const uint8_t* mask, long long shift) {
+    if (!b->tracks.on) return SFM_OK;
+    for (int k = 0; k < b->B; ++k) {
+        if (mask && !mask[k]) continue;
+        for (int v = b->boxes.item_off_h[k]; v < b->boxes.item_off_h[k + 1]; ++v) {
+            const long long first = (long long)b->snap.first_h[v] + shift;
+            if (b->tracks.off_h[v + 1] > b->tracks.off_h[v] && (first < INT32_MIN || first > INT32_MAX))
+                return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(k) + ", vehicle " + std::to_string(v) + ": its first tick moved by the " +
+                                                 std::to_string(shift) + " ticks since the snapshot does not fit int32: set the tracks "
+                                                 "again (sfm_batch_set_vehicle_tracks restarts the tick counter)");
+        }
+    }
+    return SFM_OK;
+}
+
+static const char* const NO_SNAPSHOT = "the batch has no snapshot: call sfm_batch_snapshot first (sfm_batch_upload_state and the calls "
+                                       "that set vehicles, modes, a spawn schedule or tracks drop it)";
+static const char* const EPISODES_OFF = "episodes are off: call sfm_batch_set_episodes first (sfm_batch_upload_state drops them)";
+
+// sfm_batch_restart_device after its checks: ONE launch of B workgroups, the choice read on the device
+static int batch_restart_device(SfmBatch* b, const uint8_t* d_mask, long long shift) {
+    BatchRestart r = restart_args(b, shift);
+    r.mask = d_mask;
+    HIP_TRY(b, launch_batch_restart(r, b->B, b->stream));
+    if (b->tracks.on) b->tracks.first_stale = true;                     // who was chosen is known on the device only
+    return SFM_OK;
+}
+
 // sfm_batch_run_recorded, and with want_forces also the [F][K][N_total][C] force record of every recorded tick
 static int batch_run_recorded(SfmBatch* b, int ticks, uint32_t flags, int stride, float* frames, float* zframes, int max_frames,
                               int* n_frames, bool want_forces, uint32_t force_mask, float* forces) {
@@ -490,6 +580,7 @@ int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x
     drop_batch_modes(b);                                          // a new crowd: its modes are set anew
     b->steer = {};                                                // ... and so are its commands (the rows may differ)
     b->obs = {};                                                  // ... and its observations
+    b->ep = {};                                                   // ... and its episodes (the agents are rows)
     b->snap.on = false;                                           // ... and so is its snapshot
     b->have_state = false;
     if (n > 0) {
@@ -656,6 +747,7 @@ int sfm_batch_download_vehicle_tracks(SfmBatch* b, int64_t* tick, uint8_t* prese
     int rc = bbind(b);
     if (rc) return rc;
     if (!b->tracks.on) return bfail(b, SFM_ERR_STATE, "no vehicle tracks are set (sfm_batch_set_vehicle_tracks)");
+    if ((rc = refresh_track_first(b))) return rc;
     if (tick) *tick = (int64_t)b->tracks.tick;
     const int M = b->geo[2].K;
     for (int k = 0; present && k < M; ++k) {
@@ -1002,6 +1094,7 @@ int sfm_batch_snapshot(SfmBatch* b) {
     }
     if (b->tracks.on) {
         if ((rc = snap_copy(b, b->snap.first, b->tracks.first, (size_t)b->geo[2].K))) return rc;
+        if ((rc = refresh_track_first(b))) return rc;
         b->snap.first_h = b->tracks.first_h;
         b->snap.tick = b->tracks.tick;
     }
@@ -1014,9 +1107,7 @@ int sfm_batch_snapshot(SfmBatch* b) {
 int sfm_batch_restart(SfmBatch* b, const uint8_t* mask) {
     int rc = bbind(b);
     if (rc) return rc;
-    if (!b->snap.on)
-        return bfail(b, SFM_ERR_STATE, "the batch has no snapshot: call sfm_batch_snapshot first (sfm_batch_upload_state and the calls "
-                                       "that set vehicles, modes, a spawn schedule or tracks drop it)");
+    if (!b->snap.on) return bfail(b, SFM_ERR_STATE, NO_SNAPSHOT);
     const int B = b->B;
     int chosen = B;
     if (mask) {
@@ -1028,17 +1119,7 @@ int sfm_batch_restart(SfmBatch* b, const uint8_t* mask) {
     }
     // track time per scene: the chosen scenes' tracked vehicles are found by tau at the keyframe the snapshot had them at
     const long long shift = b->tracks.on ? b->tracks.tick - b->snap.tick : 0;
-    if (b->tracks.on)
-        for (int k = 0; k < B; ++k) {
-            if (mask && !mask[k]) continue;
-            for (int v = b->boxes.item_off_h[k]; v < b->boxes.item_off_h[k + 1]; ++v) {
-                const long long first = (long long)b->snap.first_h[v] + shift;
-                if (b->tracks.off_h[v + 1] > b->tracks.off_h[v] && (first < INT32_MIN || first > INT32_MAX))
-                    return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(k) + ", vehicle " + std::to_string(v) + ": its first tick moved by the " +
-                                                     std::to_string(shift) + " ticks since the snapshot does not fit int32: set the tracks "
-                                                     "again (sfm_batch_set_vehicle_tracks restarts the tick counter)");
-            }
-        }
+    if ((rc = check_restart_shift(b, mask, shift))) return rc;
     if (chosen == 0) return SFM_OK;
     if (mask) {
         if (!b->restart.done) {                                  // (created last: a first call that failed half-way starts over)
@@ -1054,49 +1135,31 @@ int sfm_batch_restart(SfmBatch* b, const uint8_t* mask) {
             if (mask[k]) b->restart.list_h[q++] = k;
         HIP_TRY(b, hipMemcpyAsync(b->restart.list, b->restart.list_h, sizeof(int) * (size_t)chosen, hipMemcpyHostToDevice, b->stream));
     }
-    BatchRestart r;
-    memset(&r, 0, sizeof(r));
+    BatchRestart r = restart_args(b, shift);
     r.list = mask ? b->restart.list : nullptr;
-    r.scene_off = b->d_scene_off;
-    r.pk = b->pk; r.s_pk = b->snap.pk;
-    if (b->z3) { r.zv = b->zv; r.s_zv = b->snap.zv; }
-    r.own = b->own; r.s_own = b->snap.own;
-    r.draws = b->draws; r.s_draws = b->snap.draws;
-    if (b->boxes.on) {
-        const BatchGeoDev& g = b->geo[2];
-        r.item_off = b->geo_item_off[2]; r.veh_off = g.off;
-        r.ctr = g.ctr; r.s_ctr = b->snap.ctr;
-        r.pts = g.P > 0 ? g.pts : nullptr; r.s_pts = b->snap.pts;
-    }
-    if (b->modes.on) {
-        r.mode = b->modes.mode; r.s_mode = b->snap.mode;
-        r.target = b->modes.target; r.s_target = b->snap.target;
-        r.cursor = b->modes.cursor; r.s_cursor = b->snap.cursor;
-        r.sim_time = b->modes.time; r.s_sim_time = b->snap.time;
-    }
-    if (b->spawns.on) {
-        r.born = b->spawns.born; r.s_born = b->snap.born;
-        r.birth_time = b->spawns.birth; r.s_birth_time = b->snap.birth;
-    }
-    if (b->tracks.on) {
-        r.first = b->tracks.first; r.s_first = b->snap.first;
-        r.trk_off = b->tracks.off;
-        r.shift = shift;
-    }
-    if (b->n_total == 0) { r.pk = nullptr; r.own = nullptr; r.draws = nullptr; r.zv = nullptr; r.mode = nullptr; r.target = nullptr;
-                           r.cursor = nullptr; r.born = nullptr; r.birth_time = nullptr; }      // (no rows: no snapshot arrays either)
     HIP_TRY(b, launch_batch_restart(r, chosen, b->stream));
     if (mask) {
         HIP_TRY(b, hipEventRecord(b->restart.done, b->stream));
         b->restart.pending = true;
     }
     if (b->tracks.on)                                               // the host's copy, which sfm_batch_download_vehicle_tracks answers from
-        for (int k = 0; k < B; ++k) {
+        for (int k = 0; k < B; ++k) {                               // (a stale copy stays stale: the scenes not chosen here are not known)
             if (mask && !mask[k]) continue;
             for (int v = b->boxes.item_off_h[k]; v < b->boxes.item_off_h[k + 1]; ++v)
                 b->tracks.first_h[v] = b->tracks.off_h[v + 1] > b->tracks.off_h[v] ? (int32_t)((long long)b->snap.first_h[v] + shift) : b->snap.first_h[v];
         }
     return SFM_OK;
+}
+
+// The restart with its mask on the device (ABI 16): no copy, no host scan, no event wait, no pinned list.
+int sfm_batch_restart_device(SfmBatch* b, const uint8_t* d_mask) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->snap.on) return bfail(b, SFM_ERR_STATE, NO_SNAPSHOT);
+    if (!d_mask) return bfail(b, SFM_ERR_INVALID, "d_mask is NULL (device memory, one byte per scene)");
+    const long long shift = b->tracks.on ? b->tracks.tick - b->snap.tick : 0;
+    if ((rc = check_restart_shift(b, nullptr, shift))) return rc;   // every scene: the host cannot know who is chosen
+    return batch_restart_device(b, d_mask, shift);
 }
 
 int sfm_batch_run_recorded(SfmBatch* b, int ticks, uint32_t flags, int stride, float* frames, float* zframes, int max_frames,
@@ -1177,7 +1240,13 @@ int sfm_batch_download_steering(SfmBatch* b, uint8_t* kind, float* ux, float* uy
 void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes) {
     if (bytes) *bytes = 0;
     if (!b) return nullptr;
-    if (which < SFM_BATCH_PTR_COMMANDS || which > SFM_BATCH_PTR_ZSTATE) { bfail(b, SFM_ERR_INVALID, "which must be SFM_BATCH_PTR_COMMANDS, _STATE or _ZSTATE"); return nullptr; }
+    if (which < SFM_BATCH_PTR_COMMANDS || which > SFM_BATCH_PTR_DONE) { bfail(b, SFM_ERR_INVALID, "which must be SFM_BATCH_PTR_COMMANDS, _STATE, _ZSTATE, _EPISODES or _DONE"); return nullptr; }
+    if (which == SFM_BATCH_PTR_EPISODES || which == SFM_BATCH_PTR_DONE) {
+        if (!b->ep.on) { bfail(b, SFM_ERR_STATE, std::string(EPISODES_OFF) + ", so which = SFM_BATCH_PTR_EPISODES / _DONE has no buffer"); return nullptr; }
+        const bool rec = which == SFM_BATCH_PTR_EPISODES;
+        if (bytes) *bytes = (int64_t)((rec ? 8 * sizeof(float) : sizeof(uint8_t)) * (size_t)b->B);
+        return rec ? (void*)b->ep.record.get() : (void*)b->ep.done.get();
+    }
     if (!b->have_state) { bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called"); return nullptr; }
     const size_t n = (size_t)b->n_total;
     if (which == SFM_BATCH_PTR_COMMANDS) {
@@ -1270,6 +1339,92 @@ void* sfm_batch_observation_ptr(SfmBatch* b, int64_t* bytes) {
     if (b->n_total == 0) return nullptr;
     if (bytes) *bytes = (int64_t)(sizeof(float) * (size_t)b->n_total * (size_t)(SFM_BATCH_OBS_HEADER + 4 * b->obs.k));
     return b->obs.buf;
+}
+
+// Episodes (ABI 16).  Everything is checked before anything is allocated or freed.
+int sfm_batch_set_episodes(SfmBatch* b, const int32_t* agent, const float* goal_radius, const float* ped_radius, const float* veh_radius,
+                           const int32_t* max_steps) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!agent) {
+        HIP_TRY(b, hipStreamSynchronize(b->stream));             // an end_step or a restart in flight may still write the buffers
+        b->ep = {};
+        return SFM_OK;
+    }
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    if (!goal_radius || !ped_radius || !veh_radius || !max_steps)
+        return bfail(b, SFM_ERR_INVALID, "goal_radius, ped_radius, veh_radius or max_steps is NULL");
+    const size_t B = (size_t)b->B;
+    std::vector<int> off(B + 1);
+    HIP_TRY(b, hipMemcpy(off.data(), b->d_scene_off, sizeof(int) * off.size(), hipMemcpyDeviceToHost));
+    std::vector<BatchEpisodeScene> set(B);
+    for (size_t s = 0; s < B; ++s) {
+        const int n = off[s + 1] - off[s];
+        if (agent[s] < -1 || agent[s] >= n)
+            return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(s) + ": agent must be -1 (none) or a row 0 .. " + std::to_string(n - 1) +
+                                             " of the scene, got " + std::to_string(agent[s]));
+        float r2[3];
+        const float r[3] = {goal_radius[s], ped_radius[s], veh_radius[s]};
+        for (int q = 0; q < 3; ++q) {
+            if (!std::isfinite(r[q]) || !(r[q] >= 0.f) || r[q] > SFM_BATCH_MAX_SENSE_RANGE)
+                return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(s) + ": " + (q == 0 ? "goal_radius" : q == 1 ? "ped_radius" : "veh_radius") +
+                                                 " must be finite, >= 0 and <= 1e6 metres");
+            r2[q] = (float)((double)r[q] * (double)r[q]);            // r^2 rounded once, like thr2
+        }
+        if (max_steps[s] < 0) return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(s) + ": max_steps must be >= 0 (0: no time limit)");
+        set[s] = BatchEpisodeScene{agent[s], max_steps[s], r2[0], r2[1], r2[2], {0, 0, 0}};
+    }
+    const std::vector<float> nan(B, std::numeric_limits<float>::quiet_NaN());
+    BatchEpisodeDev e;
+    HIP_TRY(b, e.set.alloc(B)); HIP_TRY(b, e.age.alloc(B)); HIP_TRY(b, e.prev.alloc(B));
+    HIP_TRY(b, e.record.alloc(8 * B)); HIP_TRY(b, e.done.alloc(B));
+    HIP_TRY(b, hipMemcpy(e.set, set.data(), sizeof(BatchEpisodeScene) * B, hipMemcpyHostToDevice));
+    HIP_TRY(b, hipMemcpy(e.prev, nan.data(), sizeof(float) * B, hipMemcpyHostToDevice));
+    HIP_TRY(b, hipMemsetAsync(e.age, 0, sizeof(int) * B, b->stream));
+    HIP_TRY(b, hipMemsetAsync(e.record, 0, sizeof(float) * 8 * B, b->stream));
+    HIP_TRY(b, hipMemsetAsync(e.done, 0, B, b->stream));
+    e.on = true;
+    HIP_TRY(b, hipStreamSynchronize(b->stream));                 // the zero fills; and an end_step or a restart in flight may still write the old buffers
+    b->ep = std::move(e);
+    return SFM_OK;
+}
+
+int sfm_batch_end_step(SfmBatch* b, uint32_t flags) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (flags & ~(uint32_t)SFM_END_STEP_AUTO_RESTART) return bfail(b, SFM_ERR_INVALID, "sfm_batch_end_step takes SFM_END_STEP_AUTO_RESTART only");
+    if (!b->ep.on) return bfail(b, SFM_ERR_STATE, EPISODES_OFF);
+    const bool restart = (flags & SFM_END_STEP_AUTO_RESTART) != 0;
+    long long shift = 0;
+    if (restart) {                                               // the restart's refusals come first: nothing is launched then
+        if (!b->snap.on) return bfail(b, SFM_ERR_STATE, NO_SNAPSHOT);
+        shift = b->tracks.on ? b->tracks.tick - b->snap.tick : 0;
+        if ((rc = check_restart_shift(b, nullptr, shift))) return rc;
+    }
+    EpisodeArgs a;
+    memset(&a, 0, sizeof(a));
+    a.scene_off = b->d_scene_off;
+    a.pk = b->pk;
+    a.own = b->own;
+    for (int k = 0; k < 3; ++k) a.geo[k] = BatchGeo{b->geo_item_off[k], b->geo[k].off, b->geo[k].pts, b->geo[k].ctr};
+    a.set = b->ep.set;
+    a.age = b->ep.age;
+    a.prev_goal_d2 = b->ep.prev;
+    a.record = b->ep.record;
+    a.done = b->ep.done;
+    HIP_TRY(b, launch_batch_episode(a, b->B, b->stream));
+    return restart ? batch_restart_device(b, b->ep.done, shift) : SFM_OK;
+}
+
+int sfm_batch_download_episodes(SfmBatch* b, float* record, uint8_t* done) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->ep.on) return bfail(b, SFM_ERR_STATE, EPISODES_OFF);
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    const size_t B = (size_t)b->B;
+    if (record) HIP_TRY(b, hipMemcpy(record, b->ep.record, sizeof(float) * 8 * B, hipMemcpyDeviceToHost));
+    if (done) HIP_TRY(b, hipMemcpy(done, b->ep.done, B, hipMemcpyDeviceToHost));
+    return SFM_OK;
 }
 
 const char* sfm_batch_last_error(const SfmBatch* b) { return b ? b->err.c_str() : g_create_error.c_str(); }

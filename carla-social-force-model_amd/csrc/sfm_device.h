@@ -301,6 +301,8 @@ struct BatchArgs {
 // the live one and its snapshot copy (s_*) side by side; a null live pointer: the batch has no such array.
 struct BatchRestart {
     const int* list;          // [grid] the chosen scenes, ascending; null: workgroup g restarts scene g
+    const uint8_t* mask;      // [B] on the device (sfm_batch_restart_device; list is null then): workgroup g leaves at once while
+                              // mask[g] == 0; null: every workgroup of the grid restarts its scene
     const int* scene_off;     // [B+1]
     float4* pk;         const float4* s_pk;
     float2* zv;         const float2* s_zv;       // 3-D batches only
@@ -323,6 +325,10 @@ struct BatchRestart {
     int* first;         const int* s_first;
     const int* trk_off;       // [M+1]
     long long shift;          // tau now - tau of the snapshot
+    // episodes (sfm_batch_set_episodes): a restarted scene's episode starts over, age = 0 and prev_goal_d2 = NaN ("none yet"); null
+    // while episodes are off
+    int* age;                 // [B]
+    float* prev_goal_d2;      // [B]
 };
 
 // Observations of a batch (sfm_batch_observe, sfm_batch_observe_kernel in sfm_batch_observe.hip): everything but obs is read only.
@@ -335,6 +341,25 @@ struct ObserveArgs {
     float* obs;               // [N_total][16 + 4 k]
     int k;                    // neighbour slots per row, 1 .. SFM_BATCH_MAX_OBS_NEIGHBOURS
     int frame;                // 0 world axes, 1 the row's heading frame
+};
+
+// Episode ends of a batch (sfm_batch_end_step, sfm_batch_episode_kernel in sfm_batch_episode.hip): everything above `age` is read only.
+struct BatchEpisodeScene {    // one scene's episode settings (sfm_batch_set_episodes)
+    int agent;                // the row inside the scene whose fate ends the episode, 0 .. N_b-1 (checked on the host); -1: no agent
+    int max_steps;            // 0: no time limit
+    float goal_r2, ped_r2, veh_r2;   // radius^2, each formed in double and rounded once like thr2; 0: the test never fires
+    int pad[3];
+};
+struct EpisodeArgs {
+    const int* scene_off;     // [B+1]
+    const float4* pk;         // {x, y, vx, vy}
+    const float4* own;        // {wx, wy, target_speed, radius}
+    BatchGeo geo[3];          // borders, static obstacles, dynamic obstacles (the half of the ping-pong the next tick reads)
+    const BatchEpisodeScene* set;   // [B]
+    int* age;                 // [B] evaluations since the scene's last restart
+    float* prev_goal_d2;      // [B] goal_d2 of the evaluation before; NaN: none since the restart
+    float* record;            // [B][8]
+    uint8_t* done;            // [B]
 };
 
 // Block-major packing for sharded runs (sfm_set_partition, sfm_reorder.hip): the row order is cut into gx columns by x, each

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SFM_ABI_VERSION 15  /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles; 9: + sfm_batch_set_mode_fsm, sfm_batch_download_modes; 10: + sfm_batch_tick_forces, sfm_batch_run_recorded_forces; 11: + sfm_batch_set_spawn_schedule, sfm_batch_download_spawns, SFM_MODE_UNBORN; 12: + sfm_batch_set_vehicle_tracks, sfm_batch_download_vehicle_tracks; 13: + sfm_batch_snapshot, sfm_batch_restart; 14: + sfm_batch_set_steering, sfm_batch_set_commands, sfm_batch_download_steering, sfm_batch_device_ptr; 15: + sfm_batch_set_observation, sfm_batch_observe, sfm_batch_download_observations, sfm_batch_observation_ptr (additions only) */
+#define SFM_ABI_VERSION 16  /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles; 9: + sfm_batch_set_mode_fsm, sfm_batch_download_modes; 10: + sfm_batch_tick_forces, sfm_batch_run_recorded_forces; 11: + sfm_batch_set_spawn_schedule, sfm_batch_download_spawns, SFM_MODE_UNBORN; 12: + sfm_batch_set_vehicle_tracks, sfm_batch_download_vehicle_tracks; 13: + sfm_batch_snapshot, sfm_batch_restart; 14: + sfm_batch_set_steering, sfm_batch_set_commands, sfm_batch_download_steering, sfm_batch_device_ptr; 15: + sfm_batch_set_observation, sfm_batch_observe, sfm_batch_download_observations, sfm_batch_observation_ptr; 16: + sfm_batch_set_episodes, sfm_batch_end_step, sfm_batch_download_episodes, sfm_batch_restart_device, SFM_BATCH_PTR_EPISODES / _DONE (additions only) */
 
 typedef struct SfmHandle SfmHandle;
 
@@ -505,10 +505,15 @@ int sfm_batch_download_steering(SfmBatch* b, uint8_t* kind, float* ux, float* uy
  * stay valid until the next call that reallocates: sfm_batch_upload_state (all three) and sfm_batch_set_steering (the command
  * buffer).  What the caller writes into the command buffer on the device is NOT validated: a kind other than 1 or 2 counts as
  * 0, and a non-finite command of a steered row goes into the state as it is.  NULL (and the message in sfm_batch_last_error) for an
- * unknown `which`, before sfm_batch_upload_state, and for the command buffer while steering is off; NULL without rows. */
+ * unknown `which`, before sfm_batch_upload_state, and for the command buffer while steering is off; NULL without rows.
+ * ABI 16: SFM_BATCH_PTR_EPISODES, the episode record ([B][SFM_BATCH_EPISODE_WIDTH] float), and SFM_BATCH_PTR_DONE, the mask ([B]
+ * uint8_t, 0 / 1), as the last sfm_batch_end_step left them; valid until the next sfm_batch_set_episodes or sfm_batch_upload_state;
+ * NULL (and the message) while episodes are off. */
 #define SFM_BATCH_PTR_COMMANDS 0
 #define SFM_BATCH_PTR_STATE 1
 #define SFM_BATCH_PTR_ZSTATE 2
+#define SFM_BATCH_PTR_EPISODES 3
+#define SFM_BATCH_PTR_DONE 4
 void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes);
 /* Per-pedestrian observations computed on the device (ABI 15): what a policy or a reward reads per agent -- who is near it and how
  * they move relative to it, where the kerb, the nearest obstacle and the nearest vehicle are, where its goal is -- by ONE launch of
@@ -581,6 +586,76 @@ int sfm_batch_download_observations(SfmBatch* b, float* out);
  * next sfm_batch_upload_state or sfm_batch_set_observation.  NULL (and the message in sfm_batch_last_error) while observations are
  * off; NULL without rows. */
 void* sfm_batch_observation_ptr(SfmBatch* b, int64_t* bytes);
+/* Episode ends on the device (ABI 16): the last piece of the loop observe -> act -> step -> reset.  Per scene one AGENT row, three
+ * radii and a time limit; sfm_batch_end_step decides, by ONE launch of sfm_batch_episode_kernel (a workgroup per scene), whose
+ * episode is over and why, leaves what a reward is made of in a record, and -- with SFM_END_STEP_AUTO_RESTART -- restarts the
+ * scenes that are done from the snapshot with a second launch, the mask never leaving the device.
+ *
+ * Settings (sfm_batch_set_episodes; every array [B] on the host).  agent[b]: the row inside scene b whose fate ends the episode,
+ * 0 .. N_b-1; -1: the scene has no agent, only the time limit can end it.  goal_radius, ped_radius, veh_radius: metres, finite,
+ * 0 <= r <= SFM_BATCH_MAX_SENSE_RANGE, 0 switches the test off; the kernel compares against r2 = float32(double(r) * r), formed in
+ * double and rounded once, like R2 and thr2.  max_steps[b] >= 0, 0: no time limit.
+ *
+ * State.  Per scene age (int32, evaluations since the scene's last restart, 0 at the start) and prev_goal_d2 (float; NaN: none
+ * yet).  A snapshot neither holds nor restores them; instead EVERY restart of a scene, by host mask (sfm_batch_restart) or by
+ * device mask (sfm_batch_restart_device, the auto restart), sets that scene's age = 0 and prev_goal_d2 = NaN.
+ *
+ * Record.  Scene b owns SFM_BATCH_EPISODE_WIDTH = 8 floats, [B][8], with a its agent row:
+ *     0  done, 0.0 or 1.0
+ *     1  reason bits as a float: SFM_EPISODE_ARRIVED 1, _TIME_LIMIT 2, _PED_HIT 4, _VEH_HIT 8, _NOT_LIVE 16
+ *     2  age after this evaluation (age_old + 1), as a float
+ *     3  goal_d2 = fmaf(gx, gx, gy * gy), g the goal entry exactly as sfm_batch_observe forms it (wx - x, wy - y)
+ *     4  prev_goal_d2: the stored value, or goal_d2 itself while the stored value is NaN (the first live evaluation since the
+ *        restart); the scene's stored value then becomes goal_d2
+ *     5  ped_d2: min over the live rows j != a of the scene of fmaf(dx, dx, dy * dy), dx = x_j - x_a; +inf when there is none
+ *     6  veh_d2: min over ALL ring points of ALL the scene's vehicles of the tick's own distance fmaf(ax, ax, ay * ay), ax = x - px;
+ *        the points are read as the next tick would read them (the current half of the ping-pong); an absent tracked vehicle has
+ *        its ring at +inf and contributes +inf; +inf when the scene has no vehicle
+ *     7  wall_d2: the same minimum over all border and static-obstacle points of the scene; +inf when there are none
+ * and done[b] (uint8_t) = slot 0.
+ *
+ * Rules, all exact.  A row is live by sfm_batch_observe's test: |x| < NEAR_LIMIT and |y| < NEAR_LIMIT (a NaN position fails it).
+ * arrived iff goal_d2 < goal_r2; pedestrian hit iff ped_d2 < ped_r2; vehicle hit iff veh_d2 < veh_r2 -- all strict, so a radius of 0
+ * never fires.  time limit iff max_steps > 0 and age_old + 1 >= max_steps.  An agent that is not live (despawned, unborn, NaN
+ * position) gives reason 16, +inf in slots 3 .. 7, and leaves the stored prev_goal_d2 alone.  agent = -1 gives +inf in slots 3 .. 7
+ * and only the time-limit bit.  done = (reason != 0).  wall_d2 ends nothing: it is an ingredient for a reward, as is the progress
+ * sqrt(slot 4) - sqrt(slot 3); no reward is computed here.  Only x, y of the state are used, as in sfm_batch_observe: a 3-D batch
+ * gives the planar batch's record bit for bit.
+ * The kernel writes only the record, the mask and the episode state; a tick before or after it computes what it computed without
+ * it.  No atomics; a minimum of floats without NaNs does not depend on the order it is taken in (the live test keeps NaN rows out,
+ * ring points are finite or +inf): a scene's record is bitwise the same alone or anywhere in any batch.
+ *
+ * sfm_batch_set_episodes allocates the settings, the state (age zero-filled, prev_goal_d2 NaN-filled), the record and the mask
+ * (zero-filled) and waits for the batch's stream; agent = NULL switches episodes off and frees them.  Refused with nothing changed:
+ * before sfm_batch_upload_state (SFM_ERR_STATE), an agent outside -1 .. N_b-1, a radius that is NaN, negative, infinite or above
+ * 1e6, a negative max_steps, a NULL array beside a non-NULL agent.  sfm_batch_upload_state drops the episodes (the agents are
+ * rows), as it drops observations; every other call keeps them, and they keep the snapshot. */
+#define SFM_BATCH_EPISODE_WIDTH 8
+#define SFM_EPISODE_ARRIVED 1
+#define SFM_EPISODE_TIME_LIMIT 2
+#define SFM_EPISODE_PED_HIT 4
+#define SFM_EPISODE_VEH_HIT 8
+#define SFM_EPISODE_NOT_LIVE 16
+#define SFM_END_STEP_AUTO_RESTART 1u
+int sfm_batch_set_episodes(SfmBatch* b, const int32_t* agent, const float* goal_radius, const float* ped_radius,
+                           const float* veh_radius, const int32_t* max_steps);
+/* ONE launch on the batch's stream, ordered with the ticks, observations and restarts around it; the host does not wait.  flags:
+ * 0, or SFM_END_STEP_AUTO_RESTART: the launch is followed by sfm_batch_restart_device with the mask it wrote -- two launches, no
+ * copy; the record keeps the terminal values, and the restarted scenes' age is 0 afterwards.  SFM_ERR_STATE while episodes are
+ * off; with the flag every refusal of sfm_batch_restart_device applies to the whole call, and nothing is launched. */
+int sfm_batch_end_step(SfmBatch* b, uint32_t flags);
+/* Synchronises the batch's stream, then copies the record ([B][8] floats) and the mask ([B] bytes) as the last
+ * sfm_batch_end_step left them (zeros before the first); NULL skips a column.  SFM_ERR_STATE while episodes are off. */
+int sfm_batch_download_episodes(SfmBatch* b, float* record, uint8_t* done);
+/* sfm_batch_restart with its mask on the DEVICE: d_mask is [B] bytes of device memory -- the batch's own mask
+ * (SFM_BATCH_PTR_DONE) or any buffer of the caller's, such as a torch bool tensor -- nonzero = restart the scene.  The values are
+ * not validated, like the command buffer's.  ONE launch of B workgroups on the batch's stream: workgroup b returns at once while
+ * d_mask[b] == 0 and otherwise does what sfm_batch_restart does for scene b.  No copy, no host scan, no wait.  Tracks: the first
+ * tick moved by the ticks since the snapshot must fit int32 for the tracked vehicles of ALL scenes (the host cannot know who is
+ * chosen; SFM_ERR_INVALID otherwise), and the host's copy of the first ticks is refreshed from the device by the next
+ * sfm_batch_download_vehicle_tracks or sfm_batch_snapshot, which synchronise.  Refused with nothing launched: no snapshot
+ * (SFM_ERR_STATE), d_mask NULL (SFM_ERR_INVALID). */
+int sfm_batch_restart_device(SfmBatch* b, const uint8_t* d_mask);
 /* Current state of every scene (synchronises the batch's stream); NULL skips a column.  A planar batch leaves z alone and
  * writes vz = 0. */
 int sfm_batch_download_state(SfmBatch* b, float* x, float* y, float* z, float* vx, float* vy, float* vz);
