@@ -14,7 +14,7 @@ import numpy as np
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFM_LIB_PATH") or os.path.join(PKG_DIR, "libsfm_hip.so")   # (the override is for A/B builds of the kernels)
-ABI_VERSION = 16
+ABI_VERSION = 17
 SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_records": 5,
          **{n: 6 for n in ("sfm_batch_create", "sfm_batch_destroy", "sfm_batch_set_stream", "sfm_batch_set_params",
                            "sfm_batch_upload_state", "sfm_batch_set_borders", "sfm_batch_set_static_obstacles",
@@ -32,7 +32,8 @@ SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_
          **{n: 15 for n in ("sfm_batch_set_observation", "sfm_batch_observe", "sfm_batch_download_observations",
                             "sfm_batch_observation_ptr")},
          **{n: 16 for n in ("sfm_batch_set_episodes", "sfm_batch_end_step", "sfm_batch_download_episodes",
-                            "sfm_batch_restart_device")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
+                            "sfm_batch_restart_device")},
+         **{n: 17 for n in ("sfm_batch_set_scan", "sfm_batch_scan", "sfm_batch_download_scan")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
 
 FORCE_NAMES = ("acceleration_force", "pedestrian_force", "border_force",
                "static_obstacle_force", "dynamic_obstacle_force")
@@ -156,6 +157,10 @@ SYMBOLS = {
     "sfm_batch_end_step": (C.c_int, [_H, C.c_uint32]),
     "sfm_batch_download_episodes": (C.c_int, [_H, _F, _U8]),
     "sfm_batch_restart_device": (C.c_int, [_H, C.c_void_p]),
+    # batch range scans (ABI 17)
+    "sfm_batch_set_scan": (C.c_int, [_H, C.c_int, _F, _F, _F, _F, _F, _U8, C.c_int]),
+    "sfm_batch_scan": (C.c_int, [_H]),
+    "sfm_batch_download_scan": (C.c_int, [_H, _F]),
 }
 
 _lib = None

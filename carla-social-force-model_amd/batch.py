@@ -1,7 +1,7 @@
 """Batched scenes: many small, independent crowds stepped by ONE kernel launch per tick (C ABI: sfm_batch_*, ABI 6; waypoint
 streams and recorded runs, ABI 7; device-side vehicles, ABI 8; pedestrian modes, ABI 9; force records, ABI 10; spawn schedules, ABI 11;
 vehicle tracks, ABI 12; snapshot and restart, ABI 13; steered pedestrians, ABI 14; observations, ABI 15; episode ends and the restart
-by device mask, ABI 16).
+by device mask, ABI 16; range scans, ABI 17).
 
 Social-force models are run in bulk as many small scenes -- scenario sampling, RL environments stepped in lock-step, calibration
 sweeps over A / lambda / gamma / tau.  ``SfmBatch`` holds B scenes of 0 .. 1024 pedestrians, each with its own parameters (its own
@@ -82,6 +82,18 @@ mask ``done``; ``end_step(auto_restart=True)`` follows it with ``restart_device(
 a step of the loop copies nothing and waits for nothing: examples/batch_rl_loop_device.py.  Every restart of a scene starts its
 episode clock over.  ``episodes()`` downloads record and mask, ``episode_tensor()`` / ``done_tensor()`` alias them, and
 ``episode.episode_scene`` is the host twin, bit for bit.
+
+Range scans (ABI 17): the sensor most crowd-navigation policies are trained on, computed on the device by one launch per call.
+``set_scan(max_range, ped_radius, point_radius, R=..., mask=..., frame=...)`` chooses R rays around every scanned row (2 pi q / R
+by default, or ``angles``, or ``directions`` used as given), a range limit and two radii per scene: every other pedestrian is a disc
+of ``ped_radius``, every sampled point of a border, a static-obstacle ring or a vehicle ring a disc of ``point_radius`` (the
+model's own view of geometry; 0.1 m, the reference's sampling resolution, by default).  ``scan()`` fills, per row, ``2R`` floats:
+the distance along each ray to the first disc it meets (``max_range`` when there is none nearer) and the kind of what was hit (0
+nothing, 1 pedestrian, 2 border, 3 static obstacle, 4 vehicle) -- an occluding wall, a gap between two parked cars, a kerb
+alongside, which a list of k neighbours cannot express.  ``mask`` names the rows that are scanned (an RL loop scans its agents,
+not the crowd); the others cost nothing and read zeros.  ``scans()`` downloads them per scene, ``scan_tensor()`` is the buffer as a
+torch tensor a policy reads on the device, and ``scan.scan_scene`` is the host twin, bit for bit in both frames (the record and its
+exact rules: include/sfm_hip.h).  Scanning changes nothing a tick reads: examples/batch_lidar_loop.py.
 """
 from __future__ import annotations
 
@@ -90,6 +102,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import scan as _scan
 from ._lib import SfmLibraryError, f32, fptr, iptr, u8ptr
 
 MAX_RECORD_BYTES = 1 << 30       # SFM_BATCH_MAX_RECORD_BYTES: frames one run_recorded call may hold
@@ -543,6 +556,7 @@ def restart_mask(B, scenes=None):
 STEER_OFF, STEER_VELOCITY, STEER_PREFERRED = 0, 1, 2   # the kinds of a steered row (held as floats in the command buffer)
 PTR_COMMANDS, PTR_STATE, PTR_ZSTATE = 0, 1, 2          # SFM_BATCH_PTR_*: what sfm_batch_device_ptr / SfmBatch.device_ptr select
 PTR_EPISODES, PTR_DONE = 3, 4                          # ... the episode record [B][8] and the mask done[B] (while episodes are on)
+PTR_SCAN = 5                                           # ... the scan record [N_total][2R] (while scans are on)
 
 
 def _per_scene(v, so, width, name):
@@ -763,6 +777,7 @@ class SfmBatch:
         self.has_snapshot = False         # snapshot() has been taken and no later call has dropped it
         self.obs_k = None                 # neighbour slots of set_observation (None: observations are off)
         self.has_episodes = False         # set_episodes has been called and no later call has dropped it
+        self.scan_rays = None             # rays per row of set_scan (None: scans are off)
 
     def _check(self, rc, what):
         if rc != 0:
@@ -827,6 +842,7 @@ class SfmBatch:
         self.scene_off = so.copy()
         self.obs_k = None                 # (the upload dropped the observations with the rows)
         self.has_episodes = False         # ... and the episodes
+        self.scan_rays = None             # ... and the scans
         self.planar = planar
         self._z = pk["z"].copy()          # a planar batch keeps each scene's z on the host (the device holds x / y only)
 
@@ -1015,8 +1031,8 @@ class SfmBatch:
 
     def device_ptr(self, which):
         """(address, bytes) of a device buffer of the batch (sfm_batch_device_ptr): ``PTR_COMMANDS``, ``PTR_STATE``,
-        ``PTR_ZSTATE`` ((0, 0) for a planar batch), ``PTR_EPISODES`` or ``PTR_DONE``.  Valid until the next ``upload`` (the
-        command buffer: or ``set_steering``; the episode buffers: or ``set_episodes``)."""
+        ``PTR_ZSTATE`` ((0, 0) for a planar batch), ``PTR_EPISODES``, ``PTR_DONE`` or ``PTR_SCAN``.  Valid until the next ``upload``
+        (the command buffer: or ``set_steering``; the episode buffers: or ``set_episodes``; the scan buffer: or ``set_scan``)."""
         nbytes = C.c_int64(0)
         if self.scene_off is None:
             raise SfmLibraryError("SfmBatch.device_ptr: upload() has not been called")
@@ -1098,6 +1114,69 @@ class SfmBatch:
         if not ptr and (self.obs_k is None or self.scene_off is None or int(self.scene_off[-1]) > 0):
             self._check(-1, "sfm_batch_observation_ptr")
         w = obs_width(self.obs_k)
+        dev = f"cuda:{torch.cuda.current_device() if device is None else int(device)}"
+        if not ptr:                                                    # (without rows: no buffer)
+            return torch.zeros((0, w), dtype=torch.float32, device=dev)
+        return torch.as_tensor(_DeviceSpan(ptr, (int(nbytes.value) // (4 * w), w)), device=dev)
+
+    def set_scan(self, max_range, ped_radius=None, point_radius=_scan.POINT_RADIUS, R=None, angles=None, mask=None, frame=0,
+                 directions=None):
+        """What ``scan`` computes (sfm_batch_set_scan; see ``scan.scan_arrays`` and the module docstring): per scanned row R rays,
+        each the distance to the first disc it meets -- pedestrians are discs of ``ped_radius``, every sampled point of a border, a
+        static-obstacle ring or a vehicle ring a disc of ``point_radius`` (0 switches a kind off) -- up to ``max_range``; all three
+        one value or one per scene, in metres.  The rays: ``R`` of them at 2 pi q / R, or ``angles`` (radians; cos and sin are
+        formed in double and rounded once), or ``directions`` = (dir_x, dir_y) used as given.  ``mask``: which rows are scanned
+        (``scan.scan_mask``: None every row, a list per scene of bool arrays or row indices, or a bool array over the concatenated
+        rows).  ``frame``: 0 world axes, 1 the row's heading frame.  ``max_range=None`` switches scans off and frees the buffer.
+        Needs ``upload`` first, which also drops them; every other call keeps them, and they keep the snapshot.  Allocates and
+        zero-fills the buffer (``scan_tensor()`` must be taken again)."""
+        L = self._lib
+        if max_range is None:
+            self._check(L.sfm_batch_set_scan(self._b, 0, None, None, None, None, None, None, 0), "sfm_batch_set_scan")
+            self.scan_rays = None
+            return
+        if self.scene_off is None:
+            raise SfmLibraryError("SfmBatch.set_scan: upload() has not been called")
+        if ped_radius is None:
+            raise ValueError("set_scan needs a ped_radius (metres; 0: pedestrians are not seen)")
+        if sum(v is not None for v in (R, angles, directions)) != 1:
+            raise ValueError("set_scan takes exactly one of R, angles and directions")
+        if directions is not None:
+            dx, dy = _scan.check_directions(directions)
+        else:
+            dx, dy = _scan.ray_directions(_scan.default_angles(R) if angles is None else angles)
+        rm, rp, rq, frame = _scan.scan_arrays(self.B, max_range, ped_radius, point_radius, frame)
+        m = _scan.scan_mask(mask, self.scene_off)
+        if m is not None and m.shape[0] == 0:
+            m = None
+        self._check(L.sfm_batch_set_scan(self._b, int(dx.shape[0]), fptr(dx), fptr(dy), fptr(rm), fptr(rp), fptr(rq), u8ptr(m), frame),
+                    "sfm_batch_set_scan")
+        self.scan_rays = int(dx.shape[0])
+
+    def scan(self):
+        """Scan as the state is now (sfm_batch_scan): one launch on the batch's stream, ordered with the ticks and restarts around
+        it; the host does not wait.  Raises SfmLibraryError while scans are off."""
+        self._check(self._lib.sfm_batch_scan(self._b), "sfm_batch_scan")
+
+    def scans(self):
+        """``scan()`` and a download: a list of B float32 arrays (N_b, 2R) in scene order -- ranges, then kinds (synchronises the
+        batch's stream)."""
+        self.scan()
+        n = int(self.scene_off[-1])
+        buf = np.zeros((n, 2 * (self.scan_rays or 0)), np.float32)
+        self._check(self._lib.sfm_batch_download_scan(self._b, fptr(buf) if n else None), "sfm_batch_download_scan")
+        return split_observations(buf, self.scene_off)
+
+    def scan_tensor(self, device=None):
+        """The scan buffer as a torch tensor (N_total, 2R) float32 that aliases device memory (no copy): what a policy reads after
+        ``scan()``.  Put torch and the batch on one stream.  Take it again after ``upload`` or ``set_scan``.  Raises
+        SfmLibraryError while scans are off."""
+        import torch
+        nbytes = C.c_int64(0)
+        ptr = self._lib.sfm_batch_device_ptr(self._b, PTR_SCAN, C.byref(nbytes))
+        if not ptr and (self.scan_rays is None or self.scene_off is None or int(self.scene_off[-1]) > 0):
+            self._check(-1, "sfm_batch_device_ptr")
+        w = 2 * self.scan_rays
         dev = f"cuda:{torch.cuda.current_device() if device is None else int(device)}"
         if not ptr:                                                    # (without rows: no buffer)
             return torch.zeros((0, w), dtype=torch.float32, device=dev)

@@ -119,6 +119,17 @@ struct BatchEpisodeDev {
     DevBuf<uint8_t> done;              // [B]
 };
 
+// range scans (sfm_batch_set_scan, ABI 17): the settings and the buffer sfm_batch_scan fills; nothing a tick reads or writes
+struct BatchScanDev {
+    bool on = false;           // (not "buf is allocated": a batch without rows can be scanned and has no buffer)
+    int R = 0;
+    int frame = 0;
+    DevBuf<BatchScanScene> set;    // [B]
+    DevBuf<float2> dir;        // [R]
+    DevBuf<uint8_t> mask;      // [N_total]; not allocated: every row is scanned
+    DevBuf<float> buf;         // [N_total][2 R]
+};
+
 struct BatchRecordDev {        // grow-only device buffers of the recording calls
     DevBuf<float4> frames;     // sfm_batch_run_recorded
     DevBuf<float2> zframes;
@@ -154,7 +165,8 @@ struct SfmBatch {
     BatchSteerDev steer;
     BatchObsDev obs;
     BatchEpisodeDev ep;
-    Event c_done;                      // created by the first sfm_batch_set_steering with rows; outlives every drop of the steering
+    BatchScanDev scan;
+    Event c_done;                     // created by the first sfm_batch_set_steering with rows; outlives every drop of the steering
     std::string err;
 };
 
@@ -423,7 +435,8 @@ static int check_restart_shift(SfmBatch* b, const uint8_t* mask, long long shift
 
 static const char* const NO_SNAPSHOT = "the batch has no snapshot: call sfm_batch_snapshot first (sfm_batch_upload_state and the calls "
                                        "that set vehicles, modes, a spawn schedule or tracks drop it)";
-static const char* const EPISODES_OFF = "episodes are off: call sfm_batch_set_episodes first (sfm_batch_upload_state drops them)";
+static const char* const SCANS_OFF = "scans are off: call sfm_batch_set_scan first (sfm_batch_upload_state drops them)";
+static const char* const EPISODES_OFF ="episodes are off: call sfm_batch_set_episodes first (sfm_batch_upload_state drops them)";
 
 // sfm_batch_restart_device after its checks: ONE launch of B workgroups, the choice read on the device
 static int batch_restart_device(SfmBatch* b, const uint8_t* d_mask, long long shift) {
@@ -581,6 +594,7 @@ int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x
     b->steer = {};                                                // ... and so are its commands (the rows may differ)
     b->obs = {};                                                  // ... and its observations
     b->ep = {};                                                   // ... and its episodes (the agents are rows)
+    b->scan = {};                                                 // ... and its scans (the mask is per row)
     b->snap.on = false;                                           // ... and so is its snapshot
     b->have_state = false;
     if (n > 0) {
@@ -1240,7 +1254,13 @@ int sfm_batch_download_steering(SfmBatch* b, uint8_t* kind, float* ux, float* uy
 void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes) {
     if (bytes) *bytes = 0;
     if (!b) return nullptr;
-    if (which < SFM_BATCH_PTR_COMMANDS || which > SFM_BATCH_PTR_DONE) { bfail(b, SFM_ERR_INVALID, "which must be SFM_BATCH_PTR_COMMANDS, _STATE, _ZSTATE, _EPISODES or _DONE"); return nullptr; }
+    if (which < SFM_BATCH_PTR_COMMANDS || which > SFM_BATCH_PTR_SCAN) { bfail(b, SFM_ERR_INVALID, "which must be SFM_BATCH_PTR_COMMANDS, _STATE, _ZSTATE, _EPISODES, _DONE or _SCAN"); return nullptr; }
+    if (which == SFM_BATCH_PTR_SCAN) {
+        if (!b->scan.on) { bfail(b, SFM_ERR_STATE, std::string(SCANS_OFF) + ", so which = SFM_BATCH_PTR_SCAN has no buffer"); return nullptr; }
+        if (b->n_total == 0) return nullptr;
+        if (bytes) *bytes = (int64_t)(sizeof(float) * (size_t)b->n_total * (size_t)(2 * b->scan.R));
+        return b->scan.buf;
+    }
     if (which == SFM_BATCH_PTR_EPISODES || which == SFM_BATCH_PTR_DONE) {
         if (!b->ep.on) { bfail(b, SFM_ERR_STATE, std::string(EPISODES_OFF) + ", so which = SFM_BATCH_PTR_EPISODES / _DONE has no buffer"); return nullptr; }
         const bool rec = which == SFM_BATCH_PTR_EPISODES;
@@ -1424,6 +1444,100 @@ int sfm_batch_download_episodes(SfmBatch* b, float* record, uint8_t* done) {
     const size_t B = (size_t)b->B;
     if (record) HIP_TRY(b, hipMemcpy(record, b->ep.record, sizeof(float) * 8 * B, hipMemcpyDeviceToHost));
     if (done) HIP_TRY(b, hipMemcpy(done, b->ep.done, B, hipMemcpyDeviceToHost));
+    return SFM_OK;
+}
+
+// Range scans (ABI 17).  Everything is checked before anything is allocated or freed.
+int sfm_batch_set_scan(SfmBatch* b, int R, const float* dir_x, const float* dir_y, const float* max_range, const float* ped_radius,
+                       const float* point_radius, const uint8_t* mask, int frame) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!max_range) {
+        HIP_TRY(b, hipStreamSynchronize(b->stream));             // a scan in flight may still write the buffer
+        b->scan = {};
+        return SFM_OK;
+    }
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    if (R < 1 || R > SFM_BATCH_MAX_SCAN_RAYS)
+        return bfail(b, SFM_ERR_INVALID, "R must be 1 .. " + std::to_string(SFM_BATCH_MAX_SCAN_RAYS) + " rays per row, got " + std::to_string(R));
+    if (frame != SFM_OBS_FRAME_WORLD && frame != SFM_OBS_FRAME_HEADING)
+        return bfail(b, SFM_ERR_INVALID, "frame must be 0 (world axes) or 1 (the row's heading frame), got " + std::to_string(frame));
+    if (!dir_x || !dir_y) return bfail(b, SFM_ERR_INVALID, "dir_x or dir_y is NULL");
+    if (!ped_radius || !point_radius) return bfail(b, SFM_ERR_INVALID, "ped_radius or point_radius is NULL");
+    std::vector<float2> dir((size_t)R);
+    for (int q = 0; q < R; ++q) {
+        if (!std::isfinite(dir_x[q]) || !std::isfinite(dir_y[q]))
+            return bfail(b, SFM_ERR_INVALID, "ray " + std::to_string(q) + ": its direction is not finite");
+        dir[q] = make_float2(dir_x[q], dir_y[q]);
+    }
+    const size_t B = (size_t)b->B;
+    std::vector<BatchScanScene> set(B);
+    for (size_t s = 0; s < B; ++s) {
+        const float m = max_range[s];
+        if (!std::isfinite(m) || !(m > 0.f) || m > SFM_BATCH_MAX_SENSE_RANGE)
+            return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(s) + ": max_range must be finite, > 0 and <= 1e6 metres");
+        float r2[2];
+        const float r[2] = {ped_radius[s], point_radius[s]};
+        for (int q = 0; q < 2; ++q) {
+            if (!std::isfinite(r[q]) || !(r[q] >= 0.f) || r[q] > SFM_BATCH_MAX_SENSE_RANGE)
+                return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(s) + ": " + (q == 0 ? "ped_radius" : "point_radius") +
+                                                 " must be finite, >= 0 and <= 1e6 metres");
+            r2[q] = (float)((double)r[q] * (double)r[q]);            // r^2 rounded once, like R2
+        }
+        set[s] = BatchScanScene{m, r2[0], r2[1], 0.f};
+    }
+    const size_t n = (size_t)b->n_total, vals = n * (size_t)(2 * R);
+    BatchScanDev o;
+    HIP_TRY(b, o.set.alloc(B));
+    HIP_TRY(b, o.dir.alloc((size_t)R));
+    HIP_TRY(b, hipMemcpy(o.set, set.data(), sizeof(BatchScanScene) * B, hipMemcpyHostToDevice));
+    HIP_TRY(b, hipMemcpy(o.dir, dir.data(), sizeof(float2) * (size_t)R, hipMemcpyHostToDevice));
+    if (mask && n > 0) {
+        HIP_TRY(b, o.mask.alloc(n));
+        HIP_TRY(b, hipMemcpy(o.mask, mask, n, hipMemcpyHostToDevice));
+    }
+    if (vals > 0) {
+        HIP_TRY(b, o.buf.alloc(vals));
+        HIP_TRY(b, hipMemsetAsync(o.buf, 0, sizeof(float) * vals, b->stream));
+    }
+    o.R = R;
+    o.frame = frame;
+    o.on = true;
+    HIP_TRY(b, hipStreamSynchronize(b->stream));                 // the zero fill; and a scan in flight may still write the old buffer
+    b->scan = std::move(o);
+    return SFM_OK;
+}
+
+int sfm_batch_scan(SfmBatch* b) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->scan.on) return bfail(b, SFM_ERR_STATE, SCANS_OFF);
+    if (b->n_total == 0) return SFM_OK;
+    ScanArgs a;
+    memset(&a, 0, sizeof(a));
+    a.scene_off = b->d_scene_off;
+    a.pk = b->pk;
+    a.own = b->own;
+    for (int k = 0; k < 3; ++k) a.geo[k] = BatchGeo{b->geo_item_off[k], b->geo[k].off, b->geo[k].pts, b->geo[k].ctr};
+    a.set = b->scan.set;
+    a.dir = b->scan.dir;
+    a.mask = b->scan.mask;                                       // (null: every row)
+    a.out = b->scan.buf;
+    a.R = b->scan.R;
+    a.frame = b->scan.frame;
+    HIP_TRY(b, launch_batch_scan(a, b->B, b->stream));
+    return SFM_OK;
+}
+
+int sfm_batch_download_scan(SfmBatch* b, float* out) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->scan.on) return bfail(b, SFM_ERR_STATE, SCANS_OFF);
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    const size_t vals = (size_t)b->n_total * (size_t)(2 * b->scan.R);
+    if (vals == 0) return SFM_OK;
+    if (!out) return bfail(b, SFM_ERR_INVALID, "out is NULL");
+    HIP_TRY(b, hipMemcpy(out, b->scan.buf, sizeof(float) * vals, hipMemcpyDeviceToHost));
     return SFM_OK;
 }
 

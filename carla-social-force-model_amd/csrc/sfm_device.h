@@ -362,6 +362,26 @@ struct EpisodeArgs {
     uint8_t* done;            // [B]
 };
 
+// Range scans of a batch (sfm_batch_scan, sfm_batch_scan_kernel in sfm_batch_scan.hip): everything but out is read only.
+constexpr int SCAN_MAX_RAYS = 64;
+struct BatchScanScene {       // one scene's scan settings (sfm_batch_set_scan)
+    float max_range;          // Rmax, the fp32 value as given
+    float ped_r2, point_r2;   // radius^2, each formed in double and rounded once like R2; 0: the kind is never hit
+    float pad;
+};
+struct ScanArgs {
+    const int* scene_off;     // [B+1]
+    const float4* pk;         // {x, y, vx, vy}
+    const float4* own;        // {wx, wy, target_speed, radius}: the goal of frame 1's heading
+    BatchGeo geo[3];          // borders, static obstacles, dynamic obstacles (the half of the ping-pong the next tick reads)
+    const BatchScanScene* set;    // [B]
+    const float2* dir;        // [R] ray directions, used as given
+    const uint8_t* mask;      // [N_total] nonzero: the row is scanned; null: every row
+    float* out;               // [N_total][2 R]: ranges, then kinds
+    int R;                    // rays per row, 1 .. SCAN_MAX_RAYS
+    int frame;                // 0 world axes, 1 the row's heading frame
+};
+
 // Block-major packing for sharded runs (sfm_set_partition, sfm_reorder.hip): the row order is cut into gx columns by x, each
 // column into gy blocks by y -- block b = column * gy + position holds rows [bound[b], bound[b+1]) -- and every block is
 // strip-packed on its own, so a rank's contiguous row range is a compact rectangle of the map instead of a slab across it.

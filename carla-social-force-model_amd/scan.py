@@ -1,0 +1,282 @@
+"""The host twin of the batch's range scans (sfm_batch_scan, ABI 17; the record and its rules: include/sfm_hip.h).
+
+``scan_scene`` computes, in NumPy, the record ``SfmBatch.scans()`` returns for one scene -- bit for bit in BOTH frames: every
+operation of the rules is one correctly rounded fp32 operation or an ``fmaf``, and ``_fma32`` is an exact ``fmaf`` (the float64 sum
+is repaired to round-to-odd before the cast, so it is never rounded twice).  Per scanned live row and ray: the distance to the first
+disc the ray meets -- pedestrians are discs of ``ped_radius``, every sampled point of a border, a static-obstacle ring or a vehicle
+ring is a disc of ``point_radius`` -- and the kind of what was hit.
+
+Pure NumPy, no GPU and no library needed.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .observe import NEAR_LIMIT, _f32, _get, _polylines
+
+MAX_SCAN_RAYS = 64                   # SFM_BATCH_MAX_SCAN_RAYS
+MAX_SCAN_RANGE = 1.0e6               # SFM_BATCH_MAX_SENSE_RANGE, metres: the bound of max_range and of the radii
+KIND_NONE, KIND_PEDESTRIAN, KIND_BORDER, KIND_STATIC, KIND_VEHICLE = range(5)
+POINT_RADIUS = 0.1                   # the reference's sampling resolution of borders and rings
+
+
+def _fma32(a, b, c):
+    """fmaf(a, b, c) of fp32 arrays, exact: the product of two fp32 is exact in float64; the float64 sum s = RN(p + c) can be off
+    the true sum by a residual e (TwoSum gives it exactly), and casting s to fp32 would then round a second time.  Where e != 0
+    the sum is moved to its odd neighbour on e's side (round-to-odd); a round-to-odd float64 cast to fp32 rounds as the exact sum
+    does (53 >= 24 + 2 bits).  Returns float32."""
+    a, b, c = np.broadcast_arrays(np.asarray(a, np.float32), np.asarray(b, np.float32), np.asarray(c, np.float32))
+    with np.errstate(over="ignore", invalid="ignore"):
+        p = a.astype(np.float64) * b.astype(np.float64)
+        c64 = c.astype(np.float64)
+        s = p + c64
+        bb = s - p                                                     # TwoSum (Knuth): e = (p + c) - s exactly, for finite s
+        e = (p - (s - bb)) + (c64 - bb)
+        fix = np.isfinite(s) & (e != 0)
+        bits = np.array(s, dtype=np.float64, copy=True).view(np.int64)
+        even = (bits & 1) == 0
+        away = (e > 0) == (s > 0)                                      # the true sum lies further from zero than s
+        bits = np.where(fix & even, bits + np.where(away, 1, -1), bits)
+        return bits.view(np.float64).astype(np.float32)
+
+
+def radius2(r):
+    """r2 as the library forms it: the fp32 radius squared in double and rounded once (like ``observe.range2``)."""
+    r = np.float64(np.float32(r))
+    return np.float32(r * r)
+
+
+def default_angles(R):
+    """The default ray angles: 2 pi q / R, q = 0 .. R-1, float64."""
+    R = int(R)
+    if not 1 <= R <= MAX_SCAN_RAYS:
+        raise ValueError(f"R must be 1 .. {MAX_SCAN_RAYS} rays, got {R}")
+    return 2.0 * np.pi * np.arange(R) / R
+
+
+def ray_directions(angles):
+    """Ray angles (radians, 1 .. 64 of them) -> (dir_x, dir_y) float32 [R]: cos and sin formed in double and rounded once.  Pure
+    NumPy; raises ValueError on a shape that does not fit and on an angle that is not finite."""
+    a = np.asarray(angles)
+    if a.dtype.kind not in "iuf":
+        raise ValueError(f"angles must be numbers, got {a.dtype}")
+    a = a.astype(np.float64)
+    if a.ndim != 1 or not 1 <= a.shape[0] <= MAX_SCAN_RAYS:
+        raise ValueError(f"angles: expected 1 .. {MAX_SCAN_RAYS} values, got shape {a.shape}")
+    if not np.isfinite(a).all():
+        raise ValueError("angles must be finite")
+    return np.ascontiguousarray(np.cos(a), dtype=np.float32), np.ascontiguousarray(np.sin(a), dtype=np.float32)
+
+
+def check_directions(directions):
+    """(dir_x, dir_y) given directly -> both as float32 [R], used as given (not renormalised).  Raises ValueError on shapes that do
+    not fit, R outside 1 .. 64 and values that are not finite in float32."""
+    try:
+        dx, dy = directions
+    except (TypeError, ValueError):
+        raise ValueError("directions must be a pair (dir_x, dir_y)") from None
+    dx, dy = np.asarray(dx), np.asarray(dy)
+    if dx.dtype.kind not in "iuf" or dy.dtype.kind not in "iuf":
+        raise ValueError("directions must be numbers")
+    if dx.ndim != 1 or dx.shape != dy.shape or not 1 <= dx.shape[0] <= MAX_SCAN_RAYS:
+        raise ValueError(f"directions: expected two arrays of 1 .. {MAX_SCAN_RAYS} values, got shapes {dx.shape} and {dy.shape}")
+    with np.errstate(over="ignore"):
+        dx, dy = np.ascontiguousarray(dx, dtype=np.float32), np.ascontiguousarray(dy, dtype=np.float32)
+    if not (np.isfinite(dx).all() and np.isfinite(dy).all()):
+        raise ValueError("directions must be finite in float32")
+    return dx, dy
+
+
+def scan_arrays(B, max_range, ped_radius, point_radius=POINT_RADIUS, frame=0):
+    """Scan settings -> the per-scene arguments of sfm_batch_set_scan: (max_range, ped_radius, point_radius float32 [B], frame int).
+    Each of the three is a scalar (broadcast to every scene, like ``stream_arrays``) or B values, in metres: ``max_range`` finite,
+    > 0 and <= 1e6 in float32; the radii finite, >= 0 and <= 1e6 (0 switches the kind off).  Pure NumPy; raises ValueError on a
+    frame other than 0 or 1, a shape that does not fit, and every value the library would refuse."""
+    B = int(B)
+    if isinstance(frame, (bool, np.bool_)) or not isinstance(frame, (int, np.integer)) or int(frame) not in (0, 1):
+        raise ValueError(f"frame must be 0 (world axes) or 1 (the row's heading frame), got {frame!r}")
+
+    def col(v, name, positive):
+        a = np.asarray(v)
+        if a.dtype.kind not in "iuf":
+            raise ValueError(f"{name} must be numbers, got {a.dtype}")
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] not in (1, B)):
+            raise ValueError(f"{name}: expected a scalar or {B} values, got shape {a.shape}")
+        with np.errstate(over="ignore"):
+            r = np.ascontiguousarray(np.broadcast_to(a.reshape(-1), (B,)), dtype=np.float32)
+        ok = np.isfinite(r).all() and ((r > 0).all() if positive else (r >= 0).all()) and (r <= np.float32(MAX_SCAN_RANGE)).all()
+        if not ok:
+            raise ValueError(f"{name} must be finite, {'> 0' if positive else '>= 0'} and <= {MAX_SCAN_RANGE:g} metres")
+        return r
+
+    return col(max_range, "max_range", True), col(ped_radius, "ped_radius", False), col(point_radius, "point_radius", False), int(frame)
+
+
+def scan_mask(mask, scene_off):
+    """Which rows are scanned -> uint8 [N_total], or None for every row.  ``mask``: None; a list with one entry per scene (each a
+    bool array (N_b,), one bool for the whole scene, or row indices inside the scene as integers); or one bool ndarray (N_total,)
+    over the concatenated rows.  Pure NumPy; raises ValueError."""
+    if mask is None:
+        return None
+    so = np.asarray(scene_off)
+    B, n = len(so) - 1, int(so[-1])
+    if isinstance(mask, (list, tuple)):
+        if len(mask) != B:
+            raise ValueError(f"{len(mask)} entries of mask for {B} scenes (a list is per scene; pass an ndarray for concatenated rows)")
+        out = np.zeros(n, np.uint8)
+        for b, e in enumerate(mask):
+            nb = int(so[b + 1] - so[b])
+            a = np.asarray(e)
+            if a.dtype.kind == "b":
+                if a.ndim == 0:
+                    a = np.broadcast_to(a, (nb,))
+                if a.shape != (nb,):
+                    raise ValueError(f"scene {b}: a bool mask of shape {a.shape} for {nb} rows")
+                out[so[b]:so[b + 1]] = a
+            else:
+                a = a.reshape(-1)
+                if a.size and a.dtype.kind not in "iu":
+                    raise ValueError(f"scene {b}: row indices must be integers, got {a.dtype}")
+                if a.size and (int(a.min()) < 0 or int(a.max()) >= nb):
+                    raise ValueError(f"scene {b}: row indices must lie in 0 .. {nb - 1}")
+                out[so[b] + a.astype(np.int64)] = 1
+        return out
+    a = np.asarray(mask)
+    if a.dtype.kind not in "bu" or a.shape != (n,):
+        raise ValueError(f"a mask over the concatenated rows must be bool (or uint8) of shape ({n},), got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a != 0, dtype=np.uint8)
+
+
+def heading32(x, y, vx, vy, wx, wy):
+    """The heading of frame 1, per row, in the kernel's fp32 arithmetic: v / |v| when fmaf(vx, vx, vy * vy) > 0, else the goal
+    entry (wx - x, wy - y) / its length when that is > 0, else (1, 0); l = sqrt(.), h = (a / l, b / l), each rounded once."""
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        gx, gy = wx - x, wy - y
+        vv, gg = _fma32(vx, vx, vy * vy), _fma32(gx, gx, gy * gy)
+        use_v = vv > 0
+        use_g = ~use_v & (gg > 0)
+        a = np.where(use_v, vx, gx)
+        b = np.where(use_v, vy, gy)
+        l = np.sqrt(np.where(use_v, vv, gg).astype(np.float32))
+        hx = np.where(use_v | use_g, (a / l).astype(np.float32), np.float32(1.0)).astype(np.float32)
+        hy = np.where(use_v | use_g, (b / l).astype(np.float32), np.float32(0.0)).astype(np.float32)
+    return hx, hy
+
+
+def _walk(scene, angles, max_range, ped_radius, point_radius, frame, mask, state, vehicles, waypoints, directions, prune):
+    """The shared walk of ``scan_scene`` and ``range_census``: validates, then yields first (n, R, Rmax) and after it, per scanned
+    live row in ascending order, (i, val, kind): val (R, P) float32 the range of every candidate in the fixed order (+inf where
+    the disc is no candidate of the ray), kind (P,) int64."""
+    if frame not in (0, 1):
+        raise ValueError(f"frame must be 0 or 1, got {frame!r}")
+    ux, uy = ray_directions(angles) if directions is None else check_directions(directions)
+    R = ux.shape[0]
+    Rmax = np.float32(max_range)
+    if not (np.isfinite(Rmax) and 0 < Rmax <= np.float32(MAX_SCAN_RANGE)):
+        raise ValueError(f"max_range must be finite, > 0 and <= {MAX_SCAN_RANGE:g} metres")
+    for name, r in (("ped_radius", ped_radius), ("point_radius", point_radius)):
+        if not (np.isfinite(np.float32(r)) and 0 <= np.float32(r) <= np.float32(MAX_SCAN_RANGE)):
+            raise ValueError(f"{name} must be finite, >= 0 and <= {MAX_SCAN_RANGE:g} metres")
+    pr2, qr2 = radius2(ped_radius), radius2(point_radius)
+    loc, vel = (_get(scene, "loc"), _get(scene, "vel")) if state is None else state
+    loc, vel = np.asarray(loc, dtype=np.float64), np.asarray(vel, dtype=np.float64)
+    n = loc.reshape(-1, loc.shape[-1]).shape[0] if loc.size else 0
+    yield n, R, Rmax
+    if n == 0:
+        return
+    loc, vel = loc.reshape(n, -1), vel.reshape(n, -1)
+    x, y = _f32(loc[:, 0], 0), _f32(loc[:, 1], 0)
+    vx, vy = _f32(vel[:, 0], 0), _f32(vel[:, 1], 0)
+    scanned = np.ones(n, bool) if mask is None else np.asarray(mask).astype(bool).reshape(n)
+    live = (np.abs(x) < NEAR_LIMIT) & (np.abs(y) < NEAR_LIMIT)         # (a NaN position fails it)
+    if frame == 1:
+        wp = np.asarray(_get(scene, "waypoint") if waypoints is None else waypoints, dtype=np.float64).reshape(n, -1)
+        hx, hy = heading32(x, y, vx, vy, _f32(wp[:, 0], 0), _f32(wp[:, 1], 0))
+
+    borders = _get(scene, "borders") or []
+    statics = _get(scene, "static_obstacles") or []
+    veh = (_get(scene, "dynamic_obstacles") or []) if vehicles is None else vehicles
+    geo = [_polylines(borders, False)[0], _polylines(statics, True)[0], _polylines(veh, True)[0]]
+    gx = np.concatenate([g[:, 0] for g in geo])
+    gy = np.concatenate([g[:, 1] for g in geo])
+    gkind = np.concatenate([np.full(len(g), KIND_BORDER + q, np.int64) for q, g in enumerate(geo)])
+    can_prune = bool(prune) and bool((np.abs(ux.astype(np.float64) ** 2 + uy.astype(np.float64) ** 2 - 1.0) < 1e-6).all())
+    inf = np.float32(np.inf)
+
+    with np.errstate(over="ignore", invalid="ignore"):
+        for i in np.flatnonzero(scanned & live):
+            others = np.arange(n) != i
+            px = np.concatenate([x[others], gx])
+            py = np.concatenate([y[others], gy])
+            r2 = np.concatenate([np.full(n - 1, pr2, np.float32), np.full(len(gx), qr2, np.float32)])
+            kind = np.concatenate([np.full(n - 1, KIND_PEDESTRIAN, np.int64), gkind])
+            ax, ay = px - x[i], py - y[i]
+            keep = r2 > 0                                              # (radius 0: q = -c^2 <= 0, never a candidate)
+            if can_prune:
+                d = np.sqrt(ax.astype(np.float64) ** 2 + ay.astype(np.float64) ** 2)
+                far = d > 1.001 * (np.float64(Rmax) + 2.0 * np.sqrt(r2.astype(np.float64))) + 1e-30
+                keep &= ~far
+            ax, ay, r2, kind = ax[keep], ay[keep], r2[keep], kind[keep]
+            if frame == 1:
+                rx = _fma32(hx[i], ux, -(hy[i] * uy))
+                ry = _fma32(hy[i], ux, hx[i] * uy)
+            else:
+                rx, ry = ux, uy
+            A, Bv = ax[None, :], ay[None, :]
+            U, V = rx[:, None], ry[:, None]
+            t = _fma32(A, U, Bv * V)
+            c = _fma32(A, V, -(Bv * U))
+            q = _fma32(-c, c, r2[None, :])
+            w = np.sqrt(q)
+            cand = (q > 0) & ((t + w) > 0)
+            s = t - w
+            yield i, np.where(cand, np.where(s > 0, s, np.float32(0.0)), inf).astype(np.float32), kind
+
+
+def scan_scene(scene, angles, max_range, ped_radius, point_radius, frame=0, mask=None, state=None, vehicles=None, waypoints=None,
+               directions=None, prune=True):
+    """The scan record of one scene, (N, 2R) float32, as ``SfmBatch.scans()`` returns it: floats 0 .. R-1 the ranges, R .. 2R-1
+    the kinds (0 nothing, 1 pedestrian, 2 border, 3 static obstacle, 4 vehicle).
+
+    ``scene``: a scene dict as ``SfmBatch.upload`` takes it (or a ``scenarios.Scenario``).  ``angles``: the R ray angles (see
+    ``ray_directions``; ``default_angles(R)`` is ``set_scan``'s default), or None with ``directions`` = (dir_x, dir_y) used as
+    given.  ``max_range``, ``ped_radius``, ``point_radius``: metres, this scene's.  ``frame``: 0 world axes, 1 heading frame.
+    ``mask``: bool (N,), the rows that are scanned (None: all).  What has changed on the device since the upload is fed in as for
+    ``observe.observe_scene``: ``state`` = (loc, vel), ``vehicles`` = the scene's list of (center, ring), ``waypoints`` (N,2|3).
+
+    Chunked per row: the largest block is R x (N - 1 + points).  ``prune``: candidates further than 1.001 (Rmax + 2 r) from the row
+    are left out before the ray arithmetic when every direction has | |u|^2 - 1 | < 1e-6.  That cannot change the record: a
+    candidate needs q > 0, so |c| <= r up to rounding and t >= |a||u| - r up to rounding (2^-22 |a| each), hence its range
+    t - w >= |a| (1 - 1.3e-6) - 2.0000002 r > Rmax, and a range >= Rmax is never stored (if it is the minimum the ray is a miss;
+    if it is not, it is not the minimum).  ``prune=False`` evaluates everything."""
+    walk = _walk(scene, angles, max_range, ped_radius, point_radius, frame, mask, state, vehicles, waypoints, directions, prune)
+    n, R, Rmax = next(walk)
+    rec = np.zeros((n, 2 * R), np.float32)
+    for i, val, kind in walk:
+        if val.shape[1] == 0:
+            rec[i, :R] = Rmax
+            continue
+        idx = np.argmin(val, axis=1)                                   # the first minimum in the fixed order
+        best = val[np.arange(R), idx]
+        hit = best < Rmax
+        rec[i, :R] = np.where(hit, best, Rmax)
+        rec[i, R:] = np.where(hit, kind[idx].astype(np.float32), np.float32(0.0))
+    return rec
+
+
+def range_census(scene, angles, max_range, ped_radius, point_radius, frame=0, mask=None, state=None, vehicles=None, waypoints=None,
+                 directions=None, band=0.01):
+    """How hard a scene tests the range limit: an int64 array (5, 2), per kind the number of (row, ray, candidate) triples whose
+    range lies in [(1 - band) Rmax, Rmax) and in [Rmax, (1 + band) Rmax] -- just inside and just outside the limit.  Arguments as
+    for ``scan_scene``; nothing is pruned."""
+    walk = _walk(scene, angles, max_range, ped_radius, point_radius, frame, mask, state, vehicles, waypoints, directions, False)
+    _, _, Rmax = next(walk)
+    lo, hi = np.float64(Rmax) * (1.0 - band), np.float64(Rmax) * (1.0 + band)
+    out = np.zeros((5, 2), np.int64)
+    for _, val, kind in walk:
+        v = val.astype(np.float64)
+        for k in range(1, 5):
+            vk = v[:, kind == k]
+            out[k, 0] += int(((vk >= lo) & (vk < Rmax)).sum())
+            out[k, 1] += int(((vk >= Rmax) & (vk <= hi)).sum())
+    return out

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SFM_ABI_VERSION 16  /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles; 9: + sfm_batch_set_mode_fsm, sfm_batch_download_modes; 10: + sfm_batch_tick_forces, sfm_batch_run_recorded_forces; 11: + sfm_batch_set_spawn_schedule, sfm_batch_download_spawns, SFM_MODE_UNBORN; 12: + sfm_batch_set_vehicle_tracks, sfm_batch_download_vehicle_tracks; 13: + sfm_batch_snapshot, sfm_batch_restart; 14: + sfm_batch_set_steering, sfm_batch_set_commands, sfm_batch_download_steering, sfm_batch_device_ptr; 15: + sfm_batch_set_observation, sfm_batch_observe, sfm_batch_download_observations, sfm_batch_observation_ptr; 16: + sfm_batch_set_episodes, sfm_batch_end_step, sfm_batch_download_episodes, sfm_batch_restart_device, SFM_BATCH_PTR_EPISODES / _DONE (additions only) */
+#define SFM_ABI_VERSION 17  /* 2: + sfm_tick_begin / sfm_tick_end, sfm_set_partition, sfm_get_pair_work; 3: + sfm_set_timing; 4: + sfm_step_packed, sfm_set_dynamic_obstacles_packed; 5: + sfm_step_records; 6: + sfm_batch_*; 7: + sfm_batch_set_waypoint_streams, sfm_batch_download_waypoints, sfm_batch_run_recorded; 8: + sfm_batch_set_dynamic_boxes, sfm_batch_download_dynamic_obstacles; 9: + sfm_batch_set_mode_fsm, sfm_batch_download_modes; 10: + sfm_batch_tick_forces, sfm_batch_run_recorded_forces; 11: + sfm_batch_set_spawn_schedule, sfm_batch_download_spawns, SFM_MODE_UNBORN; 12: + sfm_batch_set_vehicle_tracks, sfm_batch_download_vehicle_tracks; 13: + sfm_batch_snapshot, sfm_batch_restart; 14: + sfm_batch_set_steering, sfm_batch_set_commands, sfm_batch_download_steering, sfm_batch_device_ptr; 15: + sfm_batch_set_observation, sfm_batch_observe, sfm_batch_download_observations, sfm_batch_observation_ptr; 16: + sfm_batch_set_episodes, sfm_batch_end_step, sfm_batch_download_episodes, sfm_batch_restart_device, SFM_BATCH_PTR_EPISODES / _DONE; 17: + sfm_batch_set_scan, sfm_batch_scan, sfm_batch_download_scan, SFM_BATCH_PTR_SCAN (additions only) */
 
 typedef struct SfmHandle SfmHandle;
 
@@ -508,12 +508,15 @@ int sfm_batch_download_steering(SfmBatch* b, uint8_t* kind, float* ux, float* uy
  * unknown `which`, before sfm_batch_upload_state, and for the command buffer while steering is off; NULL without rows.
  * ABI 16: SFM_BATCH_PTR_EPISODES, the episode record ([B][SFM_BATCH_EPISODE_WIDTH] float), and SFM_BATCH_PTR_DONE, the mask ([B]
  * uint8_t, 0 / 1), as the last sfm_batch_end_step left them; valid until the next sfm_batch_set_episodes or sfm_batch_upload_state;
- * NULL (and the message) while episodes are off. */
+ * NULL (and the message) while episodes are off.
+ * ABI 17: SFM_BATCH_PTR_SCAN, the scan record ([N_total][2 R] float), as the last sfm_batch_scan left it; valid until the next
+ * sfm_batch_set_scan or sfm_batch_upload_state; NULL (and the message) while scans are off; NULL without rows. */
 #define SFM_BATCH_PTR_COMMANDS 0
 #define SFM_BATCH_PTR_STATE 1
 #define SFM_BATCH_PTR_ZSTATE 2
 #define SFM_BATCH_PTR_EPISODES 3
 #define SFM_BATCH_PTR_DONE 4
+#define SFM_BATCH_PTR_SCAN 5
 void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes);
 /* Per-pedestrian observations computed on the device (ABI 15): what a policy or a reward reads per agent -- who is near it and how
  * they move relative to it, where the kerb, the nearest obstacle and the nearest vehicle are, where its goal is -- by ONE launch of
@@ -656,6 +659,67 @@ int sfm_batch_download_episodes(SfmBatch* b, float* record, uint8_t* done);
  * sfm_batch_download_vehicle_tracks or sfm_batch_snapshot, which synchronise.  Refused with nothing launched: no snapshot
  * (SFM_ERR_STATE), d_mask NULL (SFM_ERR_INVALID). */
 int sfm_batch_restart_device(SfmBatch* b, const uint8_t* d_mask);
+/* Range scans on the device (ABI 17): the sensor most crowd-navigation policies are trained on.  R rays around a row, each giving
+ * the distance to the first thing it meets and what that was, by ONE launch of sfm_batch_scan_kernel (a workgroup per scene)
+ * straight from the buffers the tick reads, into a device buffer the caller reads with no copy.  The record is defined bit for bit
+ * in BOTH frames: every operation below is a single correctly rounded fp32 operation or an fmaf, and the kernel does no
+ * trigonometry.
+ *
+ * Settings (sfm_batch_set_scan).  R: rays per row, 1 .. SFM_BATCH_MAX_SCAN_RAYS, one value for the batch.  dir_x, dir_y [R]: the
+ * ray directions, fp32, finite; the kernel uses them as given and does not renormalise them (a caller forms cos and sin in double
+ * and rounds once).  max_range[b]: per scene, finite, 0 < Rmax <= SFM_BATCH_MAX_SENSE_RANGE, used as the fp32 value.
+ * ped_radius[b], point_radius[b]: per scene, finite, 0 <= r <= SFM_BATCH_MAX_SENSE_RANGE; the kernel uses r2 = float32(r * r),
+ * formed in double and rounded once, like R2.  Every pedestrian is a disc of ped_radius; every sampled point of a border, of a
+ * static-obstacle ring or of a vehicle ring is a disc of point_radius -- the model's own view of geometry: the forces see sampled
+ * points, not segments (the reference samples them 0.1 m apart).  A radius of 0 switches that kind off.  The radius in `own` is
+ * not used.  mask [N_total] uint8_t, or NULL for every row: which rows are scanned (nonzero); a masked-out row costs nothing and
+ * has an all-zero record -- an RL loop scans its agents, not the crowd.  frame: SFM_OBS_FRAME_WORLD (0) or SFM_OBS_FRAME_HEADING
+ * (1), one value for the batch.
+ *
+ * Record.  Row i owns 2 R floats, row-major [N_total][2 R], in concatenated scene order: floats 0 .. R-1 the ranges, floats
+ * R .. 2R-1 the kind hit as a float: SFM_SCAN_NONE 0, _PEDESTRIAN 1, _BORDER 2, _STATIC 3, _VEHICLE 4.  A row that is masked out
+ * is all zeros, and so is a row that is not live by sfm_batch_observe's test (|x| < NEAR_LIMIT and |y| < NEAR_LIMIT; a NaN
+ * position fails it).
+ *
+ * Rules, all exact, for row i at (x, y), ray direction (ux, uy) and a disc at (px, py) with squared radius r2:
+ *     ax = px - x;  ay = py - y
+ *     t  = fmaf(ax, ux, ay * uy)
+ *     c  = fmaf(ax, uy, -(ay * ux))
+ *     q  = fmaf(-c, c, r2)
+ *     candidate iff q > 0 and (t + w) > 0, with w = sqrt(q) correctly rounded
+ *     s  = t - w;  range = s > 0 ? s : 0.0f        (inside a disc: 0)
+ * The ray's value is the first minimum, under strict `<`, of range over the candidates in a fixed order: the scene's pedestrians
+ * j != i ascending, then its border points, its static-obstacle points, its vehicle points; within a kind polylines in order and
+ * points in order.  If the minimum is < Rmax it is stored with its kind; otherwise the ray stores Rmax and kind 0.  Ghosts, the
+ * ring of an absent tracked vehicle (at +inf) and NaN positions fail q > 0 by themselves (c * c overflows or is NaN): there is no
+ * test of their own.  Vehicles are read as the next tick would read them (the current half of the ping-pong), as in
+ * sfm_batch_observe.  Only {x, y, vx, vy} of the state is used: a 3-D batch gives the planar record.
+ * Frame 1 uses sfm_batch_observe's heading decision: v when fmaf(vx, vx, vy * vy) > 0, else the goal entry g = (wx - x, wy - y)
+ * when fmaf(gx, gx, gy * gy) > 0, else (1, 0); with l = sqrt(.) and hx = a / l, hy = b / l, each correctly rounded, the ray is
+ * u' = (fmaf(hx, ux, -(hy * uy)), fmaf(hy, ux, hx * uy)), and everything else is as in frame 0.
+ * The kernel writes only the scan buffer and uses no atomics; every order is a function of the scene alone: a scene's record is
+ * bitwise the same alone or anywhere in any batch.
+ *
+ * sfm_batch_set_scan allocates and zero-fills [N_total][2 R] and waits for the batch's stream; max_range = NULL switches scans
+ * off and frees the buffer.  Refused with nothing changed: before sfm_batch_upload_state (SFM_ERR_STATE); R outside 1 .. 64; frame
+ * outside {0, 1}; NULL dir_x, dir_y, ped_radius or point_radius; a direction that is not finite; a max_range that is NaN,
+ * infinite, <= 0 or > 1e6; a radius that is NaN, negative, infinite or > 1e6.  sfm_batch_upload_state drops the scans (the mask
+ * is per row), as it drops observations; every other call keeps them, and they keep the snapshot.  A snapshot neither holds nor
+ * restores them. */
+#define SFM_BATCH_MAX_SCAN_RAYS 64
+#define SFM_SCAN_NONE 0
+#define SFM_SCAN_PEDESTRIAN 1
+#define SFM_SCAN_BORDER 2
+#define SFM_SCAN_STATIC 3
+#define SFM_SCAN_VEHICLE 4
+int sfm_batch_set_scan(SfmBatch* b, int R, const float* dir_x, const float* dir_y, const float* max_range, const float* ped_radius,
+                       const float* point_radius, const uint8_t* mask, int frame);
+/* ONE launch on the batch's stream, ordered with the ticks, observations and restarts around it; the host does not wait.
+ * SFM_ERR_STATE while scans are off.  With no rows it launches nothing and succeeds. */
+int sfm_batch_scan(SfmBatch* b);
+/* Synchronises the batch's stream, then copies the buffer ([N_total][2 R] floats) as the last sfm_batch_scan left it; before the
+ * first scan that is zeros.  SFM_ERR_STATE while scans are off. */
+int sfm_batch_download_scan(SfmBatch* b, float* out);
 /* Current state of every scene (synchronises the batch's stream); NULL skips a column.  A planar batch leaves z alone and
  * writes vz = 0. */
 int sfm_batch_download_state(SfmBatch* b, float* x, float* y, float* z, float* vx, float* vy, float* vz);
