@@ -667,7 +667,9 @@ int sfm_batch_restart_device(SfmBatch* b, const uint8_t* d_mask);
  *
  * Settings (sfm_batch_set_scan).  R: rays per row, 1 .. SFM_BATCH_MAX_SCAN_RAYS, one value for the batch.  dir_x, dir_y [R]: the
  * ray directions, fp32, finite; the kernel uses them as given and does not renormalise them (a caller forms cos and sin in double
- * and rounds once).  max_range[b]: per scene, finite, 0 < Rmax <= SFM_BATCH_MAX_SENSE_RANGE, used as the fp32 value.
+ * and rounds once).  With unit directions the range is the distance along the ray to the first disc, to the rounding of the
+ * rules below; with directions that are not unit vectors the record is defined by those rules alone and carries no geometric
+ * meaning.  max_range[b]: per scene, finite, 0 < Rmax <= SFM_BATCH_MAX_SENSE_RANGE, used as the fp32 value.
  * ped_radius[b], point_radius[b]: per scene, finite, 0 <= r <= SFM_BATCH_MAX_SENSE_RANGE; the kernel uses r2 = float32(r * r),
  * formed in double and rounded once, like R2.  Every pedestrian is a disc of ped_radius; every sampled point of a border, of a
  * static-obstacle ring or of a vehicle ring is a disc of point_radius -- the model's own view of geometry: the forces see sampled
