@@ -103,6 +103,7 @@ import numpy as np
 
 from . import _lib
 from . import scan as _scan
+from ._args import FRAME_HEADING, FRAME_WORLD, MAX_METRES as MAX_SENSE_RANGE, check_frame, per_scene, per_scene_metres
 from ._lib import SfmLibraryError, f32, fptr, iptr, u8ptr
 
 MAX_RECORD_BYTES = 1 << 30       # SFM_BATCH_MAX_RECORD_BYTES: frames one run_recorded call may hold
@@ -296,20 +297,10 @@ def stream_arrays(B, seeds, world_sides, arrive_thresholds=2.0):
     """Per-scene waypoint stream arguments -> (seed uint32[B], world_side float32[B], arrive_threshold float32[B]).  Each argument is
     a scalar (broadcast to every scene) or B values.  Seeds are integers (taken mod 2^32, like SfmEngine.set_waypoint_stream); sides
     and thresholds must be finite and >= 0.  Pure NumPy; raises ValueError."""
-    def col(v, name):
-        a = np.asarray(v)
-        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] not in (1, B)):
-            raise ValueError(f"{name}: expected a scalar or {B} values, got shape {a.shape}")
-        return np.broadcast_to(a.reshape(-1), (B,))
-    s = col(seeds, "seeds")
-    if s.dtype.kind not in "iu":
-        raise ValueError(f"seeds must be integers, got {s.dtype}")
+    s = per_scene(seeds, "seeds", B, "iu", shape_first=True)
     out = [np.ascontiguousarray(s.astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)]
     for v, name in ((world_sides, "world_sides"), (arrive_thresholds, "arrive_thresholds")):
-        a = col(v, name)
-        if a.dtype.kind not in "iuf":
-            raise ValueError(f"{name} must be numbers, got {a.dtype}")
-        a = f32(a)
+        a = f32(per_scene(v, name, B, shape_first=True))
         if not (np.isfinite(a).all() and (a >= 0).all()):
             raise ValueError(f"{name} must be finite and >= 0")
         out.append(a)
@@ -514,13 +505,7 @@ def mode_scene_arrays(B, despawn_on_arrival=True, sim_time0=0.0, arrive_threshol
     """Per-scene mode arguments -> (despawn_on_arrival int32[B], sim_time0 float32[B], arrive_threshold float32[B]).  Each argument
     is a scalar (broadcast to every scene) or B values; clocks must be finite, thresholds finite and >= 0.  Pure NumPy; raises
     ValueError."""
-    def col(v, name):
-        a = np.asarray(v)
-        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] not in (1, B)):
-            raise ValueError(f"{name}: expected a scalar or {B} values, got shape {a.shape}")
-        if a.dtype.kind not in "biuf":
-            raise ValueError(f"{name} must be numbers, got {a.dtype}")
-        return np.broadcast_to(a.reshape(-1), (B,))
+    col = lambda v, name: per_scene(v, name, B, "biuf", shape_first=True)
     despawn = np.ascontiguousarray(col(despawn_on_arrival, "despawn_on_arrival").astype(bool), dtype=np.int32)
     t0 = f32(col(sim_time0, "sim_time0"))
     if not np.isfinite(t0).all():
@@ -617,8 +602,6 @@ def pack_steering(kinds, commands, scene_off):
 
 OBS_HEADER = 16                  # SFM_BATCH_OBS_HEADER: floats of a row's record in front of its neighbour slots
 MAX_OBS_NEIGHBOURS = 16          # SFM_BATCH_MAX_OBS_NEIGHBOURS
-MAX_SENSE_RANGE = 1.0e6          # SFM_BATCH_MAX_SENSE_RANGE, metres
-FRAME_WORLD, FRAME_HEADING = 0, 1
 
 
 def obs_width(k):
@@ -634,18 +617,17 @@ def observation_arrays(B, k, sense_range, frame=0):
     in float32.  Pure NumPy; raises ValueError on a k outside 1 .. 16, a frame other than 0 or 1, and a range the library would
     refuse."""
     obs_width(k)
-    if isinstance(frame, (bool, np.bool_)) or not isinstance(frame, (int, np.integer)) or int(frame) not in (FRAME_WORLD, FRAME_HEADING):
-        raise ValueError(f"frame must be 0 (world axes) or 1 (the row's heading frame), got {frame!r}")
-    a = np.asarray(sense_range)
-    if a.dtype.kind not in "iuf":
-        raise ValueError(f"sense_range must be numbers, got {a.dtype}")
-    if a.ndim > 1 or (a.ndim == 1 and a.shape[0] not in (1, int(B))):
-        raise ValueError(f"sense_range: expected a scalar or {int(B)} values, got shape {a.shape}")
-    with np.errstate(over="ignore"):
-        r = f32(np.broadcast_to(a.reshape(-1), (int(B),)))
-    if not (np.isfinite(r).all() and (r > 0).all() and (r <= np.float32(MAX_SENSE_RANGE)).all()):
-        raise ValueError(f"sense_range must be finite, > 0 and <= {MAX_SENSE_RANGE:g} metres")
-    return int(k), r, int(frame)
+    frame = check_frame(frame)
+    return int(k), per_scene_metres(sense_range, "sense_range", int(B), True), frame
+
+
+def _split_rows(scene_off, *cols):
+    """Arrays over the concatenated rows -> per scene, in scene order, its rows of each (views): a list of B arrays for one array,
+    of B tuples for several."""
+    so = scene_off
+    if len(cols) == 1:
+        return [cols[0][so[b]:so[b + 1]] for b in range(len(so) - 1)]
+    return [tuple(c[so[b]:so[b + 1]] for c in cols) for b in range(len(so) - 1)]
 
 
 def split_observations(buf, scene_off):
@@ -655,7 +637,7 @@ def split_observations(buf, scene_off):
     buf = np.asarray(buf)
     if buf.ndim != 2 or buf.shape[0] != int(so[-1]):
         raise ValueError(f"observations of shape {buf.shape} for {int(so[-1])} pedestrians")
-    return [buf[so[b]:so[b + 1]] for b in range(len(so) - 1)]
+    return _split_rows(so, buf)
 
 
 EPISODE_WIDTH = 8                # SFM_BATCH_EPISODE_WIDTH: floats of a scene's episode record
@@ -671,26 +653,12 @@ def episode_arrays(B, agent, goal_radius=0.0, ped_radius=0.0, veh_radius=0.0, ma
     radii in metres, finite, >= 0 and <= 1e6 in float32 (0: the test is off); ``max_steps`` integers >= 0 (0: no time limit).  Pure
     NumPy; raises ValueError on a shape that does not fit and on every value the library would refuse."""
     B = int(B)
-
-    def col(v, name, kinds):
-        a = np.asarray(v)
-        if a.dtype.kind not in kinds:
-            raise ValueError(f"{name} must be {'integers' if kinds == 'iu' else 'numbers'}, got {a.dtype}")
-        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] not in (1, B)):
-            raise ValueError(f"{name}: expected a scalar or {B} values, got shape {a.shape}")
-        return np.broadcast_to(a.reshape(-1), (B,))
-
-    ag = col(agent, "agent", "iu").astype(np.int64)
+    ag = per_scene(agent, "agent", B, "iu").astype(np.int64)
     if (ag < -1).any() or (ag >= MAX_SCENE_PEDESTRIANS).any():
         raise ValueError(f"agent must be -1 (no agent) or a row 0 .. N_b-1 of its scene, got {int(ag.min())} .. {int(ag.max())}")
-    radii = []
-    for v, name in ((goal_radius, "goal_radius"), (ped_radius, "ped_radius"), (veh_radius, "veh_radius")):
-        with np.errstate(over="ignore"):
-            r = f32(col(v, name, "iuf"))
-        if not (np.isfinite(r).all() and (r >= 0).all() and (r <= np.float32(MAX_SENSE_RANGE)).all()):
-            raise ValueError(f"{name} must be finite, >= 0 and <= {MAX_SENSE_RANGE:g} metres")
-        radii.append(r)
-    ms = col(max_steps, "max_steps", "iu").astype(np.int64)
+    radii = [per_scene_metres(v, name, B, False)
+             for v, name in ((goal_radius, "goal_radius"), (ped_radius, "ped_radius"), (veh_radius, "veh_radius"))]
+    ms = per_scene(max_steps, "max_steps", B, "iu").astype(np.int64)
     if (ms < 0).any() or (ms >= 2**31).any():
         raise ValueError("max_steps must be >= 0 (0: no time limit) and fit int32")
     return (np.ascontiguousarray(ag, dtype=np.int32), *radii, np.ascontiguousarray(ms, dtype=np.int32))
@@ -783,6 +751,18 @@ class SfmBatch:
         if rc != 0:
             msg = self._lib.sfm_batch_last_error(self._b)
             raise SfmLibraryError(f"{what} failed ({rc}): {msg.decode() if msg else '?'}")
+
+    def _need_upload(self, name):
+        if self.scene_off is None:
+            raise SfmLibraryError(f"SfmBatch.{name}: upload() has not been called")
+
+    def _alias(self, ptr, shape, device, typestr="<f4"):
+        """A device buffer as a torch tensor of ``shape`` that aliases it (no copy); ``ptr`` 0 (no rows): an empty float32 tensor."""
+        import torch
+        dev = f"cuda:{torch.cuda.current_device() if device is None else int(device)}"
+        if not ptr:
+            return torch.zeros((0,) + tuple(shape[1:]), dtype=torch.float32, device=dev)
+        return torch.as_tensor(_DeviceSpan(ptr, shape, typestr), device=dev)
 
     def _check_drops(self, rc, what):
         """``_check`` for the calls that drop the snapshot once they succeed (a refused call drops nothing)."""
@@ -948,8 +928,7 @@ class SfmBatch:
             self._check(L.sfm_batch_set_episodes(self._b, None, None, None, None, None), "sfm_batch_set_episodes")
             self.has_episodes = False
             return
-        if self.scene_off is None:
-            raise SfmLibraryError("SfmBatch.set_episodes: upload() has not been called")
+        self._need_upload("set_episodes")
         ag, rg, rp, rv, ms = episode_arrays(self.B, agent, goal_radius, ped_radius, veh_radius, max_steps)
         n = np.diff(self.scene_off)
         if (ag >= n).any():
@@ -971,21 +950,15 @@ class SfmBatch:
         self._check(self._lib.sfm_batch_download_episodes(self._b, fptr(rec), u8ptr(done)), "sfm_batch_download_episodes")
         return rec, done.astype(bool)
 
-    def _episode_span(self, which, shape, typestr, device):
-        import torch
-        ptr, _ = self.device_ptr(which)
-        dev = f"cuda:{torch.cuda.current_device() if device is None else int(device)}"
-        return torch.as_tensor(_DeviceSpan(ptr, shape, typestr), device=dev)
-
     def episode_tensor(self, device=None):
         """The episode record as a torch tensor (B, 8) float32 that aliases device memory (no copy): what a reward reads after
         ``end_step()``.  Put torch and the batch on one stream.  Take it again after ``upload`` or ``set_episodes``.  Raises
         SfmLibraryError while episodes are off."""
-        return self._episode_span(PTR_EPISODES, (self.B, EPISODE_WIDTH), "<f4", device)
+        return self._alias(self.device_ptr(PTR_EPISODES)[0], (self.B, EPISODE_WIDTH), device)
 
     def done_tensor(self, device=None):
         """The mask ``done`` as a torch tensor (B,) uint8 (0 / 1) that aliases device memory: what ``restart_device`` takes."""
-        return self._episode_span(PTR_DONE, (self.B,), "|u1", device)
+        return self._alias(self.device_ptr(PTR_DONE)[0], (self.B,), device, "|u1")
 
     def set_steering(self, kinds, commands=None):
         """Which rows the caller steers, and their first commands (sfm_batch_set_steering; see ``pack_steering``): kind 1 rows take
@@ -996,8 +969,7 @@ class SfmBatch:
         if kinds is None:
             self._check(L.sfm_batch_set_steering(self._b, None, None, None, None), "sfm_batch_set_steering")
             return
-        if self.scene_off is None:
-            raise SfmLibraryError("SfmBatch.set_steering: upload() has not been called")
+        self._need_upload("set_steering")
         kd, ux, uy, uz = pack_steering(kinds, commands, self.scene_off)
         if kd.shape[0] == 0:                                           # (no rows: still a call, so that steering is on)
             kd, ux, uy, uz = np.zeros(1, np.uint8), np.zeros(1, np.float32), np.zeros(1, np.float32), np.zeros(1, np.float32)
@@ -1007,8 +979,7 @@ class SfmBatch:
         """New commands for every row, kinds as ``set_steering`` set them (sfm_batch_set_commands): one host-to-device copy on the
         batch's stream, no wait.  ``commands`` as for ``pack_steering``; rows that are not steered may hold anything finite or
         not -- they are validated by the library against the kinds it knows."""
-        if self.scene_off is None:
-            raise SfmLibraryError("SfmBatch.set_commands: upload() has not been called")
+        self._need_upload("set_commands")
         so = self.scene_off
         c = np.zeros((int(so[-1]), 3)) if commands is None else _per_scene(commands, so, 3, "commands")
         with np.errstate(over="ignore", invalid="ignore"):
@@ -1026,16 +997,14 @@ class SfmBatch:
         u = [np.zeros(max(n, 1), np.float32) for _ in range(3)]
         self._check(self._lib.sfm_batch_download_steering(self._b, u8ptr(kd), *(fptr(a) for a in u)), "sfm_batch_download_steering")
         so = self.scene_off if self.scene_off is not None else np.zeros(self.B + 1, np.int32)
-        cmd = np.stack(u, axis=1)
-        return [(kd[so[b]:so[b + 1]], cmd[so[b]:so[b + 1]]) for b in range(self.B)]
+        return _split_rows(so, kd, np.stack(u, axis=1))
 
     def device_ptr(self, which):
         """(address, bytes) of a device buffer of the batch (sfm_batch_device_ptr): ``PTR_COMMANDS``, ``PTR_STATE``,
         ``PTR_ZSTATE`` ((0, 0) for a planar batch), ``PTR_EPISODES``, ``PTR_DONE`` or ``PTR_SCAN``.  Valid until the next ``upload``
         (the command buffer: or ``set_steering``; the episode buffers: or ``set_episodes``; the scan buffer: or ``set_scan``)."""
         nbytes = C.c_int64(0)
-        if self.scene_off is None:
-            raise SfmLibraryError("SfmBatch.device_ptr: upload() has not been called")
+        self._need_upload("device_ptr")
         ptr = self._lib.sfm_batch_device_ptr(self._b, int(which), C.byref(nbytes))
         if not ptr and which in (PTR_EPISODES, PTR_DONE):
             self._check(-1, "sfm_batch_device_ptr")                    # (episodes are off: the library's message)
@@ -1044,12 +1013,8 @@ class SfmBatch:
         return int(ptr or 0), int(nbytes.value)
 
     def _tensor(self, which, width, device):
-        import torch
         ptr, nbytes = self.device_ptr(which)
-        dev = f"cuda:{torch.cuda.current_device() if device is None else int(device)}"
-        if not ptr:
-            return torch.zeros((0, width), dtype=torch.float32, device=dev)
-        return torch.as_tensor(_DeviceSpan(ptr, (nbytes // (4 * width), width)), device=dev)
+        return self._alias(ptr, (nbytes // (4 * width), width), device)
 
     def command_tensor(self, device=None):
         """The command buffer as a torch tensor (N_total, 4) float32 {ux, uy, uz, kind} that aliases device memory (no copy): what a
@@ -1081,8 +1046,7 @@ class SfmBatch:
             self._check(L.sfm_batch_set_observation(self._b, 0, None, 0), "sfm_batch_set_observation")
             self.obs_k = None
             return
-        if self.scene_off is None:
-            raise SfmLibraryError("SfmBatch.set_observation: upload() has not been called")
+        self._need_upload("set_observation")
         if sense_range is None:
             raise ValueError("set_observation needs a sense_range (metres)")
         k, r, frame = observation_arrays(self.B, k, sense_range, frame)
@@ -1108,16 +1072,12 @@ class SfmBatch:
         policy reads after ``observe()``.  Put torch and the batch on one stream
         (``set_stream(torch.cuda.current_stream().cuda_stream)``) so that the launch and the reads are ordered.  Take it again
         after ``upload`` or ``set_observation``.  Raises SfmLibraryError while observations are off."""
-        import torch
         nbytes = C.c_int64(0)
         ptr = self._lib.sfm_batch_observation_ptr(self._b, C.byref(nbytes))
         if not ptr and (self.obs_k is None or self.scene_off is None or int(self.scene_off[-1]) > 0):
             self._check(-1, "sfm_batch_observation_ptr")
         w = obs_width(self.obs_k)
-        dev = f"cuda:{torch.cuda.current_device() if device is None else int(device)}"
-        if not ptr:                                                    # (without rows: no buffer)
-            return torch.zeros((0, w), dtype=torch.float32, device=dev)
-        return torch.as_tensor(_DeviceSpan(ptr, (int(nbytes.value) // (4 * w), w)), device=dev)
+        return self._alias(ptr, (int(nbytes.value) // (4 * w), w), device)
 
     def set_scan(self, max_range, ped_radius=None, point_radius=_scan.POINT_RADIUS, R=None, angles=None, mask=None, frame=0,
                  directions=None):
@@ -1135,8 +1095,7 @@ class SfmBatch:
             self._check(L.sfm_batch_set_scan(self._b, 0, None, None, None, None, None, None, 0), "sfm_batch_set_scan")
             self.scan_rays = None
             return
-        if self.scene_off is None:
-            raise SfmLibraryError("SfmBatch.set_scan: upload() has not been called")
+        self._need_upload("set_scan")
         if ped_radius is None:
             raise ValueError("set_scan needs a ped_radius (metres; 0: pedestrians are not seen)")
         if sum(v is not None for v in (R, angles, directions)) != 1:
@@ -1171,16 +1130,12 @@ class SfmBatch:
         """The scan buffer as a torch tensor (N_total, 2R) float32 that aliases device memory (no copy): what a policy reads after
         ``scan()``.  Put torch and the batch on one stream.  Take it again after ``upload`` or ``set_scan``.  Raises
         SfmLibraryError while scans are off."""
-        import torch
         nbytes = C.c_int64(0)
         ptr = self._lib.sfm_batch_device_ptr(self._b, PTR_SCAN, C.byref(nbytes))
         if not ptr and (self.scan_rays is None or self.scene_off is None or int(self.scene_off[-1]) > 0):
             self._check(-1, "sfm_batch_device_ptr")
         w = 2 * self.scan_rays
-        dev = f"cuda:{torch.cuda.current_device() if device is None else int(device)}"
-        if not ptr:                                                    # (without rows: no buffer)
-            return torch.zeros((0, w), dtype=torch.float32, device=dev)
-        return torch.as_tensor(_DeviceSpan(ptr, (int(nbytes.value) // (4 * w), w)), device=dev)
+        return self._alias(ptr, (int(nbytes.value) // (4 * w), w), device)
 
     def set_waypoint_streams(self, seeds, world_sides, arrive_thresholds=2.0):
         """Per-scene waypoint streams for ``redraw=True`` (see ``stream_arrays``; scalars broadcast to every scene).  They stay in
@@ -1203,8 +1158,7 @@ class SfmBatch:
         """``run`` that records every scene's state before tick 0, stride, 2*stride, ... on the device.  Returns (frames, ticks_idx,
         zframes): frames a list of B float32 arrays (F, N_b, 4) {x, y, vx, vy}; ticks_idx [0, stride, ...]; zframes a list of
         (F, N_b, 2) {z, vz} for a 3-D batch, None for a planar one."""
-        if self.scene_off is None:
-            raise SfmLibraryError("SfmBatch.run_recorded: upload() has not been called")
+        self._need_upload("run_recorded")
         n = int(self.scene_off[-1])
         F = n_frames(int(ticks), int(stride), None if max_frames is None else int(max_frames))
         frames = np.zeros((F, n, 4), np.float32)
@@ -1226,8 +1180,7 @@ class SfmBatch:
         """One tick exactly as ``tick`` that also returns its forces: a list of B dicts name -> (N_b, C) float32, C = 2 {fx, fy}
         for a planar batch, 3 for a 3-D one; ``forces`` a selection of FORCE_RECORD_NAMES (None: all six).  With
         ``integrate=False`` it is Force.get_force of every scene, with nothing moved."""
-        if self.scene_off is None:
-            raise SfmLibraryError("SfmBatch.tick_forces: upload() has not been called")
+        self._need_upload("tick_forces")
         names = _record_names(forces)
         buf = np.zeros((len(names), int(self.scene_off[-1]), self._force_cols()), np.float32)
         self._check(self._lib.sfm_batch_tick_forces(self._b, self._flags(integrate, redraw), force_mask(names), fptr(buf)),
@@ -1238,8 +1191,7 @@ class SfmBatch:
         """``run_recorded`` that also records, for every recorded tick f*stride, the forces that tick computed from frame f's
         state.  Returns (frames, ticks_idx, zframes, forces): the first three exactly as ``run_recorded``; forces a list of B dicts
         name -> (F, N_b, C) float32."""
-        if self.scene_off is None:
-            raise SfmLibraryError("SfmBatch.run_recorded_forces: upload() has not been called")
+        self._need_upload("run_recorded_forces")
         names = _record_names(forces)
         n = int(self.scene_off[-1])
         F = n_frames(int(ticks), int(stride), None if max_frames is None else int(max_frames))
@@ -1270,8 +1222,7 @@ class SfmBatch:
         if plans is None:
             self._check_drops(L.sfm_batch_set_mode_fsm(self._b, *([None] * 14)), "sfm_batch_set_mode_fsm")
             return
-        if self.scene_off is None:
-            raise SfmLibraryError("SfmBatch.set_modes: upload() has not been called")
+        self._need_upload("set_modes")
         pm = pack_modes(plans, self.scene_off, scenes)
         despawn, t0, thr = mode_scene_arrays(self.B, despawn_on_arrival, sim_time0, arrive_thresholds)
         W = int(pm["wp_offsets"][-1])
@@ -1291,8 +1242,7 @@ class SfmBatch:
         if schedules is None:
             self._check_drops(L.sfm_batch_set_spawn_schedule(self._b, None, None), "sfm_batch_set_spawn_schedule")
             return
-        if self.scene_off is None:
-            raise SfmLibraryError("SfmBatch.set_spawns: upload() has not been called")
+        self._need_upload("set_spawns")
         t, c = pack_spawns(schedules, self.scene_off)
         if t.shape[0] == 0:                                            # (no rows: still a call, so that the refusals are the library's)
             t, c = np.zeros(1, np.float32), np.zeros(1, np.uint8)
@@ -1306,7 +1256,7 @@ class SfmBatch:
         born, when = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.float32)
         self._check(self._lib.sfm_batch_download_spawns(self._b, u8ptr(born), fptr(when)), "sfm_batch_download_spawns")
         so = self.scene_off if self.scene_off is not None else np.zeros(self.B + 1, np.int32)
-        return [(born[so[b]:so[b + 1]].astype(bool), when[so[b]:so[b + 1]]) for b in range(self.B)]
+        return _split_rows(so, born.astype(bool), when)
 
     def _modes(self):
         n = int(self.scene_off[-1]) if self.scene_off is not None else 0
@@ -1319,9 +1269,7 @@ class SfmBatch:
     def modes(self):
         """Per scene (mode (N_b,) uint8 with 255 = despawned and 254 = not yet spawned, mode target speed (N_b,) float32, queue cursor (N_b,) int32), in
         scene order.  Raises SfmLibraryError while no modes are set."""
-        m, t, c, _ = self._modes()
-        so = self.scene_off
-        return [(m[so[b]:so[b + 1]], t[so[b]:so[b + 1]], c[so[b]:so[b + 1]]) for b in range(self.B)]
+        return _split_rows(self.scene_off, *self._modes()[:3])
 
     def clocks(self):
         """Each scene's mode clock (sim_time, float32 [B]): sim_time0 plus one step_length per tick since ``set_modes``."""
@@ -1329,21 +1277,17 @@ class SfmBatch:
 
     def waypoints(self):
         """Per scene (waypoint (N_b,2) float32, draw counter (N_b,) uint32), in scene order."""
-        if self.scene_off is None:
-            raise SfmLibraryError("SfmBatch.waypoints: upload() has not been called")
+        self._need_upload("waypoints")
         n = int(self.scene_off[-1])
         wx, wy = np.zeros(n, np.float32), np.zeros(n, np.float32)
         draws = np.zeros(n, np.uint32)
         self._check(self._lib.sfm_batch_download_waypoints(self._b, fptr(wx), fptr(wy), draws.ctypes.data),
                     "sfm_batch_download_waypoints")
-        wp = np.stack([wx, wy], axis=1)
-        so = self.scene_off
-        return [(wp[so[b]:so[b + 1]], draws[so[b]:so[b + 1]]) for b in range(self.B)]
+        return _split_rows(self.scene_off, np.stack([wx, wy], axis=1), draws)
 
     def state_arrays(self):
         """Concatenated state: (loc (N_total,3), vel (N_total,3)) float64."""
-        if self.scene_off is None:
-            raise SfmLibraryError("SfmBatch.state: upload() has not been called")
+        self._need_upload("state")
         n = int(self.scene_off[-1])
         a = {k: np.zeros(n, np.float32) for k in ("x", "y", "z", "vx", "vy", "vz")}
         if self.planar:
@@ -1356,6 +1300,4 @@ class SfmBatch:
 
     def state(self):
         """Per scene (loc (N_b,3), vel (N_b,3)) float64, in scene order."""
-        loc, vel = self.state_arrays()
-        so = self.scene_off
-        return [(loc[so[b]:so[b + 1]], vel[so[b]:so[b + 1]]) for b in range(self.B)]
+        return _split_rows(self.scene_off, *self.state_arrays())

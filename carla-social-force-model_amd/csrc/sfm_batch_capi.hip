@@ -1,186 +1,9 @@
 // sfm_batch_capi.hip -- host side of the batched scenes (ABI 6 and later): B independent crowds on one SfmBatch, ONE launch of
-// sfm_batch_tick_kernel per tick (sfm_batch.hip).
-#include "sfm_capi_common.h"
+// sfm_batch_tick_kernel per tick (sfm_batch.hip).  The batch's types are in sfm_batch_host.h; the read-only sensors (observations,
+// episode ends, range scans) and the device pointers are in sfm_batch_sense_capi.hip.
+#include "sfm_batch_host.h"
 
 using namespace sfm;
-
-// Each feature of a batch keeps its arrays in one struct whose default value is "off": dropping the feature is `x = {}`, after the
-// caller has synchronised the stream (a tick in flight may still read the arrays).
-
-struct BatchGeoDev {           // one kind of polylines over all scenes
-    DevBuf<int> off;           // [K+1]
-    DevBuf<float2> pts;        // [P]
-    DevBuf<float4> ctr;        // [K]
-    int K = 0;
-    int P = 0;
-};
-
-// device-side vehicles (sfm_batch_set_dynamic_boxes): geo[2].ctr / .pts hold the vehicles the next tick sees, ctr_alt / pts_alt
-// (the same sizes) the half an integrating tick writes; batch_launch swaps them after each such launch
-struct BatchBoxesDev {
-    bool on = false;
-    DevBuf<float2> local;      // [P] ring-local offsets
-    DevBuf<float2> rot;        // [M] {cos yaw, sin yaw}
-    DevBuf<float4> ctr_alt;
-    DevBuf<float2> pts_alt;
-    std::vector<int32_t> item_off_h;   // the vehicles' scene_item_off [B+1] on the host
-};
-
-// scripted vehicle tracks (sfm_batch_set_vehicle_tracks, ABI 12): read-only on the device; dropped with the boxes they refer to
-struct BatchTracksDev {
-    bool on = false;
-    DevBuf<int> off;           // [M+1]
-    DevBuf<int> first;         // [M]
-    DevBuf<float4> key;        // [T] {x, y, vx, vy}
-    DevBuf<float2> rot;        // [T] {cos yaw, sin yaw}
-    long long tick = 0;        // tau: integrating ticks since the tracks were set (a kernel argument, not device state)
-    std::vector<int32_t> off_h, first_h;   // host copies: sfm_batch_download_vehicle_tracks answers without the device
-    bool first_stale = false;  // a restart by device mask moved `first` of scenes the host cannot know: first_h is refreshed from
-                               // the device before it is read (refresh_track_first)
-};
-
-// the mode state machine (sfm_batch_set_mode_fsm, ABI 9): per row over the concatenated rows, per scene [B]
-struct BatchModesDev {
-    bool on = false;
-    DevBuf<uint8_t> mode;
-    DevBuf<float> target;
-    DevBuf<float4> speeds;     // {initial_speed, crossing_speed, safety_margin, next_mode_time}
-    DevBuf<int> off;           // [N_total+1]
-    DevBuf<float2> xy;
-    DevBuf<uint8_t> cross;
-    DevBuf<int> cursor;
-    DevBuf<BatchModeScene> scene;   // [B]
-    DevBuf<float> time;        // [B] the scenes' clocks
-};
-
-// the spawn schedule (sfm_batch_set_spawn_schedule, ABI 11): per row; dropped with the modes it refers to
-struct BatchSpawnDev {
-    bool on = false;           // (not "time is allocated": a schedule over no rows still holds one element)
-    DevBuf<float> time;
-    DevBuf<uint8_t> chain;
-    DevBuf<uint8_t> born;
-    DevBuf<float> birth;
-    DevBuf<float4> pk0;        // the spawn state: the rows as they were when the schedule was set
-    DevBuf<float2> zv0;
-};
-
-// the snapshot (sfm_batch_snapshot / sfm_batch_restart, ABI 13): a copy of every array a tick can change, grow-only (`on = false`
-// drops the snapshot and keeps the memory); what it holds follows boxes / modes / spawns / tracks, which cannot change while
-// it is valid (every call that changes them drops it)
-struct BatchSnapDev {
-    bool on = false;
-    DevBuf<float4> pk, own, ctr;
-    DevBuf<float2> zv, pts;
-    DevBuf<uint32_t> draws;
-    DevBuf<uint8_t> mode, born;
-    DevBuf<float> target, time, birth;
-    DevBuf<int> cursor, first;
-    long long tick = 0;                // the tracks' tick when the snapshot was taken
-    std::vector<int32_t> first_h;      // the tracks' first_h when the snapshot was taken
-};
-
-// sfm_batch_restart's list of chosen scenes: pinned on the host, copied to `list` on the stream; `done` is recorded behind the
-// launch that reads it, and the next masked restart waits for it before it refills the pinned list
-struct BatchRestartDev {
-    DevBuf<int> list;
-    PinnedBuf<int> list_h;
-    Event done;
-    bool pending = false;
-};
-
-// steering (sfm_batch_set_steering, ABI 14): the command of every row {ux, uy, uz, kind}, an input the ticks only read.  cmd_h
-// is its pinned host copy (the kinds of the last sfm_batch_set_steering, the velocities of the last call that sent any):
-// sfm_batch_set_commands refills it and sends it with one copy on the stream; SfmBatch::c_done is recorded behind that copy, and
-// the next call waits for it before it refills
-struct BatchSteerDev {
-    bool on = false;           // (not "cmd is allocated": a batch without rows can be steered and has no buffers)
-    DevBuf<float4> cmd;        // [N_total] on the device
-    PinnedBuf<float4> cmd_h;
-    bool pending = false;
-};
-
-// observations (sfm_batch_set_observation, ABI 15): the settings and the buffer sfm_batch_observe fills; nothing a tick reads or writes
-struct BatchObsDev {
-    bool on = false;           // (not "buf is allocated": a batch without rows can be observed and has no buffer)
-    int k = 0;
-    int frame = 0;
-    DevBuf<float> range2;      // [B] sense_range^2
-    DevBuf<float> buf;         // [N_total][16 + 4 k]
-};
-
-// episodes (sfm_batch_set_episodes, ABI 16): the settings, the per-scene episode state, and the record and mask sfm_batch_end_step
-// fills; nothing a tick reads or writes
-struct BatchEpisodeDev {
-    bool on = false;
-    DevBuf<BatchEpisodeScene> set;     // [B]
-    DevBuf<int> age;                   // [B]
-    DevBuf<float> prev;                // [B] prev_goal_d2
-    DevBuf<float> record;              // [B][8]
-    DevBuf<uint8_t> done;              // [B]
-};
-
-// range scans (sfm_batch_set_scan, ABI 17): the settings and the buffer sfm_batch_scan fills; nothing a tick reads or writes
-struct BatchScanDev {
-    bool on = false;           // (not "buf is allocated": a batch without rows can be scanned and has no buffer)
-    int R = 0;
-    int frame = 0;
-    DevBuf<BatchScanScene> set;    // [B]
-    DevBuf<float2> dir;        // [R]
-    DevBuf<uint8_t> mask;      // [N_total]; not allocated: every row is scanned
-    DevBuf<float> buf;         // [N_total][2 R]
-};
-
-struct BatchRecordDev {        // grow-only device buffers of the recording calls
-    DevBuf<float4> frames;     // sfm_batch_run_recorded
-    DevBuf<float2> zframes;
-    DevBuf<float> forces;      // sfm_batch_tick_forces / sfm_batch_run_recorded_forces
-};
-
-struct SfmBatch {
-    int device = 0;
-    int B = 0;
-    hipStream_t stream = nullptr;
-    DevBuf<BatchParams> d_prm;         // [B]
-    DevBuf<int> d_scene_off;           // [B+1]
-    int n_total = 0;
-    bool z3 = false;
-    bool have_state = false;
-    DevBuf<float4> pk;                 // {x, y, vx, vy}; the five state arrays grow together
-    DevBuf<float2> zv;                 // {z, vz}
-    DevBuf<float4> own;                // {wx, wy, target_speed, radius}
-    DevBuf<uint8_t> crossing;
-    DevBuf<uint32_t> draws;            // waypoint draw counters (zeroed by every upload)
-    bool any_rad = false;
-    DevBuf<int> geo_item_off[3];       // [B+1] per kind, zero-filled while the kind has no polylines; they outlive the polylines
-    BatchGeoDev geo[3];                // borders, static, dynamic obstacles
-    DevBuf<BatchStream> d_streams;     // [B] once sfm_batch_set_waypoint_streams has been called
-    BatchRecordDev rec;
-    BatchBoxesDev boxes;
-    BatchTracksDev tracks;
-    BatchModesDev modes;
-    BatchSpawnDev spawns;
-    bool spawn_used = false;           // a schedule was set since the last sfm_batch_set_mode_fsm: a second one is refused
-    BatchSnapDev snap;
-    BatchRestartDev restart;
-    BatchSteerDev steer;
-    BatchObsDev obs;
-    BatchEpisodeDev ep;
-    BatchScanDev scan;
-    Event c_done;                     // created by the first sfm_batch_set_steering with rows; outlives every drop of the steering
-    std::string err;
-};
-
-static int bfail(SfmBatch* b, int code, const std::string& msg) {
-    if (b) b->err = msg; else g_create_error = msg;
-    return code;
-}
-
-static int bbind(SfmBatch* b) {
-    if (!b) return SFM_ERR_INVALID;
-    hipError_t e = hipSetDevice(b->device);
-    if (e != hipSuccess) { b->err = std::string("hipSetDevice: ") + hipGetErrorString(e); return SFM_ERR_HIP; }
-    return SFM_OK;
-}
 
 // one scene's parameters, folded as fill_args folds a handle's
 static BatchParams batch_params(const SfmParams& p) {
@@ -324,7 +147,7 @@ static int batch_launch(SfmBatch* b, uint32_t flags, float4* frame = nullptr, fl
     a.zv = b->z3 ? b->zv : nullptr;
     a.own = b->own;
     a.crossing = b->crossing;
-    for (int k = 0; k < 3; ++k) a.geo[k] = BatchGeo{b->geo_item_off[k], b->geo[k].off, b->geo[k].pts, b->geo[k].ctr};
+    for (int k = 0; k < 3; ++k) a.geo[k] = batch_geo(b, k);
     a.flags = flags;
     a.streams = b->d_streams;
     a.draws = b->draws;
@@ -417,29 +240,27 @@ static BatchRestart restart_args(SfmBatch* b, long long shift) {
     return r;
 }
 
-// A tracked vehicle's first tick moved by `shift` must fit int32: scene k's vehicles (mask null or mask[k]), else SFM_ERR_INVALID
-static int check_restart_shift(SfmBatch* b, const uint8_t* mask, long long shift) {
+int sfm::batch_restart_checks(SfmBatch* b, const uint8_t* mask, const std::string& bad_choice, long long* shift) {
+    if (!b->snap.on) return bfail(b, SFM_ERR_STATE, NO_SNAPSHOT);
+    if (!bad_choice.empty()) return bfail(b, SFM_ERR_INVALID, bad_choice);
+    // track time per scene: the chosen scenes' tracked vehicles are found by tau at the keyframe the snapshot had them at
+    *shift = b->tracks.on ? b->tracks.tick - b->snap.tick : 0;
     if (!b->tracks.on) return SFM_OK;
     for (int k = 0; k < b->B; ++k) {
         if (mask && !mask[k]) continue;
         for (int v = b->boxes.item_off_h[k]; v < b->boxes.item_off_h[k + 1]; ++v) {
-            const long long first = (long long)b->snap.first_h[v] + shift;
+            const long long first = (long long)b->snap.first_h[v] + *shift;
             if (b->tracks.off_h[v + 1] > b->tracks.off_h[v] && (first < INT32_MIN || first > INT32_MAX))
                 return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(k) + ", vehicle " + std::to_string(v) + ": its first tick moved by the " +
-                                                 std::to_string(shift) + " ticks since the snapshot does not fit int32: set the tracks "
+                                                 std::to_string(*shift) + " ticks since the snapshot does not fit int32: set the tracks "
                                                  "again (sfm_batch_set_vehicle_tracks restarts the tick counter)");
         }
     }
     return SFM_OK;
 }
 
-static const char* const NO_SNAPSHOT = "the batch has no snapshot: call sfm_batch_snapshot first (sfm_batch_upload_state and the calls "
-                                       "that set vehicles, modes, a spawn schedule or tracks drop it)";
-static const char* const SCANS_OFF = "scans are off: call sfm_batch_set_scan first (sfm_batch_upload_state drops them)";
-static const char* const EPISODES_OFF ="episodes are off: call sfm_batch_set_episodes first (sfm_batch_upload_state drops them)";
-
 // sfm_batch_restart_device after its checks: ONE launch of B workgroups, the choice read on the device
-static int batch_restart_device(SfmBatch* b, const uint8_t* d_mask, long long shift) {
+int sfm::batch_restart_device(SfmBatch* b, const uint8_t* d_mask, long long shift) {
     BatchRestart r = restart_args(b, shift);
     r.mask = d_mask;
     HIP_TRY(b, launch_batch_restart(r, b->B, b->stream));
@@ -463,7 +284,7 @@ static int batch_run_recorded(SfmBatch* b, int ticks, uint32_t flags, int stride
     }
     rc = check_batch_flags(b, flags, "recorded run");
     if (rc) return rc;
-    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, NO_STATE);
     if (zframes && !b->z3) return bfail(b, SFM_ERR_INVALID, "zframes on a planar batch (it has no z / vz to record)");
     const int F = (int)std::min<long long>(max_frames, ((long long)ticks + stride - 1) / stride);
     if (F > 0 && !frames) return bfail(b, SFM_ERR_INVALID, "frames is NULL");
@@ -792,7 +613,7 @@ int sfm_batch_tick(SfmBatch* b, uint32_t flags) {
     if (rc) return rc;
     rc = check_batch_flags(b, flags, "tick");
     if (rc) return rc;
-    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, NO_STATE);
     return batch_launch(b, flags);
 }
 
@@ -806,7 +627,7 @@ int sfm_batch_tick_forces(SfmBatch* b, uint32_t flags, uint32_t force_mask, floa
     if (!forces) return bfail(b, SFM_ERR_INVALID, "forces is NULL");
     rc = check_batch_flags(b, flags, "tick");
     if (rc) return rc;
-    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, NO_STATE);
     const size_t vals = (size_t)K * (size_t)b->n_total * (b->z3 ? 3 : 2);
     if (vals > 0) {
         HIP_TRY(b, hipStreamSynchronize(b->stream));             // a tick in flight may still write the old buffer
@@ -825,7 +646,7 @@ int sfm_batch_run(SfmBatch* b, int ticks, uint32_t flags) {
     if (ticks < 0) return bfail(b, SFM_ERR_INVALID, "ticks < 0");
     rc = check_batch_flags(b, flags, "run");
     if (rc) return rc;
-    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, NO_STATE);
     for (int t = 0; t < ticks; ++t) {
         rc = batch_launch(b, flags | SFM_TICK_INTEGRATE);
         if (rc) return rc;
@@ -836,7 +657,7 @@ int sfm_batch_run(SfmBatch* b, int ticks, uint32_t flags) {
 int sfm_batch_download_state(SfmBatch* b, float* x, float* y, float* z, float* vx, float* vy, float* vz) {
     int rc = bbind(b);
     if (rc) return rc;
-    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, NO_STATE);
     HIP_TRY(b, hipStreamSynchronize(b->stream));
     const size_t n = (size_t)b->n_total;
     if (n == 0) return SFM_OK;
@@ -888,7 +709,7 @@ int sfm_batch_set_waypoint_streams(SfmBatch* b, const uint32_t* seed, const floa
 int sfm_batch_download_waypoints(SfmBatch* b, float* wx, float* wy, uint32_t* draws) {
     int rc = bbind(b);
     if (rc) return rc;
-    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, NO_STATE);
     HIP_TRY(b, hipStreamSynchronize(b->stream));
     const size_t n = (size_t)b->n_total;
     if (n == 0) return SFM_OK;
@@ -918,7 +739,7 @@ int sfm_batch_set_mode_fsm(SfmBatch* b, const uint8_t* mode, const float* target
         b->snap.on = false;
         return SFM_OK;
     }
-    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, NO_STATE);
     if (!target_speed || !initial_speed || !crossing_speed || !safety_margin || !next_mode_time || !wp_offsets || !despawn_on_arrival ||
         !sim_time0 || !arrive_threshold)
         return bfail(b, SFM_ERR_INVALID, "a required mode array is NULL");
@@ -1013,7 +834,7 @@ int sfm_batch_set_spawn_schedule(SfmBatch* b, const float* spawn_time, const uin
         b->snap.on = false;
         return SFM_OK;
     }
-    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, NO_STATE);
     if (!b->modes.on)
         return bfail(b, SFM_ERR_STATE, "a spawn schedule needs modes: call sfm_batch_set_mode_fsm first (a newborn starts from its initial mode)");
     if (b->spawn_used)
@@ -1084,7 +905,7 @@ int sfm_batch_download_spawns(SfmBatch* b, uint8_t* born, float* birth_time) {
 int sfm_batch_snapshot(SfmBatch* b) {
     int rc = bbind(b);
     if (rc) return rc;
-    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, NO_STATE);
     b->snap.on = false;                                             // (a failure below leaves the batch without a snapshot)
     const size_t n = (size_t)b->n_total, B = (size_t)b->B;
     if ((rc = snap_copy(b, b->snap.pk, b->pk, n))) return rc;
@@ -1121,19 +942,18 @@ int sfm_batch_snapshot(SfmBatch* b) {
 int sfm_batch_restart(SfmBatch* b, const uint8_t* mask) {
     int rc = bbind(b);
     if (rc) return rc;
-    if (!b->snap.on) return bfail(b, SFM_ERR_STATE, NO_SNAPSHOT);
     const int B = b->B;
     int chosen = B;
+    std::string bad;
     if (mask) {
         chosen = 0;
-        for (int k = 0; k < B; ++k) {
-            if (mask[k] > 1) return bfail(b, SFM_ERR_INVALID, "mask must hold 0 or 1 (scene " + std::to_string(k) + ")");
+        for (int k = 0; k < B && bad.empty(); ++k) {
+            if (mask[k] > 1) bad = "mask must hold 0 or 1 (scene " + std::to_string(k) + ")";
             chosen += mask[k];
         }
     }
-    // track time per scene: the chosen scenes' tracked vehicles are found by tau at the keyframe the snapshot had them at
-    const long long shift = b->tracks.on ? b->tracks.tick - b->snap.tick : 0;
-    if ((rc = check_restart_shift(b, mask, shift))) return rc;
+    long long shift = 0;
+    if ((rc = batch_restart_checks(b, mask, bad, &shift))) return rc;
     if (chosen == 0) return SFM_OK;
     if (mask) {
         if (!b->restart.done) {                                  // (created last: a first call that failed half-way starts over)
@@ -1169,10 +989,8 @@ int sfm_batch_restart(SfmBatch* b, const uint8_t* mask) {
 int sfm_batch_restart_device(SfmBatch* b, const uint8_t* d_mask) {
     int rc = bbind(b);
     if (rc) return rc;
-    if (!b->snap.on) return bfail(b, SFM_ERR_STATE, NO_SNAPSHOT);
-    if (!d_mask) return bfail(b, SFM_ERR_INVALID, "d_mask is NULL (device memory, one byte per scene)");
-    const long long shift = b->tracks.on ? b->tracks.tick - b->snap.tick : 0;
-    if ((rc = check_restart_shift(b, nullptr, shift))) return rc;   // every scene: the host cannot know who is chosen
+    long long shift = 0;                                         // (every scene: the host cannot know who is chosen)
+    if ((rc = batch_restart_checks(b, nullptr, d_mask ? "" : "d_mask is NULL (device memory, one byte per scene)", &shift))) return rc;
     return batch_restart_device(b, d_mask, shift);
 }
 
@@ -1190,7 +1008,7 @@ int sfm_batch_run_recorded_forces(SfmBatch* b, int ticks, uint32_t flags, int st
 int sfm_batch_set_steering(SfmBatch* b, const uint8_t* kind, const float* ux, const float* uy, const float* uz) {
     int rc = bbind(b);
     if (rc) return rc;
-    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, NO_STATE);
     const size_t n = (size_t)b->n_total;
     if (kind) {
         for (size_t i = 0; i < n; ++i)
@@ -1217,7 +1035,7 @@ int sfm_batch_set_steering(SfmBatch* b, const uint8_t* kind, const float* ux, co
 int sfm_batch_set_commands(SfmBatch* b, const float* ux, const float* uy, const float* uz) {
     int rc = bbind(b);
     if (rc) return rc;
-    if (!b->steer.on) return bfail(b, SFM_ERR_STATE, "steering is off: call sfm_batch_set_steering first (sfm_batch_upload_state drops it)");
+    if (!b->steer.on) return bfail(b, SFM_ERR_STATE, STEERING_OFF);
     rc = check_batch_commands(b, b->steer.cmd_h, nullptr, ux, uy, uz);
     if (rc) return rc;
     const size_t n = (size_t)b->n_total;
@@ -1236,7 +1054,7 @@ int sfm_batch_set_commands(SfmBatch* b, const float* ux, const float* uy, const 
 int sfm_batch_download_steering(SfmBatch* b, uint8_t* kind, float* ux, float* uy, float* uz) {
     int rc = bbind(b);
     if (rc) return rc;
-    if (!b->steer.on) return bfail(b, SFM_ERR_STATE, "steering is off: call sfm_batch_set_steering first (sfm_batch_upload_state drops it)");
+    if (!b->steer.on) return bfail(b, SFM_ERR_STATE, STEERING_OFF);
     HIP_TRY(b, hipStreamSynchronize(b->stream));
     const size_t n = (size_t)b->n_total;
     if (n == 0) return SFM_OK;
@@ -1248,296 +1066,6 @@ int sfm_batch_download_steering(SfmBatch* b, uint8_t* kind, float* ux, float* uy
         if (uy) uy[i] = c[i].y;
         if (uz) uz[i] = c[i].z;
     }
-    return SFM_OK;
-}
-
-void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes) {
-    if (bytes) *bytes = 0;
-    if (!b) return nullptr;
-    if (which < SFM_BATCH_PTR_COMMANDS || which > SFM_BATCH_PTR_SCAN) { bfail(b, SFM_ERR_INVALID, "which must be SFM_BATCH_PTR_COMMANDS, _STATE, _ZSTATE, _EPISODES, _DONE or _SCAN"); return nullptr; }
-    if (which == SFM_BATCH_PTR_SCAN) {
-        if (!b->scan.on) { bfail(b, SFM_ERR_STATE, std::string(SCANS_OFF) + ", so which = SFM_BATCH_PTR_SCAN has no buffer"); return nullptr; }
-        if (b->n_total == 0) return nullptr;
-        if (bytes) *bytes = (int64_t)(sizeof(float) * (size_t)b->n_total * (size_t)(2 * b->scan.R));
-        return b->scan.buf;
-    }
-    if (which == SFM_BATCH_PTR_EPISODES || which == SFM_BATCH_PTR_DONE) {
-        if (!b->ep.on) { bfail(b, SFM_ERR_STATE, std::string(EPISODES_OFF) + ", so which = SFM_BATCH_PTR_EPISODES / _DONE has no buffer"); return nullptr; }
-        const bool rec = which == SFM_BATCH_PTR_EPISODES;
-        if (bytes) *bytes = (int64_t)((rec ? 8 * sizeof(float) : sizeof(uint8_t)) * (size_t)b->B);
-        return rec ? (void*)b->ep.record.get() : (void*)b->ep.done.get();
-    }
-    if (!b->have_state) { bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called"); return nullptr; }
-    const size_t n = (size_t)b->n_total;
-    if (which == SFM_BATCH_PTR_COMMANDS) {
-        if (!b->steer.on) { bfail(b, SFM_ERR_STATE, "steering is off: call sfm_batch_set_steering first (sfm_batch_upload_state drops it)"); return nullptr; }
-        if (bytes) *bytes = (int64_t)(sizeof(float4) * n);
-        return b->steer.cmd;
-    }
-    if (which == SFM_BATCH_PTR_ZSTATE) {
-        if (!b->z3 || n == 0) return nullptr;                    // a planar batch has no {z, vz}
-        if (bytes) *bytes = (int64_t)(sizeof(float2) * n);
-        return b->zv;
-    }
-    if (n == 0) return nullptr;
-    if (bytes) *bytes = (int64_t)(sizeof(float4) * n);
-    return b->pk;
-}
-
-// Observations (ABI 15).  Everything is checked before anything is allocated or freed.
-int sfm_batch_set_observation(SfmBatch* b, int k, const float* sense_range, int frame) {
-    int rc = bbind(b);
-    if (rc) return rc;
-    if (!sense_range) {
-        HIP_TRY(b, hipStreamSynchronize(b->stream));             // an observe in flight may still write the buffer
-        b->obs = {};
-        return SFM_OK;
-    }
-    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
-    if (k < 1 || k > SFM_BATCH_MAX_OBS_NEIGHBOURS)
-        return bfail(b, SFM_ERR_INVALID, "k must be 1 .. " + std::to_string(SFM_BATCH_MAX_OBS_NEIGHBOURS) + " neighbour slots, got " + std::to_string(k));
-    if (frame != SFM_OBS_FRAME_WORLD && frame != SFM_OBS_FRAME_HEADING)
-        return bfail(b, SFM_ERR_INVALID, "frame must be 0 (world axes) or 1 (the row's heading frame), got " + std::to_string(frame));
-    std::vector<float> r2((size_t)b->B);
-    for (int s = 0; s < b->B; ++s) {
-        const float r = sense_range[s];
-        if (!std::isfinite(r) || !(r > 0.f) || r > SFM_BATCH_MAX_SENSE_RANGE)
-            return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(s) + ": sense_range must be finite, > 0 and <= 1e6 metres");
-        r2[s] = (float)((double)r * (double)r);                      // R^2 rounded once, like thr2
-    }
-    const size_t vals = (size_t)b->n_total * (size_t)(SFM_BATCH_OBS_HEADER + 4 * k);
-    BatchObsDev o;
-    HIP_TRY(b, o.range2.alloc((size_t)b->B));
-    HIP_TRY(b, hipMemcpy(o.range2, r2.data(), sizeof(float) * r2.size(), hipMemcpyHostToDevice));
-    if (vals > 0) {
-        HIP_TRY(b, o.buf.alloc(vals));
-        HIP_TRY(b, hipMemsetAsync(o.buf, 0, sizeof(float) * vals, b->stream));
-    }
-    o.k = k;
-    o.frame = frame;
-    o.on = true;
-    HIP_TRY(b, hipStreamSynchronize(b->stream));                 // the zero fill; and an observe in flight may still write the old buffer
-    b->obs = std::move(o);
-    return SFM_OK;
-}
-
-int sfm_batch_observe(SfmBatch* b) {
-    int rc = bbind(b);
-    if (rc) return rc;
-    if (!b->obs.on) return bfail(b, SFM_ERR_STATE, "observations are off: call sfm_batch_set_observation first (sfm_batch_upload_state drops them)");
-    if (b->n_total == 0) return SFM_OK;
-    ObserveArgs a;
-    memset(&a, 0, sizeof(a));
-    a.scene_off = b->d_scene_off;
-    a.pk = b->pk;
-    a.own = b->own;
-    for (int k = 0; k < 3; ++k) a.geo[k] = BatchGeo{b->geo_item_off[k], b->geo[k].off, b->geo[k].pts, b->geo[k].ctr};
-    a.range2 = b->obs.range2;
-    a.obs = b->obs.buf;
-    a.k = b->obs.k;
-    a.frame = b->obs.frame;
-    HIP_TRY(b, launch_batch_observe(a, b->B, b->stream));
-    return SFM_OK;
-}
-
-int sfm_batch_download_observations(SfmBatch* b, float* out) {
-    int rc = bbind(b);
-    if (rc) return rc;
-    if (!b->obs.on) return bfail(b, SFM_ERR_STATE, "observations are off: call sfm_batch_set_observation first (sfm_batch_upload_state drops them)");
-    HIP_TRY(b, hipStreamSynchronize(b->stream));
-    const size_t vals = (size_t)b->n_total * (size_t)(SFM_BATCH_OBS_HEADER + 4 * b->obs.k);
-    if (vals == 0) return SFM_OK;
-    if (!out) return bfail(b, SFM_ERR_INVALID, "out is NULL");
-    HIP_TRY(b, hipMemcpy(out, b->obs.buf, sizeof(float) * vals, hipMemcpyDeviceToHost));
-    return SFM_OK;
-}
-
-void* sfm_batch_observation_ptr(SfmBatch* b, int64_t* bytes) {
-    if (bytes) *bytes = 0;
-    if (!b) return nullptr;
-    if (!b->obs.on) { bfail(b, SFM_ERR_STATE, "observations are off: call sfm_batch_set_observation first (sfm_batch_upload_state drops them)"); return nullptr; }
-    if (b->n_total == 0) return nullptr;
-    if (bytes) *bytes = (int64_t)(sizeof(float) * (size_t)b->n_total * (size_t)(SFM_BATCH_OBS_HEADER + 4 * b->obs.k));
-    return b->obs.buf;
-}
-
-// Episodes (ABI 16).  Everything is checked before anything is allocated or freed.
-int sfm_batch_set_episodes(SfmBatch* b, const int32_t* agent, const float* goal_radius, const float* ped_radius, const float* veh_radius,
-                           const int32_t* max_steps) {
-    int rc = bbind(b);
-    if (rc) return rc;
-    if (!agent) {
-        HIP_TRY(b, hipStreamSynchronize(b->stream));             // an end_step or a restart in flight may still write the buffers
-        b->ep = {};
-        return SFM_OK;
-    }
-    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
-    if (!goal_radius || !ped_radius || !veh_radius || !max_steps)
-        return bfail(b, SFM_ERR_INVALID, "goal_radius, ped_radius, veh_radius or max_steps is NULL");
-    const size_t B = (size_t)b->B;
-    std::vector<int> off(B + 1);
-    HIP_TRY(b, hipMemcpy(off.data(), b->d_scene_off, sizeof(int) * off.size(), hipMemcpyDeviceToHost));
-    std::vector<BatchEpisodeScene> set(B);
-    for (size_t s = 0; s < B; ++s) {
-        const int n = off[s + 1] - off[s];
-        if (agent[s] < -1 || agent[s] >= n)
-            return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(s) + ": agent must be -1 (none) or a row 0 .. " + std::to_string(n - 1) +
-                                             " of the scene, got " + std::to_string(agent[s]));
-        float r2[3];
-        const float r[3] = {goal_radius[s], ped_radius[s], veh_radius[s]};
-        for (int q = 0; q < 3; ++q) {
-            if (!std::isfinite(r[q]) || !(r[q] >= 0.f) || r[q] > SFM_BATCH_MAX_SENSE_RANGE)
-                return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(s) + ": " + (q == 0 ? "goal_radius" : q == 1 ? "ped_radius" : "veh_radius") +
-                                                 " must be finite, >= 0 and <= 1e6 metres");
-            r2[q] = (float)((double)r[q] * (double)r[q]);            // r^2 rounded once, like thr2
-        }
-        if (max_steps[s] < 0) return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(s) + ": max_steps must be >= 0 (0: no time limit)");
-        set[s] = BatchEpisodeScene{agent[s], max_steps[s], r2[0], r2[1], r2[2], {0, 0, 0}};
-    }
-    const std::vector<float> nan(B, std::numeric_limits<float>::quiet_NaN());
-    BatchEpisodeDev e;
-    HIP_TRY(b, e.set.alloc(B)); HIP_TRY(b, e.age.alloc(B)); HIP_TRY(b, e.prev.alloc(B));
-    HIP_TRY(b, e.record.alloc(8 * B)); HIP_TRY(b, e.done.alloc(B));
-    HIP_TRY(b, hipMemcpy(e.set, set.data(), sizeof(BatchEpisodeScene) * B, hipMemcpyHostToDevice));
-    HIP_TRY(b, hipMemcpy(e.prev, nan.data(), sizeof(float) * B, hipMemcpyHostToDevice));
-    HIP_TRY(b, hipMemsetAsync(e.age, 0, sizeof(int) * B, b->stream));
-    HIP_TRY(b, hipMemsetAsync(e.record, 0, sizeof(float) * 8 * B, b->stream));
-    HIP_TRY(b, hipMemsetAsync(e.done, 0, B, b->stream));
-    e.on = true;
-    HIP_TRY(b, hipStreamSynchronize(b->stream));                 // the zero fills; and an end_step or a restart in flight may still write the old buffers
-    b->ep = std::move(e);
-    return SFM_OK;
-}
-
-int sfm_batch_end_step(SfmBatch* b, uint32_t flags) {
-    int rc = bbind(b);
-    if (rc) return rc;
-    if (flags & ~(uint32_t)SFM_END_STEP_AUTO_RESTART) return bfail(b, SFM_ERR_INVALID, "sfm_batch_end_step takes SFM_END_STEP_AUTO_RESTART only");
-    if (!b->ep.on) return bfail(b, SFM_ERR_STATE, EPISODES_OFF);
-    const bool restart = (flags & SFM_END_STEP_AUTO_RESTART) != 0;
-    long long shift = 0;
-    if (restart) {                                               // the restart's refusals come first: nothing is launched then
-        if (!b->snap.on) return bfail(b, SFM_ERR_STATE, NO_SNAPSHOT);
-        shift = b->tracks.on ? b->tracks.tick - b->snap.tick : 0;
-        if ((rc = check_restart_shift(b, nullptr, shift))) return rc;
-    }
-    EpisodeArgs a;
-    memset(&a, 0, sizeof(a));
-    a.scene_off = b->d_scene_off;
-    a.pk = b->pk;
-    a.own = b->own;
-    for (int k = 0; k < 3; ++k) a.geo[k] = BatchGeo{b->geo_item_off[k], b->geo[k].off, b->geo[k].pts, b->geo[k].ctr};
-    a.set = b->ep.set;
-    a.age = b->ep.age;
-    a.prev_goal_d2 = b->ep.prev;
-    a.record = b->ep.record;
-    a.done = b->ep.done;
-    HIP_TRY(b, launch_batch_episode(a, b->B, b->stream));
-    return restart ? batch_restart_device(b, b->ep.done, shift) : SFM_OK;
-}
-
-int sfm_batch_download_episodes(SfmBatch* b, float* record, uint8_t* done) {
-    int rc = bbind(b);
-    if (rc) return rc;
-    if (!b->ep.on) return bfail(b, SFM_ERR_STATE, EPISODES_OFF);
-    HIP_TRY(b, hipStreamSynchronize(b->stream));
-    const size_t B = (size_t)b->B;
-    if (record) HIP_TRY(b, hipMemcpy(record, b->ep.record, sizeof(float) * 8 * B, hipMemcpyDeviceToHost));
-    if (done) HIP_TRY(b, hipMemcpy(done, b->ep.done, B, hipMemcpyDeviceToHost));
-    return SFM_OK;
-}
-
-// Range scans (ABI 17).  Everything is checked before anything is allocated or freed.
-int sfm_batch_set_scan(SfmBatch* b, int R, const float* dir_x, const float* dir_y, const float* max_range, const float* ped_radius,
-                       const float* point_radius, const uint8_t* mask, int frame) {
-    int rc = bbind(b);
-    if (rc) return rc;
-    if (!max_range) {
-        HIP_TRY(b, hipStreamSynchronize(b->stream));             // a scan in flight may still write the buffer
-        b->scan = {};
-        return SFM_OK;
-    }
-    if (!b->have_state) return bfail(b, SFM_ERR_STATE, "sfm_batch_upload_state has not been called");
-    if (R < 1 || R > SFM_BATCH_MAX_SCAN_RAYS)
-        return bfail(b, SFM_ERR_INVALID, "R must be 1 .. " + std::to_string(SFM_BATCH_MAX_SCAN_RAYS) + " rays per row, got " + std::to_string(R));
-    if (frame != SFM_OBS_FRAME_WORLD && frame != SFM_OBS_FRAME_HEADING)
-        return bfail(b, SFM_ERR_INVALID, "frame must be 0 (world axes) or 1 (the row's heading frame), got " + std::to_string(frame));
-    if (!dir_x || !dir_y) return bfail(b, SFM_ERR_INVALID, "dir_x or dir_y is NULL");
-    if (!ped_radius || !point_radius) return bfail(b, SFM_ERR_INVALID, "ped_radius or point_radius is NULL");
-    std::vector<float2> dir((size_t)R);
-    for (int q = 0; q < R; ++q) {
-        if (!std::isfinite(dir_x[q]) || !std::isfinite(dir_y[q]))
-            return bfail(b, SFM_ERR_INVALID, "ray " + std::to_string(q) + ": its direction is not finite");
-        dir[q] = make_float2(dir_x[q], dir_y[q]);
-    }
-    const size_t B = (size_t)b->B;
-    std::vector<BatchScanScene> set(B);
-    for (size_t s = 0; s < B; ++s) {
-        const float m = max_range[s];
-        if (!std::isfinite(m) || !(m > 0.f) || m > SFM_BATCH_MAX_SENSE_RANGE)
-            return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(s) + ": max_range must be finite, > 0 and <= 1e6 metres");
-        float r2[2];
-        const float r[2] = {ped_radius[s], point_radius[s]};
-        for (int q = 0; q < 2; ++q) {
-            if (!std::isfinite(r[q]) || !(r[q] >= 0.f) || r[q] > SFM_BATCH_MAX_SENSE_RANGE)
-                return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(s) + ": " + (q == 0 ? "ped_radius" : "point_radius") +
-                                                 " must be finite, >= 0 and <= 1e6 metres");
-            r2[q] = (float)((double)r[q] * (double)r[q]);            // r^2 rounded once, like R2
-        }
-        set[s] = BatchScanScene{m, r2[0], r2[1], 0.f};
-    }
-    const size_t n = (size_t)b->n_total, vals = n * (size_t)(2 * R);
-    BatchScanDev o;
-    HIP_TRY(b, o.set.alloc(B));
-    HIP_TRY(b, o.dir.alloc((size_t)R));
-    HIP_TRY(b, hipMemcpy(o.set, set.data(), sizeof(BatchScanScene) * B, hipMemcpyHostToDevice));
-    HIP_TRY(b, hipMemcpy(o.dir, dir.data(), sizeof(float2) * (size_t)R, hipMemcpyHostToDevice));
-    if (mask && n > 0) {
-        HIP_TRY(b, o.mask.alloc(n));
-        HIP_TRY(b, hipMemcpy(o.mask, mask, n, hipMemcpyHostToDevice));
-    }
-    if (vals > 0) {
-        HIP_TRY(b, o.buf.alloc(vals));
-        HIP_TRY(b, hipMemsetAsync(o.buf, 0, sizeof(float) * vals, b->stream));
-    }
-    o.R = R;
-    o.frame = frame;
-    o.on = true;
-    HIP_TRY(b, hipStreamSynchronize(b->stream));                 // the zero fill; and a scan in flight may still write the old buffer
-    b->scan = std::move(o);
-    return SFM_OK;
-}
-
-int sfm_batch_scan(SfmBatch* b) {
-    int rc = bbind(b);
-    if (rc) return rc;
-    if (!b->scan.on) return bfail(b, SFM_ERR_STATE, SCANS_OFF);
-    if (b->n_total == 0) return SFM_OK;
-    ScanArgs a;
-    memset(&a, 0, sizeof(a));
-    a.scene_off = b->d_scene_off;
-    a.pk = b->pk;
-    a.own = b->own;
-    for (int k = 0; k < 3; ++k) a.geo[k] = BatchGeo{b->geo_item_off[k], b->geo[k].off, b->geo[k].pts, b->geo[k].ctr};
-    a.set = b->scan.set;
-    a.dir = b->scan.dir;
-    a.mask = b->scan.mask;                                       // (null: every row)
-    a.out = b->scan.buf;
-    a.R = b->scan.R;
-    a.frame = b->scan.frame;
-    HIP_TRY(b, launch_batch_scan(a, b->B, b->stream));
-    return SFM_OK;
-}
-
-int sfm_batch_download_scan(SfmBatch* b, float* out) {
-    int rc = bbind(b);
-    if (rc) return rc;
-    if (!b->scan.on) return bfail(b, SFM_ERR_STATE, SCANS_OFF);
-    HIP_TRY(b, hipStreamSynchronize(b->stream));
-    const size_t vals = (size_t)b->n_total * (size_t)(2 * b->scan.R);
-    if (vals == 0) return SFM_OK;
-    if (!out) return bfail(b, SFM_ERR_INVALID, "out is NULL");
-    HIP_TRY(b, hipMemcpy(out, b->scan.buf, sizeof(float) * vals, hipMemcpyDeviceToHost));
     return SFM_OK;
 }
 

@@ -26,9 +26,9 @@
 
 namespace sfm {
 
-__device__ __forceinline__ bool episode_live(float x, float y) {       // observe's test (a NaN position fails it)
-    return fabsf(x) < NEAR_LIMIT && fabsf(y) < NEAR_LIMIT;
-}
+// The live test of the agent, and of every pedestrian it could touch, is row_live (sfm_device.h), the one the observe and scan
+// kernels take: a ghost parked far away fails it, and so does a NaN position.  One definition, so that no sensor
+// can count a row as live that another does not.
 
 // this lane's share of the minimum of dist2 over ALL points of ALL polylines of one kind of scene b
 __device__ __forceinline__ float episode_points_min(const BatchGeo& g, int b, float x, float y, float m) {
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_episode_kernel(const EpisodeA
     if (ag >= 0) {                                                     // uniform
         const float4 s = a.pk[s0 + ag];
         x = s.x; y = s.y;
-        live = episode_live(x, y);
+        live = row_live(x, y);
     }
     float mp = inf, mv = inf, mw = inf;
     if (live) {                                                        // uniform
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_episode_kernel(const EpisodeA
             const float4 pj = a.pk[s0 + j];
             const float dx = pj.x - x, dy = pj.y - y;
             const float d2 = fmaf(dx, dx, dy * dy);
-            mp = (j != ag && episode_live(pj.x, pj.y)) ? fminf(mp, d2) : mp;
+            mp = (j != ag && row_live(pj.x, pj.y)) ? fminf(mp, d2) : mp;
         }
         mv = episode_points_min(a.geo[2], b, x, y, mv);
         mw = episode_points_min(a.geo[0], b, x, y, mw);

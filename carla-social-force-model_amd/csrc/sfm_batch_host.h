@@ -1,0 +1,212 @@
+// sfm_batch_host.h -- what the two host files of the batched scenes share: the batch itself (SfmBatch and the struct of each of its
+// features), its error plumbing, and the messages for a feature that is off.  sfm_batch_capi.hip holds the ticks and everything they
+// read or write; sfm_batch_sense_capi.hip the read-only sensors (observations, episode ends, range scans) and the device pointers.
+#pragma once
+#include "sfm_capi_common.h"
+#include "sfm_metres.h"
+
+namespace sfm {
+
+// Each feature of a batch keeps its arrays in one struct whose default value is "off": dropping the feature is `x = {}`, after the
+// caller has synchronised the stream (a tick in flight may still read the arrays).
+
+struct BatchGeoDev {           // one kind of polylines over all scenes
+    DevBuf<int> off;           // [K+1]
+    DevBuf<float2> pts;        // [P]
+    DevBuf<float4> ctr;        // [K]
+    int K = 0;
+    int P = 0;
+};
+
+// device-side vehicles (sfm_batch_set_dynamic_boxes): geo[2].ctr / .pts hold the vehicles the next tick sees, ctr_alt / pts_alt
+// (the same sizes) the half an integrating tick writes; batch_launch swaps them after each such launch
+struct BatchBoxesDev {
+    bool on = false;
+    DevBuf<float2> local;      // [P] ring-local offsets
+    DevBuf<float2> rot;        // [M] {cos yaw, sin yaw}
+    DevBuf<float4> ctr_alt;
+    DevBuf<float2> pts_alt;
+    std::vector<int32_t> item_off_h;   // the vehicles' scene_item_off [B+1] on the host
+};
+
+// scripted vehicle tracks (sfm_batch_set_vehicle_tracks, ABI 12): read-only on the device; dropped with the boxes they refer to
+struct BatchTracksDev {
+    bool on = false;
+    DevBuf<int> off;           // [M+1]
+    DevBuf<int> first;         // [M]
+    DevBuf<float4> key;        // [T] {x, y, vx, vy}
+    DevBuf<float2> rot;        // [T] {cos yaw, sin yaw}
+    long long tick = 0;        // tau: integrating ticks since the tracks were set (a kernel argument, not device state)
+    std::vector<int32_t> off_h, first_h;   // host copies: sfm_batch_download_vehicle_tracks answers without the device
+    bool first_stale = false;  // a restart by device mask moved `first` of scenes the host cannot know: first_h is refreshed from
+                               // the device before it is read (refresh_track_first)
+};
+
+// the mode state machine (sfm_batch_set_mode_fsm, ABI 9): per row over the concatenated rows, per scene [B]
+struct BatchModesDev {
+    bool on = false;
+    DevBuf<uint8_t> mode;
+    DevBuf<float> target;
+    DevBuf<float4> speeds;     // {initial_speed, crossing_speed, safety_margin, next_mode_time}
+    DevBuf<int> off;           // [N_total+1]
+    DevBuf<float2> xy;
+    DevBuf<uint8_t> cross;
+    DevBuf<int> cursor;
+    DevBuf<BatchModeScene> scene;   // [B]
+    DevBuf<float> time;        // [B] the scenes' clocks
+};
+
+// the spawn schedule (sfm_batch_set_spawn_schedule, ABI 11): per row; dropped with the modes it refers to
+struct BatchSpawnDev {
+    bool on = false;           // (not "time is allocated": a schedule over no rows still holds one element)
+    DevBuf<float> time;
+    DevBuf<uint8_t> chain;
+    DevBuf<uint8_t> born;
+    DevBuf<float> birth;
+    DevBuf<float4> pk0;        // the spawn state: the rows as they were when the schedule was set
+    DevBuf<float2> zv0;
+};
+
+// the snapshot (sfm_batch_snapshot / sfm_batch_restart, ABI 13): a copy of every array a tick can change, grow-only (`on = false`
+// drops the snapshot and keeps the memory); what it holds follows boxes / modes / spawns / tracks, which cannot change while
+// it is valid (every call that changes them drops it)
+struct BatchSnapDev {
+    bool on = false;
+    DevBuf<float4> pk, own, ctr;
+    DevBuf<float2> zv, pts;
+    DevBuf<uint32_t> draws;
+    DevBuf<uint8_t> mode, born;
+    DevBuf<float> target, time, birth;
+    DevBuf<int> cursor, first;
+    long long tick = 0;                // the tracks' tick when the snapshot was taken
+    std::vector<int32_t> first_h;      // the tracks' first_h when the snapshot was taken
+};
+
+// sfm_batch_restart's list of chosen scenes: pinned on the host, copied to `list` on the stream; `done` is recorded behind the
+// launch that reads it, and the next masked restart waits for it before it refills the pinned list
+struct BatchRestartDev {
+    DevBuf<int> list;
+    PinnedBuf<int> list_h;
+    Event done;
+    bool pending = false;
+};
+
+// steering (sfm_batch_set_steering, ABI 14): the command of every row {ux, uy, uz, kind}, an input the ticks only read.  cmd_h
+// is its pinned host copy (the kinds of the last sfm_batch_set_steering, the velocities of the last call that sent any):
+// sfm_batch_set_commands refills it and sends it with one copy on the stream; SfmBatch::c_done is recorded behind that copy, and
+// the next call waits for it before it refills
+struct BatchSteerDev {
+    bool on = false;           // (not "cmd is allocated": a batch without rows can be steered and has no buffers)
+    DevBuf<float4> cmd;        // [N_total] on the device
+    PinnedBuf<float4> cmd_h;
+    bool pending = false;
+};
+
+// observations (sfm_batch_set_observation, ABI 15): the settings and the buffer sfm_batch_observe fills; nothing a tick reads or writes
+struct BatchObsDev {
+    bool on = false;           // (not "buf is allocated": a batch without rows can be observed and has no buffer)
+    int k = 0;
+    int frame = 0;
+    DevBuf<float> range2;      // [B] sense_range^2
+    DevBuf<float> buf;         // [N_total][16 + 4 k]
+};
+
+// episodes (sfm_batch_set_episodes, ABI 16): the settings, the per-scene episode state, and the record and mask sfm_batch_end_step
+// fills; nothing a tick reads or writes
+struct BatchEpisodeDev {
+    bool on = false;
+    DevBuf<BatchEpisodeScene> set;     // [B]
+    DevBuf<int> age;                   // [B]
+    DevBuf<float> prev;                // [B] prev_goal_d2
+    DevBuf<float> record;              // [B][8]
+    DevBuf<uint8_t> done;              // [B]
+};
+
+// range scans (sfm_batch_set_scan, ABI 17): the settings and the buffer sfm_batch_scan fills; nothing a tick reads or writes
+struct BatchScanDev {
+    bool on = false;           // (not "buf is allocated": a batch without rows can be scanned and has no buffer)
+    int R = 0;
+    int frame = 0;
+    DevBuf<BatchScanScene> set;    // [B]
+    DevBuf<float2> dir;        // [R]
+    DevBuf<uint8_t> mask;      // [N_total]; not allocated: every row is scanned
+    DevBuf<float> buf;         // [N_total][2 R]
+};
+
+struct BatchRecordDev {        // grow-only device buffers of the recording calls
+    DevBuf<float4> frames;     // sfm_batch_run_recorded
+    DevBuf<float2> zframes;
+    DevBuf<float> forces;      // sfm_batch_tick_forces / sfm_batch_run_recorded_forces
+};
+}  // namespace sfm
+
+struct SfmBatch {
+    int device = 0;
+    int B = 0;
+    hipStream_t stream = nullptr;
+    sfm::DevBuf<sfm::BatchParams> d_prm;    // [B]
+    sfm::DevBuf<int> d_scene_off;           // [B+1]
+    int n_total = 0;
+    bool z3 = false;
+    bool have_state = false;
+    sfm::DevBuf<float4> pk;                 // {x, y, vx, vy}; the five state arrays grow together
+    sfm::DevBuf<float2> zv;                 // {z, vz}
+    sfm::DevBuf<float4> own;                // {wx, wy, target_speed, radius}
+    sfm::DevBuf<uint8_t> crossing;
+    sfm::DevBuf<uint32_t> draws;            // waypoint draw counters (zeroed by every upload)
+    bool any_rad = false;
+    sfm::DevBuf<int> geo_item_off[3];       // [B+1] per kind, zero-filled while the kind has no polylines; they outlive the polylines
+    sfm::BatchGeoDev geo[3];                // borders, static, dynamic obstacles
+    sfm::DevBuf<sfm::BatchStream> d_streams;    // [B] once sfm_batch_set_waypoint_streams has been called
+    sfm::BatchRecordDev rec;
+    sfm::BatchBoxesDev boxes;
+    sfm::BatchTracksDev tracks;
+    sfm::BatchModesDev modes;
+    sfm::BatchSpawnDev spawns;
+    bool spawn_used = false;                // a schedule was set since the last sfm_batch_set_mode_fsm: a second one is refused
+    sfm::BatchSnapDev snap;
+    sfm::BatchRestartDev restart;
+    sfm::BatchSteerDev steer;
+    sfm::BatchObsDev obs;
+    sfm::BatchEpisodeDev ep;
+    sfm::BatchScanDev scan;
+    sfm::Event c_done;                      // created by the first sfm_batch_set_steering with rows; outlives every drop of the steering
+    std::string err;
+};
+
+namespace sfm {
+
+inline int bfail(SfmBatch* b, int code, const std::string& msg) {
+    if (b) b->err = msg; else g_create_error = msg;
+    return code;
+}
+
+inline int bbind(SfmBatch* b) {
+    if (!b) return SFM_ERR_INVALID;
+    hipError_t e = hipSetDevice(b->device);
+    if (e != hipSuccess) { b->err = std::string("hipSetDevice: ") + hipGetErrorString(e); return SFM_ERR_HIP; }
+    return SFM_OK;
+}
+
+// one message per thing that is missing
+constexpr const char* NO_STATE = "sfm_batch_upload_state has not been called";
+constexpr const char* NO_SNAPSHOT = "the batch has no snapshot: call sfm_batch_snapshot first (sfm_batch_upload_state and the calls "
+                                    "that set vehicles, modes, a spawn schedule or tracks drop it)";
+constexpr const char* STEERING_OFF = "steering is off: call sfm_batch_set_steering first (sfm_batch_upload_state drops it)";
+constexpr const char* OBSERVATIONS_OFF = "observations are off: call sfm_batch_set_observation first (sfm_batch_upload_state drops them)";
+constexpr const char* EPISODES_OFF = "episodes are off: call sfm_batch_set_episodes first (sfm_batch_upload_state drops them)";
+constexpr const char* SCANS_OFF = "scans are off: call sfm_batch_set_scan first (sfm_batch_upload_state drops them)";
+
+// one kind of the scenes' geometry as the kernels take it, and what the sensors see of the scenes
+inline BatchGeo batch_geo(const SfmBatch* b, int k) { return BatchGeo{b->geo_item_off[k], b->geo[k].off, b->geo[k].pts, b->geo[k].ctr}; }
+inline BatchSceneView batch_scene_view(const SfmBatch* b) {
+    return BatchSceneView{b->d_scene_off, b->pk, b->own, {batch_geo(b, 0), batch_geo(b, 1), batch_geo(b, 2)}};
+}
+
+// The restarts (sfm_batch_capi.hip), which sfm_batch_end_step shares.  batch_restart_checks: what every restart refuses before it
+// sends or launches anything, in this order -- no snapshot; bad_choice, what the caller found wrong with its choice of scenes (empty:
+// nothing); a tracked vehicle of scene k (mask null or mask[k]) whose first tick, moved by *shift, does not fit int32.
+int batch_restart_checks(SfmBatch* b, const uint8_t* mask, const std::string& bad_choice, long long* shift);
+int batch_restart_device(SfmBatch* b, const uint8_t* d_mask, long long shift);
+
+}  // namespace sfm

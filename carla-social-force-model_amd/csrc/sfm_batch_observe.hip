@@ -96,7 +96,7 @@ __device__ __forceinline__ void observe_store(const ObserveArgs& a, const Observ
     const float inf = __builtin_inff();
     const float x = s.x, y = s.y, vx = s.z, vy = s.w;
     float4* out = reinterpret_cast<float4*>(a.obs + (size_t)(s0 + i) * (size_t)(16 + 4 * k));
-    const bool live = fabsf(x) < NEAR_LIMIT && fabsf(y) < NEAR_LIMIT;  // (a NaN position fails it)
+    const bool live = row_live(x, y);                                  // (a NaN position fails it)
     if (!live) {
         const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
         out[0] = z4; out[1] = z4; out[2] = z4; out[3] = z4;

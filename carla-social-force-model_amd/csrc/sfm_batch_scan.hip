@@ -103,7 +103,7 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_scan_kernel(const ScanArgs a)
         if (t < n) {
             const float4 s = sh.pk[t];
             const bool want = !a.mask || a.mask[s0 + t] != 0;
-            const bool live = fabsf(s.x) < NEAR_LIMIT && fabsf(s.y) < NEAR_LIMIT;    // (a NaN position fails it)
+            const bool live = row_live(s.x, s.y);
             scan = want && live;
             if (want && !live) {
                 float* out = a.out + (size_t)(s0 + t) * (size_t)(2 * R);
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_scan_kernel(const ScanArgs a)
         const float x = s.x, y = s.y;
         const float2 u0 = sh.dir[ray];
         float ux = u0.x, uy = u0.y;
-        if (a.frame) {                                                 // uniform: the ray in the row's heading frame
+        if (a.frame) {                                                 // uniform: the ray in the row's heading frame (observe_store's rule)
             const float vx = s.z, vy = s.w;
             const float4 o = a.own[s0 + row];
             const float gx = o.x - x, gy = o.y - y;

@@ -1,5 +1,6 @@
-// sfm_capi_common.h -- what the two halves of the C ABI share: sfm_capi.hip (one crowd on a handle) and sfm_batch_capi.hip (batched
-// scenes).  The kernels' launch functions, the error plumbing, and the parameter checks and folding both apply.
+// sfm_capi_common.h -- what the two halves of the C ABI share: sfm_capi.hip (one crowd on a handle) and sfm_batch_capi.hip with
+// sfm_batch_sense_capi.hip (batched scenes).  The kernels' launch functions, the error plumbing, and the parameter checks and
+// folding both apply.
 #pragma once
 #include "sfm_devbuf.h"
 #include "sfm_device.h"

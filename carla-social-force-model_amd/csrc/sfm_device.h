@@ -331,12 +331,19 @@ struct BatchRestart {
     float* prev_goal_d2;      // [B]
 };
 
-// Observations of a batch (sfm_batch_observe, sfm_batch_observe_kernel in sfm_batch_observe.hip): everything but obs is read only.
-struct ObserveArgs {
+// What the batch's read-only sensors (observations, episode ends, range scans) see of the scenes: the common head of their arguments.
+struct BatchSceneView {
     const int* scene_off;     // [B+1]
     const float4* pk;         // {x, y, vx, vy}
-    const float4* own;        // {wx, wy, target_speed, radius}
+    const float4* own;        // {wx, wy, target_speed, radius}: the goal, also of frame 1's heading
     BatchGeo geo[3];          // borders, static obstacles, dynamic obstacles (the half of the ping-pong the next tick reads)
+};
+
+// A live row: not a ghost parked far away, not a NaN position (which fails the comparison).
+__device__ __forceinline__ bool row_live(float x, float y) { return fabsf(x) < NEAR_LIMIT && fabsf(y) < NEAR_LIMIT; }
+
+// Observations of a batch (sfm_batch_observe, sfm_batch_observe_kernel in sfm_batch_observe.hip): everything but obs is read only.
+struct ObserveArgs : BatchSceneView {
     const float* range2;      // [B] sense_range^2, formed in double and rounded once
     float* obs;               // [N_total][16 + 4 k]
     int k;                    // neighbour slots per row, 1 .. SFM_BATCH_MAX_OBS_NEIGHBOURS
@@ -350,11 +357,7 @@ struct BatchEpisodeScene {    // one scene's episode settings (sfm_batch_set_epi
     float goal_r2, ped_r2, veh_r2;   // radius^2, each formed in double and rounded once like thr2; 0: the test never fires
     int pad[3];
 };
-struct EpisodeArgs {
-    const int* scene_off;     // [B+1]
-    const float4* pk;         // {x, y, vx, vy}
-    const float4* own;        // {wx, wy, target_speed, radius}
-    BatchGeo geo[3];          // borders, static obstacles, dynamic obstacles (the half of the ping-pong the next tick reads)
+struct EpisodeArgs : BatchSceneView {
     const BatchEpisodeScene* set;   // [B]
     int* age;                 // [B] evaluations since the scene's last restart
     float* prev_goal_d2;      // [B] goal_d2 of the evaluation before; NaN: none since the restart
@@ -369,11 +372,7 @@ struct BatchScanScene {       // one scene's scan settings (sfm_batch_set_scan)
     float ped_r2, point_r2;   // radius^2, each formed in double and rounded once like R2; 0: the kind is never hit
     float pad;
 };
-struct ScanArgs {
-    const int* scene_off;     // [B+1]
-    const float4* pk;         // {x, y, vx, vy}
-    const float4* own;        // {wx, wy, target_speed, radius}: the goal of frame 1's heading
-    BatchGeo geo[3];          // borders, static obstacles, dynamic obstacles (the half of the ping-pong the next tick reads)
+struct ScanArgs : BatchSceneView {
     const BatchScanScene* set;    // [B]
     const float2* dir;        // [R] ray directions, used as given
     const uint8_t* mask;      // [N_total] nonzero: the row is scanned; null: every row
@@ -381,6 +380,9 @@ struct ScanArgs {
     int R;                    // rays per row, 1 .. SCAN_MAX_RAYS
     int frame;                // 0 world axes, 1 the row's heading frame
 };
+
+static_assert(sizeof(BatchSceneView) == 120 && sizeof(ObserveArgs) == 120 + 24 && sizeof(EpisodeArgs) == 120 + 40 && sizeof(ScanArgs) == 120 + 40,
+              "the kernels' argument layout: the view is the head of each sensor's arguments, which follow it without padding");
 
 // Block-major packing for sharded runs (sfm_set_partition, sfm_reorder.hip): the row order is cut into gx columns by x, each
 // column into gy blocks by y -- block b = column * gy + position holds rows [bound[b], bound[b+1]) -- and every block is

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .observe import NEAR_LIMIT, _d2, _f32, _get, _polylines, range2
+from .observe import _d2, _f32, _get, _polylines, range2, live as _live
 
 EPISODE_WIDTH = 8
 EP_DONE, EP_REASON, EP_AGE, EP_GOAL_D2, EP_PREV_GOAL_D2, EP_PED_D2, EP_VEH_D2, EP_WALL_D2 = range(8)
@@ -53,7 +53,7 @@ def episode_scene(scene, agent, radii, max_steps, age=0, prev=np.nan, state=None
     if agent >= 0:
         loc = loc.reshape(n, -1)
         x, y = _f32(loc[:, 0], 0), _f32(loc[:, 1], 0)
-        ok = (np.abs(x) < NEAR_LIMIT) & (np.abs(y) < NEAR_LIMIT)          # (a NaN position fails it)
+        ok = _live(x, y)
         live = bool(ok[agent])
         if not live:
             reason = REASON_NOT_LIVE

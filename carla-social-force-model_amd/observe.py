@@ -37,6 +37,11 @@ def _d2(ax, ay):
         return (xx + yy).astype(np.float32)
 
 
+def live(x, y):
+    """Which rows are live, as the three sensor kernels decide it (row_live, sfm_device.h); a NaN position fails it."""
+    return (np.abs(x) < NEAR_LIMIT) & (np.abs(y) < NEAR_LIMIT)
+
+
 def range2(sense_range):
     """R2 as the library forms it: the fp32 range squared in double and rounded once."""
     r = np.float64(np.float32(sense_range))
@@ -79,7 +84,8 @@ def candidate_counts(scene, sense_range, state=None):
 
 def heading(rec0):
     """The heading (N,2) float64 of every row of a frame-0 record: v / |v| when fmaf(vx, vx, vy * vy) > 0, else the goal's direction
-    when fmaf(gx, gx, gy * gy) > 0, else (1, 0).  The tests are on fp32 values, the division is in float64."""
+    when fmaf(gx, gx, gy * gy) > 0, else (1, 0).  The tests are on fp32 values, the division is in float64.
+    ``scan.heading32`` is the same rule in the kernels' own fp32 arithmetic, for tests that compare bit for bit."""
     rec0 = np.asarray(rec0, dtype=np.float32)
     g, v = rec0[:, 0:2], rec0[:, 2:4]
     vv, gg = _d2(v[:, 0], v[:, 1]), _d2(g[:, 0], g[:, 1])
@@ -132,7 +138,6 @@ def observe_scene(scene, k, sense_range, frame=0, state=None, vehicles=None, veh
     wp = np.asarray(_get(scene, "waypoint") if waypoints is None else waypoints, dtype=np.float64).reshape(n, -1)
     wx, wy = _f32(wp[:, 0], 0), _f32(wp[:, 1], 0)
     ts = _f32(_get(scene, "target_speed") if target_speed is None else target_speed, 0)
-    live = (np.abs(x) < NEAR_LIMIT) & (np.abs(y) < NEAR_LIMIT)         # (a NaN position fails it)
 
     with np.errstate(over="ignore", invalid="ignore"):
         # neighbours: the first k candidates in ascending (d2, j) order -- a stable sort of d2 over ascending j
@@ -172,7 +177,7 @@ def observe_scene(scene, k, sense_range, frame=0, state=None, vehicles=None, veh
                 rec[:, 11] = np.where(present, ov[:, 1] - vy, np.float32(0.0))
             flags += np.where(present, np.float32(bit), np.float32(0.0))
         rec[:, 7] = flags
-    rec[~live] = 0.0
+    rec[~live(x, y)] = 0.0
     if frame == 1:
         with np.errstate(over="ignore", invalid="ignore"):
             rec = rotate_record(rec, heading(rec)).astype(np.float32)

@@ -12,10 +12,10 @@ from __future__ import annotations
 
 import numpy as np
 
-from .observe import NEAR_LIMIT, _f32, _get, _polylines
+from ._args import MAX_METRES as MAX_SCAN_RANGE, check_frame, per_scene_metres
+from .observe import _f32, _get, _polylines, live as _live
 
 MAX_SCAN_RAYS = 64                   # SFM_BATCH_MAX_SCAN_RAYS
-MAX_SCAN_RANGE = 1.0e6               # SFM_BATCH_MAX_SENSE_RANGE, metres: the bound of max_range and of the radii
 KIND_NONE, KIND_PEDESTRIAN, KIND_BORDER, KIND_STATIC, KIND_VEHICLE = range(5)
 POINT_RADIUS = 0.1                   # the reference's sampling resolution of borders and rings
 
@@ -92,24 +92,9 @@ def scan_arrays(B, max_range, ped_radius, point_radius=POINT_RADIUS, frame=0):
     Each of the three is a scalar (broadcast to every scene, like ``stream_arrays``) or B values, in metres: ``max_range`` finite,
     > 0 and <= 1e6 in float32; the radii finite, >= 0 and <= 1e6 (0 switches the kind off).  Pure NumPy; raises ValueError on a
     frame other than 0 or 1, a shape that does not fit, and every value the library would refuse."""
-    B = int(B)
-    if isinstance(frame, (bool, np.bool_)) or not isinstance(frame, (int, np.integer)) or int(frame) not in (0, 1):
-        raise ValueError(f"frame must be 0 (world axes) or 1 (the row's heading frame), got {frame!r}")
-
-    def col(v, name, positive):
-        a = np.asarray(v)
-        if a.dtype.kind not in "iuf":
-            raise ValueError(f"{name} must be numbers, got {a.dtype}")
-        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] not in (1, B)):
-            raise ValueError(f"{name}: expected a scalar or {B} values, got shape {a.shape}")
-        with np.errstate(over="ignore"):
-            r = np.ascontiguousarray(np.broadcast_to(a.reshape(-1), (B,)), dtype=np.float32)
-        ok = np.isfinite(r).all() and ((r > 0).all() if positive else (r >= 0).all()) and (r <= np.float32(MAX_SCAN_RANGE)).all()
-        if not ok:
-            raise ValueError(f"{name} must be finite, {'> 0' if positive else '>= 0'} and <= {MAX_SCAN_RANGE:g} metres")
-        return r
-
-    return col(max_range, "max_range", True), col(ped_radius, "ped_radius", False), col(point_radius, "point_radius", False), int(frame)
+    B, frame = int(B), check_frame(frame)
+    return (per_scene_metres(max_range, "max_range", B, True), per_scene_metres(ped_radius, "ped_radius", B, False),
+            per_scene_metres(point_radius, "point_radius", B, False), frame)
 
 
 def scan_mask(mask, scene_off):
@@ -149,7 +134,8 @@ def scan_mask(mask, scene_off):
 
 def heading32(x, y, vx, vy, wx, wy):
     """The heading of frame 1, per row, in the kernel's fp32 arithmetic: v / |v| when fmaf(vx, vx, vy * vy) > 0, else the goal
-    entry (wx - x, wy - y) / its length when that is > 0, else (1, 0); l = sqrt(.), h = (a / l, b / l), each rounded once."""
+    entry (wx - x, wy - y) / its length when that is > 0, else (1, 0); l = sqrt(.), h = (a / l, b / l), each rounded once.
+    ``observe.heading`` is the same rule with a float64 division, for tests that compare within a tolerance."""
     with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
         gx, gy = wx - x, wy - y
         vv, gg = _fma32(vx, vx, vy * vy), _fma32(gx, gx, gy * gy)
@@ -188,7 +174,7 @@ def _walk(scene, angles, max_range, ped_radius, point_radius, frame, mask, state
     x, y = _f32(loc[:, 0], 0), _f32(loc[:, 1], 0)
     vx, vy = _f32(vel[:, 0], 0), _f32(vel[:, 1], 0)
     scanned = np.ones(n, bool) if mask is None else np.asarray(mask).astype(bool).reshape(n)
-    live = (np.abs(x) < NEAR_LIMIT) & (np.abs(y) < NEAR_LIMIT)         # (a NaN position fails it)
+    live = _live(x, y)
     if frame == 1:
         wp = np.asarray(_get(scene, "waypoint") if waypoints is None else waypoints, dtype=np.float64).reshape(n, -1)
         hx, hy = heading32(x, y, vx, vy, _f32(wp[:, 0], 0), _f32(wp[:, 1], 0))
