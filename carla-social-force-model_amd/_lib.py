@@ -33,7 +33,10 @@ SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_
                             "sfm_batch_observation_ptr")},
          **{n: 16 for n in ("sfm_batch_set_episodes", "sfm_batch_end_step", "sfm_batch_download_episodes",
                             "sfm_batch_restart_device")},
-         **{n: 17 for n in ("sfm_batch_set_scan", "sfm_batch_scan", "sfm_batch_download_scan")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
+         # (the restart noise came without a bump of the ABI number: additions only, include/sfm_hip.h says why)
+         **{n: 17 for n in ("sfm_batch_set_scan", "sfm_batch_scan", "sfm_batch_download_scan",
+                            "sfm_batch_set_restart_noise", "sfm_batch_download_restart_noise")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
+UNBUMPED = ("sfm_batch_set_restart_noise", "sfm_batch_download_restart_noise")   # ... and those a build of the SAME number may lack
 
 FORCE_NAMES = ("acceleration_force", "pedestrian_force", "border_force",
                "static_obstacle_force", "dynamic_obstacle_force")
@@ -161,6 +164,9 @@ SYMBOLS = {
     "sfm_batch_set_scan": (C.c_int, [_H, C.c_int, _F, _F, _F, _F, _F, _U8, C.c_int]),
     "sfm_batch_scan": (C.c_int, [_H]),
     "sfm_batch_download_scan": (C.c_int, [_H, _F]),
+    # batch restart noise (ABI 17, added without a bump)
+    "sfm_batch_set_restart_noise": (C.c_int, [_H, _U32, _F, _F, _F, _F, _F, _F, C.c_int, _I]),
+    "sfm_batch_download_restart_noise": (C.c_int, [_H, _U32, _U32]),
 }
 
 _lib = None
@@ -200,6 +206,8 @@ def load():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
+            if name in UNBUMPED and os.environ.get("SFM_LIB_PATH"):        # an older build of the same ABI number (A/B of builds)
+                continue
             raise SfmLibraryError(f"{LIB_PATH} does not export {name} (stale build?)") from e
         fn.restype = res
         fn.argtypes = args

@@ -94,6 +94,16 @@ alongside, which a list of k neighbours cannot express.  ``mask`` names the rows
 not the crowd); the others cost nothing and read zeros.  ``scans()`` downloads them per scene, ``scan_tensor()`` is the buffer as a
 torch tensor a policy reads on the device, and ``scan.scan_scene`` is the host twin, bit for bit in both frames (the record and its
 exact rules: include/sfm_hip.h).  Scanning changes nothing a tick reads: examples/batch_lidar_loop.py.
+
+Restart noise (ABI 17, added without a bump): resets that sample.  A plain restart is the snapshot bit for bit, so every episode of
+a scene starts alike; ``set_restart_noise(seeds, pos_box, goal_box, min_gap, point_gap, tries, track_delay)`` lets every restart
+(``restart``, ``restart_device``, ``end_step(auto_restart=True)``) be followed by one more launch that draws each row's start from a
+box around its snapshot position, again while it is too near a row already placed, a lower-index proposal or a point of the
+scene's geometry, draws the goals from a box around the snapshot goal and lets tracked vehicles arrive up to ``track_delay`` ticks
+later -- all keyed by the scene's seed and its restart counter, so reproducible and the same alone or in any batch.
+``restart_noise()`` downloads the counters (restarts per scene, rows of the latest restart no try could place),
+``reset_count_tensor()`` aliases the first, and ``reset.resample_scene`` is the host twin, bit for bit (the exact rule:
+include/sfm_hip.h): examples/batch_rl_loop_randomised.py.
 """
 from __future__ import annotations
 
@@ -600,6 +610,51 @@ def pack_steering(kinds, commands, scene_off):
     return kd, f32(u[:, 0]), f32(u[:, 1]), f32(u[:, 2])
 
 
+PTR_RESETS = 6                   # SFM_BATCH_PTR_RESETS: the restart counters [B] uint32 (while restart noise is on)
+MAX_RESTART_TRIES = 32           # SFM_BATCH_MAX_RESTART_TRIES
+
+
+def pack_restart_noise(seeds, pos_box, scene_off, goal_box=None, min_gap=0.0, point_gap=0.0, tries=8, track_delay=None, vehicles=None):
+    """Restart noise -> the arguments of sfm_batch_set_restart_noise: (seeds uint32 [B], pos_hx, pos_hy float32 [N_total], goal_hx,
+    goal_hy float32 [N_total] or None, min_gap, point_gap float32 [B], tries int, track_delay int32 [M] or None).  ``seeds``: a
+    scalar (broadcast to every scene) or B integers 0 .. 2^32-1.  ``pos_box`` / ``goal_box``: half-extents (hx, hy) in metres -- a
+    list with one entry per scene (each (N_b,2), or one (2,) pair for the whole scene), or an ndarray (N_total,2), or one (2,) pair
+    for every row; finite, >= 0 and <= 1e6 in float32; ``goal_box=None``: the goals stay.  ``min_gap`` / ``point_gap``: a scalar or B
+    values in metres, finite, >= 0 and <= 1e6.  ``tries``: an integer 1 .. 32.  ``track_delay``: None, or ``vehicles`` (M) integers
+    0 .. 2^31-1, one per device-side vehicle in scene order (a scalar is broadcast).  Pure NumPy; raises ValueError on a shape that
+    does not fit and on every value the library would refuse."""
+    so = np.asarray(scene_off)
+    B, n = len(so) - 1, int(so[-1])
+    sd = per_scene(seeds, "seeds", B, "iu")
+    if (sd < 0).any() or (sd > 0xFFFFFFFF).any():
+        raise ValueError("seeds must be integers 0 .. 2^32-1")
+    if isinstance(tries, (bool, np.bool_)) or not isinstance(tries, (int, np.integer)) or not 1 <= int(tries) <= MAX_RESTART_TRIES:
+        raise ValueError(f"tries must be an integer 1 .. {MAX_RESTART_TRIES}, got {tries!r}")
+
+    def box(v, name):
+        a = _per_scene(v, so, 3, name)
+        if a.shape[0] and a[:, 2].any():
+            raise ValueError(f"{name} must hold two half-extents (hx, hy) per row")
+        with np.errstate(over="ignore", invalid="ignore"):
+            h = np.ascontiguousarray(a[:, :2], dtype=np.float32)
+        if not (np.isfinite(h).all() and (h >= 0).all() and (h <= np.float32(MAX_SENSE_RANGE)).all()):
+            raise ValueError(f"{name} must be finite, >= 0 and <= {MAX_SENSE_RANGE:g} metres")
+        return f32(h[:, 0]), f32(h[:, 1])
+
+    phx, phy = box(pos_box, "pos_box")
+    ghx, ghy = (None, None) if goal_box is None else box(goal_box, "goal_box")
+    gaps = [per_scene_metres(v, name, B, False) for v, name in ((min_gap, "min_gap"), (point_gap, "point_gap"))]
+    delay = None
+    if track_delay is not None:
+        if vehicles is None:
+            raise ValueError("track_delay needs the number of device-side vehicles (vehicles=M)")
+        d = per_scene(track_delay, "track_delay", int(vehicles), "iu").astype(np.int64)
+        if (d < 0).any() or (d >= 2**31).any():
+            raise ValueError("track_delay must be >= 0 and fit int32")
+        delay = np.ascontiguousarray(d, dtype=np.int32)
+    return np.ascontiguousarray(sd, dtype=np.uint32), phx, phy, ghx, ghy, gaps[0], gaps[1], int(tries), delay
+
+
 OBS_HEADER = 16                  # SFM_BATCH_OBS_HEADER: floats of a row's record in front of its neighbour slots
 MAX_OBS_NEIGHBOURS = 16          # SFM_BATCH_MAX_OBS_NEIGHBOURS
 
@@ -746,6 +801,7 @@ class SfmBatch:
         self.obs_k = None                 # neighbour slots of set_observation (None: observations are off)
         self.has_episodes = False         # set_episodes has been called and no later call has dropped it
         self.scan_rays = None             # rays per row of set_scan (None: scans are off)
+        self.has_restart_noise = False    # set_restart_noise has been called and no later call has dropped it
 
     def _check(self, rc, what):
         if rc != 0:
@@ -823,6 +879,7 @@ class SfmBatch:
         self.obs_k = None                 # (the upload dropped the observations with the rows)
         self.has_episodes = False         # ... and the episodes
         self.scan_rays = None             # ... and the scans
+        self.has_restart_noise = False    # ... and the restart noise
         self.planar = planar
         self._z = pk["z"].copy()          # a planar batch keeps each scene's z on the host (the device holds x / y only)
 
@@ -918,6 +975,55 @@ class SfmBatch:
             ptr = mask.data_ptr()
         self._check(self._lib.sfm_batch_restart_device(self._b, C.c_void_p(ptr or None)), "sfm_batch_restart_device")
 
+    def set_restart_noise(self, seeds, pos_box, goal_box=None, min_gap=0.0, point_gap=0.0, tries=8, track_delay=None):
+        """How a restarted scene may differ from the snapshot (sfm_batch_set_restart_noise; see ``pack_restart_noise`` and the
+        module docstring): every restart -- ``restart``, ``restart_device``, ``end_step(auto_restart=True)`` -- is followed by one
+        more launch that draws each row's start from the box ``pos_box`` around its snapshot position, again (up to ``tries``
+        times) while it is nearer than ``min_gap`` to a row that is placed or to a lower-index proposal, or nearer than
+        ``point_gap`` to a point of the scene's geometry; draws each live row's goal from ``goal_box`` around the snapshot goal;
+        and lets a tracked vehicle arrive up to ``track_delay`` ticks later.  Keyed by the scene's seed and its restart counter:
+        reproducible, and the same alone or in any batch (``reset.resample_scene`` is the host twin).  ``pos_box=None`` switches it
+        off.  Needs ``upload`` first, which also drops it; every other call keeps it (the delays go with the tracks), and it
+        keeps the snapshot.  Zeroes the counters (``reset_count_tensor()`` must be taken again)."""
+        L = self._lib
+        if pos_box is None:
+            self._check(L.sfm_batch_set_restart_noise(self._b, *([None] * 7), 0, None), "sfm_batch_set_restart_noise")
+            self.has_restart_noise = False
+            return
+        self._need_upload("set_restart_noise")
+        M = int(self._dyn[0][-1]) if self._dyn is not None else 0
+        sd, phx, phy, ghx, ghy, g1, g2, tries, delay = pack_restart_noise(seeds, pos_box, self.scene_off, goal_box, min_gap, point_gap,
+                                                                           tries, track_delay, M)
+        if phx.shape[0] == 0:                                          # (no rows: the library takes any non-NULL pointer)
+            phx = phy = np.zeros(1, np.float32)
+            ghx = ghy = None if ghx is None else np.zeros(1, np.float32)
+        if delay is not None and delay.shape[0] == 0:
+            delay = np.zeros(1, np.int32)
+        self._check(L.sfm_batch_set_restart_noise(self._b, sd.ctypes.data, fptr(phx), fptr(phy), fptr(ghx), fptr(ghy), fptr(g1), fptr(g2),
+                                                  tries, iptr(delay)), "sfm_batch_set_restart_noise")
+        self.has_restart_noise = True
+
+    def restart_noise(self):
+        """(resets (B,) uint32, fallbacks (B,) uint32): how often each scene has restarted since ``set_restart_noise``, and how many
+        rows of its latest restart no try could place (they start at their snapshot position).  Synchronises the batch's stream;
+        raises SfmLibraryError while restart noise is off."""
+        resets, fallbacks = np.zeros(self.B, np.uint32), np.zeros(self.B, np.uint32)
+        self._check(self._lib.sfm_batch_download_restart_noise(self._b, resets.ctypes.data, fallbacks.ctypes.data),
+                    "sfm_batch_download_restart_noise")
+        return resets, fallbacks
+
+    def reset_count_tensor(self, device=None):
+        """``resets`` as a torch tensor (B,) that aliases device memory (no copy; int32 bits of the uint32 counters): the episode
+        index a curriculum or a logger reads on the device.  Take it again after ``upload`` or ``set_restart_noise``.  Raises
+        SfmLibraryError while restart noise is off."""
+        if not self.has_restart_noise:
+            raise SfmLibraryError("SfmBatch.reset_count_tensor: restart noise is off (set_restart_noise; upload drops it)")
+        nbytes = C.c_int64(0)
+        ptr = self._lib.sfm_batch_device_ptr(self._b, PTR_RESETS, C.byref(nbytes))
+        if not ptr:
+            self._check(-1, "sfm_batch_device_ptr")
+        return self._alias(ptr, (self.B,), device, "<i4")
+
     def set_episodes(self, agent, goal_radius=0.0, ped_radius=0.0, veh_radius=0.0, max_steps=0):
         """Which row of every scene is its agent and what ends its episode (sfm_batch_set_episodes; see ``episode_arrays`` and the
         module docstring).  ``agent=None`` switches episodes off and frees the buffers.  Needs ``upload`` first, which also drops
@@ -1001,8 +1107,9 @@ class SfmBatch:
 
     def device_ptr(self, which):
         """(address, bytes) of a device buffer of the batch (sfm_batch_device_ptr): ``PTR_COMMANDS``, ``PTR_STATE``,
-        ``PTR_ZSTATE`` ((0, 0) for a planar batch), ``PTR_EPISODES``, ``PTR_DONE`` or ``PTR_SCAN``.  Valid until the next ``upload``
-        (the command buffer: or ``set_steering``; the episode buffers: or ``set_episodes``; the scan buffer: or ``set_scan``)."""
+        ``PTR_ZSTATE`` ((0, 0) for a planar batch), ``PTR_EPISODES``, ``PTR_DONE``, ``PTR_SCAN`` or, while restart noise is on,
+        ``PTR_RESETS``.  Valid until the next ``upload`` (the command buffer: or ``set_steering``; the episode buffers: or
+        ``set_episodes``; the scan buffer: or ``set_scan``; the restart counters: or ``set_restart_noise``)."""
         nbytes = C.c_int64(0)
         self._need_upload("device_ptr")
         ptr = self._lib.sfm_batch_device_ptr(self._b, int(which), C.byref(nbytes))

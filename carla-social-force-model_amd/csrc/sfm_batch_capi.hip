@@ -62,6 +62,7 @@ static int check_batch_commands(SfmBatch* b, const float4* kinds, const uint8_t*
 
 // What the drops take along: the tracks refer to the boxes, the spawn schedule to the modes.  (The caller synchronised the stream.)
 static void drop_batch_boxes(SfmBatch* b) {
+    drop_noise_delays(b);
     b->tracks = {};
     b->boxes = {};
 }
@@ -250,9 +251,11 @@ int sfm::batch_restart_checks(SfmBatch* b, const uint8_t* mask, const std::strin
         if (mask && !mask[k]) continue;
         for (int v = b->boxes.item_off_h[k]; v < b->boxes.item_off_h[k + 1]; ++v) {
             const long long first = (long long)b->snap.first_h[v] + *shift;
-            if (b->tracks.off_h[v + 1] > b->tracks.off_h[v] && (first < INT32_MIN || first > INT32_MAX))
+            if (b->tracks.off_h[v + 1] > b->tracks.off_h[v] && (first < INT32_MIN || first + b->noise.max_delay > INT32_MAX))
                 return bfail(b, SFM_ERR_INVALID, "scene " + std::to_string(k) + ", vehicle " + std::to_string(v) + ": its first tick moved by the " +
-                                                 std::to_string(*shift) + " ticks since the snapshot does not fit int32: set the tracks "
+                                                 std::to_string(*shift) + " ticks since the snapshot" +
+                                                 (b->noise.max_delay ? " and by the largest delay of the restart noise, " + std::to_string(b->noise.max_delay) + "," : "") +
+                                                 " does not fit int32: set the tracks "
                                                  "again (sfm_batch_set_vehicle_tracks restarts the tick counter)");
         }
     }
@@ -265,7 +268,7 @@ int sfm::batch_restart_device(SfmBatch* b, const uint8_t* d_mask, long long shif
     r.mask = d_mask;
     HIP_TRY(b, launch_batch_restart(r, b->B, b->stream));
     if (b->tracks.on) b->tracks.first_stale = true;                     // who was chosen is known on the device only
-    return SFM_OK;
+    return batch_restart_noise(b, nullptr, d_mask, b->B);
 }
 
 // sfm_batch_run_recorded, and with want_forces also the [F][K][N_total][C] force record of every recorded tick
@@ -416,6 +419,7 @@ int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x
     b->obs = {};                                                  // ... and its observations
     b->ep = {};                                                   // ... and its episodes (the agents are rows)
     b->scan = {};                                                 // ... and its scans (the mask is per row)
+    b->noise = {};                                                // ... and its restart noise (the boxes are per row)
     b->snap.on = false;                                           // ... and so is its snapshot
     b->have_state = false;
     if (n > 0) {
@@ -530,6 +534,7 @@ int sfm_batch_set_vehicle_tracks(SfmBatch* b, const int32_t* trk_off, const int3
         return bfail(b, SFM_ERR_STATE, "vehicle tracks need device-side vehicles: call sfm_batch_set_dynamic_boxes first");
     if (!trk_off) {                                              // tracks off: the vehicles run free from where they are
         HIP_TRY(b, hipStreamSynchronize(b->stream));
+        drop_noise_delays(b);
         b->tracks = {};
         b->snap.on = false;
         return SFM_OK;
@@ -557,6 +562,7 @@ int sfm_batch_set_vehicle_tracks(SfmBatch* b, const int32_t* trk_off, const int3
     std::vector<int32_t> first((size_t)M, 0);
     if (first_tick) first.assign(first_tick, first_tick + M);
     HIP_TRY(b, hipStreamSynchronize(b->stream));                 // a tick in flight may still read the old tracks
+    drop_noise_delays(b);
     b->tracks = {};
     b->snap.on = false;
     HIP_TRY(b, b->tracks.off.alloc((size_t)M + 1));
@@ -982,7 +988,7 @@ int sfm_batch_restart(SfmBatch* b, const uint8_t* mask) {
             for (int v = b->boxes.item_off_h[k]; v < b->boxes.item_off_h[k + 1]; ++v)
                 b->tracks.first_h[v] = b->tracks.off_h[v + 1] > b->tracks.off_h[v] ? (int32_t)((long long)b->snap.first_h[v] + shift) : b->snap.first_h[v];
         }
-    return SFM_OK;
+    return batch_restart_noise(b, r.list, nullptr, chosen);
 }
 
 // The restart with its mask on the device (ABI 16): no copy, no host scan, no event wait, no pinned list.

@@ -1,6 +1,7 @@
 // sfm_batch_host.h -- what the two host files of the batched scenes share: the batch itself (SfmBatch and the struct of each of its
 // features), its error plumbing, and the messages for a feature that is off.  sfm_batch_capi.hip holds the ticks and everything they
-// read or write; sfm_batch_sense_capi.hip the read-only sensors (observations, episode ends, range scans) and the device pointers.
+// read or write; sfm_batch_sense_capi.hip the read-only sensors (observations, episode ends, range scans) and the device pointers;
+// sfm_batch_reset_capi.hip the restart noise.
 #pragma once
 #include "sfm_capi_common.h"
 #include "sfm_metres.h"
@@ -133,6 +134,21 @@ struct BatchScanDev {
     DevBuf<float> buf;         // [N_total][2 R]
 };
 
+// restart noise (sfm_batch_set_restart_noise): how a restarted scene may differ from the snapshot, and the two per-scene counters the
+// noise kernel keeps; an input the restarts only read, like steering.  The delays refer to the tracks and are dropped with them.
+struct BatchNoiseDev {
+    bool on = false;
+    int tries = 0;
+    DevBuf<uint32_t> seed;         // [B]
+    DevBuf<uint32_t> resets;       // [B] restarts of the scene since the noise was set
+    DevBuf<uint32_t> fallbacks;    // [B] rows of the scene's latest restart that no try could place
+    DevBuf<float2> gap2;           // [B] {min_gap^2, point_gap^2}
+    DevBuf<float2> pos_box;        // [N_total] {hx, hy}
+    DevBuf<float2> goal_box;       // [N_total]; not allocated: the goals stay
+    DevBuf<int> delay;             // [M]; not allocated: no traffic timing
+    long long max_delay = 0;       // the largest delay: what a restart's int32 fit check adds
+};
+
 struct BatchRecordDev {        // grow-only device buffers of the recording calls
     DevBuf<float4> frames;     // sfm_batch_run_recorded
     DevBuf<float2> zframes;
@@ -170,6 +186,7 @@ struct SfmBatch {
     sfm::BatchObsDev obs;
     sfm::BatchEpisodeDev ep;
     sfm::BatchScanDev scan;
+    sfm::BatchNoiseDev noise;
     sfm::Event c_done;                      // created by the first sfm_batch_set_steering with rows; outlives every drop of the steering
     std::string err;
 };
@@ -195,6 +212,7 @@ constexpr const char* NO_SNAPSHOT = "the batch has no snapshot: call sfm_batch_s
 constexpr const char* STEERING_OFF = "steering is off: call sfm_batch_set_steering first (sfm_batch_upload_state drops it)";
 constexpr const char* OBSERVATIONS_OFF = "observations are off: call sfm_batch_set_observation first (sfm_batch_upload_state drops them)";
 constexpr const char* EPISODES_OFF = "episodes are off: call sfm_batch_set_episodes first (sfm_batch_upload_state drops them)";
+constexpr const char* NOISE_OFF = "restart noise is off: call sfm_batch_set_restart_noise first (sfm_batch_upload_state drops it)";
 constexpr const char* SCANS_OFF = "scans are off: call sfm_batch_set_scan first (sfm_batch_upload_state drops them)";
 
 // one kind of the scenes' geometry as the kernels take it, and what the sensors see of the scenes
@@ -208,5 +226,10 @@ inline BatchSceneView batch_scene_view(const SfmBatch* b) {
 // nothing); a tracked vehicle of scene k (mask null or mask[k]) whose first tick, moved by *shift, does not fit int32.
 int batch_restart_checks(SfmBatch* b, const uint8_t* mask, const std::string& bad_choice, long long* shift);
 int batch_restart_device(SfmBatch* b, const uint8_t* d_mask, long long shift);
+// The noise launch of a restart (sfm_batch_reset_capi.hip), right behind launch_batch_restart on the batch's stream with the same
+// choice of scenes; nothing while the noise is off.  With delays set it marks the host's copy of the tracks' first ticks stale.
+int batch_restart_noise(SfmBatch* b, const int* d_list, const uint8_t* d_mask, int scenes);
+// The delays go with the tracks they refer to (the caller synchronised the stream).
+inline void drop_noise_delays(SfmBatch* b) { b->noise.delay = {}; b->noise.max_delay = 0; }
 
 }  // namespace sfm

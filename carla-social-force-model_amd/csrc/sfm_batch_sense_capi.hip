@@ -20,7 +20,7 @@ static int check_frame(SfmBatch* b, int frame) {
 
 // One lookup for the device buffers a caller may see: which = SFM_BATCH_PTR_*, or PTR_OBSERVATIONS for sfm_batch_observation_ptr's.
 // off: why there is none (its feature is off, no state was uploaded), else p and bytes -- both 0 where the buffer has no element.
-constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_SCAN + 1;     // (not part of the ABI: sfm_batch_device_ptr refuses it)
+constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_RESETS + 1;   // (not part of the ABI: sfm_batch_device_ptr refuses it)
 struct BatchBuffer { const char* off; void* p; size_t bytes; };
 static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     const size_t n = (size_t)b->n_total, B = (size_t)b->B;
@@ -36,6 +36,9 @@ static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     case SFM_BATCH_PTR_DONE:
         if (!b->ep.on) return {EPISODES_OFF, nullptr, 0};
         return which == SFM_BATCH_PTR_EPISODES ? have(b->ep.record, 8 * sizeof(float) * B) : have(b->ep.done, B);
+    case SFM_BATCH_PTR_RESETS:
+        if (!b->noise.on) return {NOISE_OFF, nullptr, 0};
+        return have(b->noise.resets, sizeof(uint32_t) * B);
     }
     if (!b->have_state) return {NO_STATE, nullptr, 0};
     if (which == SFM_BATCH_PTR_COMMANDS) {
@@ -71,7 +74,10 @@ extern "C" {
 void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes) {
     if (bytes) *bytes = 0;
     if (!b) return nullptr;
-    if (which < SFM_BATCH_PTR_COMMANDS || which > SFM_BATCH_PTR_SCAN) { bfail(b, SFM_ERR_INVALID, "which must be SFM_BATCH_PTR_COMMANDS, _STATE, _ZSTATE, _EPISODES, _DONE or _SCAN"); return nullptr; }
+    // SFM_BATCH_PTR_RESETS came without an ABI bump: while restart noise is off it is refused as the unknown value it was, word for
+    // word, so a caller of ABI 17 as it was sees no difference
+    const int last = b->noise.on ? SFM_BATCH_PTR_RESETS : SFM_BATCH_PTR_SCAN;
+    if (which < SFM_BATCH_PTR_COMMANDS || which > last) { bfail(b, SFM_ERR_INVALID, "which must be SFM_BATCH_PTR_COMMANDS, _STATE, _ZSTATE, _EPISODES, _DONE or _SCAN"); return nullptr; }
     return buffer_ptr(b, which, which == SFM_BATCH_PTR_SCAN ? ", so which = SFM_BATCH_PTR_SCAN has no buffer" :
                                 which == SFM_BATCH_PTR_EPISODES || which == SFM_BATCH_PTR_DONE ? ", so which = SFM_BATCH_PTR_EPISODES / _DONE has no buffer" : "", bytes);
 }

@@ -52,6 +52,7 @@ hipError_t launch_batch_park_unborn(const int* scene_off, const uint8_t* born, f
 hipError_t launch_batch_place_tracks(const BatchTracks& t, const int* off, const float2* local, float4* ctr, float2* pts, int M,
                                      hipStream_t st);
 hipError_t launch_batch_restart(const BatchRestart& r, int scenes, hipStream_t st);
+hipError_t launch_batch_restart_noise(const RestartNoiseArgs& a, int scenes, hipStream_t st);
 hipError_t launch_batch_observe(const ObserveArgs& a, int B, hipStream_t st);
 hipError_t launch_batch_episode(const EpisodeArgs& a, int B, hipStream_t st);
 hipError_t launch_batch_scan(const ScanArgs& a, int B, hipStream_t st);

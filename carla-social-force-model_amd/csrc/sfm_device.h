@@ -45,6 +45,21 @@ __device__ __forceinline__ float waypoint_coord(uint32_t seed, uint32_t ped, uin
     return (float)(h >> 8) * 5.9604644775390625e-08f * side;   // 2^-24
 }
 
+// Counter-based restart noise (sfm_batch_set_restart_noise): the random word of component c of try t of restart e of item i -- a row's
+// index inside its scene, or a vehicle's -- under the scene's seed is
+//     h = mix32(seed ^ mix32(mix32(RESET_SALT ^ (8 i + c)) + 0x9E3779B9 (32 e + t))),        u = (h >> 8) * 2^-24 in [0, 1)
+// (c: 0, 1 the position offset; 2, 3 the goal offset, t = 0; 4 a vehicle's delay, t = 0; t < 32).  RESET_SALT and the inner mix keep
+// the words apart from waypoint_coord's under an equal seed.  An offset inside a box of half-extent ext is o = fmaf(2 u, ext, -ext)
+// in [-ext, ext): 2 u is exact.
+constexpr uint32_t RESET_SALT = 0x5BD1E995u;
+__device__ __forceinline__ uint32_t reset_word(uint32_t seed, uint32_t i, uint32_t e, uint32_t t, uint32_t c) {
+    return mix32(seed ^ mix32(mix32(RESET_SALT ^ (8u * i + c)) + 0x9E3779B9u * (32u * e + t)));
+}
+__device__ __forceinline__ float reset_offset(uint32_t h, float ext) {
+    const float u = (float)(h >> 8) * 5.9604644775390625e-08f;   // 2^-24
+    return fmaf(2.0f * u, ext, -ext);
+}
+
 struct Geo {                  // CSR polylines / rings
     const int* off;           // [K+1]
     const float2* pts;        // [P] {x, y}
@@ -379,6 +394,31 @@ struct ScanArgs : BatchSceneView {
     float* out;               // [N_total][2 R]: ranges, then kinds
     int R;                    // rays per row, 1 .. SCAN_MAX_RAYS
     int frame;                // 0 world axes, 1 the row's heading frame
+};
+
+// Restart noise of a batch (sfm_batch_set_restart_noise, sfm_batch_restart_noise_kernel in sfm_batch_reset.hip): launched behind
+// sfm_batch_restart_kernel with the same choice of scenes (list / mask as in BatchRestart); the rule is specified in include/sfm_hip.h.
+constexpr int RESET_MAX_TRIES = 32;
+struct RestartNoiseArgs {
+    BatchSceneView v;         // the scene offsets and the geometry; v.pk / v.own are the arrays below
+    const int* list;          // [grid] the chosen scenes; null: workgroup g takes scene g
+    const uint8_t* mask;      // [B] on the device; null: every workgroup of the grid takes its scene
+    float4* pk;               // {x, y, vx, vy}: x, y of the placed rows are rewritten
+    float4* own;              // {wx, wy, ..}: wx, wy of the live rows are rewritten while goal_box is set
+    const uint32_t* seed;     // [B]
+    uint32_t* resets;         // [B] e: restarts of the scene since the noise was set
+    uint32_t* fallbacks;      // [B] rows of the scene's latest restart that no try could place
+    const float2* pos_box;    // [N_total] {hx, hy}
+    const float2* goal_box;   // [N_total]; null: the goals stay
+    const float2* gap2;       // [B] {min_gap^2, point_gap^2}, each formed in double and rounded once
+    int tries;                // 1 .. RESET_MAX_TRIES
+    // traffic timing; delay == null: off
+    const int* delay;         // [M] per vehicle, >= 0
+    int* first;               // [M] the tracks' first ticks (BatchTracks::first, writable)
+    BatchTracks trk;          // .tick: the tick the vehicles are placed for (tau: what the next tick reads)
+    const float2* veh_local;  // [P] ring points in the vehicle frame
+    float4* veh_ctr;          // [M] the half of the ping-pong the next tick reads
+    float2* veh_pts;          // [P]
 };
 
 static_assert(sizeof(BatchSceneView) == 120 && sizeof(ObserveArgs) == 120 + 24 && sizeof(EpisodeArgs) == 120 + 40 && sizeof(ScanArgs) == 120 + 40,

@@ -659,6 +659,68 @@ int sfm_batch_download_episodes(SfmBatch* b, float* record, uint8_t* done);
  * sfm_batch_download_vehicle_tracks or sfm_batch_snapshot, which synchronise.  Refused with nothing launched: no snapshot
  * (SFM_ERR_STATE), d_mask NULL (SFM_ERR_INVALID). */
 int sfm_batch_restart_device(SfmBatch* b, const uint8_t* d_mask);
+/* Restart noise: randomised restarts, sampled on the device.  Without it a restarted scene is the snapshot bit for bit, so every
+ * episode of a scene starts alike.  With it, every restart of a scene -- sfm_batch_restart, sfm_batch_restart_device, the auto
+ * restart of sfm_batch_end_step -- is followed, on the batch's stream, by ONE more launch (sfm_batch_restart_noise_kernel, a
+ * workgroup per scene with the same choice of scenes) that draws the starts from a box around each row's snapshot position,
+ * re-draws them until nobody is too near anybody or anything, draws the goals from a box around the snapshot goal and lets
+ * scripted traffic arrive later.  Every draw is keyed by a counter, so a restart is reproducible.  A batch that never sets restart
+ * noise launches exactly what it launched before.
+ * These two entry points and SFM_BATCH_PTR_RESETS were added WITHOUT a bump of SFM_ABI_VERSION (it stays 17): they are additions
+ * only, nothing that existed changes its meaning, and a build that has them is recognised by the symbols themselves.
+ *
+ * Settings.  seeds [B] uint32.  pos_hx, pos_hy [N_total]: the half-extents (metres) of the box a row's start is drawn from, finite,
+ * 0 <= h <= SFM_BATCH_MAX_SENSE_RANGE; goal_hx, goal_hy [N_total] likewise for the goal, both NULL: the goals stay.  min_gap,
+ * point_gap [B]: metres, finite, 0 <= g <= SFM_BATCH_MAX_SENSE_RANGE; the kernel compares against g2 = float32(double(g) * g),
+ * formed in double and rounded once like R2.  tries: 1 .. SFM_BATCH_MAX_RESTART_TRIES, one value for the batch.  track_delay [M]
+ * int32 >= 0 per device-side vehicle, or NULL: none.
+ *
+ * The rule, all exact: every value is one correctly rounded fp32 operation or an fmaf, every decision a strict `<`.  For a scene b
+ * that restarts, first sfm_batch_restart_kernel's copies run unchanged.  Then, with e = resets[b] read before this restart:
+ * 1. Random numbers.  The word of component c of try t for item i (a row's index inside its scene, or a vehicle's) is
+ *        h = mix32(seed_b ^ mix32(mix32(0x5BD1E995 ^ (8 i + c)) + 0x9E3779B9 (32 e + t)))      (mod 2^32; mix32: lowbias32,
+ *    sfm_device.h, where this formula is reset_word), u = (h >> 8) * 2^-24 in [0, 1), and an offset inside a half-extent ext is
+ *    o = fmaf(2 u, ext, -ext), in [-ext, ext); 2 u is exact.  The constant and the inner mix32 keep the words apart from the
+ *    waypoint stream's under an equal seed.
+ * 2. Row classes, from the restored state.  Not live (sfm_batch_observe's test fails: unborn, despawned, NaN): untouched, and never
+ *    in anyone's way.  Fixed (live, hx == 0 and hy == 0): stays where it is and is a blocker from the start.  Movable: the rest.
+ * 3. Placement rounds t = 0 .. tries-1.  Every movable row not yet placed proposes p = (x_s + o_x, y_s + o_y) around its snapshot
+ *    position (components 0 and 1; each coordinate one fp32 add).  With d2 = fmaf(dx, dx, dy * dy) the proposal is rejected iff
+ *    d2 < min_gap2 to a blocker (a fixed row, or a row placed in an earlier round); or d2 < min_gap2 to the proposal of a
+ *    lower-index row of the SAME round, accepted or not; or d2 < point_gap2 to a point of the scene's borders, static obstacles
+ *    or vehicle rings as they stand after step 5.  A gap of 0 never rejects.  Accepted rows are placed and become blockers for the
+ *    next round.  (The lower-index rule is conservative on purpose: the outcome is a function of the proposals alone, whatever the
+ *    order of evaluation.)
+ * 4. Fallbacks.  A movable row still not placed after the last round stays at its snapshot position, unchecked; their number at the
+ *    scene's latest restart is fallbacks[b].  Velocities, z, modes and everything else stay as restored.
+ * 5. Traffic timing, BEFORE the rounds.  A tracked vehicle k (item i = its index inside the scene) with track_delay[k] = D > 0 gets
+ *    first_tick[k] += (uint64(h) * (D + 1)) >> 32 with the word of c = 4, t = 0 -- 0 .. D ticks -- and is placed again as tau sees
+ *    it, the computation of sfm_batch_set_vehicle_tracks: centre, velocity and ring of its keyframe, absent -> +inf.
+ *    A restart's int32 fit check adds the largest delay, and the host's copy of the first ticks is refreshed from the device as
+ *    after sfm_batch_restart_device.
+ * 6. Goals.  With goal boxes, every live row's {wx, wy} gets + fmaf(2 u, g_ext, -g_ext) (components 2 and 3, t = 0); no rejection.
+ * 7. resets[b] = e + 1.
+ * A scene's result depends on its own seed, its own rows and e only: it is bitwise the same alone or anywhere in any batch.  Scenes
+ * that are not chosen are not touched, counters included.
+ *
+ * sfm_batch_set_restart_noise allocates the settings and zero-fills resets and fallbacks, and waits for the batch's stream; seeds =
+ * NULL switches the noise off and frees them.  It builds the new buffers before it drops the old ones.  Refused with nothing
+ * changed (the noise set before stays in force): before sfm_batch_upload_state (SFM_ERR_STATE); tries outside 1 .. 32; a
+ * half-extent or gap that is NaN, negative, infinite or > 1e6; NULL pos_hx / pos_hy with rows, only one of goal_hx / goal_hy, NULL
+ * min_gap / point_gap; a negative track_delay; track_delay without vehicle tracks (SFM_ERR_STATE).  Restart noise is an input like
+ * steering: sfm_batch_upload_state drops it, because the rows may differ; every other call keeps it, and it keeps the snapshot --
+ * except that the delays go with the tracks they refer to (sfm_batch_set_vehicle_tracks, sfm_batch_set_dynamic_boxes and
+ * sfm_batch_set_dynamic_obstacles drop the delays and keep the rest).
+ * sfm_batch_download_restart_noise synchronises the batch's stream and copies resets and fallbacks ([B] uint32 each; NULL skips a
+ * column); SFM_ERR_STATE while the noise is off.  SFM_BATCH_PTR_RESETS (sfm_batch_device_ptr): resets on the device, [B] uint32,
+ * valid until the next sfm_batch_set_restart_noise or sfm_batch_upload_state; while the noise is off the value is refused as the
+ * unknown `which` it was before. */
+#define SFM_BATCH_PTR_RESETS 6
+#define SFM_BATCH_MAX_RESTART_TRIES 32
+int sfm_batch_set_restart_noise(SfmBatch* b, const uint32_t* seeds, const float* pos_hx, const float* pos_hy, const float* goal_hx,
+                                const float* goal_hy, const float* min_gap, const float* point_gap, int tries,
+                                const int32_t* track_delay);
+int sfm_batch_download_restart_noise(SfmBatch* b, uint32_t* resets, uint32_t* fallbacks);
 /* Range scans on the device (ABI 17): the sensor most crowd-navigation policies are trained on.  R rays around a row, each giving
  * the distance to the first thing it meets and what that was, by ONE launch of sfm_batch_scan_kernel (a workgroup per scene)
  * straight from the buffers the tick reads, into a device buffer the caller reads with no copy.  The record is defined bit for bit
