@@ -33,10 +33,12 @@ SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_
                             "sfm_batch_observation_ptr")},
          **{n: 16 for n in ("sfm_batch_set_episodes", "sfm_batch_end_step", "sfm_batch_download_episodes",
                             "sfm_batch_restart_device")},
-         # (the restart noise came without a bump of the ABI number: additions only, include/sfm_hip.h says why)
+         # (the restart noise and the grids came without a bump of the ABI number: additions only, include/sfm_hip.h says why)
          **{n: 17 for n in ("sfm_batch_set_scan", "sfm_batch_scan", "sfm_batch_download_scan",
-                            "sfm_batch_set_restart_noise", "sfm_batch_download_restart_noise")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
-UNBUMPED = ("sfm_batch_set_restart_noise", "sfm_batch_download_restart_noise")   # ... and those a build of the SAME number may lack
+                            "sfm_batch_set_restart_noise", "sfm_batch_download_restart_noise",
+                            "sfm_batch_set_grid", "sfm_batch_grid", "sfm_batch_download_grid")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
+UNBUMPED = ("sfm_batch_set_restart_noise", "sfm_batch_download_restart_noise",
+            "sfm_batch_set_grid", "sfm_batch_grid", "sfm_batch_download_grid")   # ... and those a build of the SAME number may lack
 
 FORCE_NAMES = ("acceleration_force", "pedestrian_force", "border_force",
                "static_obstacle_force", "dynamic_obstacle_force")
@@ -167,6 +169,10 @@ SYMBOLS = {
     # batch restart noise (ABI 17, added without a bump)
     "sfm_batch_set_restart_noise": (C.c_int, [_H, _U32, _F, _F, _F, _F, _F, _F, C.c_int, _I]),
     "sfm_batch_download_restart_noise": (C.c_int, [_H, _U32, _U32]),
+    # batch occupancy grids (ABI 17, added without a bump)
+    "sfm_batch_set_grid": (C.c_int, [_H, C.c_int, _F, _U8, C.c_int]),
+    "sfm_batch_grid": (C.c_int, [_H]),
+    "sfm_batch_download_grid": (C.c_int, [_H, _F]),
 }
 
 _lib = None

@@ -104,6 +104,17 @@ later -- all keyed by the scene's seed and its restart counter, so reproducible 
 ``restart_noise()`` downloads the counters (restarts per scene, rows of the latest restart no try could place),
 ``reset_count_tensor()`` aliases the first, and ``reset.resample_scene`` is the host twin, bit for bit (the exact rule:
 include/sfm_hip.h): examples/batch_rl_loop_randomised.py.
+
+Occupancy grids (ABI 17, added without a bump): the local map of a CNN policy, computed on the device by one launch per call.
+``set_grid(cell, G=..., mask=..., frame=...)`` chooses a G x G grid (G <= 32) of ``cell`` metres per cell (one value, or one per
+scene) centred on every gridded row, in world axes or in the row's heading frame (x forward).  ``grid()`` fills, per gridded row,
+6 channels of G x G floats: the number of other live pedestrians per cell, the sum of their velocities relative to the row (two
+channels; a sum, divide by the count for a mean), and the number of sampled border, static-obstacle and vehicle points per cell
+-- the geometry a torch sequence over ``state_tensor()`` cannot see.  The rows named by ``mask`` get compact slots in ascending
+row order, so the buffer is ``(M, 6, G, G)`` for M gridded rows, not one record per row of the batch.  ``grids()`` downloads them
+per scene, ``grid_rows()`` names the row of every slot, ``grid_tensor()`` is the buffer as a torch tensor a conv layer reads as it
+stands, and ``grid.grid_scene`` is the host twin, bit for bit in both frames, velocity sums included (the record and its exact
+rules: include/sfm_hip.h).  Gridding changes nothing a tick reads: examples/batch_grid_loop.py.
 """
 from __future__ import annotations
 
@@ -112,6 +123,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import grid as _grid
 from . import scan as _scan
 from ._args import FRAME_HEADING, FRAME_WORLD, MAX_METRES as MAX_SENSE_RANGE, check_frame, per_scene, per_scene_metres
 from ._lib import SfmLibraryError, f32, fptr, iptr, u8ptr
@@ -552,6 +564,7 @@ STEER_OFF, STEER_VELOCITY, STEER_PREFERRED = 0, 1, 2   # the kinds of a steered 
 PTR_COMMANDS, PTR_STATE, PTR_ZSTATE = 0, 1, 2          # SFM_BATCH_PTR_*: what sfm_batch_device_ptr / SfmBatch.device_ptr select
 PTR_EPISODES, PTR_DONE = 3, 4                          # ... the episode record [B][8] and the mask done[B] (while episodes are on)
 PTR_SCAN = 5                                           # ... the scan record [N_total][2R] (while scans are on)
+PTR_GRID = 7                                           # ... the grid record [M][6][G][G] (while grids are on; 6 is PTR_RESETS)
 
 
 def _per_scene(v, so, width, name):
@@ -801,6 +814,8 @@ class SfmBatch:
         self.obs_k = None                 # neighbour slots of set_observation (None: observations are off)
         self.has_episodes = False         # set_episodes has been called and no later call has dropped it
         self.scan_rays = None             # rays per row of set_scan (None: scans are off)
+        self.grid_cells = None            # cells per side of set_grid (None: grids are off)
+        self._grid_rows = self._grid_counts = None
         self.has_restart_noise = False    # set_restart_noise has been called and no later call has dropped it
 
     def _check(self, rc, what):
@@ -879,6 +894,8 @@ class SfmBatch:
         self.obs_k = None                 # (the upload dropped the observations with the rows)
         self.has_episodes = False         # ... and the episodes
         self.scan_rays = None             # ... and the scans
+        self.grid_cells = None            # ... and the grids
+        self._grid_rows = self._grid_counts = None
         self.has_restart_noise = False    # ... and the restart noise
         self.planar = planar
         self._z = pk["z"].copy()          # a planar batch keeps each scene's z on the host (the device holds x / y only)
@@ -1108,13 +1125,16 @@ class SfmBatch:
     def device_ptr(self, which):
         """(address, bytes) of a device buffer of the batch (sfm_batch_device_ptr): ``PTR_COMMANDS``, ``PTR_STATE``,
         ``PTR_ZSTATE`` ((0, 0) for a planar batch), ``PTR_EPISODES``, ``PTR_DONE``, ``PTR_SCAN`` or, while restart noise is on,
-        ``PTR_RESETS``.  Valid until the next ``upload`` (the command buffer: or ``set_steering``; the episode buffers: or
-        ``set_episodes``; the scan buffer: or ``set_scan``; the restart counters: or ``set_restart_noise``)."""
+        ``PTR_RESETS``, or, while grids are on, ``PTR_GRID`` ((0, 0) without gridded rows).  Valid until the next ``upload`` (the
+        command buffer: or ``set_steering``; the episode buffers: or ``set_episodes``; the scan buffer: or ``set_scan``; the
+        restart counters: or ``set_restart_noise``; the grid buffer: or ``set_grid``)."""
         nbytes = C.c_int64(0)
         self._need_upload("device_ptr")
         ptr = self._lib.sfm_batch_device_ptr(self._b, int(which), C.byref(nbytes))
         if not ptr and which in (PTR_EPISODES, PTR_DONE):
             self._check(-1, "sfm_batch_device_ptr")                    # (episodes are off: the library's message)
+        if not ptr and which == PTR_GRID and self.grid_cells is not None and len(self._grid_rows) == 0:
+            return 0, 0                                                # (grids are on and no row is gridded: no buffer)
         if not ptr and int(self.scene_off[-1]) > 0 and not (which == PTR_ZSTATE and self.planar):
             self._check(-1, "sfm_batch_device_ptr")                    # (without rows, and {z, vz} of a planar batch: no buffer)
         return int(ptr or 0), int(nbytes.value)
@@ -1243,6 +1263,66 @@ class SfmBatch:
             self._check(-1, "sfm_batch_device_ptr")
         w = 2 * self.scan_rays
         return self._alias(ptr, (int(nbytes.value) // (4 * w), w), device)
+
+    def set_grid(self, cell, G=16, mask=None, frame=0):
+        """What ``grid`` computes (sfm_batch_set_grid; see ``grid.grid_arrays`` and the module docstring): per gridded row a
+        ``G`` x ``G`` grid (1 .. 32) of ``cell`` metres per cell (one value or one per scene) centred on the row, 6 channels.
+        ``mask``: which rows are gridded (``scan.scan_mask``: None every row, a list per scene of bool arrays or row indices, or a
+        bool array over the concatenated rows); they get the slots 0 .. M-1 in ascending row order (``grid_rows()``).  ``frame``: 0
+        world axes, 1 the row's heading frame.  ``cell=None`` switches grids off and frees the buffer.  Needs ``upload`` first,
+        which also drops them; every other call keeps them, and they keep the snapshot.  Allocates and zero-fills the buffer
+        (``grid_tensor()`` must be taken again)."""
+        L = self._lib
+        if cell is None:
+            self._check(L.sfm_batch_set_grid(self._b, 0, None, None, 0), "sfm_batch_set_grid")
+            self.grid_cells = self._grid_rows = self._grid_counts = None
+            return
+        self._need_upload("set_grid")
+        G, c, frame = _grid.grid_arrays(self.B, G, cell, frame)
+        m = _scan.scan_mask(mask, self.scene_off)
+        rows, counts = _grid.grid_slots(m, self.scene_off)
+        if m is not None and m.shape[0] == 0:
+            m = None
+        self._check(L.sfm_batch_set_grid(self._b, G, fptr(c), u8ptr(m), frame), "sfm_batch_set_grid")
+        self.grid_cells, self._grid_rows, self._grid_counts = G, rows, counts
+
+    def _need_grid(self, name):
+        if self.grid_cells is None:                                    # (the library's message, from the call itself)
+            self._check(self._lib.sfm_batch_grid(self._b), "sfm_batch_grid")
+            raise SfmLibraryError(f"SfmBatch.{name}: grids are off")
+
+    def grid(self):
+        """Compute the grids as the state is now (sfm_batch_grid): one launch on the batch's stream, ordered with the ticks and
+        restarts around it; the host does not wait.  Raises SfmLibraryError while grids are off."""
+        self._check(self._lib.sfm_batch_grid(self._b), "sfm_batch_grid")
+
+    def grid_rows(self):
+        """The global (concatenated) row of every slot of the grid buffer, int64 [M], ascending."""
+        self._need_grid("grid_rows")
+        return self._grid_rows.copy()
+
+    def grids(self):
+        """``grid()`` and a download: a list of B float32 arrays (m_b, 6, G, G) in scene order, m_b the scene's gridded rows in
+        ascending order (synchronises the batch's stream)."""
+        self.grid()
+        self._need_grid("grids")
+        G, M = self.grid_cells, len(self._grid_rows)
+        buf = np.zeros((M, _grid.GRID_CHANNELS, G, G), np.float32)
+        self._check(self._lib.sfm_batch_download_grid(self._b, fptr(buf) if M else None), "sfm_batch_download_grid")
+        cut = np.concatenate([[0], np.cumsum(self._grid_counts)])
+        return [buf[cut[s]:cut[s + 1]] for s in range(self.B)]
+
+    def grid_tensor(self, device=None):
+        """The grid buffer as a torch tensor (M, 6, G, G) float32 that aliases device memory (no copy): what a conv policy reads
+        after ``grid()``.  Put torch and the batch on one stream.  Take it again after ``upload`` or ``set_grid``.  Raises
+        SfmLibraryError while grids are off."""
+        self._need_grid("grid_tensor")
+        nbytes = C.c_int64(0)
+        ptr = self._lib.sfm_batch_device_ptr(self._b, PTR_GRID, C.byref(nbytes))
+        if not ptr and len(self._grid_rows) > 0:
+            self._check(-1, "sfm_batch_device_ptr")
+        G = self.grid_cells
+        return self._alias(ptr, (int(nbytes.value) // (4 * _grid.GRID_CHANNELS * G * G), _grid.GRID_CHANNELS, G, G), device)
 
     def set_waypoint_streams(self, seeds, world_sides, arrive_thresholds=2.0):
         """Per-scene waypoint streams for ``redraw=True`` (see ``stream_arrays``; scalars broadcast to every scene).  They stay in

@@ -420,6 +420,7 @@ int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x
     b->ep = {};                                                   // ... and its episodes (the agents are rows)
     b->scan = {};                                                 // ... and its scans (the mask is per row)
     b->noise = {};                                                // ... and its restart noise (the boxes are per row)
+    b->grid = {};                                                 // ... and its grids (the slots are per row)
     b->snap.on = false;                                           // ... and so is its snapshot
     b->have_state = false;
     if (n > 0) {

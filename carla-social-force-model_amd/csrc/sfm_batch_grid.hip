@@ -1,0 +1,238 @@
+// sfm_batch_grid.hip -- egocentric occupancy grids of batched scenes for gfx950 (MI355X): ONE launch for the whole batch
+// (sfm_batch_grid; the record and its rules are specified in include/sfm_hip.h).
+//
+// What a policy sees per agent: a G x G map centred on the row -- per cell the number of other pedestrians, the sum of their
+// velocities relative to the row, and the number of sampled border, static-obstacle and vehicle points.  Computed from the buffers
+// the tick reads (state, own, the scene offsets, the three geometry CSRs) into a device buffer [M][6][G][G] of floats, one compact
+// slot per gridded row.  The kernel writes nothing else, so a tick before or after it computes what it computed without it.
+//
+// Shape (workgroup b, 4 waves):
+//   1. the scene's {x, y, vx, vy} is staged in LDS and the geometry counts are cleared, then a barrier;
+//   2. the rows that have a slot are compacted, in ascending order, into an LDS list by ballots and per-wave counts; when the
+//      scene's geometry fits one tile of GRID_TILE points it is staged in LDS once, else every row reads it from memory (a point
+//      is used once per row, by one lane);
+//   3. per gridded row, in list order (a row that is not live gets its zeros and is done):
+//      (a) lane t takes pedestrians t, t + BLOCK, ..: the cell of each and its relative velocity; the sources that fall inside
+//          the grid are compacted, by ballots again and so in ascending j, into an LDS list {cell, relative velocity};
+//          every lane takes geometry points e, e + BLOCK, .. of the three kinds' contiguous runs and counts the cell of each with an
+//          integer LDS add (the result of integer adds does not depend on their order);
+//      (b) a lane owns the cells tid, tid + BLOCK, .. (G^2 <= 1024: up to 4) and walks the source list in order -- broadcast LDS
+//          reads -- counting its matches and adding their velocities: ascending j, fp32 adds from 0.0f, no float atomic;
+//   4. the lane stores the 6 channels of its cells (consecutive lanes store consecutive floats) and clears the geometry counts it
+//      read; the next row's adds come behind the barriers of its phase (a).
+// No register array is indexed at run time, so nothing goes to scratch.
+// Determinism: no float atomics, every order is a function of the scene alone -- a scene's record is bitwise the same alone or
+// anywhere in any batch.
+#include "sfm_device.h"
+
+#pragma clang fp contract(off)     // every operation of the rules is a single rounding, or an explicit fmaf
+
+namespace sfm {
+
+constexpr int GRID_TILE = 1024;    // geometry points the LDS tile holds
+
+struct GridShared {
+    float4 pk[BATCH_MAX_N];                                            // {x, y, vx, vy}
+    float2 tile[GRID_TILE];                                            // the scene's geometry points, when they fit
+    float2 rv[BATCH_MAX_N];                                            // the sources inside the grid, ascending: relative velocity ...
+    unsigned short cid[BATCH_MAX_N];                                   // ... and cell
+    unsigned short rows[BATCH_MAX_N];                                  // the gridded rows, ascending
+    int cnt[3][GRID_MAX_CELLS];                                        // geometry points per kind and cell
+    int wcount[WAVES_PER_BLOCK];
+};
+static_assert(sizeof(GridShared) <= 80 * 1024, "two workgroups share a CU's 160 KiB of LDS");
+
+// the rotation into the heading frame: the rules of include/sfm_hip.h
+__device__ __forceinline__ void grid_rotate(bool rot, float hx, float hy, float& a, float& b) {
+    if (rot) {
+        const float ra = fmaf(hx, a, hy * b), rb = fmaf(hx, b, -(hy * a));
+        a = ra;
+        b = rb;
+    }
+}
+
+// the cell [cv][cu] of a source at (ax, ay) relative to the row, as cv * G + cu; -1: outside (NaN and +-inf fail the compares)
+__device__ __forceinline__ int grid_cell(float ax, float ay, bool rot, float hx, float hy, float c, float half, float g, int G) {
+    grid_rotate(rot, hx, hy, ax, ay);
+    const float pu = ax / c + half;                                    // the division is rounded first (correctly: hipcc's default
+    const float pv = ay / c + half;                                    // for fp32 divide), then the sum
+    const bool in = pu >= 0.0f && pu < g && pv >= 0.0f && pv < g;
+    return in ? (int)pv * G + (int)pu : -1;
+}
+
+__global__ __launch_bounds__(BLOCK) void sfm_batch_grid_kernel(const GridArgs a) {
+    __shared__ GridShared sh;
+    const int b = blockIdx.x;
+    const int s0 = a.scene_off[b], n = a.scene_off[b + 1] - s0;        // 0 <= n <= BATCH_MAX_N (checked on the host)
+    if (n <= 0) return;
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int G = a.G, cells = G * G;                                  // 1 .. GRID_MAX_G, cells <= GRID_MAX_CELLS
+    for (int t = tid; t < n; t += BLOCK) sh.pk[t] = a.pk[s0 + t];
+    for (int q = tid; q < 3 * GRID_MAX_CELLS; q += BLOCK) (&sh.cnt[0][0])[q] = 0;
+    __syncthreads();
+
+    // 2. the gridded rows, ascending
+    int n_grid = 0;
+#pragma unroll 1
+    for (int base = 0; base < n; base += BLOCK) {                      // uniform
+        const int t = base + tid;
+        const bool want = t < n && (!a.slot || a.slot[s0 + t] >= 0);
+        const unsigned long long m = __ballot(want);
+        if (lane == 0) sh.wcount[wave] = __popcll(m);
+        __syncthreads();
+        int before = n_grid, all = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES_PER_BLOCK; ++w) {
+            const int cw = sh.wcount[w];
+            before += w < wave ? cw : 0;
+            all += cw;
+        }
+        if (want) sh.rows[before + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)t;
+        n_grid += all;
+        __syncthreads();                                               // the list; and wcount is rewritten by the next pass
+    }
+    if (n_grid == 0) return;                                           // uniform
+
+    // the scene's points per kind: one contiguous run of the kind's CSR (an empty kind's arrays are not read)
+    const int bk0 = a.geo[0].item_off[b], bk1 = a.geo[0].item_off[b + 1];
+    const int sk0 = a.geo[1].item_off[b], sk1 = a.geo[1].item_off[b + 1];
+    const int vk0 = a.geo[2].item_off[b], vk1 = a.geo[2].item_off[b + 1];
+    const int bp0 = bk1 > bk0 ? a.geo[0].off[bk0] : 0, nb = bk1 > bk0 ? a.geo[0].off[bk1] - bp0 : 0;
+    const int sp0 = sk1 > sk0 ? a.geo[1].off[sk0] : 0, ns = sk1 > sk0 ? a.geo[1].off[sk1] - sp0 : 0;
+    const int vp0 = vk1 > vk0 ? a.geo[2].off[vk0] : 0, nv = vk1 > vk0 ? a.geo[2].off[vk1] - vp0 : 0;
+    const int P = nb + ns + nv;                                        // virtual index e: borders, static, vehicles
+    const bool one_tile = P <= GRID_TILE;
+    auto point = [&](int e) {
+        return e < nb ? a.geo[0].pts[bp0 + e] : e < nb + ns ? a.geo[1].pts[sp0 + (e - nb)] : a.geo[2].pts[vp0 + (e - nb - ns)];
+    };
+    if (one_tile && P > 0) {                                           // the whole scene's geometry fits: staged once
+        for (int e = tid; e < P; e += BLOCK) sh.tile[e] = point(e);
+        __syncthreads();
+    }
+
+    const float c = a.cell[b], g = (float)G, half = 0.5f * g;          // (both exact)
+    const bool rot = a.frame != 0;                                     // uniform
+    const size_t per_row = (size_t)GRID_CHANNELS * (size_t)cells;
+#pragma unroll 1
+    for (int pos = 0; pos < n_grid; ++pos) {                           // uniform
+        const int row = __builtin_amdgcn_readfirstlane((int)sh.rows[pos]);
+        const float4 s = sh.pk[row];
+        const size_t slot = a.slot ? (size_t)a.slot[s0 + row] : (size_t)(s0 + row);
+        float* out = a.out + slot * per_row;
+        if (!row_live(s.x, s.y)) {                                     // uniform: a gridded row that is not live reads zeros
+            for (int q = tid; q < (int)per_row; q += BLOCK) out[q] = 0.0f;
+            continue;
+        }
+        const float x = s.x, y = s.y, vx = s.z, vy = s.w;
+        float hx = 1.0f, hy = 0.0f;
+        if (rot) {                                                     // the scan kernel's heading, fp32 throughout
+            const float4 o = a.own[s0 + row];
+            const float gx = o.x - x, gy = o.y - y;
+            const float vv = fmaf(vx, vx, vy * vy), gg = fmaf(gx, gx, gy * gy);
+            if (vv > 0.0f) { const float l = sqrtf(vv); hx = vx / l; hy = vy / l; }
+            else if (gg > 0.0f) { const float l = sqrtf(gg); hx = gx / l; hy = gy / l; }
+        }
+
+        // (a) the pedestrians inside the grid, ascending, with their cells and relative velocities
+        int n_src = 0;
+#pragma unroll 1
+        for (int base = 0; base < n; base += BLOCK) {                  // uniform
+            const int t = base + tid;
+            int cell = -1;
+            float rx = 0.0f, ry = 0.0f;
+            if (t < n && t != row) {
+                const float4 p = sh.pk[t];
+                if (row_live(p.x, p.y)) {
+                    cell = grid_cell(p.x - x, p.y - y, rot, hx, hy, c, half, g, G);
+                    rx = p.z - vx;
+                    ry = p.w - vy;
+                    grid_rotate(rot, hx, hy, rx, ry);
+                }
+            }
+            const bool in = cell >= 0;
+            const unsigned long long m = __ballot(in);
+            if (lane == 0) sh.wcount[wave] = __popcll(m);
+            __syncthreads();                                           // (also: everyone is done with the list of the row before)
+            int before = n_src, all = 0;
+#pragma unroll
+            for (int w = 0; w < WAVES_PER_BLOCK; ++w) {
+                const int cw = sh.wcount[w];
+                before += w < wave ? cw : 0;
+                all += cw;
+            }
+            if (in) {
+                const int k = before + __popcll(m & ((1ull << lane) - 1ull));
+                sh.cid[k] = (unsigned short)cell;
+                sh.rv[k] = make_float2(rx, ry);
+            }
+            n_src += all;
+            __syncthreads();                                           // the list; and wcount is rewritten by the next pass
+        }
+        // ... and the geometry points per kind and cell (behind the barriers above: the counts of the row before were cleared)
+        for (int e = tid; e < P; e += BLOCK) {
+            const float2 p = one_tile ? sh.tile[e] : point(e);
+            const int cell = grid_cell(p.x - x, p.y - y, rot, hx, hy, c, half, g, G);
+            if (cell >= 0) atomicAdd(&sh.cnt[e < nb ? 0 : e < nb + ns ? 1 : 2][cell], 1);
+        }
+        if (P > 0) __syncthreads();                                    // uniform
+
+        // (b) a lane owns cells tid + q BLOCK and walks the sources in order
+        int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+        float x0 = 0.0f, x1 = 0.0f, x2 = 0.0f, x3 = 0.0f, y0 = 0.0f, y1 = 0.0f, y2 = 0.0f, y3 = 0.0f;
+        // one source, in its turn (a macro: the accumulators stay plain registers)
+#define GRID_ADD(cell, v)                                                                                      \
+        do {                                                                                                   \
+            const int cid_ = __builtin_amdgcn_readfirstlane(cell);                                             \
+            const bool mine_ = (cid_ & (BLOCK - 1)) == tid;                                                    \
+            const int q_ = cid_ / BLOCK; /* uniform */                                                         \
+            if (q_ == 0) { c0 += mine_; x0 = mine_ ? x0 + (v).x : x0; y0 = mine_ ? y0 + (v).y : y0; }          \
+            else if (q_ == 1) { c1 += mine_; x1 = mine_ ? x1 + (v).x : x1; y1 = mine_ ? y1 + (v).y : y1; }     \
+            else if (q_ == 2) { c2 += mine_; x2 = mine_ ? x2 + (v).x : x2; y2 = mine_ ? y2 + (v).y : y2; }     \
+            else { c3 += mine_; x3 = mine_ ? x3 + (v).x : x3; y3 = mine_ ? y3 + (v).y : y3; }                  \
+        } while (0)
+        int k = 0;
+#pragma unroll 1
+        for (; k + 4 <= n_src; k += 4) {                               // uniform: the LDS reads are broadcasts, four in flight
+            const int e0 = sh.cid[k], e1 = sh.cid[k + 1], e2 = sh.cid[k + 2], e3 = sh.cid[k + 3];
+            const float2 v0 = sh.rv[k], v1 = sh.rv[k + 1], v2 = sh.rv[k + 2], v3 = sh.rv[k + 3];
+            GRID_ADD(e0, v0);
+            GRID_ADD(e1, v1);
+            GRID_ADD(e2, v2);
+            GRID_ADD(e3, v3);
+        }
+#pragma unroll 1
+        for (; k < n_src; ++k) {
+            const int e = sh.cid[k];
+            const float2 v = sh.rv[k];
+            GRID_ADD(e, v);
+        }
+#undef GRID_ADD
+
+        // 4. the row's 6 G^2 floats
+        auto store = [&](int cell, int count, float sx, float sy) {
+            if (cell >= cells) return;
+            out[cell] = (float)count;
+            out[cells + cell] = sx;
+            out[2 * cells + cell] = sy;
+#pragma unroll
+            for (int kind = 0; kind < 3; ++kind) {
+                const int pts = P > 0 ? sh.cnt[kind][cell] : 0;
+                out[(3 + kind) * cells + cell] = (float)pts;
+                if (pts) sh.cnt[kind][cell] = 0;                       // (only this lane reads or clears the cell)
+            }
+        };
+        store(tid, c0, x0, y0);
+        store(tid + BLOCK, c1, x1, y1);
+        store(tid + 2 * BLOCK, c2, x2, y2);
+        store(tid + 3 * BLOCK, c3, x3, y3);
+    }
+}
+
+hipError_t launch_batch_grid(const GridArgs& a, int B, hipStream_t st) {
+    hipLaunchKernelGGL(sfm_batch_grid_kernel, dim3(B), dim3(BLOCK), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace sfm

@@ -1,6 +1,6 @@
 // sfm_batch_host.h -- what the two host files of the batched scenes share: the batch itself (SfmBatch and the struct of each of its
 // features), its error plumbing, and the messages for a feature that is off.  sfm_batch_capi.hip holds the ticks and everything they
-// read or write; sfm_batch_sense_capi.hip the read-only sensors (observations, episode ends, range scans) and the device pointers;
+// read or write; sfm_batch_sense_capi.hip the read-only sensors (observations, episode ends, range scans, occupancy grids) and the device pointers;
 // sfm_batch_reset_capi.hip the restart noise.
 #pragma once
 #include "sfm_capi_common.h"
@@ -134,6 +134,17 @@ struct BatchScanDev {
     DevBuf<float> buf;         // [N_total][2 R]
 };
 
+// occupancy grids (sfm_batch_set_grid): the settings and the buffer sfm_batch_grid fills; nothing a tick reads or writes
+struct BatchGridDev {
+    bool on = false;           // (not "buf is allocated": a batch without gridded rows can be gridded and has no buffer)
+    int G = 0;
+    int frame = 0;
+    size_t M = 0;              // gridded rows: the slots of buf
+    DevBuf<float> cell;        // [B]
+    DevBuf<int> slot;          // [N_total]; not allocated: every row is gridded, slot = row
+    DevBuf<float> buf;         // [M][6][G][G]
+};
+
 // restart noise (sfm_batch_set_restart_noise): how a restarted scene may differ from the snapshot, and the two per-scene counters the
 // noise kernel keeps; an input the restarts only read, like steering.  The delays refer to the tracks and are dropped with them.
 struct BatchNoiseDev {
@@ -187,6 +198,7 @@ struct SfmBatch {
     sfm::BatchEpisodeDev ep;
     sfm::BatchScanDev scan;
     sfm::BatchNoiseDev noise;
+    sfm::BatchGridDev grid;
     sfm::Event c_done;                      // created by the first sfm_batch_set_steering with rows; outlives every drop of the steering
     std::string err;
 };
@@ -214,6 +226,7 @@ constexpr const char* OBSERVATIONS_OFF = "observations are off: call sfm_batch_s
 constexpr const char* EPISODES_OFF = "episodes are off: call sfm_batch_set_episodes first (sfm_batch_upload_state drops them)";
 constexpr const char* NOISE_OFF = "restart noise is off: call sfm_batch_set_restart_noise first (sfm_batch_upload_state drops it)";
 constexpr const char* SCANS_OFF = "scans are off: call sfm_batch_set_scan first (sfm_batch_upload_state drops them)";
+constexpr const char* GRIDS_OFF = "grids are off: call sfm_batch_set_grid first (sfm_batch_upload_state drops them)";
 
 // one kind of the scenes' geometry as the kernels take it, and what the sensors see of the scenes
 inline BatchGeo batch_geo(const SfmBatch* b, int k) { return BatchGeo{b->geo_item_off[k], b->geo[k].off, b->geo[k].pts, b->geo[k].ctr}; }

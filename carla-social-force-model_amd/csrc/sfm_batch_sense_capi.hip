@@ -1,5 +1,5 @@
-// sfm_batch_sense_capi.hip -- host side of the batch's read-only sensors (ABI 15 to 17): observations, episode ends and range scans,
-// and the device pointers a caller shares with them.  Each sensor reads the scenes through one BatchSceneView and writes only its own
+// sfm_batch_sense_capi.hip -- host side of the batch's read-only sensors (ABI 15 to 17): observations, episode ends, range scans and
+// occupancy grids, and the device pointers a caller shares with them.  Each sensor reads the scenes through one BatchSceneView and writes only its own
 // buffers -- nothing a tick reads or writes.  The batch's types are in sfm_batch_host.h; the ticks, the restarts and everything else
 // in sfm_batch_capi.hip.
 #include "sfm_batch_host.h"
@@ -20,7 +20,7 @@ static int check_frame(SfmBatch* b, int frame) {
 
 // One lookup for the device buffers a caller may see: which = SFM_BATCH_PTR_*, or PTR_OBSERVATIONS for sfm_batch_observation_ptr's.
 // off: why there is none (its feature is off, no state was uploaded), else p and bytes -- both 0 where the buffer has no element.
-constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_RESETS + 1;   // (not part of the ABI: sfm_batch_device_ptr refuses it)
+constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_GRID + 1;     // (not part of the ABI: sfm_batch_device_ptr refuses it)
 struct BatchBuffer { const char* off; void* p; size_t bytes; };
 static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     const size_t n = (size_t)b->n_total, B = (size_t)b->B;
@@ -39,6 +39,9 @@ static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     case SFM_BATCH_PTR_RESETS:
         if (!b->noise.on) return {NOISE_OFF, nullptr, 0};
         return have(b->noise.resets, sizeof(uint32_t) * B);
+    case SFM_BATCH_PTR_GRID:
+        if (!b->grid.on) return {GRIDS_OFF, nullptr, 0};
+        return have(b->grid.buf, sizeof(float) * b->grid.M * (size_t)(SFM_BATCH_GRID_CHANNELS * b->grid.G * b->grid.G));
     }
     if (!b->have_state) return {NO_STATE, nullptr, 0};
     if (which == SFM_BATCH_PTR_COMMANDS) {
@@ -76,8 +79,10 @@ void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes) {
     if (!b) return nullptr;
     // SFM_BATCH_PTR_RESETS came without an ABI bump: while restart noise is off it is refused as the unknown value it was, word for
     // word, so a caller of ABI 17 as it was sees no difference
-    const int last = b->noise.on ? SFM_BATCH_PTR_RESETS : SFM_BATCH_PTR_SCAN;
-    if (which < SFM_BATCH_PTR_COMMANDS || which > last) { bfail(b, SFM_ERR_INVALID, "which must be SFM_BATCH_PTR_COMMANDS, _STATE, _ZSTATE, _EPISODES, _DONE or _SCAN"); return nullptr; }
+    // (SFM_BATCH_PTR_GRID likewise, while grids are off)
+    const bool known = (which >= SFM_BATCH_PTR_COMMANDS && which <= SFM_BATCH_PTR_SCAN) || (which == SFM_BATCH_PTR_RESETS && b->noise.on) ||
+                       (which == SFM_BATCH_PTR_GRID && b->grid.on);
+    if (!known) { bfail(b, SFM_ERR_INVALID, "which must be SFM_BATCH_PTR_COMMANDS, _STATE, _ZSTATE, _EPISODES, _DONE or _SCAN"); return nullptr; }
     return buffer_ptr(b, which, which == SFM_BATCH_PTR_SCAN ? ", so which = SFM_BATCH_PTR_SCAN has no buffer" :
                                 which == SFM_BATCH_PTR_EPISODES || which == SFM_BATCH_PTR_DONE ? ", so which = SFM_BATCH_PTR_EPISODES / _DONE has no buffer" : "", bytes);
 }
@@ -262,5 +267,56 @@ int sfm_batch_scan(SfmBatch* b) {
 }
 
 int sfm_batch_download_scan(SfmBatch* b, float* out) { return download_buffer(b, SFM_BATCH_PTR_SCAN, out); }
+
+// Occupancy grids (ABI 17, added without a bump).  Everything is checked before anything is allocated or freed.
+int sfm_batch_set_grid(SfmBatch* b, int G, const float* cell, const uint8_t* mask, int frame) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!cell) {
+        HIP_TRY(b, hipStreamSynchronize(b->stream));             // a grid launch in flight may still write the buffer
+        b->grid = {};
+        return SFM_OK;
+    }
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, NO_STATE);
+    if (G < 1 || G > SFM_BATCH_MAX_GRID)
+        return bfail(b, SFM_ERR_INVALID, "G must be 1 .. " + std::to_string(SFM_BATCH_MAX_GRID) + " cells per side, got " + std::to_string(G));
+    if ((rc = check_frame(b, frame))) return rc;
+    const size_t B = (size_t)b->B, n = (size_t)b->n_total;
+    for (size_t s = 0; s < B; ++s)
+        if ((rc = batch_metres(b, s, "cell", cell[s], true, nullptr))) return rc;   // (the size goes to the kernel as the fp32 value given)
+    BatchGridDev o;
+    o.M = n;                                                     // no mask: every row, slot = row
+    if (mask && n > 0) {
+        std::vector<int32_t> slot(n);
+        o.M = pack_grid_slots(mask, n, slot.data());
+        HIP_TRY(b, o.slot.alloc(n));
+        HIP_TRY(b, hipMemcpy(o.slot, slot.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    }
+    const size_t vals = o.M * (size_t)SFM_BATCH_GRID_CHANNELS * (size_t)G * (size_t)G;
+    HIP_TRY(b, o.cell.alloc(B));
+    HIP_TRY(b, hipMemcpy(o.cell, cell, sizeof(float) * B, hipMemcpyHostToDevice));
+    if (vals > 0) {
+        HIP_TRY(b, o.buf.alloc(vals));
+        HIP_TRY(b, hipMemsetAsync(o.buf, 0, sizeof(float) * vals, b->stream));
+    }
+    o.G = G;
+    o.frame = frame;
+    o.on = true;
+    HIP_TRY(b, hipStreamSynchronize(b->stream));                 // the zero fill; and a grid launch in flight may still write the old buffer
+    b->grid = std::move(o);
+    return SFM_OK;
+}
+
+int sfm_batch_grid(SfmBatch* b) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->grid.on) return bfail(b, SFM_ERR_STATE, GRIDS_OFF);
+    if (b->grid.M == 0) return SFM_OK;                           // no gridded row: nothing to write
+    const GridArgs a{batch_scene_view(b), b->grid.cell, b->grid.slot /* null: every row */, b->grid.buf, b->grid.G, b->grid.frame};
+    HIP_TRY(b, launch_batch_grid(a, b->B, b->stream));
+    return SFM_OK;
+}
+
+int sfm_batch_download_grid(SfmBatch* b, float* out) { return download_buffer(b, SFM_BATCH_PTR_GRID, out); }
 
 }  // extern "C"

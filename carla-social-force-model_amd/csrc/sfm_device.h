@@ -396,6 +396,19 @@ struct ScanArgs : BatchSceneView {
     int frame;                // 0 world axes, 1 the row's heading frame
 };
 
+// Occupancy grids of a batch (sfm_batch_grid, sfm_batch_grid_kernel in sfm_batch_grid.hip): everything but out is read only.
+constexpr int GRID_MAX_G = 32;                         // cells per side
+constexpr int GRID_MAX_CELLS = GRID_MAX_G * GRID_MAX_G;
+constexpr int GRID_CHANNELS = 6;
+struct GridArgs : BatchSceneView {
+    const float* cell;        // [B] the cell size, the fp32 value as given
+    const int* slot;          // [N_total] the row's slot in out, -1: the row is not gridded; null: every row, slot = row
+    float* out;               // [M][6][G][G]
+    int G;                    // cells per side, 1 .. GRID_MAX_G
+    int frame;                // 0 world axes, 1 the row's heading frame
+};
+static_assert(sizeof(GridArgs) == 120 + 32, "the grid kernel's arguments follow the view without padding");
+
 // Restart noise of a batch (sfm_batch_set_restart_noise, sfm_batch_restart_noise_kernel in sfm_batch_reset.hip): launched behind
 // sfm_batch_restart_kernel with the same choice of scenes (list / mask as in BatchRestart); the rule is specified in include/sfm_hip.h.
 constexpr int RESET_MAX_TRIES = 32;

@@ -784,6 +784,65 @@ int sfm_batch_scan(SfmBatch* b);
 /* Synchronises the batch's stream, then copies the buffer ([N_total][2 R] floats) as the last sfm_batch_scan left it; before the
  * first scan that is zeros.  SFM_ERR_STATE while scans are off. */
 int sfm_batch_download_scan(SfmBatch* b, float* out);
+/* Egocentric occupancy grids on the device: the local map crowd-navigation policies are trained on beside the neighbour list and
+ * the lidar.  A G x G grid centred on a row; per cell how many other pedestrians stand in it, how they move relative to the row,
+ * and how many sampled points of borders, static obstacles and vehicles lie in it, by ONE launch of sfm_batch_grid_kernel (a
+ * workgroup per scene) straight from the buffers the tick reads, into a device buffer a policy can feed to a convolution as it
+ * stands.  The record is defined bit for bit in BOTH frames: every operation below is a single correctly rounded fp32 operation or
+ * an fmaf.
+ * These three entry points and SFM_BATCH_PTR_GRID were added WITHOUT a bump of SFM_ABI_VERSION (it stays 17), like the restart
+ * noise: additions only, nothing that existed changes its meaning, and a build that has them is recognised by the symbols.
+ *
+ * Settings (sfm_batch_set_grid).  G: cells per side, 1 .. SFM_BATCH_MAX_GRID, one value for the batch.  cell[b]: the cell size in
+ * metres, per scene, finite, 0 < c <= SFM_BATCH_MAX_SENSE_RANGE, used as the fp32 value.  mask [N_total] uint8_t, or NULL for every
+ * row: which rows are gridded (nonzero); a row without a slot costs nothing.  frame: SFM_OBS_FRAME_WORLD (0) or
+ * SFM_OBS_FRAME_HEADING (1), one value for the batch.
+ *
+ * Record.  The gridded rows get compact slots: a row's slot is its rank among the masked rows of the whole batch in ascending
+ * (concatenated) row order; with M of them the buffer is [M][SFM_BATCH_GRID_CHANNELS][G][G] float, slot-major, the cell [cv][cu]
+ * of channel ch at ((slot * 6 + ch) * G + cv) * G + cu.  The grid spans [-G/2 c, G/2 c) on both axes around the row; u runs along
+ * x and v along y (frame 1: x is forward, y to the left).  Channel 0: the number of pedestrian sources in the cell -- a source is a
+ * row j != i of the scene that is live by sfm_batch_observe's test.  Channels 1 and 2: the SUM (not the mean: divide by channel 0)
+ * of those pedestrians' relative velocities (vx_j - vx, vy_j - vy), rotated in frame 1 like the positions, formed in ascending j by
+ * fp32 adds starting from 0.0f.  Channels 3, 4, 5: the number of border points, static-obstacle ring points and vehicle ring points
+ * in the cell -- the model's own sampled view of geometry, as in sfm_batch_scan.  Counts are exact in fp32.  A gridded row that is
+ * not live (|x| < NEAR_LIMIT and |y| < NEAR_LIMIT fails; a NaN position fails it) is all zeros.
+ *
+ * Rules, all exact, for row i at (x, y), a cell size c and a source at (px, py):
+ *     ax = px - x;  ay = py - y
+ *     frame 0:  fx = ax;  fy = ay                                     (no rotation is performed)
+ *     frame 1:  fx = fmaf(hx, ax, hy * ay);  fy = fmaf(hx, ay, -(hy * ax))
+ *     half = 0.5f * G                                                 (exact)
+ *     pu = fx / c + half;  pv = fy / c + half                         (the division is rounded first, then the sum)
+ *     inside iff 0 <= pu < G and 0 <= pv < G                          (float compares)
+ *     cu = (int)pu;  cv = (int)pv
+ * (hx, hy) is sfm_batch_scan's heading of frame 1, fp32 throughout: v when fmaf(vx, vx, vy * vy) > 0, else the goal entry
+ * g = (wx - x, wy - y) when fmaf(gx, gx, gy * gy) > 0, else (1, 0); with l = sqrt(.), hx = a / l, hy = b / l, each correctly
+ * rounded.  NaN and +-inf fail the compares by themselves, so the ring of an absent tracked vehicle (at +inf) is never binned and
+ * there is no test of its own.  The sum decides the cell: a source whose fx / c is a tiny negative number is rounded up to
+ * pu = half and lies in cell (int)half, and one whose pu rounds up to G is outside.  Vehicles are read as the next tick would read
+ * them.  Only {x, y, vx, vy} of the state is used: a 3-D batch gives the planar record.  Vehicle velocities per cell are not
+ * recorded.
+ * The kernel writes only the grid buffer and uses no float atomics; every order is a function of the scene alone: a scene's
+ * record is bitwise the same alone or anywhere in any batch.
+ *
+ * sfm_batch_set_grid allocates and zero-fills the buffer (its size is computed in 64 bits) and waits for the batch's stream;
+ * cell = NULL switches grids off and frees the buffer.  Refused with nothing changed: before sfm_batch_upload_state
+ * (SFM_ERR_STATE); G outside 1 .. 32; frame outside {0, 1}; a cell size that is NaN, infinite, <= 0 or > 1e6.
+ * sfm_batch_upload_state drops the grids (the slots are per row); every other call keeps them, and they keep the snapshot.  A
+ * snapshot neither holds nor restores them.
+ * SFM_BATCH_PTR_GRID (sfm_batch_device_ptr): the grid buffer, valid until the next sfm_batch_set_grid or sfm_batch_upload_state;
+ * NULL without gridded rows; while grids are off the value is refused as the unknown `which` it was before. */
+#define SFM_BATCH_PTR_GRID 7
+#define SFM_BATCH_MAX_GRID 32
+#define SFM_BATCH_GRID_CHANNELS 6
+int sfm_batch_set_grid(SfmBatch* b, int G, const float* cell, const uint8_t* mask, int frame);
+/* ONE launch on the batch's stream, ordered with the ticks, the other sensors and the restarts around it; the host does not wait.
+ * SFM_ERR_STATE while grids are off.  With no gridded row it launches nothing and succeeds. */
+int sfm_batch_grid(SfmBatch* b);
+/* Synchronises the batch's stream, then copies the buffer ([M][6][G][G] floats) as the last sfm_batch_grid left it; before the
+ * first that is zeros.  SFM_ERR_STATE while grids are off. */
+int sfm_batch_download_grid(SfmBatch* b, float* out);
 /* Current state of every scene (synchronises the batch's stream); NULL skips a column.  A planar batch leaves z alone and
  * writes vz = 0. */
 int sfm_batch_download_state(SfmBatch* b, float* x, float* y, float* z, float* vx, float* vy, float* vz);
