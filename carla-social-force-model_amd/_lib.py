@@ -107,6 +107,7 @@ SYMBOLS = {
     "sfm_set_timing": (C.c_int, [_H, C.c_int]),
     "sfm_profile_dominant_kernel": (C.c_int, [_H, C.c_int, C.POINTER(C.c_float)]),
     "sfm_kernel_variant": (C.c_char_p, [_H]),
+    "sfm_fused_form": (C.c_char_p, [_H]),
     "sfm_get_pair_work": (C.c_int, [_H, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "sfm_set_partition": (C.c_int, [_H, C.c_int, C.c_int, _I]),
     "sfm_tick_begin": (C.c_int, [_H, C.c_uint32]),

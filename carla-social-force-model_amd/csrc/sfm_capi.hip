@@ -178,6 +178,8 @@ struct SfmHandle {
     int ipw_last = 0;
     int ipw_override = 0, team_override = 0;
     char variant[64] = "none";
+    bool fused_lean = true;                // SFM_FUSED_LEAN: the fused tick may take its lean form (fused_lean_takes)
+    bool fused_lean_ran = false;           // ... and the last fused launch did
 };
 
 static int fail(SfmHandle* h, int code, const char* msg) {
@@ -246,6 +248,8 @@ int sfm_create(const SfmParams* params, int device_id, SfmHandle** out) {
     if (ov) h->pair_geo_mode = atoi(ov);
     ov = getenv("SFM_FUSED");
     if (ov) h->fused_mode = atoi(ov);
+    ov = getenv("SFM_FUSED_LEAN");
+    if (ov) h->fused_lean = atoi(ov) != 0;
     ov = getenv("SFM_REORDER");
     if (ov) h->reorder_mode = atoi(ov);
     ov = getenv("SFM_GEO_SLICES");
@@ -993,7 +997,10 @@ static int fused_launch(SfmHandle* h, uint32_t flags, int mode, int* sl) {
                       h->own, h->fused.own_alt, n_g, h->n_t, n_g % 8 == 0 ? 1 : 0,
                       geo ? h->fused.fgeo + (size_t)(*sl ^ 1) * grow : nullptr, geo ? h->fused.fgeo + (size_t)*sl * grow : nullptr, slices,
                       geo ? h->n_t * slices : 0, n_pair, mode};
-    HIP_TRY(h, launch_fused_tick(h->rad, a, f, h->stream, nw));
+    // whole planar crowds of a multiple of 1024 pedestrians take the lean form of the kernel (same bits; SFM_FUSED_LEAN=0: never)
+    h->fused_lean_ran = h->fused_lean && fused_lean_takes(h->rad, a, f);
+    if (h->fused_lean_ran) HIP_TRY(h, launch_fused_tick_lean(a, f, h->stream));
+    else HIP_TRY(h, launch_fused_tick(h->rad, a, f, h->stream, nw));
     if (mode != 0) {
         h->cur ^= 1;
         swap(h->own, h->fused.own_alt);
@@ -1803,6 +1810,10 @@ int sfm_get_timing(SfmHandle* h, float* elapsed_ms, int* ticks, int* launches) {
 }
 
 const char* sfm_kernel_variant(const SfmHandle* h) { return h ? h->variant : "none"; }
+const char* sfm_fused_form(const SfmHandle* h) {
+    if (!h || !h->used_fused) return "none";
+    return h->fused_lean_ran ? "sfm_fused_tick_kernel<lean>" : "sfm_fused_tick_kernel<general>";
+}
 
 int sfm_get_pair_work(SfmHandle* h, long long* tile_pair_items, long long* pair_terms) {
     int rc = bind(h);

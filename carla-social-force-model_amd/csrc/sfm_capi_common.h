@@ -23,6 +23,8 @@ hipError_t launch_sym_list(const TickArgs& a, const SymArgs& sa, hipStream_t st,
 hipError_t launch_sym_pair(bool rad, const TickArgs& a, const SymArgs& sa, hipStream_t st);
 hipError_t launch_sym_epilogue(bool rad, const TickArgs& a, const SymArgs& sa, hipStream_t st);
 hipError_t launch_fused_tick(bool rad, const TickArgs& a, const FusedArgs& f, hipStream_t st, int waves);
+bool fused_lean_takes(bool rad, const TickArgs& a, const FusedArgs& f);
+hipError_t launch_fused_tick_lean(const TickArgs& a, const FusedArgs& f, hipStream_t st);
 int fused_pair_workgroups(int n_g);
 hipError_t launch_sym_pair_geo(bool rad, const TickArgs& a, const SymArgs& sa, hipStream_t st);
 int sym_item_count(int n_t);

@@ -220,6 +220,27 @@ struct alignas(16) FusedArgs {
                               //    front of a run; 1: integrate by one tick, store, then the pairs of the new state
 };
 
+// The lean form of the fused tick (lean::sfm_fused_tick_kernel): a whole planar crowd of a multiple of 1024 pedestrians (up to 4096)
+// without radii, border / obstacle forces or vehicles.  Only what that path reads: 128 bytes, two scalar loads.
+constexpr uint32_t LEAN_EN_ACC = 0x100u, LEAN_EN_PED = 0x200u, LEAN_INTEGRATE = 0x400u;
+struct alignas(16) LeanTickArgs {
+    const float4* pk_cur;     // {x, y, vx, vy}
+    float4* pk_next;
+    const float4* own_cur;    // {wx, wy, target_speed, radius} going with pk_cur
+    float4* own_next;
+    const float2* slab_prev;  // [n_g][N]: FusedArgs::slab_prev
+    float2* slab_next;
+    uint32_t* draws;          // waypoint draw counters
+    const uint32_t* ids;      // caller's index of the pedestrian in each row; null = identity
+    IxConst ped;
+    float inv_tau, dt, max_speed_factor, arrive_thr2;
+    uint32_t seed;
+    float world_side;
+    uint32_t bits;            // TickArgs::flags (bits 0, 1) | LEAN_EN_ACC | LEAN_EN_PED | LEAN_INTEGRATE (FusedArgs::mode != 0)
+    uint32_t pad;
+};
+static_assert(sizeof(LeanTickArgs) == 128, "the lean fused tick's arguments: two 64-byte scalar loads");
+
 // Batched scenes (sfm_batch.hip, sfm_batch_* in the C ABI): B independent crowds of up to BATCH_MAX_N pedestrians, stepped by ONE
 // launch per tick, a workgroup per scene.  State is fp32 SoA over all scenes concatenated (scene b owns rows
 // [scene_off[b], scene_off[b+1])); every scene carries its own parameters and geometry.

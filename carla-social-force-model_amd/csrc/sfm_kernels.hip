@@ -2318,6 +2318,293 @@ __global__ void sfm_arrived_kernel(const float4* __restrict__ pk, const float4* 
     mask[i] = fmaf(ddx, ddx, ddy * ddy) < thr2 ? 1 : 0;
 }
 
+// ---- the lean form of the fused tick: a whole planar crowd of N_G * 128 pedestrians, N_G a multiple of 8 (N = 1024 ... 4096), no
+// radii, no border / obstacle role, no vehicles, 16 waves, the XCD-blocked item order.  The same arithmetic in the same order as
+// sfm_fused_tick_kernel<false, 16, false, false> above -- the two agree bit for bit (tests/test_fused_lean_gpu.py) -- with what that
+// kernel carries for the other shapes taken out:
+//   * the arguments are LeanTickArgs, 128 bytes (two scalar loads), not TickArgs + FusedArgs;
+//   * every group and tile exists and every row is live, so `present` / `live` / `work` are gone, and N, the slab strides and the
+//     rows of a part are constants: a column sum's rows sit at immediate offsets from one address;
+//   * the second travelling chain's sums are rotated onto the first chain's lanes inside the wave (ds_bpermute_b32: chain B's sums
+//     end XB lanes from chain A's) and added there as fi + fi2, the association of the general form's combine: one row per wave
+//     goes to LDS and the combine reads half as much.
+// In a namespace of its own so that the kernel keeps the name profiles and counter summaries know the fused tick by.
+struct LeanShared {                              // LDS of one workgroup (FusedShared<false, 16, false> without rad and fi2)
+    float4 st[2 * GROUP];
+    float2 q[8][2 * GROUP];
+    float2 part[2 * GROUP];
+    int badrow[2 * GROUP];
+    int any;
+    float2 fi[16][WAVE];
+    float2 fj[16][WAVE];
+    float4 trav[4][2 * WAVE];
+};
+
+namespace lean {
+
+template <int N_G>
+__global__ __launch_bounds__(16 * WAVE, 8) void sfm_fused_tick_kernel(const LeanTickArgs a) {
+    constexpr int NW = 16, PARTS = 8, SPW = 4 * WAVE / NW, D = NW / 8, HALF = SPW / 2;
+    constexpr int N = N_G * GROUP;               // = N_pad: whole groups
+    constexpr int PER = N_G / PARTS;             // slab rows per part
+    static_assert(N_G % 8 == 0 && N_G >= 8 && N_G <= 32, "the lean form takes 8, 16, 24 or 32 groups");
+    __shared__ __attribute__((aligned(16))) char smem[sizeof(LeanShared)];
+    LeanShared& sh = *reinterpret_cast<LeanShared*>(smem);
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wave = uniform(tid >> 6);
+    const bool en_acc = (a.bits & LEAN_EN_ACC) != 0, en_ped = (a.bits & LEAN_EN_PED) != 0, integrate = (a.bits & LEAN_INTEGRATE) != 0;
+    // the XCD-blocked item map of the general form (see there), s a constant
+    int GX, GY;
+    bool diag_item;
+    {
+        constexpr int s = N_G >> 2;
+        const int bid = (int)blockIdx.x;
+        const int x = bid & 7;
+        int k = bid >> 3;
+        if (x < 6) {
+            const int I = x < 3 ? 0 : (x < 5 ? 1 : 2), J = x < 3 ? x + 1 : (x < 5 ? x - 1 : 3);
+            GX = I * s + k / s;
+            GY = J * s + k % s;
+            diag_item = false;
+        } else {
+            constexpr int per_band = (s * s) >> 1;
+            const int I = 2 * (x - 6) + (k >= per_band ? 1 : 0);
+            if (k >= per_band) k -= per_band;
+            if (k < (s >> 1)) {
+                GX = I * s + 2 * k; GY = GX + 1;
+                diag_item = true;
+            } else {
+                int t = k - (s >> 1), u = 0;
+                while (t >= s - 1 - u) { t -= s - 1 - u; ++u; }      // triangular index -> (u, v), u < v < s
+                GX = I * s + u; GY = I * s + u + 1 + t;
+                diag_item = false;
+            }
+        }
+    }
+
+    // ---- 1. the state of this launch (the general form's step 1): own rows, then the column sums, every load before the first use
+    const int quarter = wave & 3;
+    const int p = quarter * WAVE + lane;
+    const bool lower = wave < 4;
+    const int G = (quarter < 2) ? GX : GY;
+    const int i = G * GROUP + (quarter & 1) * WAVE + lane;
+    float4 st = make_float4(0.f, 0.f, 0.f, 0.f), o = st;
+    uint32_t nd0 = 0, pid = 0;
+    if (lower) {
+        st = a.pk_cur[i];
+        if (integrate) {
+            o = a.own_cur[i];
+            if ((a.bits & 2u) && diag_item) { nd0 = a.draws[i]; pid = a.ids ? a.ids[i] : (uint32_t)i; }
+        }
+    }
+    if (tid == 0) sh.any = 0;
+    {
+        const int pp = (wave & 1) * WAVE + lane;
+        const int part = wave >> 1;
+        const int Gq = (wave & 1) ? GY : GX;
+        float4 acc4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (integrate && en_ped) {
+            // row k of the part: a wave-uniform base (scalar) + one 32-bit lane offset for all of them
+            constexpr uint32_t ROW = N * sizeof(float2);
+            const char* rows = reinterpret_cast<const char*>(a.slab_prev) + (uint32_t)(part * PER) * ROW;
+            const uint32_t at = (uint32_t)(Gq * (GROUP / 2) + lane) * (uint32_t)sizeof(float4);
+            auto col = [&](int k) {
+                uint32_t ro = (uint32_t)k * ROW;
+                asm("" : "+s"(ro));              // (kept scalar: the row's base is formed on the SALU, not as a 64-bit add per lane)
+                return *reinterpret_cast<const float4*>(rows + ro + at);
+            };
+            if (PER == 4) {                      // the general form's four-row case
+                const float4 v0 = col(0), v1 = col(1), v2 = col(2), v3 = col(3);
+                __builtin_amdgcn_sched_barrier(0);                   // (all four in flight before the first add waits)
+                acc4 = make_float4((v0.x + v1.x) + (v2.x + v3.x), (v0.y + v1.y) + (v2.y + v3.y),
+                                   (v0.z + v1.z) + (v2.z + v3.z), (v0.w + v1.w) + (v2.w + v3.w));
+            } else {                             // ... and its eight-wide loop, one trip: absent rows are 0 and still added
+                float4 v[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = (k < PER) ? col(k < PER ? k : 0) : make_float4(0.f, 0.f, 0.f, 0.f);
+                __builtin_amdgcn_sched_barrier(0);
+                acc4.x += ((v[0].x + v[1].x) + (v[2].x + v[3].x)) + ((v[4].x + v[5].x) + (v[6].x + v[7].x));
+                acc4.y += ((v[0].y + v[1].y) + (v[2].y + v[3].y)) + ((v[4].y + v[5].y) + (v[6].y + v[7].y));
+                acc4.z += ((v[0].z + v[1].z) + (v[2].z + v[3].z)) + ((v[4].z + v[5].z) + (v[6].z + v[7].z));
+                acc4.w += ((v[0].w + v[1].w) + (v[2].w + v[3].w)) + ((v[4].w + v[5].w) + (v[6].w + v[7].w));
+            }
+        }
+        sh.q[part][2 * pp] = make_float2(acc4.x, acc4.y);
+        sh.q[part][2 * pp + 1] = make_float2(acc4.z, acc4.w);
+    }
+    __syncthreads();
+    auto put_state = [&](const float4 ns) {
+        sh.st[p] = ns;
+        const float4 t = make_float4(ns.x, ns.y, a.ped.lam * ns.z, a.ped.lam * ns.w);
+        float* pl = reinterpret_cast<float*>(sh.trav) + (p >> 6) * 2 * WAVE + (p & (WAVE - 1));      // plane c at + c * 4 * 2 * WAVE
+        pl[0] = t.x; pl[WAVE] = t.x;
+        pl[8 * WAVE] = t.y; pl[9 * WAVE] = t.y;
+        pl[16 * WAVE] = t.z; pl[17 * WAVE] = t.z;
+        pl[24 * WAVE] = t.w; pl[25 * WAVE] = t.w;
+    };
+    auto finish = [&](const float2 g) {
+        const float fpx = en_ped ? a.ped.negA * g.x : 0.f, fpy = en_ped ? a.ped.negA * g.y : 0.f;
+        const float x = st.x, y = st.y, vx = st.z, vy = st.w, ts = o.z;
+        float wx = o.x, wy = o.y;
+        float fax = 0.f, fay = 0.f, faz = 0.f;
+        if (en_acc) acceleration_force<false, true>(a, wx, wy, x, y, vx, vy, 0.f, ts, fax, fay, faz);
+        const float Fx = (fax + fpx) + 0.f, Fy = (fay + fpy) + 0.f;         // (+ the general form's absent border / obstacle sum)
+        float nvx, nvy, nvz;
+        capped_velocity<false, true>(a, vx, vy, 0.f, Fx, Fy, 0.f, ts, nvx, nvy, nvz);
+        float nx = x, ny = y;
+        if (a.bits & 1u) { nx = fmaf(a.dt, nvx, x); ny = fmaf(a.dt, nvy, y); }
+        const float4 ns = make_float4(nx, ny, nvx, nvy);
+        if (diag_item) {                                             // this workgroup stores the group
+            if (a.bits & 2u) {
+                const float ax_ = wx - x, ay_ = wy - y;
+                if (fmaf(ax_, ax_, ay_ * ay_) < a.arrive_thr2) {
+                    const uint32_t nd = nd0 + 1u;
+                    const float2 w = next_waypoint(a.seed, pid, nd, a.world_side);
+                    wx = w.x; wy = w.y;
+                    a.draws[i] = nd;
+                }
+            }
+            a.own_next[i] = make_float4(wx, wy, o.z, o.w);
+            a.pk_next[i] = ns;
+        }
+        put_state(ns);
+    };
+    bool bad = false;
+    if (lower) {
+        if (integrate) {
+            float2 g = sh.q[0][p];
+#pragma unroll
+            for (int k = 1; k < PARTS; ++k) { const float2 q = sh.q[k][p]; g.x += q.x; g.y += q.y; }
+            bad = en_ped && (!(fabsf(g.x) < __builtin_inff()) || !(fabsf(g.y) < __builtin_inff()));
+            if (bad) sh.any = 1; else finish(g);
+        } else {
+            put_state(st);                                           // the first launch of a run: as stored
+        }
+        sh.badrow[p] = bad ? 1 : 0;
+    }
+    __syncthreads();
+    if (sh.any) {
+        // coincident pairs: the exact ordered body on the rows that caught a NaN (the general form's loop)
+        for (int q = wave; q < 2 * GROUP; q += NW) {
+            if (!sh.badrow[q]) continue;                                  // uniform
+            const int Gq = (q < GROUP) ? GX : GY;
+            const int ip = Gq * GROUP + (q & (GROUP - 1));
+            const float4 si = a.pk_cur[ip];
+            const float xi = uniform(si.x), yi = uniform(si.y), vxi = uniform(si.z), vyi = uniform(si.w);
+            float gx = 0.f, gy = 0.f;
+            for (int j0 = 0; j0 < N; j0 += WAVE) {
+                const int j = j0 + lane;
+                const float4 pj = a.pk_cur[j];
+                float cx = 0.f, cy = 0.f, cz = 0.f, rinv;
+                moussaid<false, false, true>(a.ped, pj.x - xi, pj.y - yi, 0.f, vxi - pj.z, vyi - pj.w, 0.f, 0.f, cx, cy, cz, rinv);
+                const bool valid = j != ip;
+                gx += valid ? cx : 0.f;
+                gy += valid ? cy : 0.f;
+            }
+            gx = wave_sum(gx);
+            gy = wave_sum(gy);
+            if (lane == 0) sh.part[q] = make_float2(gx, gy);
+        }
+        __syncthreads();
+        if (bad) finish(sh.part[p]);
+        __syncthreads();
+    }
+
+    // ---- 2. this workgroup's tile pairs on the new state: the general form's wave map and double steps
+    int ia, ib, sig0;
+    bool diag = false;
+    if (diag_item) {
+        const int sel = wave / (NW / 2);
+        const int lw = wave % (NW / 2);
+        const int base = sel * GROUP;
+        if (lw < 2 * D) {
+            ia = ib = base + (lw / D) * WAVE;
+            sig0 = 1 + (lw % D) * SPW;
+            diag = true;
+        } else {
+            ia = base; ib = base + WAVE;
+            sig0 = (lw - 2 * D) * SPW;
+        }
+    } else {
+        const int q = wave / (NW / 4);
+        ia = (q >> 1) * WAVE;
+        ib = GROUP + (q & 1) * WAVE;
+        sig0 = (wave % (NW / 4)) * SPW;
+    }
+    float fxi = 0.f, fyi = 0.f, fxb = 0.f, fyb = 0.f;
+    const IxConst& c = a.ped;
+    const float4 pj = sh.st[ib + lane];
+    const float ujx = c.lam * pj.z, ujy = c.lam * pj.w;
+    const int s0 = diag ? 1 + ((sig0 - 1) >> 1) : sig0 >> 1;
+    const float* pl = reinterpret_cast<const float*>(sh.trav) + (ia >> 6) * 2 * WAVE + lane + s0;
+    v2f fjx = bcast(0.f), fjy = bcast(0.f);
+    auto chain = [&](auto xb_tag) __attribute__((always_inline)) {
+        constexpr int XB = decltype(xb_tag)::value;
+        const bool tail_one_sided = diag && (s0 + XB + HALF - 1 == 32);       // sigma = 32 on a diagonal tile: one-sided (uniform)
+        v2f X, Y, U, V;
+        X.x = pl[0]; X.y = pl[XB]; Y.x = pl[8 * WAVE]; Y.y = pl[8 * WAVE + XB];
+        U.x = pl[16 * WAVE]; U.y = pl[16 * WAVE + XB]; V.x = pl[24 * WAVE]; V.y = pl[24 * WAVE + XB];
+#pragma unroll
+        for (int s_ = 0; s_ < HALF; ++s_) {
+            v2f Xn = X, Yn = Y, Un = U, Vn = V;
+            if (s_ + 1 < HALF) {                                         // the next double step's operands are in flight during this one
+                Xn.x = pl[s_ + 1]; Xn.y = pl[s_ + 1 + XB]; Yn.x = pl[8 * WAVE + s_ + 1]; Yn.y = pl[8 * WAVE + s_ + 1 + XB];
+                Un.x = pl[16 * WAVE + s_ + 1]; Un.y = pl[16 * WAVE + s_ + 1 + XB]; Vn.x = pl[24 * WAVE + s_ + 1]; Vn.y = pl[24 * WAVE + s_ + 1 + XB];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            v2f cx, cy;
+            moussaid_planar_x2<false>(c, pj.x, pj.y, ujx, ujy, X, Y, U, V, cx, cy, bcast(0.f));
+            fxi = rot_in(fxi) + cx.x; fyi = rot_in(fyi) + cy.x;
+            fxb = rot_in(fxb) + cx.y; fyb = rot_in(fyb) + cy.y;
+            if (s_ + 1 == HALF && tail_one_sided) { fjx.x -= cx.x; fjy.x -= cy.x; }      // (chain B's last pair: the travelling side only)
+            else { fjx -= cx; fjy -= cy; }
+            X = Xn; Y = Yn; U = Un; V = Vn;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // chain B's sums end XB lanes behind chain A's: onto chain A's lanes, and fi + fi2 as the general form's combine adds them
+        const int from = ((lane - XB) & (WAVE - 1)) << 2;
+        fxi += __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(fxb)));
+        fyi += __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(fyb)));
+    };
+    if (diag) chain(std::integral_constant<int, 16>{});
+    else chain(std::integral_constant<int, 32>{});
+    sh.fi[wave][(lane + s0 + HALF - 1) & (WAVE - 1)] = make_float2(fxi, fyi);
+    sh.fj[wave][lane] = make_float2(fjx.x + fjx.y, fjy.x + fjy.y);
+    __syncthreads();
+    if (!lower) return;
+    const int tl = (p >> 6) & 1, l = lane;
+    float2 r = make_float2(0.f, 0.f);
+    int row;
+    if (diag_item) {
+        const int w0 = (p < GROUP) ? 0 : NW / 2;
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            const float2 u = sh.fi[w0 + tl * D + k][l], v = sh.fj[w0 + tl * D + k][l];
+            r.x += u.x + v.x; r.y += u.y + v.y;
+        }
+#pragma unroll
+        for (int k = 0; k < 2 * D; ++k) {
+            const float2 u = tl ? sh.fj[w0 + 2 * D + k][l] : sh.fi[w0 + 2 * D + k][l];
+            r.x += u.x; r.y += u.y;
+        }
+        row = G;
+    } else if (p < GROUP) {
+#pragma unroll
+        for (int k = 0; k < NW / 2; ++k) { const float2 u = sh.fi[tl * (NW / 2) + k][l]; r.x += u.x; r.y += u.y; }
+        row = GY;
+    } else {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int k = 0; k < NW / 4; ++k) { const float2 u = sh.fj[(2 * h + tl) * (NW / 4) + k][l]; r.x += u.x; r.y += u.y; }
+        row = GX;
+    }
+    a.slab_next[(uint32_t)row * (uint32_t)N + (uint32_t)i] = r;
+}
+
+}  // namespace lean
+
 // ------------------------------------------------------------------------------------------------------
 // launch helpers (host)
 // ------------------------------------------------------------------------------------------------------
@@ -2514,6 +2801,28 @@ hipError_t launch_fused_tick(bool rad, const TickArgs& a, const FusedArgs& f, hi
     const dim3 grid(f.n_geo_wg + f.n_pair_wg + n_adv);
     if (nw == 8) { if (rad) launch_fused_t<true, 8>(grid, geo, z3, a, f, st); else launch_fused_t<false, 8>(grid, geo, z3, a, f, st); }
     else { if (rad) launch_fused_t<true, 16>(grid, geo, z3, a, f, st); else launch_fused_t<false, 16>(grid, geo, z3, a, f, st); }
+    return hipGetLastError();
+}
+
+// the lean form (lean::sfm_fused_tick_kernel) takes a whole planar crowd of 8, 16, 24 or 32 whole groups in the XCD-blocked item order,
+// without radii and without geometry or vehicle workgroups
+bool fused_lean_takes(bool rad, const TickArgs& a, const FusedArgs& f) {
+    return !rad && !f.slabz_next && f.n_geo_wg == 0 && f.blocked && f.n_g <= 32 && f.n_g % 8 == 0 && a.N == f.n_g * GROUP && a.N_pad == a.N &&
+           f.n_t == 2 * f.n_g;
+}
+
+hipError_t launch_fused_tick_lean(const TickArgs& a, const FusedArgs& f, hipStream_t st) {
+    if (!fused_lean_takes(false, a, f)) return hipErrorInvalidValue;
+    LeanTickArgs l{a.pk_cur, a.pk_next, f.own_cur, f.own_next, f.slab_prev, f.slab_next, a.draws, a.ids, a.ped,
+                   a.inv_tau, a.dt, a.max_speed_factor, a.arrive_thr2, a.seed, a.world_side,
+                   (a.flags & 3u) | (a.en_acc ? LEAN_EN_ACC : 0u) | (a.en_ped ? LEAN_EN_PED : 0u) | (f.mode != 0 ? LEAN_INTEGRATE : 0u), 0u};
+    const dim3 grid(f.n_pair_wg), block(16 * WAVE);
+    switch (f.n_g) {
+        case 8: hipLaunchKernelGGL((lean::sfm_fused_tick_kernel<8>), grid, block, 0, st, l); break;
+        case 16: hipLaunchKernelGGL((lean::sfm_fused_tick_kernel<16>), grid, block, 0, st, l); break;
+        case 24: hipLaunchKernelGGL((lean::sfm_fused_tick_kernel<24>), grid, block, 0, st, l); break;
+        default: hipLaunchKernelGGL((lean::sfm_fused_tick_kernel<32>), grid, block, 0, st, l); break;
+    }
     return hipGetLastError();
 }
 

@@ -445,6 +445,10 @@ class SfmEngine:
     def kernel_variant(self):
         return self._lib.sfm_kernel_variant(self._h).decode()
 
+    def fused_form(self):
+        """The form of sfm_fused_tick_kernel the last device-resident run launched: '...<lean>', '...<general>' or 'none'."""
+        return self._lib.sfm_fused_form(self._h).decode()
+
     def pair_work(self):
         """(tile-pair work items, Moussaid terms evaluated) of the symmetric pair kernel in the last tick."""
         items, terms = C.c_longlong(0), C.c_longlong(0)

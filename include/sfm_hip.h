@@ -260,6 +260,11 @@ int sfm_set_timing(SfmHandle* h, int enable);
 int sfm_profile_dominant_kernel(SfmHandle* h, int reps, float* avg_us);
 /* Name of the pair kernel variant the last tick used (for profiles), static storage. */
 const char* sfm_kernel_variant(const SfmHandle* h);
+/* Which form of sfm_fused_tick_kernel the last launch of a device-resident run was: "sfm_fused_tick_kernel<lean>" (a whole planar
+ * crowd of a multiple of 1024 pedestrians, up to 4096, without radii, border / obstacle forces or vehicles; SFM_FUSED_LEAN=0 at
+ * sfm_create turns it off), "sfm_fused_tick_kernel<general>", or "none" when the last run was not a fused one.  The two forms
+ * give the same bits; sfm_kernel_variant does not tell them apart.  Static storage. */
+const char* sfm_fused_form(const SfmHandle* h);
 /* Work the symmetric pair kernel did in the last tick (measurement only; no reference counterpart -- the reference
  * always evaluates all N(N-1) ordered pairs, forces.py:74-117): tile-pair work items (whole 2-D grid, or the compacted
  * list when the provably-negligible tile pairs are cut) and the Moussaid terms evaluated for them (one per unordered

@@ -1,0 +1,134 @@
+"""The lean form of the fused tick (csrc/sfm_kernels.hip, lean::sfm_fused_tick_kernel): whole planar crowds of a
+multiple of 1024 pedestrians (up to 4096) without radii, border / obstacle forces or vehicles.  It does the general form's arithmetic
+in the general form's order, so the two must agree BIT FOR BIT; ``SFM_FUSED_LEAN=0`` at creation keeps a handle on the general form.
+``SfmEngine.fused_form()`` says which form the last run launched (``kernel_variant()`` is "sfm_fused_tick_kernel" for both: other
+tests pin that string)."""
+import numpy as np
+import pytest
+
+import _parity as P
+from carla_social_force_model_amd import scenarios
+from carla_social_force_model_amd.config import default_sfm_config
+from carla_social_force_model_amd.engine import SfmEngine
+from oracle import c_oracle
+from oracle import sfm_oracle as O
+
+pytestmark = pytest.mark.gpu
+LEAN, GENERAL = "sfm_fused_tick_kernel<lean>", "sfm_fused_tick_kernel<general>"
+FORCES = ("acceleration_force", "pedestrian_force")
+
+
+def _crowd(n, kind):
+    sc = scenarios.make_scenario(n, 9100 + n)
+    if kind == "coincident":
+        sc.loc[n // 2] = sc.loc[n // 2 + 70]                  # two pedestrians of different tiles at the same place (NaN -> the exact rows)
+        sc.loc[5] = sc.loc[6]                                 # ... and two of the same tile
+    if kind == "redraw":
+        sc.loc[::2, :2] = sc.waypoint[::2, :2]                # every other pedestrian stands on its waypoint: it draws at once
+    return sc
+
+
+def _engine(sc, monkeypatch, lean, use_radius=False):
+    monkeypatch.setenv("SFM_FUSED", "1")
+    monkeypatch.setenv("SFM_CUTOFF", "0")
+    if lean:
+        monkeypatch.delenv("SFM_FUSED_LEAN", raising=False)
+    else:
+        monkeypatch.setenv("SFM_FUSED_LEAN", "0")
+    cfg = default_sfm_config(FORCES)
+    cfg["use_ped_radius"] = use_radius
+    eng = SfmEngine(cfg, 0.05)
+    eng.upload_state(sc.loc, sc.vel, sc.waypoint, sc.target_speed, sc.radius, None)
+    eng.set_waypoint_stream(sc.seed, 0.3 * sc.world_side, 2.0)
+    return eng
+
+
+def _snapshot(eng):
+    loc, vel, wp = eng.state()
+    return [np.asarray(loc).copy(), np.asarray(vel).copy(), np.asarray(wp).copy(), eng.draw_counts().copy()]
+
+
+def _same(a, b, what):
+    for name, x, y in zip(("x", "v", "waypoint", "draws"), a, b):
+        assert np.isfinite(x).all(), (what, name)
+        assert np.array_equal(x, y), (what, name, int((np.asarray(x) != np.asarray(y)).sum()))
+
+
+@pytest.mark.parametrize("n,kind", [(1024, "plain"), (2048, "plain"), (3072, "plain"), (1024, "coincident"), (1024, "redraw")])
+def test_lean_equals_general_bit_for_bit(n, kind, monkeypatch):
+    """Two handles on one crowd, one held on the general form: state, waypoints and draw counters after each of eight sfm_run(1)."""
+    sc = _crowd(n, kind)
+    general = _engine(sc, monkeypatch, lean=False)
+    lean = _engine(sc, monkeypatch, lean=True)
+    try:
+        for k in range(8):
+            general.run(1, redraw=True)
+            lean.run(1, redraw=True)
+            assert general.fused_form() == GENERAL and lean.fused_form() == LEAN, (general.fused_form(), lean.fused_form())
+            assert "sfm_fused_tick_kernel" in lean.kernel_variant()
+            a, b = _snapshot(general), _snapshot(lean)
+            _same(b, a, f"N={n} {kind} tick {k}")
+        if kind == "redraw":
+            assert int(b[3].sum()) >= n // 2                  # the draws did happen
+    finally:
+        general.close()
+        lean.close()
+
+
+@pytest.mark.parametrize("n,use_radius", [(960, False), (1024, True)])
+def test_other_shapes_stay_on_the_general_form(n, use_radius, monkeypatch):
+    sc = scenarios.make_scenario(n, 9100 + n, density=0.25 if use_radius else 1.0)
+    eng = _engine(sc, monkeypatch, lean=True, use_radius=use_radius)
+    try:
+        assert eng.fused_form() == "none"
+        eng.run(2, redraw=True)
+        assert eng.kernel_variant() == "sfm_fused_tick_kernel" and eng.fused_form() == GENERAL, (eng.kernel_variant(), eng.fused_form())
+    finally:
+        eng.close()
+
+
+def test_lean_against_the_oracle(monkeypatch):
+    """N = 1024 on the lean form, re-synchronised with the oracle every tick: v' at 1e-5 (P.check_velocity), x' at 1e-6."""
+    n = 1024
+    sc = _crowd(n, "plain")
+    prm = O.OracleParams.from_config(default_sfm_config(FORCES))
+    eng = _engine(sc, monkeypatch, lean=True)
+    try:
+        loc, vel, wp = sc.loc.copy(), sc.vel.copy(), sc.waypoint.copy()
+        crossing = np.zeros(n, bool)
+        worst_v = worst_x = 0.0
+        for k in range(4):
+            eng.run(1, redraw=True)
+            assert eng.fused_form() == LEAN
+            dloc, dvel, dwp = eng.state()
+            with np.errstate(all="ignore"):
+                _, _, v_new, expo, _ = c_oracle.tick(loc, vel, wp, sc.target_speed, sc.radius, crossing, O.Geometry(), prm, 0.05,
+                                                     rows=(0, n), theta_tol=P.THETA_TOL)
+            worst_v = max(worst_v, P.check_velocity(dvel, v_new, expo, 0.05))
+            x_new = loc + 0.05 * v_new
+            x_new[:, 2] = loc[:, 2]
+            allow = 1e-6 * np.maximum(1.0, np.abs(x_new).max(axis=1)) + 0.05 * 0.05 * expo * 1.001   # (a row at a discontinuity: dt * dt * exposure)
+            err = np.abs(dloc - x_new).max(axis=1)
+            worst_x = max(worst_x, float((err / np.maximum(1.0, np.abs(x_new).max(axis=1))).max()))
+            assert (err <= allow).all(), f"tick {k}: x' off by {err.max():.3g}"
+            loc, vel = dloc, dvel
+            wp = np.concatenate([dwp, np.zeros((n, 1))], axis=1)
+        print(f"\nlean fused tick vs oracle, N={n}: worst v' rel {worst_v:.3g}  worst x' rel {worst_x:.3g}")
+    finally:
+        eng.close()
+
+
+def test_lean_run_cutting(monkeypatch):
+    """Runs of 4 + 4 + 1 ticks leave what one run of 9 leaves (the later runs carry the partial forces, no launch in front)."""
+    sc = _crowd(1024, "redraw")
+    cut = _engine(sc, monkeypatch, lean=True)
+    whole = _engine(sc, monkeypatch, lean=True)
+    try:
+        for t in (4, 4, 1):
+            cut.run(t, redraw=True)
+        whole.run(9, redraw=True)
+        assert cut.fused_form() == LEAN and whole.fused_form() == LEAN
+        _same(_snapshot(cut), _snapshot(whole), "4 + 4 + 1 against 9")
+    finally:
+        cut.close()
+        whole.close()
