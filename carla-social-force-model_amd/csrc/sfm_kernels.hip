@@ -1475,6 +1475,23 @@ __device__ __forceinline__ size_t pool_slot(const SymArgs& sa, int t, int u, uin
     return (size_t)(owner - sa.t_lo) * (size_t)n_t + shift;
 }
 
+// The column-sum trees: four rows as (a + b) + (c + d), eight as two of those.  The association sets the bits.
+__device__ __forceinline__ float sum4(float a, float b, float c, float d) { return (a + b) + (c + d); }
+__device__ __forceinline__ float2 sum4(float2 a, float2 b, float2 c, float2 d) { return make_float2(sum4(a.x, b.x, c.x, d.x), sum4(a.y, b.y, c.y, d.y)); }
+__device__ __forceinline__ float4 sum4(float4 a, float4 b, float4 c, float4 d) {
+    return make_float4(sum4(a.x, b.x, c.x, d.x), sum4(a.y, b.y, c.y, d.y), sum4(a.z, b.z, c.z, d.z), sum4(a.w, b.w, c.w, d.w));
+}
+__device__ __forceinline__ float2 sum8(const float2 (&v)[8]) {
+    return make_float2(sum4(v[0].x, v[1].x, v[2].x, v[3].x) + sum4(v[4].x, v[5].x, v[6].x, v[7].x),
+                       sum4(v[0].y, v[1].y, v[2].y, v[3].y) + sum4(v[4].y, v[5].y, v[6].y, v[7].y));
+}
+__device__ __forceinline__ float4 sum8(const float4 (&v)[8]) {
+    return make_float4(sum4(v[0].x, v[1].x, v[2].x, v[3].x) + sum4(v[4].x, v[5].x, v[6].x, v[7].x),
+                       sum4(v[0].y, v[1].y, v[2].y, v[3].y) + sum4(v[4].y, v[5].y, v[6].y, v[7].y),
+                       sum4(v[0].z, v[1].z, v[2].z, v[3].z) + sum4(v[4].z, v[5].z, v[6].z, v[7].z),
+                       sum4(v[0].w, v[1].w, v[2].w, v[3].w) + sum4(v[4].w, v[5].w, v[6].w, v[7].w));
+}
+
 constexpr int EPI_WAVES = 16;
 constexpr int EPI_INFLIGHT = 8;            // slab-row loads a wave keeps in flight under a cutoff (a multiple of 4; the sum's association follows it)
 
@@ -1581,13 +1598,15 @@ __global__ __launch_bounds__(EW * WAVE) void sfm_sym_epilogue_kernel(const TickA
                 }
 #pragma unroll
                 for (int q = 0; q < EPI_INFLIGHT; q += 4) {
-                    acc.x += (v[q].x + v[q + 1].x) + (v[q + 2].x + v[q + 3].x);
-                    acc.y += (v[q].y + v[q + 1].y) + (v[q + 2].y + v[q + 3].y);
-                    if (Z3) accz += (vz[q] + vz[q + 1]) + (vz[q + 2] + vz[q + 3]);
+                    const float2 s4 = sum4(v[q], v[q + 1], v[q + 2], v[q + 3]);
+                    acc.x += s4.x;
+                    acc.y += s4.y;
+                    if (Z3) accz += sum4(vz[q], vz[q + 1], vz[q + 2], vz[q + 3]);
                 }
             }
         }
     } else if (a.en_ped && a.tile_box) {
+        // (the kept-list block below is the strip branch's; as one lambda for both: 63 -> 62 VGPRs planar, 69 -> 71 in 3-D, spills moved)
         // cutoff on, flat: wave w owns partner tiles w, w + EW, ...; its lanes test 64 of them at a time, four such chunks with
         // their boxes in flight together, the kept tiles go to a list in LDS and their rows are read EPI_INFLIGHT at a time
         // (only the rows of evaluated tile pairs, ascending order within a chunk: deterministic)
@@ -1632,9 +1651,10 @@ __global__ __launch_bounds__(EW * WAVE) void sfm_sym_epilogue_kernel(const TickA
                 }
 #pragma unroll
                 for (int q = 0; q < EPI_INFLIGHT; q += 4) {
-                    acc.x += (v[q].x + v[q + 1].x) + (v[q + 2].x + v[q + 3].x);
-                    acc.y += (v[q].y + v[q + 1].y) + (v[q + 2].y + v[q + 3].y);
-                    if (Z3) accz += (vz[q] + vz[q + 1]) + (vz[q + 2] + vz[q + 3]);
+                    const float2 s4 = sum4(v[q], v[q + 1], v[q + 2], v[q + 3]);
+                    acc.x += s4.x;
+                    acc.y += s4.y;
+                    if (Z3) accz += sum4(vz[q], vz[q + 1], vz[q + 2], vz[q + 3]);
                 }
             }
         }
@@ -1644,9 +1664,10 @@ __global__ __launch_bounds__(EW * WAVE) void sfm_sym_epilogue_kernel(const TickA
         for (; u + 3 * EW < sa.n_t; u += 4 * EW) {          // 4 independent loads in flight
             const float2 v0 = col[(size_t)u * sa.stride], v1 = col[(size_t)(u + EW) * sa.stride];
             const float2 v2 = col[(size_t)(u + 2 * EW) * sa.stride], v3 = col[(size_t)(u + 3 * EW) * sa.stride];
-            acc.x += (v0.x + v1.x) + (v2.x + v3.x);
-            acc.y += (v0.y + v1.y) + (v2.y + v3.y);
-            if (Z3) accz += (colz[(size_t)u * sa.stride] + colz[(size_t)(u + EW) * sa.stride]) + (colz[(size_t)(u + 2 * EW) * sa.stride] + colz[(size_t)(u + 3 * EW) * sa.stride]);
+            const float2 s4 = sum4(v0, v1, v2, v3);
+            acc.x += s4.x;
+            acc.y += s4.y;
+            if (Z3) accz += sum4(colz[(size_t)u * sa.stride], colz[(size_t)(u + EW) * sa.stride], colz[(size_t)(u + 2 * EW) * sa.stride], colz[(size_t)(u + 3 * EW) * sa.stride]);
         }
         for (; u < sa.n_t; u += EW) {
             const float2 v = col[(size_t)u * sa.stride];
@@ -1683,7 +1704,8 @@ __global__ __launch_bounds__(EW * WAVE) void sfm_sym_epilogue_kernel(const TickA
     }
 
     // 2. coincident pairs in this tile: recompute its rows with the exact ordered body (rare)
-    // (the same loop as the fused tick's bad-row pass; shared, it flipped s_cbranch_scc0 / scc1 polarity in both kernels)
+    // (the same loop as the fused tick's bad-row pass; as one function it moved this kernel's SGPR spills, 4 -> 6, and swapped v_sub /
+    //  v_subrev and e32 / e64 compare encodings in the fused tick: only the lean form came out unchanged)
     if (exact) {
         for (int p = wave; p < WAVE; p += EW) {
             const int ip = t * WAVE + p;
@@ -1859,6 +1881,52 @@ struct FusedShared {                             // LDS of one pair-role workgro
     }
 };
 
+// ---- the pieces both forms of the fused tick are built from (sfm_fused_tick_kernel below, lean::sfm_fused_tick_kernel behind it)
+
+// The XCD-blocked work-item map: workgroup bid of a crowd of 4 s groups -> its group pair (GX, GY).  S: s where it is a constant of the
+// kernel (the lean form), 0 where it comes with the arguments.
+// n_g a multiple of 8: the groups go in four bands of s, and the workgroups that land on one XCD (w mod 8, observed on
+// MI355X; nothing but speed depends on it) take their group pairs from one pair of bands -- XCDs 0-5 the six pairs of
+// different bands (s x s workgroups each), XCDs 6 and 7 two bands' inner pairs each (s/2 diagonal items of neighbouring
+// groups + s (s-1) / 2 pairs per band = s x s for two bands).  An XCD's L2 then fetches the column sums of 2 s groups
+// instead of all 4 s: half the traffic across the fabric at the start of the launch.
+template <int S = 0>
+__device__ __forceinline__ void fused_blocked_item(int bid, int s_arg, int& GX, int& GY, bool& diag_item) {
+    const int s = S ? S : s_arg;
+    const int x = bid & 7;
+    int k = bid >> 3;
+    if (x < 6) {
+        const int I = x < 3 ? 0 : (x < 5 ? 1 : 2), J = x < 3 ? x + 1 : (x < 5 ? x - 1 : 3);
+        GX = I * s + k / s;
+        GY = J * s + k % s;
+        diag_item = false;
+    } else {
+        const int per_band = (s * s) >> 1;
+        const int I = 2 * (x - 6) + (k >= per_band ? 1 : 0);
+        if (k >= per_band) k -= per_band;
+        if (k < (s >> 1)) {
+            GX = I * s + 2 * k; GY = GX + 1;
+            diag_item = true;
+        } else {
+            int t = k - (s >> 1), u = 0;
+            while (t >= s - 1 - u) { t -= s - 1 - u; ++u; }      // triangular index -> (u, v), u < v < s
+            GX = I * s + u; GY = I * s + u + 1 + t;
+            diag_item = false;
+        }
+    }
+}
+
+// Pedestrian slot p of the workgroup as a travelling operand: {x, y, lambda vx, lambda vy} into the four planes of trav, each tile
+// twice back to back (plane c at + c * 4 * 2 * WAVE floats)
+__device__ __forceinline__ void put_travelling(float4 (&trav)[4][2 * WAVE], int p, float lam, const float4 ns) {
+    const float4 t = make_float4(ns.x, ns.y, lam * ns.z, lam * ns.w);
+    float* pl = reinterpret_cast<float*>(trav) + (p >> 6) * 2 * WAVE + (p & (WAVE - 1));
+    pl[0] = t.x; pl[WAVE] = t.x;
+    pl[8 * WAVE] = t.y; pl[9 * WAVE] = t.y;
+    pl[16 * WAVE] = t.z; pl[17 * WAVE] = t.z;
+    pl[24 * WAVE] = t.w; pl[25 * WAVE] = t.w;
+}
+
 template <bool RAD, int NW, bool Z3, bool GEO>   // NW waves per workgroup (8 or 16): 256 / NW systolic steps each
 __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_tick_kernel(const TickArgs a, const FusedArgs f) {   // 8 waves per SIMD: two 16-wave (four 8-wave) workgroups per CU (3-D, 8 waves: LDS allows three)
     constexpr int PARTS = NW / 2;                // the slab rows are split over this many 128-thread parts
@@ -1895,33 +1963,7 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
         GX = geo_tile >> 1; GY = n_g;
         diag_item = false;
     } else if (f.blocked) {
-        // n_g a multiple of 8: the groups go in four bands of s, and the workgroups that land on one XCD (w mod 8, observed on
-        // MI355X; nothing but speed depends on it) take their group pairs from one pair of bands -- XCDs 0-5 the six pairs of
-        // different bands (s x s workgroups each), XCDs 6 and 7 two bands' inner pairs each (s/2 diagonal items of neighbouring
-        // groups + s (s-1) / 2 pairs per band = s x s for two bands).  An XCD's L2 then fetches the column sums of 2 s groups
-        // instead of all 4 s: half the traffic across the fabric at the start of the launch.
-        const int s = n_g >> 2;
-        const int x = bid & 7;
-        int k = bid >> 3;
-        if (x < 6) {
-            const int I = x < 3 ? 0 : (x < 5 ? 1 : 2), J = x < 3 ? x + 1 : (x < 5 ? x - 1 : 3);
-            GX = I * s + k / s;
-            GY = J * s + k % s;
-            diag_item = false;
-        } else {
-            const int per_band = (s * s) >> 1;
-            const int I = 2 * (x - 6) + (k >= per_band ? 1 : 0);
-            if (k >= per_band) k -= per_band;
-            if (k < (s >> 1)) {
-                GX = I * s + 2 * k; GY = GX + 1;
-                diag_item = true;
-            } else {
-                int t = k - (s >> 1), u = 0;
-                while (t >= s - 1 - u) { t -= s - 1 - u; ++u; }      // triangular index -> (u, v), u < v < s
-                GX = I * s + u; GY = I * s + u + 1 + t;
-                diag_item = false;
-            }
-        }
+        fused_blocked_item(bid, n_g >> 2, GX, GY, diag_item);
     } else {
         // first the diagonal items (group bx with group bx + half_up), then the group pairs (bx, bx + shift) shift by shift; the
         // last shift of an even n_g (antipodal pairs) has only its lower half
@@ -1964,8 +2006,7 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
                 float2 gv[FUSED_GEO_SLICES_MAX];
 #pragma unroll
                 for (int k = 0; k < FUSED_GEO_SLICES_MAX; ++k) gv[k] = k < f.geo_slices ? f.geo_prev[(size_t)k * a.N_pad + i] : make_float2(0.f, 0.f);
-                geo_f = make_float2(((gv[0].x + gv[1].x) + (gv[2].x + gv[3].x)) + ((gv[4].x + gv[5].x) + (gv[6].x + gv[7].x)),
-                                    ((gv[0].y + gv[1].y) + (gv[2].y + gv[3].y)) + ((gv[4].y + gv[5].y) + (gv[6].y + gv[7].y)));
+                geo_f = sum8(gv);
             }
             if ((a.flags & 2u) && diag_item) { nd0 = a.draws[i]; pid = a.ids ? a.ids[i] : (uint32_t)i; }
         }
@@ -1996,17 +2037,14 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
                 // every wave of every workgroup runs this before its first systolic step)
                 const float4 v0 = col[(size_t)r00 * stride4], v1 = col[(size_t)(r00 + 1) * stride4];
                 const float4 v2 = col[(size_t)(r00 + 2) * stride4], v3 = col[(size_t)(r00 + 3) * stride4];
-                acc4 = make_float4((v0.x + v1.x) + (v2.x + v3.x), (v0.y + v1.y) + (v2.y + v3.y),
-                                   (v0.z + v1.z) + (v2.z + v3.z), (v0.w + v1.w) + (v2.w + v3.w));
+                acc4 = sum4(v0, v1, v2, v3);
             } else if (!Z3) {
                 for (int r0 = r00; r0 < r1; r0 += 8) {
                     float4 v[8];
 #pragma unroll
                     for (int k = 0; k < 8; ++k) v[k] = (r0 + k < r1) ? col[(size_t)(r0 + k) * stride4] : make_float4(0.f, 0.f, 0.f, 0.f);
-                    acc4.x += ((v[0].x + v[1].x) + (v[2].x + v[3].x)) + ((v[4].x + v[5].x) + (v[6].x + v[7].x));
-                    acc4.y += ((v[0].y + v[1].y) + (v[2].y + v[3].y)) + ((v[4].y + v[5].y) + (v[6].y + v[7].y));
-                    acc4.z += ((v[0].z + v[1].z) + (v[2].z + v[3].z)) + ((v[4].z + v[5].z) + (v[6].z + v[7].z));
-                    acc4.w += ((v[0].w + v[1].w) + (v[2].w + v[3].w)) + ((v[4].w + v[5].w) + (v[6].w + v[7].w));
+                    const float4 s8 = sum8(v);
+                    acc4.x += s8.x; acc4.y += s8.y; acc4.z += s8.z; acc4.w += s8.w;
                 }
             } else {
                 // (four rows in flight instead of eight: the z rows ride along and the registers are the same 64 per lane)
@@ -2018,12 +2056,10 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
                         v[k] = (r0 + k < r1) ? col[(size_t)(r0 + k) * stride4] : make_float4(0.f, 0.f, 0.f, 0.f);
                         vz[k] = (r0 + k < r1) ? colz[(size_t)(r0 + k) * stride4] : make_float2(0.f, 0.f);
                     }
-                    acc4.x += (v[0].x + v[1].x) + (v[2].x + v[3].x);
-                    acc4.y += (v[0].y + v[1].y) + (v[2].y + v[3].y);
-                    acc4.z += (v[0].z + v[1].z) + (v[2].z + v[3].z);
-                    acc4.w += (v[0].w + v[1].w) + (v[2].w + v[3].w);
-                    accz.x += (vz[0].x + vz[1].x) + (vz[2].x + vz[3].x);
-                    accz.y += (vz[0].y + vz[1].y) + (vz[2].y + vz[3].y);
+                    const float4 s4 = sum4(v[0], v[1], v[2], v[3]);
+                    const float2 s4z = sum4(vz[0], vz[1], vz[2], vz[3]);
+                    acc4.x += s4.x; acc4.y += s4.y; acc4.z += s4.z; acc4.w += s4.w;
+                    accz.x += s4z.x; accz.y += s4z.y;
                 }
             }
         }
@@ -2036,12 +2072,7 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
     // forces.py:40-52): acceleration towards the waypoint, capped velocity, position, arrival -> next waypoint
     auto put_state = [&](const float4 ns, const float2 nsz) {   // pedestrian slot p of the workgroup in the state the pairs are evaluated on
         sh.st[p] = ns;
-        const float4 t = make_float4(ns.x, ns.y, a.ped.lam * ns.z, a.ped.lam * ns.w);
-        float* pl = reinterpret_cast<float*>(sh.trav) + (p >> 6) * 2 * WAVE + (p & (WAVE - 1));      // plane c at + c * 4 * 2 * WAVE
-        pl[0] = t.x; pl[WAVE] = t.x;
-        pl[8 * WAVE] = t.y; pl[9 * WAVE] = t.y;
-        pl[16 * WAVE] = t.z; pl[17 * WAVE] = t.z;
-        pl[24 * WAVE] = t.w; pl[25 * WAVE] = t.w;
+        put_travelling(sh.trav, p, a.ped.lam, ns);
         if (Z3) {
             sh.stz[Z3 ? p : 0] = nsz;
             const float2 tz = make_float2(nsz.x, a.ped.lam * nsz.y);
@@ -2050,6 +2081,8 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
             plz[8 * WAVE] = tz.y; plz[9 * WAVE] = tz.y;
         }
     };
+    // (the lean form's finish is this one without z, geo_f and the FusedArgs; as one function over the argument struct the NaN tests came
+    //  out as other compares, v_cmp_class -> v_cmp_nlg, and two or three v_mov fewer, in both forms)
     auto finish = [&](const float2 g, const float gz) {
         const float fpx = a.en_ped ? a.ped.negA * g.x : 0.f, fpy = a.en_ped ? a.ped.negA * g.y : 0.f;
         const float fpz = (Z3 && a.en_ped) ? a.ped.negA * gz : 0.f;
@@ -2157,6 +2190,8 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
     }
 
     // ---- 2. this workgroup's tile pairs on the new state: every wave SPW systolic steps (sfm_pair_sym_kernel's step)
+    // (the lean form has this map without `work`; as one function, with `work` inside it or derived from ia / ib behind it, it cost this
+    //  kernel 1 to 4 scalar instructions in one form or another of every variant tried -- the two diagonal branches' tests no longer merge)
     int ia, ib, sig0;                             // LDS slots of the travelling / resident tile's lane 0, first rotation
     bool diag = false, work = true;
     if (diag_item) {
@@ -2204,6 +2239,8 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
         const float* plz = reinterpret_cast<const float*>(sh.travz) + (Z3 ? (ia >> 6) * 2 * WAVE + lane + s0 : 0);
         const float* plr = &sh.radt[RAD ? (ia >> 6) : 0][RAD ? lane + s0 : 0];
         v2f fjx = bcast(0.f), fjy = bcast(0.f), fjzv = bcast(0.f);
+        // (the lean form's chain is this one at RAD = Z3 = false, PRE = true; as one function the lean form is unchanged, the radius and
+        //  3-D forms of this kernel wait once or twice more: + 1 or 2 s_waitcnt)
         auto chain = [&](auto xb_tag) __attribute__((always_inline)) {
             constexpr int XB = decltype(xb_tag)::value;
             const bool tail_one_sided = diag && (s0 + XB + HALF - 1 == 32);       // sigma = 32 on a diagonal tile: one-sided (uniform)
@@ -2258,6 +2295,8 @@ __global__ __launch_bounds__(NW * WAVE, (NW == 8 && Z3) ? 6 : 8) void sfm_fused_
     __syncthreads();
     if (!lower || !present) return;
     const int tl = (p >> 6) & 1, l = lane;       // tile of the group, pedestrian of the tile
+    // (the combine below is the lean form's over other accessors; as one function over fi / fj it cost the lean form 3 scalar instructions
+    //  and changed this kernel's LDS address arithmetic, v_lshl_or / v_lshlrev counts)
     // sums of wave w for pedestrian l of its travelling / resident tile, z in the third component
     auto fi = [&](int w) {
         float2 v = sh.fi[w][l];
@@ -2319,9 +2358,10 @@ __global__ void sfm_arrived_kernel(const float4* __restrict__ pk, const float4* 
 }
 
 // ---- the lean form of the fused tick: a whole planar crowd of N_G * 128 pedestrians, N_G a multiple of 8 (N = 1024 ... 4096), no
-// radii, no border / obstacle role, no vehicles, 16 waves, the XCD-blocked item order.  The same arithmetic in the same order as
-// sfm_fused_tick_kernel<false, 16, false, false> above -- the two agree bit for bit (tests/test_fused_lean_gpu.py) -- with what that
-// kernel carries for the other shapes taken out:
+// radii, no border / obstacle role, no vehicles, 16 waves, the XCD-blocked item order.  It agrees bit for bit with
+// sfm_fused_tick_kernel<false, 16, false, false> above (tests/test_fused_lean_gpu.py).  The item map, the travelling-plane write and the
+// column-sum trees are the general form's own functions; the wave map, the double-step chain, the integration, the exact rows and the
+// combine are copies of its code (see the notes there on what one definition cost).  Particular to this form:
 //   * the arguments are LeanTickArgs, 128 bytes (two scalar loads), not TickArgs + FusedArgs;
 //   * every group and tile exists and every row is live, so `present` / `live` / `work` are gone, and N, the slab strides and the
 //     rows of a part are constants: a column sum's rows sit at immediate offsets from one address;
@@ -2354,34 +2394,9 @@ __global__ __launch_bounds__(16 * WAVE, 8) void sfm_fused_tick_kernel(const Lean
     const int lane = tid & (WAVE - 1);
     const int wave = uniform(tid >> 6);
     const bool en_acc = (a.bits & LEAN_EN_ACC) != 0, en_ped = (a.bits & LEAN_EN_PED) != 0, integrate = (a.bits & LEAN_INTEGRATE) != 0;
-    // the XCD-blocked item map of the general form (see there), s a constant
     int GX, GY;
     bool diag_item;
-    {
-        constexpr int s = N_G >> 2;
-        const int bid = (int)blockIdx.x;
-        const int x = bid & 7;
-        int k = bid >> 3;
-        if (x < 6) {
-            const int I = x < 3 ? 0 : (x < 5 ? 1 : 2), J = x < 3 ? x + 1 : (x < 5 ? x - 1 : 3);
-            GX = I * s + k / s;
-            GY = J * s + k % s;
-            diag_item = false;
-        } else {
-            constexpr int per_band = (s * s) >> 1;
-            const int I = 2 * (x - 6) + (k >= per_band ? 1 : 0);
-            if (k >= per_band) k -= per_band;
-            if (k < (s >> 1)) {
-                GX = I * s + 2 * k; GY = GX + 1;
-                diag_item = true;
-            } else {
-                int t = k - (s >> 1), u = 0;
-                while (t >= s - 1 - u) { t -= s - 1 - u; ++u; }      // triangular index -> (u, v), u < v < s
-                GX = I * s + u; GY = I * s + u + 1 + t;
-                diag_item = false;
-            }
-        }
-    }
+    fused_blocked_item<(N_G >> 2)>((int)blockIdx.x, N_G >> 2, GX, GY, diag_item);
 
     // ---- 1. the state of this launch (the general form's step 1): own rows, then the column sums, every load before the first use
     const int quarter = wave & 3;
@@ -2417,17 +2432,14 @@ __global__ __launch_bounds__(16 * WAVE, 8) void sfm_fused_tick_kernel(const Lean
             if (PER == 4) {                      // the general form's four-row case
                 const float4 v0 = col(0), v1 = col(1), v2 = col(2), v3 = col(3);
                 __builtin_amdgcn_sched_barrier(0);                   // (all four in flight before the first add waits)
-                acc4 = make_float4((v0.x + v1.x) + (v2.x + v3.x), (v0.y + v1.y) + (v2.y + v3.y),
-                                   (v0.z + v1.z) + (v2.z + v3.z), (v0.w + v1.w) + (v2.w + v3.w));
+                acc4 = sum4(v0, v1, v2, v3);
             } else {                             // ... and its eight-wide loop, one trip: absent rows are 0 and still added
                 float4 v[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) v[k] = (k < PER) ? col(k < PER ? k : 0) : make_float4(0.f, 0.f, 0.f, 0.f);
                 __builtin_amdgcn_sched_barrier(0);
-                acc4.x += ((v[0].x + v[1].x) + (v[2].x + v[3].x)) + ((v[4].x + v[5].x) + (v[6].x + v[7].x));
-                acc4.y += ((v[0].y + v[1].y) + (v[2].y + v[3].y)) + ((v[4].y + v[5].y) + (v[6].y + v[7].y));
-                acc4.z += ((v[0].z + v[1].z) + (v[2].z + v[3].z)) + ((v[4].z + v[5].z) + (v[6].z + v[7].z));
-                acc4.w += ((v[0].w + v[1].w) + (v[2].w + v[3].w)) + ((v[4].w + v[5].w) + (v[6].w + v[7].w));
+                const float4 s8 = sum8(v);
+                acc4.x += s8.x; acc4.y += s8.y; acc4.z += s8.z; acc4.w += s8.w;
             }
         }
         sh.q[part][2 * pp] = make_float2(acc4.x, acc4.y);
@@ -2436,12 +2448,7 @@ __global__ __launch_bounds__(16 * WAVE, 8) void sfm_fused_tick_kernel(const Lean
     __syncthreads();
     auto put_state = [&](const float4 ns) {
         sh.st[p] = ns;
-        const float4 t = make_float4(ns.x, ns.y, a.ped.lam * ns.z, a.ped.lam * ns.w);
-        float* pl = reinterpret_cast<float*>(sh.trav) + (p >> 6) * 2 * WAVE + (p & (WAVE - 1));      // plane c at + c * 4 * 2 * WAVE
-        pl[0] = t.x; pl[WAVE] = t.x;
-        pl[8 * WAVE] = t.y; pl[9 * WAVE] = t.y;
-        pl[16 * WAVE] = t.z; pl[17 * WAVE] = t.z;
-        pl[24 * WAVE] = t.w; pl[25 * WAVE] = t.w;
+        put_travelling(sh.trav, p, a.ped.lam, ns);
     };
     auto finish = [&](const float2 g) {
         const float fpx = en_ped ? a.ped.negA * g.x : 0.f, fpy = en_ped ? a.ped.negA * g.y : 0.f;
@@ -2608,6 +2615,10 @@ __global__ __launch_bounds__(16 * WAVE, 8) void sfm_fused_tick_kernel(const Lean
 // ------------------------------------------------------------------------------------------------------
 // launch helpers (host)
 // ------------------------------------------------------------------------------------------------------
+// A run-time flag as a compile-time one: f(std::true_type{}) or f(std::false_type{}); nested calls name every combination once
+template <class F>
+static auto with_flag(bool flag, F&& f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
+
 template <int IPW, bool Z3, bool RAD, int TEAM>
 static hipError_t launch_one(const TickArgs& a, hipStream_t st) {
     const int n_local = a.i_end - a.i_begin;
@@ -2633,8 +2644,7 @@ static hipError_t launch_ipw(int ipw, const TickArgs& a, hipStream_t st) {
 
 template <int TEAM>
 static hipError_t launch_team(int ipw, bool z3, bool rad, const TickArgs& a, hipStream_t st) {
-    if (z3) return rad ? launch_ipw<true, true, TEAM>(ipw, a, st) : launch_ipw<true, false, TEAM>(ipw, a, st);
-    return rad ? launch_ipw<false, true, TEAM>(ipw, a, st) : launch_ipw<false, false, TEAM>(ipw, a, st);
+    return with_flag(z3, [&](auto Z3) { return with_flag(rad, [&](auto RAD) { return launch_ipw<Z3.value, RAD.value, TEAM>(ipw, a, st); }); });
 }
 
 hipError_t launch_tick(int ipw, int team, bool z3, bool rad, const TickArgs& a, hipStream_t st) {
@@ -2660,13 +2670,10 @@ hipError_t launch_geometry(bool rad, const TickArgs& a, hipStream_t st) {
         extra = (a.list_n_t * (a.list_n_t / 2 + 1) + threads - 1) / threads;
         b.list_block0 = grid;
     }
-    if (thin) {
-        if (rad) hipLaunchKernelGGL((sfm_geometry_kernel<true, 8>), dim3(grid + extra, a.geo_slices), dim3(8 * WAVE), 0, st, b);
-        else hipLaunchKernelGGL((sfm_geometry_kernel<false, 8>), dim3(grid + extra, a.geo_slices), dim3(8 * WAVE), 0, st, b);
-    } else {
-        if (rad) hipLaunchKernelGGL((sfm_geometry_kernel<true, GEO_WAVES>), dim3(grid + extra, a.geo_slices), dim3(GEO_BLOCK), 0, st, b);
-        else hipLaunchKernelGGL((sfm_geometry_kernel<false, GEO_WAVES>), dim3(grid + extra, a.geo_slices), dim3(GEO_BLOCK), 0, st, b);
-    }
+    with_flag(rad, [&](auto RAD) {
+        if (thin) hipLaunchKernelGGL((sfm_geometry_kernel<RAD.value, 8>), dim3(grid + extra, a.geo_slices), dim3(8 * WAVE), 0, st, b);
+        else hipLaunchKernelGGL((sfm_geometry_kernel<RAD.value, GEO_WAVES>), dim3(grid + extra, a.geo_slices), dim3(GEO_BLOCK), 0, st, b);
+    });
     return hipGetLastError();
 }
 
@@ -2688,18 +2695,6 @@ hipError_t launch_sym_list(const TickArgs& a, const SymArgs& sa, hipStream_t st,
     return hipGetLastError();
 }
 
-template <bool RAD, bool CUT>
-static void launch_sym_pair_t(dim3 grid, const TickArgs& a, const SymArgs& sa, hipStream_t st) {
-    if (sa.slabz) hipLaunchKernelGGL((sfm_pair_sym_kernel<RAD, CUT, true>), grid, dim3(BLOCK), 0, st, a.pk_cur, a.zv_cur, a.radius, a.ped, sa);
-    else hipLaunchKernelGGL((sfm_pair_sym_kernel<RAD, CUT, false>), grid, dim3(BLOCK), 0, st, a.pk_cur, a.zv_cur, a.radius, a.ped, sa);
-}
-
-template <bool RAD, bool CUT>
-static void launch_sym_pair_geo_t(dim3 grid, const TickArgs& a, const SymArgs& sa, int tiles, int stride, hipStream_t st) {
-    if (sa.slabz) hipLaunchKernelGGL((sfm_pair_geo_kernel<RAD, CUT, true>), grid, dim3(BLOCK), 0, st, a, sa, tiles, stride);
-    else hipLaunchKernelGGL((sfm_pair_geo_kernel<RAD, CUT, false>), grid, dim3(BLOCK), 0, st, a, sa, tiles, stride);
-}
-
 // List mode: the grid is a few times what fits at once, each workgroup a contiguous run of the list.  The list holds the items of the
 // OWN tiles (a shard's list is an eighth of the whole crowd's: with the whole crowd's 16 rounds its workgroups got 0.8 items each and
 // a third of the launch was workgroups that found nothing -- c5, one rank of 8: 151.7 us per tick at 16 rounds, 148.2 at 8,
@@ -2716,8 +2711,9 @@ hipError_t launch_sym_pair(bool rad, const TickArgs& a, const SymArgs& sa, hipSt
         grid = dim3(256 * 8 * list_rounds(sa));
     }
     const bool cut = sa.vmax != nullptr;           // list cutoff: the per-step reach and exponent tests are on as well
-    if (rad) { if (cut) launch_sym_pair_t<true, true>(grid, a, sa, st); else launch_sym_pair_t<true, false>(grid, a, sa, st); }
-    else { if (cut) launch_sym_pair_t<false, true>(grid, a, sa, st); else launch_sym_pair_t<false, false>(grid, a, sa, st); }
+    with_flag(rad, [&](auto RAD) { with_flag(cut, [&](auto CUT) { with_flag(sa.slabz != nullptr, [&](auto Z3) {
+        hipLaunchKernelGGL((sfm_pair_sym_kernel<RAD.value, CUT.value, Z3.value>), grid, dim3(BLOCK), 0, st, a.pk_cur, a.zv_cur, a.radius, a.ped, sa);
+    }); }); });
     return hipGetLastError();
 }
 
@@ -2730,8 +2726,9 @@ hipError_t launch_sym_pair_geo(bool rad, const TickArgs& a, const SymArgs& sa, h
     int stride = n_geo > 256 * 4 ? std::max(1, (n_geo + n_pair) / n_geo) : 1;
     if (stride > 1 && !(stride & 1)) --stride;      // odd: workgroup w runs on CU w mod 256, an even stride would put every geometry workgroup on a few CUs
     const bool cut = sa.vmax != nullptr;           // as launch_sym_pair: list cutoff -> the per-step tests are on
-    if (rad) { if (cut) launch_sym_pair_geo_t<true, true>(grid, a, sa, tiles, stride, st); else launch_sym_pair_geo_t<true, false>(grid, a, sa, tiles, stride, st); }
-    else { if (cut) launch_sym_pair_geo_t<false, true>(grid, a, sa, tiles, stride, st); else launch_sym_pair_geo_t<false, false>(grid, a, sa, tiles, stride, st); }
+    with_flag(rad, [&](auto RAD) { with_flag(cut, [&](auto CUT) { with_flag(sa.slabz != nullptr, [&](auto Z3) {
+        hipLaunchKernelGGL((sfm_pair_geo_kernel<RAD.value, CUT.value, Z3.value>), grid, dim3(BLOCK), 0, st, a, sa, tiles, stride);
+    }); }); });
     return hipGetLastError();
 }
 
@@ -2765,8 +2762,7 @@ static void launch_sym_epilogue_t(const TickArgs& a, const SymArgs& sa, hipStrea
     b.adv.block0 = sa.t_hi - sa.t_lo;
     const int extra = a.adv.M > 0 ? (a.adv.M + EW - 1) / EW : 0;
     const dim3 grid(sa.t_hi - sa.t_lo + extra);
-    if (sa.slabz) hipLaunchKernelGGL((sfm_sym_epilogue_kernel<RAD, EW, true>), grid, dim3(EW * WAVE), 0, st, b, sb);
-    else hipLaunchKernelGGL((sfm_sym_epilogue_kernel<RAD, EW, false>), grid, dim3(EW * WAVE), 0, st, b, sb);
+    with_flag(sa.slabz != nullptr, [&](auto Z3) { hipLaunchKernelGGL((sfm_sym_epilogue_kernel<RAD, EW, Z3.value>), grid, dim3(EW * WAVE), 0, st, b, sb); });
 }
 
 // 16 waves per tile for small and mid-sized crowds (one dependent round of slab-row loads); from 1024 tiles on there are
@@ -2774,8 +2770,7 @@ static void launch_sym_epilogue_t(const TickArgs& a, const SymArgs& sa, hipStrea
 hipError_t launch_sym_epilogue(bool rad, const TickArgs& a, const SymArgs& sa, hipStream_t st) {
     if (a.N <= 0) return hipSuccess;
     const bool thin = sa.n_t >= 1024;
-    if (rad) { if (thin) launch_sym_epilogue_t<true, 4>(a, sa, st); else launch_sym_epilogue_t<true, EPI_WAVES>(a, sa, st); }
-    else { if (thin) launch_sym_epilogue_t<false, 4>(a, sa, st); else launch_sym_epilogue_t<false, EPI_WAVES>(a, sa, st); }
+    with_flag(rad, [&](auto RAD) { if (thin) launch_sym_epilogue_t<RAD.value, 4>(a, sa, st); else launch_sym_epilogue_t<RAD.value, EPI_WAVES>(a, sa, st); });
     return hipGetLastError();
 }
 
@@ -2783,24 +2778,15 @@ hipError_t launch_sym_epilogue(bool rad, const TickArgs& a, const SymArgs& sa, h
 // number of pair workgroups of the fused tick: diagonal items, full shifts, the half shift of an even n_g
 int fused_pair_workgroups(int n_g) { return (n_g + 1) / 2 + n_g * ((n_g - 1) / 2) + ((n_g & 1) ? 0 : n_g / 2); }
 
-template <bool RAD, int NW>
-static void launch_fused_t(dim3 grid, bool geo, bool z3, const TickArgs& a, const FusedArgs& f, hipStream_t st) {
-    if (z3) {
-        if (geo) hipLaunchKernelGGL((sfm_fused_tick_kernel<RAD, NW, true, true>), grid, dim3(NW * WAVE), 0, st, a, f);
-        else hipLaunchKernelGGL((sfm_fused_tick_kernel<RAD, NW, true, false>), grid, dim3(NW * WAVE), 0, st, a, f);
-    } else {
-        if (geo) hipLaunchKernelGGL((sfm_fused_tick_kernel<RAD, NW, false, true>), grid, dim3(NW * WAVE), 0, st, a, f);
-        else hipLaunchKernelGGL((sfm_fused_tick_kernel<RAD, NW, false, false>), grid, dim3(NW * WAVE), 0, st, a, f);
-    }
-}
-
 hipError_t launch_fused_tick(bool rad, const TickArgs& a, const FusedArgs& f, hipStream_t st, int nw) {
     if (a.N <= 1 || f.n_g < 1) return hipErrorInvalidValue;
     const bool geo = f.n_geo_wg > 0, z3 = f.slabz_next != nullptr;
     const int n_adv = (geo && a.adv.M > 0) ? (a.adv.M + nw - 1) / nw : 0;
     const dim3 grid(f.n_geo_wg + f.n_pair_wg + n_adv);
-    if (nw == 8) { if (rad) launch_fused_t<true, 8>(grid, geo, z3, a, f, st); else launch_fused_t<false, 8>(grid, geo, z3, a, f, st); }
-    else { if (rad) launch_fused_t<true, 16>(grid, geo, z3, a, f, st); else launch_fused_t<false, 16>(grid, geo, z3, a, f, st); }
+    with_flag(rad, [&](auto RAD) { with_flag(z3, [&](auto Z3) { with_flag(geo, [&](auto GEO) {
+        if (nw == 8) hipLaunchKernelGGL((sfm_fused_tick_kernel<RAD.value, 8, Z3.value, GEO.value>), grid, dim3(8 * WAVE), 0, st, a, f);
+        else hipLaunchKernelGGL((sfm_fused_tick_kernel<RAD.value, 16, Z3.value, GEO.value>), grid, dim3(16 * WAVE), 0, st, a, f);
+    }); }); });
     return hipGetLastError();
 }
 

@@ -54,7 +54,8 @@ def _same(a, b, what):
         assert np.array_equal(x, y), (what, name, int((np.asarray(x) != np.asarray(y)).sum()))
 
 
-@pytest.mark.parametrize("n,kind", [(1024, "plain"), (2048, "plain"), (3072, "plain"), (1024, "coincident"), (1024, "redraw")])
+@pytest.mark.parametrize("n,kind", [(1024, "plain"), (2048, "plain"), (3072, "plain"), (4096, "plain"), (1024, "coincident"), (4096, "coincident"),
+                                    (1024, "redraw")])
 def test_lean_equals_general_bit_for_bit(n, kind, monkeypatch):
     """Two handles on one crowd, one held on the general form: state, waypoints and draw counters after each of eight sfm_run(1)."""
     sc = _crowd(n, kind)
