@@ -33,12 +33,16 @@ SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_
                             "sfm_batch_observation_ptr")},
          **{n: 16 for n in ("sfm_batch_set_episodes", "sfm_batch_end_step", "sfm_batch_download_episodes",
                             "sfm_batch_restart_device")},
-         # (the restart noise and the grids came without a bump of the ABI number: additions only, include/sfm_hip.h says why)
+         # (the restart noise, the grids and the observed tracks came without a bump of the ABI number: additions only, include/sfm_hip.h says why)
          **{n: 17 for n in ("sfm_batch_set_scan", "sfm_batch_scan", "sfm_batch_download_scan",
                             "sfm_batch_set_restart_noise", "sfm_batch_download_restart_noise",
-                            "sfm_batch_set_grid", "sfm_batch_grid", "sfm_batch_download_grid")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
+                            "sfm_batch_set_grid", "sfm_batch_grid", "sfm_batch_download_grid",
+                            "sfm_batch_set_observed", "sfm_batch_run_observed", "sfm_batch_score",
+                            "sfm_batch_download_scores")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
 UNBUMPED = ("sfm_batch_set_restart_noise", "sfm_batch_download_restart_noise",
-            "sfm_batch_set_grid", "sfm_batch_grid", "sfm_batch_download_grid")   # ... and those a build of the SAME number may lack
+            "sfm_batch_set_grid", "sfm_batch_grid", "sfm_batch_download_grid",
+            "sfm_batch_set_observed", "sfm_batch_run_observed", "sfm_batch_score",
+            "sfm_batch_download_scores")   # ... and those a build of the SAME number may lack
 
 FORCE_NAMES = ("acceleration_force", "pedestrian_force", "border_force",
                "static_obstacle_force", "dynamic_obstacle_force")
@@ -174,6 +178,11 @@ SYMBOLS = {
     "sfm_batch_set_grid": (C.c_int, [_H, C.c_int, _F, _U8, C.c_int]),
     "sfm_batch_grid": (C.c_int, [_H]),
     "sfm_batch_download_grid": (C.c_int, [_H, _F]),
+    # batch observed tracks (ABI 17, added without a bump)
+    "sfm_batch_set_observed": (C.c_int, [_H, C.c_void_p, _I, _F, _U8, _F, C.c_int]),
+    "sfm_batch_run_observed": (C.c_int, [_H, C.c_int, C.c_int, C.c_uint32]),
+    "sfm_batch_score": (C.c_int, [_H]),
+    "sfm_batch_download_scores": (C.c_int, [_H, _F, _F]),
 }
 
 _lib = None

@@ -115,6 +115,21 @@ row order, so the buffer is ``(M, 6, G, G)`` for M gridded rows, not one record 
 per scene, ``grid_rows()`` names the row of every slot, ``grid_tensor()`` is the buffer as a torch tensor a conv layer reads as it
 stands, and ``grid.grid_scene`` is the host twin, bit for bit in both frames, velocity sums included (the record and its exact
 rules: include/sfm_hip.h).  Gridding changes nothing a tick reads: examples/batch_grid_loop.py.
+
+Observed tracks (ABI 17, added without a bump): calibration against recorded motion with no host in the loop, the protocol of
+Johansson et al. 2007.  ``set_observed(tracks, roles, every, v0)`` puts each scene's recording on the device -- ``(F_b, n_b, 2)``
+positions per scene, NaN where a pedestrian is not seen, one frame every ``every`` ticks -- and gives every row a role: 0 not part
+of the data (left alone bit for bit), 1 replayed, 2 scored.  ``run_observed(first, frames)`` launches, per frame, one frame kernel
+and then ``every`` ticks: a replayed row is put on its track with the velocity that carries it to its next frame (a velocity
+command, so nothing drifts), parked like a despawned row while it is not seen -- people enter and leave --, and a scored row is
+placed at its first frame, simulated by the model from there on and compared with its track at every later frame it is seen in;
+the error sums stay on the device.  ``score()`` reduces them per scene to ``{rows, samples, sum_d, sum_d2, sum_final_d}``
+(``replay.metrics``: ADE, RMSE, FDE); ``scene_scores()`` / ``row_scores()`` download them, ``scene_score_tensor()`` /
+``row_score_tensor()`` alias them.  A sweep is ``set_params``, ``run_observed(0, F)``, ``scene_scores()``: one copy of B x 5
+floats per candidate.  Steering is switched on if it is off (rows of role 0 keep the caller's commands); ``upload``, ``set_modes``,
+``set_spawns`` and ``set_steering(None)`` drop the tracks.  ``replay.replay_frame`` and ``replay.score_scene`` are the host twins, bit for
+bit, and ``replay.scene_from_tracks`` packs a recording into a scene (the exact rules: include/sfm_hip.h):
+examples/batch_calibration_sweep.py.
 """
 from __future__ import annotations
 
@@ -124,6 +139,7 @@ import numpy as np
 
 from . import _lib
 from . import grid as _grid
+from . import replay as _replay
 from . import scan as _scan
 from ._args import FRAME_HEADING, FRAME_WORLD, MAX_METRES as MAX_SENSE_RANGE, check_frame, per_scene, per_scene_metres
 from ._lib import SfmLibraryError, f32, fptr, iptr, u8ptr
@@ -565,6 +581,7 @@ PTR_COMMANDS, PTR_STATE, PTR_ZSTATE = 0, 1, 2          # SFM_BATCH_PTR_*: what s
 PTR_EPISODES, PTR_DONE = 3, 4                          # ... the episode record [B][8] and the mask done[B] (while episodes are on)
 PTR_SCAN = 5                                           # ... the scan record [N_total][2R] (while scans are on)
 PTR_GRID = 7                                           # ... the grid record [M][6][G][G] (while grids are on; 6 is PTR_RESETS)
+PTR_ROW_SCORES, PTR_SCENE_SCORES = 8, 9                # ... the row scores [N_total][4] and scene scores [B][5] (while observed tracks are on)
 
 
 def _per_scene(v, so, width, name):
@@ -817,6 +834,7 @@ class SfmBatch:
         self.grid_cells = None            # cells per side of set_grid (None: grids are off)
         self._grid_rows = self._grid_counts = None
         self.has_restart_noise = False    # set_restart_noise has been called and no later call has dropped it
+        self.observed_every = None        # ticks per observed frame of set_observed (None: observed tracks are off)
 
     def _check(self, rc, what):
         if rc != 0:
@@ -897,6 +915,7 @@ class SfmBatch:
         self.grid_cells = None            # ... and the grids
         self._grid_rows = self._grid_counts = None
         self.has_restart_noise = False    # ... and the restart noise
+        self.observed_every = None        # ... and the observed tracks
         self.planar = planar
         self._z = pk["z"].copy()          # a planar batch keeps each scene's z on the host (the device holds x / y only)
 
@@ -1091,6 +1110,7 @@ class SfmBatch:
         L = self._lib
         if kinds is None:
             self._check(L.sfm_batch_set_steering(self._b, None, None, None, None), "sfm_batch_set_steering")
+            self.observed_every = None                                 # (observed tracks are replayed through the commands)
             return
         self._need_upload("set_steering")
         kd, ux, uy, uz = pack_steering(kinds, commands, self.scene_off)
@@ -1324,6 +1344,81 @@ class SfmBatch:
         G = self.grid_cells
         return self._alias(ptr, (int(nbytes.value) // (4 * _grid.GRID_CHANNELS * G * G), _grid.GRID_CHANNELS, G, G), device)
 
+    def set_observed(self, tracks, roles=None, every=1, v0=None):
+        """The recording every scene is calibrated against (sfm_batch_set_observed; see ``replay.pack_observed`` and the module
+        docstring).  ``tracks``: a list of B arrays (F_b, n_b, 2), NaN in both components where a row is not seen, F_b <= 16384;
+        ``roles``: per row 0 (not part of the data), 1 (replayed) or 2 (scored), a list of B arrays or one array over the
+        concatenated rows; ``every``: ticks between two frames; ``v0``: optional initial velocities (n_b, 2), NaN = take it from
+        the track.  ``tracks=None`` switches the observed tracks off.  Needs a planar ``upload`` first and no modes; switches
+        steering on (every kind 0) if it is off -- ``command_tensor()`` must then be taken again.  ``upload``, ``set_modes``,
+        ``set_spawns`` and ``set_steering(None)`` drop the tracks; every other call keeps them."""
+        L = self._lib
+        if tracks is None:
+            self._check(L.sfm_batch_set_observed(self._b, None, None, None, None, None, 0), "sfm_batch_set_observed")
+            self.observed_every = None
+            return
+        self._need_upload("set_observed")
+        if roles is None:
+            raise ValueError("set_observed needs roles")
+        if isinstance(every, (bool, np.bool_)) or not isinstance(every, (int, np.integer)):
+            raise ValueError(f"every must be an integer >= 1, got {every!r}")
+        off, frames, obs, r, v = _replay.pack_observed(tracks, roles, self.scene_off, v0)
+        one_f, one_u = np.zeros((1, 2), np.float32), np.zeros(1, np.uint8)
+        self._check(L.sfm_batch_set_observed(self._b, off.ctypes.data, iptr(frames), fptr(obs if obs.shape[0] else one_f),
+                                             u8ptr(r if r.shape[0] else one_u), None if v is None else fptr(v if v.shape[0] else one_f),
+                                             int(every)), "sfm_batch_set_observed")
+        self.observed_every = int(every)
+
+    def _need_observed(self, name):
+        if self.observed_every is None:                                # (the library's message, from the call itself)
+            self._check(self._lib.sfm_batch_score(self._b), "sfm_batch_score")
+            raise SfmLibraryError(f"SfmBatch.{name}: observed tracks are off")
+
+    def run_observed(self, first, frames, redraw=False):
+        """Frames ``first`` .. ``first + frames - 1`` of the recording (sfm_batch_run_observed): per frame one frame kernel, then
+        ``every`` integrating ticks, all on the batch's stream with no copy and no wait.  ``first=0`` clears the row scores and
+        places every row of role 1 or 2; a later ``first`` continues a run.  Raises SfmLibraryError while observed tracks are off."""
+        self._check(self._lib.sfm_batch_run_observed(self._b, int(first), int(frames), self._flags(True, redraw)), "sfm_batch_run_observed")
+
+    def score(self):
+        """Reduce the row scores to per-scene scores (sfm_batch_score): one launch on the batch's stream; the host does not wait."""
+        self._check(self._lib.sfm_batch_score(self._b), "sfm_batch_score")
+
+    def row_scores(self):
+        """Per scene (n_b, 4) float32 {samples, sum_d, sum_d2, last_d2} as the last frame kernel left them, in scene order
+        (synchronises the batch's stream)."""
+        self._need_observed("row_scores")
+        n = int(self.scene_off[-1])
+        buf = np.zeros((n, 4), np.float32)
+        self._check(self._lib.sfm_batch_download_scores(self._b, fptr(buf) if n else None, None), "sfm_batch_download_scores")
+        return _split_rows(self.scene_off, buf)
+
+    def scene_scores(self):
+        """``score()`` and a download: (B, 5) float32 {rows, samples, sum_d, sum_d2, sum_final_d} (``replay.metrics`` turns them
+        into ADE, RMSE, FDE); synchronises the batch's stream."""
+        self.score()
+        buf = np.zeros((self.B, _replay.SCENE_SCORE_WIDTH), np.float32)
+        self._check(self._lib.sfm_batch_download_scores(self._b, None, fptr(buf)), "sfm_batch_download_scores")
+        return buf
+
+    def _score_tensor(self, which, width, name, device):
+        self._need_observed(name)
+        nbytes = C.c_int64(0)
+        ptr = self._lib.sfm_batch_device_ptr(self._b, which, C.byref(nbytes))
+        if not ptr and (which == PTR_SCENE_SCORES or int(self.scene_off[-1]) > 0):
+            self._check(-1, "sfm_batch_device_ptr")
+        return self._alias(ptr, (int(nbytes.value) // (4 * width), width), device)
+
+    def row_score_tensor(self, device=None):
+        """The row scores as a torch tensor (N_total, 4) float32 that aliases device memory (no copy).  Take it again after
+        ``set_observed``.  Raises SfmLibraryError while observed tracks are off."""
+        return self._score_tensor(PTR_ROW_SCORES, 4, "row_score_tensor", device)
+
+    def scene_score_tensor(self, device=None):
+        """The scene scores as a torch tensor (B, 5) float32 that aliases device memory, as the last ``score()`` left them: an
+        argmin over candidates needs no copy.  Take it again after ``set_observed``."""
+        return self._score_tensor(PTR_SCENE_SCORES, _replay.SCENE_SCORE_WIDTH, "scene_score_tensor", device)
+
     def set_waypoint_streams(self, seeds, world_sides, arrive_thresholds=2.0):
         """Per-scene waypoint streams for ``redraw=True`` (see ``stream_arrays``; scalars broadcast to every scene).  They stay in
         effect across ``upload`` and ``set_params``; every upload zeroes the draw counters."""
@@ -1418,6 +1513,7 @@ class SfmBatch:
                                                    fptr(pm["wp_y"]) if W else None, u8ptr(pm["wp_crossing"]) if W else None,
                                                    iptr(despawn), fptr(t0), fptr(thr), fptr(pm["first_vehicle_extent"])),
                           "sfm_batch_set_mode_fsm")
+        self.observed_every = None                                     # (the modes own parking and birth: the observed tracks are dropped)
 
     def set_spawns(self, schedules):
         """The spawn schedule of every scene (sfm_batch_set_spawn_schedule): ``schedules`` one per scene (see ``pack_spawns``;
@@ -1434,6 +1530,7 @@ class SfmBatch:
         if t.shape[0] == 0:                                            # (no rows: still a call, so that the refusals are the library's)
             t, c = np.zeros(1, np.float32), np.zeros(1, np.uint8)
         self._check_drops(L.sfm_batch_set_spawn_schedule(self._b, fptr(t), u8ptr(c)), "sfm_batch_set_spawn_schedule")
+        self.observed_every = None
 
     def spawns(self):
         """Per scene (born (N_b,) bool, birth_time (N_b,) float32: the scene's clock before the row's birth tick -- the clock

@@ -111,7 +111,7 @@ static int check_batch_geo(SfmBatch* b, const int32_t* scene_item_off, const int
 }
 
 // flags a batch tick takes: SFM_TICK_INTEGRATE, and SFM_TICK_REDRAW_WAYPOINTS once the streams are set and while no modes are
-static int check_batch_flags(SfmBatch* b, uint32_t flags, const char* what) {
+int sfm::check_batch_flags(SfmBatch* b, uint32_t flags, const char* what) {
     if (b->modes.on && (flags & ~(uint32_t)SFM_TICK_INTEGRATE))
         return bfail(b, SFM_ERR_INVALID, std::string("a batch ") + what + " with modes set (sfm_batch_set_mode_fsm) takes SFM_TICK_INTEGRATE "
                                          "only: arrivals pop the waypoint queues, so SFM_TICK_REDRAW_WAYPOINTS does not apply");
@@ -138,8 +138,7 @@ static int batch_force_slots(SfmBatch* b, uint32_t force_mask, uint32_t* slots, 
 
 // one tick of the whole batch; frame / zframe: this tick's frame slot of a recorded run (null: not recorded); force_rec: this
 // tick's [K][N_total][C] force record with force_slots from batch_force_slots (null: not recorded)
-static int batch_launch(SfmBatch* b, uint32_t flags, float4* frame = nullptr, float2* zframe = nullptr, float* force_rec = nullptr,
-                        uint32_t force_slots = 0xFFFFFFFFu) {
+int sfm::batch_launch(SfmBatch* b, uint32_t flags, float4* frame, float2* zframe, float* force_rec, uint32_t force_slots) {
     BatchArgs a;
     memset(&a, 0, sizeof(a));
     a.scene_off = b->d_scene_off;
@@ -346,6 +345,7 @@ int sfm_batch_create(int B, const SfmParams* params, int device_id, SfmBatch** o
     b->B = B;
     std::vector<BatchParams> q((size_t)B);
     for (int k = 0; k < B; ++k) q[k] = batch_params(params[k]);
+    for (int k = 0; k < B; ++k) b->dt_h.push_back(params[k].step_length);
     std::vector<int> zeros((size_t)B + 1, 0);
     bool ok = b->d_prm.alloc((size_t)B) == hipSuccess && b->d_scene_off.alloc((size_t)B + 1) == hipSuccess &&
               hipMemcpy(b->d_prm, q.data(), sizeof(BatchParams) * (size_t)B, hipMemcpyHostToDevice) == hipSuccess &&
@@ -387,8 +387,12 @@ int sfm_batch_set_params(SfmBatch* b, const SfmParams* params) {
         return bfail(b, SFM_ERR_STATE, "use_ped_radius on a batch whose state was uploaded without radii: upload the state again");
     std::vector<BatchParams> q((size_t)b->B);
     for (int k = 0; k < b->B; ++k) q[k] = batch_params(params[k]);
+    std::vector<float> dt((size_t)b->B);
+    for (int k = 0; k < b->B; ++k) dt[k] = params[k].step_length;
     HIP_TRY(b, hipStreamSynchronize(b->stream));
+    if ((rc = batch_replay_step_lengths(b, dt.data()))) return rc;  // (observed tracks: 1 / (every * step_length) follows)
     HIP_TRY(b, hipMemcpy(b->d_prm, q.data(), sizeof(BatchParams) * (size_t)b->B, hipMemcpyHostToDevice));
+    b->dt_h = dt;
     b->any_rad = any_rad;
     return SFM_OK;
 }
@@ -421,6 +425,7 @@ int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x
     b->scan = {};                                                 // ... and its scans (the mask is per row)
     b->noise = {};                                                // ... and its restart noise (the boxes are per row)
     b->grid = {};                                                 // ... and its grids (the slots are per row)
+    b->replay = {};                                               // ... and its observed tracks (the roles are per row)
     b->snap.on = false;                                           // ... and so is its snapshot
     b->have_state = false;
     if (n > 0) {
@@ -440,6 +445,7 @@ int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x
         HIP_TRY(b, hipMemset(b->draws, 0, sizeof(uint32_t) * n));
     }
     HIP_TRY(b, hipMemcpy(b->d_scene_off, scene_off, sizeof(int) * ((size_t)b->B + 1), hipMemcpyHostToDevice));
+    b->scene_off_h.assign(scene_off, scene_off + b->B + 1);
     b->n_total = N;
     b->z3 = z != nullptr;
     b->have_state = true;
@@ -776,6 +782,7 @@ int sfm_batch_set_mode_fsm(SfmBatch* b, const uint8_t* mode, const float* target
     for (int e = 0; e < W; ++e) xy[e] = make_float2(wp_x[e], wp_y[e]);
     HIP_TRY(b, hipStreamSynchronize(b->stream));                 // a tick in flight may still read the old arrays
     drop_batch_modes(b);
+    b->replay = {};                                               // (observed tracks: the modes own parking and birth)
     b->snap.on = false;
     HIP_TRY(b, b->modes.mode.alloc(n)); HIP_TRY(b, b->modes.target.alloc(n)); HIP_TRY(b, b->modes.speeds.alloc(n));
     HIP_TRY(b, b->modes.off.alloc(n + 1)); HIP_TRY(b, b->modes.cursor.alloc(n));
@@ -873,6 +880,7 @@ int sfm_batch_set_spawn_schedule(SfmBatch* b, const float* spawn_time, const uin
         }
     const size_t m = n > 0 ? n : 1;
     b->snap.on = false;
+    b->replay = {};                                               // (observed tracks: the schedule owns parking and birth)
     HIP_TRY(b, b->spawns.time.alloc(m)); HIP_TRY(b, b->spawns.chain.alloc(m)); HIP_TRY(b, b->spawns.born.alloc(m));
     HIP_TRY(b, b->spawns.birth.alloc(m)); HIP_TRY(b, b->spawns.pk0.alloc(m)); HIP_TRY(b, b->spawns.zv0.alloc(m));
     if (n > 0) {
@@ -1027,7 +1035,7 @@ int sfm_batch_set_steering(SfmBatch* b, const uint8_t* kind, const float* ux, co
     }
     HIP_TRY(b, hipStreamSynchronize(b->stream));                 // a tick or a copy in flight may still read the buffers
     b->steer = {};
-    if (!kind) return SFM_OK;
+    if (!kind) { b->replay = {}; return SFM_OK; }                // (observed tracks are replayed through the commands)
     if (n > 0) {
         HIP_TRY(b, b->steer.cmd.alloc(n));
         HIP_TRY(b, b->steer.cmd_h.alloc(n));

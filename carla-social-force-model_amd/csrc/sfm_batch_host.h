@@ -1,7 +1,7 @@
 // sfm_batch_host.h -- what the two host files of the batched scenes share: the batch itself (SfmBatch and the struct of each of its
 // features), its error plumbing, and the messages for a feature that is off.  sfm_batch_capi.hip holds the ticks and everything they
 // read or write; sfm_batch_sense_capi.hip the read-only sensors (observations, episode ends, range scans, occupancy grids) and the device pointers;
-// sfm_batch_reset_capi.hip the restart noise.
+// sfm_batch_reset_capi.hip the restart noise; sfm_batch_replay_capi.hip the observed tracks.
 #pragma once
 #include "sfm_capi_common.h"
 #include "sfm_metres.h"
@@ -160,6 +160,22 @@ struct BatchNoiseDev {
     long long max_delay = 0;       // the largest delay: what a restart's int32 fit check adds
 };
 
+// observed tracks (sfm_batch_set_observed): the recording, each row's role in it, and the scores the frame kernel accumulates; the
+// ticks read and write none of it (they see the state and the commands the frame kernel wrote)
+struct BatchReplayDev {
+    bool on = false;
+    int every = 1;                 // ticks between two observed frames
+    DevBuf<float2> obs;            // the frames of every scene, frame-major
+    DevBuf<long long> obs_off;     // [B]
+    DevBuf<int> frames;            // [B] F_b
+    DevBuf<float> inv_h;           // [B] 1 / (every * step_length)
+    DevBuf<uint8_t> role;          // [N_total]
+    DevBuf<int2> span;             // [N_total] {f0, f1}
+    DevBuf<float2> v0;             // [N_total]; NaN: take it from the track
+    DevBuf<float4> score;          // [N_total] {samples, sum_d, sum_d2, last_d2}
+    DevBuf<float> scene;           // [B][5] what sfm_batch_score left
+};
+
 struct BatchRecordDev {        // grow-only device buffers of the recording calls
     DevBuf<float4> frames;     // sfm_batch_run_recorded
     DevBuf<float2> zframes;
@@ -199,6 +215,9 @@ struct SfmBatch {
     sfm::BatchScanDev scan;
     sfm::BatchNoiseDev noise;
     sfm::BatchGridDev grid;
+    sfm::BatchReplayDev replay;
+    std::vector<int32_t> scene_off_h;       // the scene offsets [B+1] of the last sfm_batch_upload_state, on the host
+    std::vector<float> dt_h;                // [B] the scenes' step lengths (sfm_batch_create, sfm_batch_set_params)
     sfm::Event c_done;                      // created by the first sfm_batch_set_steering with rows; outlives every drop of the steering
     std::string err;
 };
@@ -226,6 +245,8 @@ constexpr const char* OBSERVATIONS_OFF = "observations are off: call sfm_batch_s
 constexpr const char* EPISODES_OFF = "episodes are off: call sfm_batch_set_episodes first (sfm_batch_upload_state drops them)";
 constexpr const char* NOISE_OFF = "restart noise is off: call sfm_batch_set_restart_noise first (sfm_batch_upload_state drops it)";
 constexpr const char* SCANS_OFF = "scans are off: call sfm_batch_set_scan first (sfm_batch_upload_state drops them)";
+constexpr const char* OBSERVED_OFF = "observed tracks are off: call sfm_batch_set_observed first (sfm_batch_upload_state, setting modes or a "
+                                     "spawn schedule and switching steering off drop them)";
 constexpr const char* GRIDS_OFF = "grids are off: call sfm_batch_set_grid first (sfm_batch_upload_state drops them)";
 
 // one kind of the scenes' geometry as the kernels take it, and what the sensors see of the scenes
@@ -242,6 +263,14 @@ int batch_restart_device(SfmBatch* b, const uint8_t* d_mask, long long shift);
 // The noise launch of a restart (sfm_batch_reset_capi.hip), right behind launch_batch_restart on the batch's stream with the same
 // choice of scenes; nothing while the noise is off.  With delays set it marks the host's copy of the tracks' first ticks stale.
 int batch_restart_noise(SfmBatch* b, const int* d_list, const uint8_t* d_mask, int scenes);
+// What sfm_batch_run_observed shares with sfm_batch_run (sfm_batch_capi.hip, where both are described): the check of a tick's
+// flags, and the launch of one tick of the whole batch.
+int check_batch_flags(SfmBatch* b, uint32_t flags, const char* what);
+int batch_launch(SfmBatch* b, uint32_t flags, float4* frame = nullptr, float2* zframe = nullptr, float* force_rec = nullptr,
+                 uint32_t force_slots = 0xFFFFFFFFu);
+// Observed tracks (sfm_batch_replay_capi.hip): inv_h follows the step lengths (sfm_batch_set_params calls it with the stream
+// synchronised and b->dt_h current; it refuses what sfm_batch_set_observed refuses).
+int batch_replay_step_lengths(SfmBatch* b, const float* dt);
 // The delays go with the tracks they refer to (the caller synchronised the stream).
 inline void drop_noise_delays(SfmBatch* b) { b->noise.delay = {}; b->noise.max_delay = 0; }
 

@@ -20,7 +20,7 @@ static int check_frame(SfmBatch* b, int frame) {
 
 // One lookup for the device buffers a caller may see: which = SFM_BATCH_PTR_*, or PTR_OBSERVATIONS for sfm_batch_observation_ptr's.
 // off: why there is none (its feature is off, no state was uploaded), else p and bytes -- both 0 where the buffer has no element.
-constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_GRID + 1;     // (not part of the ABI: sfm_batch_device_ptr refuses it)
+constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_SCENE_SCORES + 1;     // (not part of the ABI: sfm_batch_device_ptr refuses it)
 struct BatchBuffer { const char* off; void* p; size_t bytes; };
 static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     const size_t n = (size_t)b->n_total, B = (size_t)b->B;
@@ -42,6 +42,10 @@ static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     case SFM_BATCH_PTR_GRID:
         if (!b->grid.on) return {GRIDS_OFF, nullptr, 0};
         return have(b->grid.buf, sizeof(float) * b->grid.M * (size_t)(SFM_BATCH_GRID_CHANNELS * b->grid.G * b->grid.G));
+    case SFM_BATCH_PTR_ROW_SCORES:
+    case SFM_BATCH_PTR_SCENE_SCORES:
+        if (!b->replay.on) return {OBSERVED_OFF, nullptr, 0};
+        return which == SFM_BATCH_PTR_ROW_SCORES ? have(b->replay.score, sizeof(float4) * n) : have(b->replay.scene, 5 * sizeof(float) * B);
     }
     if (!b->have_state) return {NO_STATE, nullptr, 0};
     if (which == SFM_BATCH_PTR_COMMANDS) {
@@ -79,9 +83,10 @@ void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes) {
     if (!b) return nullptr;
     // SFM_BATCH_PTR_RESETS came without an ABI bump: while restart noise is off it is refused as the unknown value it was, word for
     // word, so a caller of ABI 17 as it was sees no difference
-    // (SFM_BATCH_PTR_GRID likewise, while grids are off)
+    // (SFM_BATCH_PTR_GRID likewise, while grids are off, and SFM_BATCH_PTR_ROW_SCORES / _SCENE_SCORES while observed tracks are off)
     const bool known = (which >= SFM_BATCH_PTR_COMMANDS && which <= SFM_BATCH_PTR_SCAN) || (which == SFM_BATCH_PTR_RESETS && b->noise.on) ||
-                       (which == SFM_BATCH_PTR_GRID && b->grid.on);
+                       (which == SFM_BATCH_PTR_GRID && b->grid.on) ||
+                       ((which == SFM_BATCH_PTR_ROW_SCORES || which == SFM_BATCH_PTR_SCENE_SCORES) && b->replay.on);
     if (!known) { bfail(b, SFM_ERR_INVALID, "which must be SFM_BATCH_PTR_COMMANDS, _STATE, _ZSTATE, _EPISODES, _DONE or _SCAN"); return nullptr; }
     return buffer_ptr(b, which, which == SFM_BATCH_PTR_SCAN ? ", so which = SFM_BATCH_PTR_SCAN has no buffer" :
                                 which == SFM_BATCH_PTR_EPISODES || which == SFM_BATCH_PTR_DONE ? ", so which = SFM_BATCH_PTR_EPISODES / _DONE has no buffer" : "", bytes);

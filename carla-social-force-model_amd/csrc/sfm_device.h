@@ -455,6 +455,30 @@ struct RestartNoiseArgs {
     float2* veh_pts;          // [P]
 };
 
+// Observed tracks of a batch (sfm_batch_set_observed, sfm_batch_replay_kernel and sfm_batch_score_kernel in sfm_batch_replay.hip;
+// the rules are specified in include/sfm_hip.h).  The frame kernel writes pk, cmd and score of the rows of role 1 and 2 only.
+constexpr uint8_t ROLE_NONE = 0, ROLE_REPLAYED = 1, ROLE_SCORED = 2;
+constexpr int SCENE_SCORE_WIDTH = 5;  // {rows, samples, sum_d, sum_d2, sum_final_d}
+struct ReplayArgs {
+    const int* scene_off;     // [B+1]
+    float4* pk;               // {x, y, vx, vy}
+    float4* cmd;              // {ux, uy, uz, kind}: the steering command buffer
+    float4* score;            // [N_total] {samples, sum_d, sum_d2, last_d2}
+    const float2* obs;        // the track frames of every scene, frame-major: obs[obs_off[b] + f * n_b + i]; NaN: not seen
+    const long long* obs_off; // [B]
+    const int* frames;        // [B] F_b
+    const float* inv_h;       // [B] 1 / (every * step_length), formed in double and rounded once
+    const uint8_t* role;      // [N_total] ROLE_*
+    const int2* span;         // [N_total] {f0, f1}: first and last observed frame; f0 > f1: never seen
+    const float2* v0;         // [N_total] initial velocity; NaN: take it from the track
+    int f;                    // the frame this launch places
+};
+struct ScoreArgs {
+    const int* scene_off;     // [B+1]
+    const float4* score;      // [N_total]
+    float* out;               // [B][SCENE_SCORE_WIDTH]
+};
+
 static_assert(sizeof(BatchSceneView) == 120 && sizeof(ObserveArgs) == 120 + 24 && sizeof(EpisodeArgs) == 120 + 40 && sizeof(ScanArgs) == 120 + 40,
               "the kernels' argument layout: the view is the head of each sensor's arguments, which follow it without padding");
 

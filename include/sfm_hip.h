@@ -848,6 +848,97 @@ int sfm_batch_grid(SfmBatch* b);
 /* Synchronises the batch's stream, then copies the buffer ([M][6][G][G] floats) as the last sfm_batch_grid left it; before the
  * first that is zeros.  SFM_ERR_STATE while grids are off. */
 int sfm_batch_download_grid(SfmBatch* b, float* out);
+/* Observed tracks on the device: the calibration protocol of Johansson et al. 2007.  A few pedestrians are simulated by the model,
+ * everybody else in the scene replays the recorded motion, and the simulated ones are scored by their displacement from their own
+ * recorded tracks -- the reference's update_ped_info -> PedState.update_state (run_simulation.py:79-87, pedestrian_state.py:79-81)
+ * with the recording and the error sums living on the device.  A sweep is sfm_batch_set_params, sfm_batch_run_observed(0, F),
+ * sfm_batch_score, and one copy of B x 5 floats per candidate.
+ * These four entry points and SFM_BATCH_PTR_ROW_SCORES / _SCENE_SCORES were added WITHOUT a bump of SFM_ABI_VERSION (it stays 17),
+ * like the restart noise and the grids: additions only, and a build that has them is recognised by the symbols.
+ *
+ * Data (sfm_batch_set_observed), set once.  Per scene b its track frames: frames[b] = F_b, 0 <= F_b <=
+ * SFM_BATCH_MAX_OBSERVED_FRAMES, of n_b positions each, float2 {x, y}, frame-major: the position of row i (inside the scene) in
+ * frame f is obs_xy[2 (obs_off[b] + f n_b + i)] and the float behind it; obs_off [B+1] counts positions, obs_off[0] = 0,
+ * obs_off[b+1] = obs_off[b] + F_b n_b.  A row not seen in a frame holds NaN in BOTH components; every other value is finite with
+ * |x|, |y| <= SFM_BATCH_MAX_SENSE_RANGE (1e6 m).  All frames together hold at most SFM_BATCH_MAX_RECORD_BYTES.  Per row
+ * role [N_total]: SFM_ROLE_NONE 0, not part of the data -- every kernel below leaves the row alone, bit for bit; SFM_ROLE_REPLAYED 1;
+ * SFM_ROLE_SCORED 2, simulated by the model and compared with its track.  Per row an optional initial velocity v0_xy [N_total][2]
+ * (NULL: none given): NaN in both components means "take it from the track"; otherwise finite.  every >= 1: the ticks between two
+ * observed frames, one value for the batch.  Derived on the host: per scene inv_h[b] = float32(1 / (every * step_length_b)),
+ * formed in double and rounded once (while observed tracks are on, sfm_batch_set_params forms it again from the new step lengths,
+ * and refuses, with nothing changed, step lengths this call would refuse); per row the span
+ * [f0, f1] of its first and last observed frame, empty for a row that is never seen.
+ *
+ * The frame kernel (sfm_batch_replay_kernel, ONE launch per frame, a workgroup per scene) takes the frame f as an argument and
+ * writes only the state {x, y, vx, vy}, the command {ux, uy, uz, kind} and the score record of rows of role 1 and 2.  Every value
+ * is one correctly rounded fp32 operation or an fmaf, every decision a plain comparison.  "Observed at g": 0 <= g < F_b and the
+ * row's position in frame g is not NaN.  "Parked": position = where a despawned row waits (keyed by the index inside the scene,
+ * beyond NEAR_LIMIT: sfm_batch_observe's live test fails for it and it exerts no force on anyone), velocity 0, command
+ * {0, 0, 0, 1}, so the ticks hold it there.  With o = the row's position in frame f:
+ *   Role 1, observed at f: position := o bit for bit; velocity v := (o' - o) * inv_h per component (one subtraction, one
+ *     multiplication) with o' the position in frame f + 1 if the row is observed there; else (o - o") * inv_h with o" that of
+ *     frame f - 1 if observed there; else v0 if given; else 0.  State velocity := v, command := {v.x, v.y, 0, 1}: the following
+ *     `every` ticks move it by their own fma(step_length, v, x), and the next frame puts it back on the track -- nothing drifts.
+ *   Role 1, not observed at f (f >= F_b, outside its span, or a gap): parked.
+ *   Role 2 with f < f0, f > f1 or an empty span: parked.
+ *   Role 2, f == f0: position := o; velocity := v0 if given, else the forward difference above if the row is observed at f + 1,
+ *     else 0; command {0, 0, 0, 0}: the model moves it from here on.
+ *   Role 2, f0 < f <= f1: state untouched, command {0, 0, 0, 0}.  If observed at f, with {x, y} of the state as the ticks left
+ *     it: dx = x - o.x, dy = y - o.y, d2 = fmaf(dx, dx, dy * dy), d = sqrtf(d2) (correctly rounded), and the row's record
+ *     {samples, sum_d, sum_d2, last_d2} becomes {samples + 1, sum_d + d, sum_d2 + d2, d2}.  The lane that owns the row is its only
+ *     writer, so the sums are taken in frame order.  A gap inside the span is not scored.  A state that is not finite goes into
+ *     the sums as it is (NaN or inf): nothing is filtered.
+ * The record is four floats per row, [N_total][4]; samples is a count held as a float (exact: at most 16 384).
+ *
+ * Steering.  Observed rows are driven through the command buffer: if steering is off, sfm_batch_set_observed switches it on with
+ * every kind 0, and the ticks' steered form is what runs from then on.  Rows of role 0 keep whatever steering the caller gave them,
+ * so an ego policy can live in a replayed scene.  sfm_batch_set_steering and sfm_batch_set_commands overwrite the kinds and
+ * commands the frame kernel wrote, as they overwrite what a caller changed on the device; the next frame writes them again.
+ *
+ * What drops the observed tracks: sfm_batch_upload_state (the roles are per row); the "on" forms of sfm_batch_set_mode_fsm and
+ * sfm_batch_set_spawn_schedule (they own parking and birth); sfm_batch_set_steering(kind = NULL).  Every other call keeps them.
+ * A snapshot neither holds nor restores the scores; sfm_batch_restart puts back rows of every role, and the next frame kernel places
+ * roles 1 and 2 again.
+ *
+ * sfm_batch_set_observed uploads all this, zero-fills the scores and waits for the batch's stream; obs_off = NULL switches the
+ * observed tracks off and frees them (steering stays as it is).  Refused with nothing sent, freed or launched, the batch staying
+ * usable: no state uploaded (SFM_ERR_STATE); a 3-D batch; modes or a spawn schedule set (SFM_ERR_STATE); NULL frames or role (with
+ * rows); NULL obs_xy with positions; every < 1; an F_b outside 0 .. 16384; obs_off that does not fit the frames; more than
+ * SFM_BATCH_MAX_RECORD_BYTES of frames; a role above 2; a position that is half NaN, infinite or beyond 1e6 m; a v0 that is half
+ * NaN or not finite; a scene whose every * step_length is not finite and positive in fp32. */
+#define SFM_BATCH_MAX_OBSERVED_FRAMES 16384
+#define SFM_ROLE_NONE 0
+#define SFM_ROLE_REPLAYED 1
+#define SFM_ROLE_SCORED 2
+#define SFM_BATCH_PTR_ROW_SCORES 8
+#define SFM_BATCH_PTR_SCENE_SCORES 9
+#define SFM_BATCH_SCENE_SCORE_WIDTH 5
+int sfm_batch_set_observed(SfmBatch* b, const int64_t* obs_off, const int32_t* frames, const float* obs_xy, const uint8_t* role,
+                           const float* v0_xy, int every);
+/* Frames first_frame .. first_frame + frames - 1: per frame ONE launch of the frame kernel, then `every` ticks exactly as
+ * sfm_batch_run(b, every, flags) launches them -- all on the batch's stream, no copy and no wait in between.  flags must contain
+ * SFM_TICK_INTEGRATE (SFM_TICK_REDRAW_WAYPOINTS as for sfm_batch_run).  first_frame = 0 first clears the row scores with one
+ * hipMemsetAsync; a later first_frame continues a run.  Frames beyond a scene's F_b park its rows of role 1 and 2, so scenes of
+ * different lengths share a batch.  Starting at frame 0 places every row of role 1 or 2: a scene made only of such rows needs no
+ * snapshot between candidates (rows of role 0, waypoint draws and vehicles still need sfm_batch_restart).  Refused with nothing
+ * launched: observed tracks off (SFM_ERR_STATE), flags without SFM_TICK_INTEGRATE or with a flag sfm_batch_run refuses,
+ * first_frame < 0, frames < 0, first_frame + frames beyond 2^31 - 1. */
+int sfm_batch_run_observed(SfmBatch* b, int first_frame, int frames, uint32_t flags);
+/* Per scene five floats, [B][SFM_BATCH_SCENE_SCORE_WIDTH], from the row scores by ONE launch of sfm_batch_score_kernel (a
+ * workgroup per scene) on the batch's stream: rows (those with samples > 0), samples, sum_d, sum_d2 and sum_final_d (the sum of
+ * sqrtf(last_d2)), each over the rows with samples > 0.  ADE = sum_d / samples, RMSE = sqrt(sum_d2 / samples), FDE = sum_final_d /
+ * rows.  The counts are exact in fp32 (1 024 rows x 16 384 frames = 2^24).  The order of summation is part of the definition: lane
+ * t of 256 adds its rows t, t + 256, ... in ascending order starting from +0; then an xor-shuffle tree of widths 32, 16, .. 1
+ * inside each wave of 64 (both partners form the same sum, addition commutes); then thread 0 adds waves 0 .. 3 in ascending
+ * order.  No float atomics: a scene's scores are bitwise the same alone or anywhere in any batch.  SFM_ERR_STATE while observed
+ * tracks are off. */
+int sfm_batch_score(SfmBatch* b);
+/* Synchronises the batch's stream, then copies the row scores ([N_total][4] floats, as the last frame kernel left them) and the
+ * scene scores ([B][5] floats, as the last sfm_batch_score left them; zeros before the first); NULL skips either.  SFM_ERR_STATE
+ * while observed tracks are off.  SFM_BATCH_PTR_ROW_SCORES and SFM_BATCH_PTR_SCENE_SCORES (sfm_batch_device_ptr) are the two
+ * buffers on the device, valid until the next sfm_batch_set_observed or a call that drops the tracks; while observed tracks are off
+ * the values are refused as the unknown `which` they were before. */
+int sfm_batch_download_scores(SfmBatch* b, float* row_scores, float* scene_scores);
 /* Current state of every scene (synchronises the batch's stream); NULL skips a column.  A planar batch leaves z alone and
  * writes vz = 0. */
 int sfm_batch_download_state(SfmBatch* b, float* x, float* y, float* z, float* vx, float* vy, float* vz);
