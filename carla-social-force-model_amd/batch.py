@@ -130,6 +130,22 @@ floats per candidate.  Steering is switched on if it is off (rows of role 0 keep
 ``set_spawns`` and ``set_steering(None)`` drop the tracks.  ``replay.replay_frame`` and ``replay.score_scene`` are the host twins, bit for
 bit, and ``replay.scene_from_tracks`` packs a recording into a scene (the exact rules: include/sfm_hip.h):
 examples/batch_calibration_sweep.py.
+
+Driven vehicles (ABI 17, added without a bump): device-side vehicles whose motion is decided while the batch runs -- a driving
+policy trained against the crowd, a planner under test, a braking controller.  ``set_vehicle_driving(kinds, commands)`` gives
+every vehicle a command ``(a, b, c)`` that each integrating tick reads inside its one launch: kind 1 takes ``(a, b)`` as the new
+velocity and turns the heading to it (a stopped vehicle keeps its heading); kind 2 is a unicycle -- signed speed ``a`` along the
+heading, which this tick first turns by ``(b, c) = (cos, sin)`` of the turn (the kernel does no trigonometry; ``a < 0``
+reverses); kind 0 runs free or follows its track as ever.  The stored velocity becomes the commanded one, so the dynamic obstacle
+force and gap acceptance see it from the next tick on.  ``set_vehicle_commands`` sends new commands with one copy on the stream,
+``vehicle_command_tensor()`` aliases the buffer for torch, ``vehicle_driving()`` downloads kinds, commands, headings and
+velocities.  The heading is state: ``snapshot`` holds it, every restart puts it back.  ``set_vehicle_observation(k, sense_range,
+frame, goals, mask)`` and ``observe_vehicles()`` are the sensor centred on a vehicle, one launch: goal, velocity, heading, the
+``k`` nearest live pedestrians in ``(d2, j)`` order, ``clear_d2`` (ring to crowd, for collisions and near misses), ``other_d2``
+(the scene's other vehicles), the nearest border and static points, the signed speed; ``vehicle_observations()`` downloads it,
+``vehicle_observation_tensor()`` aliases it.  ``upload`` and ``set_dynamic_boxes`` drop both, every other call keeps them.
+``scenarios.drive_vehicles`` and ``observe.observe_vehicles_scene`` are the host twins, bit for bit (the exact rules:
+include/sfm_hip.h): examples/batch_av_loop.py.
 """
 from __future__ import annotations
 
@@ -640,6 +656,80 @@ def pack_steering(kinds, commands, scene_off):
     return kd, f32(u[:, 0]), f32(u[:, 1]), f32(u[:, 2])
 
 
+DRIVE_OFF, DRIVE_VELOCITY, DRIVE_UNICYCLE = 0, 1, 2    # the kinds of a driven vehicle (held as floats in the vehicle command buffer)
+PTR_VEHICLE_COMMANDS, PTR_VEHICLE_OBS = 10, 11         # ... the vehicle commands [M][4] (while driving is on) and the vehicle
+                                                       # observations [M][16 + 4k] (while vehicle observations are on)
+
+
+def _per_vehicle(v, item_off, width, name):
+    """``_per_scene`` over the vehicles: a list / tuple with one entry per scene, or one ndarray over the M vehicles of all scenes, or
+    one value (``width`` 0) / one (``width``,) vector for every vehicle -> a float64 array (M,) or (M, width)."""
+    io = np.asarray(item_off)
+    B, M = len(io) - 1, int(io[-1])
+
+    def rows(e, nb, where):
+        a = np.asarray(e, dtype=np.float64)
+        if a.ndim == (1 if width else 0) and (not width or a.shape[0] == width):
+            a = np.broadcast_to(a, (nb, width) if width else (nb,))
+        if a.size == 0 and nb == 0:
+            a = np.zeros((0, width) if width else (0,))
+        if a.shape != ((nb, width) if width else (nb,)):
+            raise ValueError(f"{where}{name} of shape {a.shape} for {nb} vehicles")
+        return a
+
+    if isinstance(v, (list, tuple)):
+        if len(v) != B:
+            raise ValueError(f"{len(v)} entries of {name} for {B} scenes (a list is per scene; pass an ndarray for all vehicles)")
+        parts = [rows(np.zeros(width if width else ()) if e is None else e, int(io[b + 1] - io[b]), f"scene {b}: ") for b, e in enumerate(v)]
+        return np.concatenate(parts, axis=0) if parts else np.zeros((0, width) if width else (0,))
+    return rows(v, M, "")
+
+
+def pack_vehicle_driving(kinds, commands, item_off):
+    """Driving -> the arguments of sfm_batch_set_vehicle_driving: (kind uint8 [M], a, b, c float32 [M]).  ``item_off`` (B+1,): the
+    vehicles' scene offsets (``pack_boxes(...)[0]``).  ``kinds``: a list with one entry per scene (each (M_b,), or one value for the
+    scene's vehicles), or an ndarray (M,) over the vehicles of all scenes, or one value for every vehicle; 0 not driven, 1 velocity
+    (a, b) = v', 2 unicycle (a, b, c) = (signed speed, cos, sin of the tick's turn).  ``commands``: likewise with (M_b, 3) / (3,)
+    entries, or None (zeros).  ``kinds=None``: (None, a, b, c), the commands alone.  Pure NumPy; raises ValueError on a shape that
+    does not fit, a kind that is not 0, 1 or 2, and a command that is not finite in float32 on a driven vehicle (with
+    ``kinds=None``: on any vehicle)."""
+    io = np.asarray(item_off)
+    M = int(io[-1])
+    kd = None
+    if kinds is not None:
+        k = _per_vehicle(kinds, io, 0, "kinds")
+        if M and not np.isin(k, (0.0, 1.0, 2.0)).all():
+            raise ValueError("kinds must hold 0 (not driven), 1 (velocity) or 2 (unicycle)")
+        kd = np.ascontiguousarray(k, dtype=np.uint8)
+    c = np.zeros((M, 3)) if commands is None else _per_vehicle(commands, io, 3, "commands")
+    with np.errstate(over="ignore", invalid="ignore"):
+        u = np.ascontiguousarray(c, dtype=np.float32)
+    bad = ~np.isfinite(u).all(axis=1) & (np.ones(M, bool) if kd is None else kd != 0)
+    if bad.any():
+        raise ValueError(f"vehicle {int(np.flatnonzero(bad)[0])}: the command of a driven vehicle must be finite in float32")
+    return kd, f32(u[:, 0]), f32(u[:, 1]), f32(u[:, 2])
+
+
+def vehicle_observation_arrays(item_off, k, sense_range, frame=0, goals=None, mask=None):
+    """Vehicle observation settings -> the arguments of sfm_batch_set_vehicle_observation: (k int, sense_range float32 [B], frame
+    int, goal_x, goal_y float32 [M] or None, mask uint8 [M] or None).  ``sense_range`` as for ``observation_arrays``; ``goals``: None
+    (zeros) or, as for ``pack_vehicle_driving``, (M_b, 2) per scene / (M, 2) / one (2,) goal, finite in float32; ``mask``: None (every
+    vehicle) or bools likewise.  Pure NumPy; raises ValueError on what the library would refuse."""
+    io = np.asarray(item_off)
+    obs_width(k)
+    frame = check_frame(frame)
+    r = per_scene_metres(sense_range, "sense_range", len(io) - 1, True)
+    gx = gy = None
+    if goals is not None:
+        with np.errstate(over="ignore", invalid="ignore"):
+            g = np.ascontiguousarray(_per_vehicle(goals, io, 2, "goals"), dtype=np.float32)
+        if not np.isfinite(g).all():
+            raise ValueError("goals must be finite in float32")
+        gx, gy = f32(g[:, 0]), f32(g[:, 1])
+    mk = None if mask is None else np.ascontiguousarray(_per_vehicle(mask, io, 0, "mask") != 0, dtype=np.uint8)
+    return int(k), r, frame, gx, gy, mk
+
+
 PTR_RESETS = 6                   # SFM_BATCH_PTR_RESETS: the restart counters [B] uint32 (while restart noise is on)
 MAX_RESTART_TRIES = 32           # SFM_BATCH_MAX_RESTART_TRIES
 
@@ -835,6 +925,9 @@ class SfmBatch:
         self._grid_rows = self._grid_counts = None
         self.has_restart_noise = False    # set_restart_noise has been called and no later call has dropped it
         self.observed_every = None        # ticks per observed frame of set_observed (None: observed tracks are off)
+        self._boxes = False               # the vehicles last set move on the device (set_dynamic_boxes with at least one vehicle)
+        self.driving = False              # set_vehicle_driving has been called and no later call has dropped it
+        self.vobs_k = None                # pedestrian slots of set_vehicle_observation (None: vehicle observations are off)
 
     def _check(self, rc, what):
         if rc != 0:
@@ -903,7 +996,8 @@ class SfmBatch:
         self._check_drops(L.sfm_batch_set_dynamic_obstacles(self._b, *(iptr(a) for a in dy[:2]), *(fptr(a) for a in dy[2:])),
                           "sfm_batch_set_dynamic_obstacles")
         self._dyn = (dy[0].copy(), dy[1].copy())
-        z, vz = (None, None) if planar else (pk["z"], pk["vz"])
+        self._boxes, self.driving, self.vobs_k = False, False, None    # (the vehicles were replaced: driving and their observations go)
+        z, vz =(None, None) if planar else (pk["z"], pk["vz"])
         self._check_drops(L.sfm_batch_upload_state(self._b, iptr(so), fptr(pk["x"]), fptr(pk["y"]), fptr(z), fptr(pk["vx"]),
                                                    fptr(pk["vy"]), fptr(vz), fptr(pk["wx"]), fptr(pk["wy"]),
                                                    fptr(pk["target_speed"]), fptr(pk["radius"]), u8ptr(pk["crossing"])),
@@ -928,6 +1022,7 @@ class SfmBatch:
         self._check_drops(self._lib.sfm_batch_set_dynamic_boxes(self._b, *(iptr(a) for a in boxes[:2]),
                                                                 *(fptr(a) for a in boxes[2:])), "sfm_batch_set_dynamic_boxes")
         self._dyn = (boxes[0].copy(), boxes[1].copy())
+        self._boxes, self.driving, self.vobs_k = int(boxes[0][-1]) > 0, False, None    # (new vehicles: driving and their observations go)
 
     def dynamic_obstacles(self):
         """Per scene, its vehicles as the next tick sees them: a list of (center (2,), ring (P,2)) float64 like
@@ -1225,6 +1320,108 @@ class SfmBatch:
             self._check(-1, "sfm_batch_observation_ptr")
         w = obs_width(self.obs_k)
         return self._alias(ptr, (int(nbytes.value) // (4 * w), w), device)
+
+    def _vehicle_off(self, name):
+        """The device-side vehicles' scene offsets (B+1,), or SfmLibraryError: ``name`` needs them."""
+        if self._dyn is None or not self._boxes:
+            raise SfmLibraryError(f"SfmBatch.{name}: this needs device-side vehicles (upload(..., device_vehicles=True) or "
+                                  "set_dynamic_boxes)")
+        return self._dyn[0]
+
+    def set_vehicle_driving(self, kinds, commands=None):
+        """Which device-side vehicles the caller drives, and their first commands (sfm_batch_set_vehicle_driving; see
+        ``pack_vehicle_driving`` and the module docstring): a kind 1 vehicle takes (a, b) as its velocity, a kind 2 vehicle moves at
+        the signed speed a along its heading turned by (b, c) = (cos, sin) of this tick's turn.  ``kinds=None`` switches driving
+        off.  Needs device-side vehicles; ``upload`` and ``set_dynamic_boxes`` drop it, every other call keeps it, and it keeps the
+        snapshot.  Reallocates the command buffer (``vehicle_command_tensor()`` must be taken again)."""
+        L = self._lib
+        if kinds is None:
+            self._check(L.sfm_batch_set_vehicle_driving(self._b, None, None, None, None), "sfm_batch_set_vehicle_driving")
+            self.driving = False
+            return
+        kd, a, b, c = pack_vehicle_driving(kinds, commands, self._vehicle_off("set_vehicle_driving"))
+        self._check(L.sfm_batch_set_vehicle_driving(self._b, u8ptr(kd), fptr(a), fptr(b), fptr(c)), "sfm_batch_set_vehicle_driving")
+        self.driving = True
+
+    def set_vehicle_commands(self, commands):
+        """New commands for every vehicle, kinds as ``set_vehicle_driving`` set them (sfm_batch_set_vehicle_commands): one
+        host-to-device copy on the batch's stream, no wait.  ``commands`` as for ``pack_vehicle_driving``; a vehicle that is not
+        driven may hold anything -- the library validates against the kinds it knows."""
+        io = self._vehicle_off("set_vehicle_commands")
+        c = np.zeros((int(io[-1]), 3)) if commands is None else _per_vehicle(commands, io, 3, "commands")
+        with np.errstate(over="ignore", invalid="ignore"):
+            u = np.ascontiguousarray(c, dtype=np.float32)
+        a, b, c = f32(u[:, 0]), f32(u[:, 1]), f32(u[:, 2])                    # (kept alive across the call)
+        self._check(self._lib.sfm_batch_set_vehicle_commands(self._b, fptr(a), fptr(b), fptr(c)), "sfm_batch_set_vehicle_commands")
+
+    def vehicle_driving(self):
+        """Per scene (kind (M_b,) uint8, command (M_b,3), heading (M_b,2), velocity (M_b,2) float32): kinds and commands as the next
+        tick reads them, headings and velocities as the last tick left them (synchronises the batch's stream).  Raises
+        SfmLibraryError while driving is off."""
+        io = self._dyn[0] if self._dyn is not None else np.zeros(self.B + 1, np.int32)
+        M = max(int(io[-1]), 1)
+        kd = np.zeros(M, np.uint8)
+        cols = [np.zeros(M, np.float32) for _ in range(7)]
+        self._check(self._lib.sfm_batch_download_vehicle_driving(self._b, u8ptr(kd), *(fptr(a) for a in cols)),
+                    "sfm_batch_download_vehicle_driving")
+        return _split_rows(io, kd, np.stack(cols[0:3], axis=1), np.stack(cols[3:5], axis=1), np.stack(cols[5:7], axis=1))
+
+    def _vehicle_tensor(self, which, width, device):
+        nbytes = C.c_int64(0)
+        ptr = self._lib.sfm_batch_device_ptr(self._b, int(which), C.byref(nbytes))
+        if not ptr:
+            self._check(-1, "sfm_batch_device_ptr")
+        return self._alias(ptr, (int(nbytes.value) // (4 * width), width), device)
+
+    def vehicle_command_tensor(self, device=None):
+        """The vehicle command buffer as a torch tensor (M, 4) float32 {a, b, c, kind} that aliases device memory (no copy): what a
+        driving policy writes.  Put torch and the batch on one stream so that writes and ticks are ordered.  What is written here is
+        not validated: a kind other than 1 or 2 counts as 0.  ``set_vehicle_commands`` sends the kinds of ``set_vehicle_driving``
+        and so overwrites kinds changed here.  Take it again after ``set_vehicle_driving``."""
+        if not self.driving:
+            raise SfmLibraryError("SfmBatch.vehicle_command_tensor: vehicle driving is off (set_vehicle_driving)")
+        return self._vehicle_tensor(PTR_VEHICLE_COMMANDS, 4, device)
+
+    def set_vehicle_observation(self, k, sense_range=None, frame=0, goals=None, mask=None):
+        """What ``observe_vehicles`` computes (sfm_batch_set_vehicle_observation; see ``vehicle_observation_arrays`` and the module
+        docstring): ``k`` pedestrian slots per vehicle, a sense range in metres, world axes (``frame=0``) or the vehicle's heading
+        frame (``frame=1``), a goal per vehicle and a mask of the vehicles that are observed.  ``k=None`` switches the
+        observations off.  Needs ``upload`` and device-side vehicles; ``upload`` and ``set_dynamic_boxes`` drop them, every other
+        call keeps them.  Allocates and zero-fills the buffer (``vehicle_observation_tensor()`` must be taken again)."""
+        L = self._lib
+        if k is None:
+            self._check(L.sfm_batch_set_vehicle_observation(self._b, 0, None, 0, None, None, None), "sfm_batch_set_vehicle_observation")
+            self.vobs_k = None
+            return
+        self._need_upload("set_vehicle_observation")
+        if sense_range is None:
+            raise ValueError("set_vehicle_observation needs a sense_range (metres)")
+        k, r, frame, gx, gy, mk = vehicle_observation_arrays(self._vehicle_off("set_vehicle_observation"), k, sense_range, frame, goals, mask)
+        self._check(L.sfm_batch_set_vehicle_observation(self._b, k, fptr(r), frame, fptr(gx), fptr(gy), u8ptr(mk)),
+                    "sfm_batch_set_vehicle_observation")
+        self.vobs_k = k
+
+    def observe_vehicles(self):
+        """Compute every observed vehicle's record as the batch is now (sfm_batch_observe_vehicles): one launch on the batch's
+        stream; the host does not wait.  Raises SfmLibraryError while vehicle observations are off."""
+        self._check(self._lib.sfm_batch_observe_vehicles(self._b), "sfm_batch_observe_vehicles")
+
+    def vehicle_observations(self):
+        """``observe_vehicles()`` and a download: a list of B float32 arrays (M_b, 16 + 4k) in scene order (synchronises the
+        batch's stream)."""
+        self.observe_vehicles()
+        io = self._dyn[0]
+        buf = np.zeros((int(io[-1]), obs_width(self.vobs_k)), np.float32)
+        self._check(self._lib.sfm_batch_download_vehicle_observations(self._b, fptr(buf)), "sfm_batch_download_vehicle_observations")
+        return _split_rows(io, buf)
+
+    def vehicle_observation_tensor(self, device=None):
+        """The vehicle observation buffer as a torch tensor (M, 16 + 4k) float32 that aliases device memory (no copy): what a
+        driving policy and its reward read after ``observe_vehicles()``.  Put torch and the batch on one stream.  Take it again
+        after ``set_vehicle_observation``.  Raises SfmLibraryError while vehicle observations are off."""
+        if self.vobs_k is None:
+            raise SfmLibraryError("SfmBatch.vehicle_observation_tensor: vehicle observations are off (set_vehicle_observation)")
+        return self._vehicle_tensor(PTR_VEHICLE_OBS, obs_width(self.vobs_k), device)
 
     def set_scan(self, max_range, ped_radius=None, point_radius=_scan.POINT_RADIUS, R=None, angles=None, mask=None, frame=0,
                  directions=None):

@@ -24,8 +24,11 @@
 // this tick's dynamic-force scan reads -- into the other half of a ping-pong (a.veh_*_out), which the host swaps in after the
 // launch.  With vehicle tracks set (sfm_batch_set_vehicle_tracks, a.trk.off) a vehicle that has keyframes is not moved but
 // teleported: the same waves write the keyframe the NEXT tick sees (or the absent state) from the read-only track arrays.
-// No launch reads what it writes, so no barrier is added: the one barrier below is followed by `if (slice != 0) return;`,
-// and a later barrier would wait on waves that have left.
+// With driving on (sfm_batch_set_vehicle_driving, a.veh_cmd) a vehicle whose command has kind 1 or 2 is moved by drive_vehicle instead,
+// keyframes or not: centre, velocity and ring go to the other half like everyone's, and the heading -- state from then on -- is
+// rewritten IN PLACE (a.veh_head) by lane 0 of the one wave that reads it in this launch.
+// No launch reads what another wave of it writes, so no barrier is added: the one barrier below is followed by
+// `if (slice != 0) return;`, and a later barrier would wait on waves that have left.
 // Pedestrian modes (sfm_batch_set_mode_fsm, the MODES instantiation): the lane that owns a row runs the handle's sfm_mode_kernel for it
 // after the barrier (target of this tick, idle wake-up on the scene's clock, gap acceptance against the scene's geo[2] items), the
 // border mask follows the mode, and after the step an arrival pops the row's queue or despawns it (parked far away, keyed by its index
@@ -368,7 +371,18 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_tick_kernel(const BatchArgs a
         // (geo[2] is only read here: the moved centres and rings go to veh_*_out, which nothing in this launch reads)
         const DynAdvance d{const_cast<float4*>(a.geo[2].ctr), a.geo[2].off, a.veh_local, a.veh_rot, const_cast<float2*>(a.geo[2].pts),
                            0, a.prm[b].dt, 0, a.veh_ctr_out, a.veh_pts_out};
-        if (a.trk.off) {                                                // uniform: tracks are set -- a vehicle with keyframes is teleported
+        if (a.veh_cmd) {                                                // uniform: driving is on -- a vehicle whose command has kind 1 or 2
+            const int lane = threadIdx.x & (WAVE - 1);                    // is moved by it (keyframes or not), the others as below
+            for (int k = k0 + wave; k < k1; k += WAVES_PER_BLOCK) {
+                const float4 u = a.veh_cmd[k];
+                if (u.w == 1.0f || u.w == 2.0f)
+                    drive_vehicle(u, d.dt, a.geo[2].ctr, a.geo[2].off, a.veh_local, a.veh_head, a.veh_ctr_out, a.veh_pts_out, k, lane);
+                else if (a.trk.off && a.trk.off[k + 1] > a.trk.off[k])
+                    track_vehicle(a.trk, k, lane, a.geo[2].off, a.veh_local, a.veh_ctr_out, a.veh_pts_out);
+                else
+                    advance_vehicle(d, k, lane, true);
+            }
+        } else if (a.trk.off) {                                         // uniform: tracks are set -- a vehicle with keyframes is teleported
             for (int k = k0 + wave; k < k1; k += WAVES_PER_BLOCK) {       // to the one the next tick sees, the others run free as ever
                 if (a.trk.off[k + 1] > a.trk.off[k])
                     track_vehicle(a.trk, k, threadIdx.x & (WAVE - 1), a.geo[2].off, a.veh_local, a.veh_ctr_out, a.veh_pts_out);
@@ -515,6 +529,7 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_restart_kernel(const BatchRes
         const int k0 = r.item_off[b], k1 = r.item_off[b + 1];
         restart_copy(r.ctr, r.s_ctr, k0, k1);
         restart_copy(r.pts, r.s_pts, r.veh_off[k0], r.veh_off[k1]);
+        restart_copy(r.rot, r.s_rot, k0, k1);                           // the headings: a driven vehicle's tick turns them
         if (r.first)
             for (int k = k0 + (int)threadIdx.x; k < k1; k += BLOCK)
                 r.first[k] = r.trk_off[k + 1] > r.trk_off[k] ? (int)((long long)r.s_first[k] + r.shift) : r.s_first[k];

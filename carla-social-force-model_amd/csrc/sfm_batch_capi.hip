@@ -64,6 +64,8 @@ static int check_batch_commands(SfmBatch* b, const float4* kinds, const uint8_t*
 static void drop_batch_boxes(SfmBatch* b) {
     drop_noise_delays(b);
     b->tracks = {};
+    b->drive = {};                                                // (the commands and the vehicle observations are per vehicle)
+    b->vobs = {};
     b->boxes = {};
 }
 
@@ -161,6 +163,10 @@ int sfm::batch_launch(SfmBatch* b, uint32_t flags, float4* frame, float2* zframe
         a.veh_rot = b->boxes.rot;
         a.veh_on = 1;
         if (b->tracks.on) a.trk = BatchTracks{b->tracks.off, b->tracks.first, b->tracks.key, b->tracks.rot, b->tracks.tick + 1};   // this launch writes tick tau + 1
+        if (b->drive.on && b->geo[2].K > 0) {                    // (no vehicles: no command buffer, and nobody to drive)
+            a.veh_cmd = b->drive.cmd;
+            a.veh_head = b->boxes.rot;
+        }
     }
     if (b->modes.on)
         a.fsm = BatchModes{b->modes.mode, b->modes.target, b->modes.speeds, b->modes.off, b->modes.xy, b->modes.cross, b->modes.cursor, b->modes.scene, b->modes.time};
@@ -218,6 +224,7 @@ static BatchRestart restart_args(SfmBatch* b, long long shift) {
         r.item_off = b->geo_item_off[2]; r.veh_off = g.off;
         r.ctr = g.ctr; r.s_ctr = b->snap.ctr;
         r.pts = g.P > 0 ? g.pts : nullptr; r.s_pts = b->snap.pts;
+        r.rot = b->boxes.rot; r.s_rot = b->snap.rot;
     }
     if (b->modes.on) {
         r.mode = b->modes.mode; r.s_mode = b->snap.mode;
@@ -931,6 +938,7 @@ int sfm_batch_snapshot(SfmBatch* b) {
         const BatchGeoDev& g = b->geo[2];
         if ((rc = snap_copy(b, b->snap.ctr, g.ctr, (size_t)g.K))) return rc;
         if ((rc = snap_copy(b, b->snap.pts, g.pts, (size_t)g.P))) return rc;
+        if ((rc = snap_copy(b, b->snap.rot, b->boxes.rot, (size_t)g.K))) return rc;   // the headings: state once vehicles are driven
     }
     if (b->modes.on) {
         if ((rc = snap_copy(b, b->snap.mode, b->modes.mode, n))) return rc;

@@ -1,7 +1,8 @@
 // sfm_batch_host.h -- what the two host files of the batched scenes share: the batch itself (SfmBatch and the struct of each of its
 // features), its error plumbing, and the messages for a feature that is off.  sfm_batch_capi.hip holds the ticks and everything they
 // read or write; sfm_batch_sense_capi.hip the read-only sensors (observations, episode ends, range scans, occupancy grids) and the device pointers;
-// sfm_batch_reset_capi.hip the restart noise; sfm_batch_replay_capi.hip the observed tracks.
+// sfm_batch_reset_capi.hip the restart noise; sfm_batch_replay_capi.hip the observed tracks; sfm_batch_drive_capi.hip the driven
+// vehicles and the vehicle observations.
 #pragma once
 #include "sfm_capi_common.h"
 #include "sfm_metres.h"
@@ -74,7 +75,7 @@ struct BatchSpawnDev {
 struct BatchSnapDev {
     bool on = false;
     DevBuf<float4> pk, own, ctr;
-    DevBuf<float2> zv, pts;
+    DevBuf<float2> zv, pts, rot;
     DevBuf<uint32_t> draws;
     DevBuf<uint8_t> mode, born;
     DevBuf<float> target, time, birth;
@@ -176,6 +177,28 @@ struct BatchReplayDev {
     DevBuf<float> scene;           // [B][5] what sfm_batch_score left
 };
 
+// driven vehicles (sfm_batch_set_vehicle_driving): the command of every vehicle {a, b, c, kind}, an input the ticks only read, and
+// its pinned host copy, kept and sent as the steering's (sfm_batch_set_vehicle_commands; SfmBatch::v_done is recorded behind the
+// copy).  The headings the driven ticks turn are BatchBoxesDev::rot.  Dropped with the boxes they refer to.
+struct BatchDriveDev {
+    bool on = false;           // (not "cmd is allocated": a batch without vehicles can be driven and has no buffers)
+    DevBuf<float4> cmd;        // [M] on the device
+    PinnedBuf<float4> cmd_h;
+    bool pending = false;
+};
+
+// vehicle observations (sfm_batch_set_vehicle_observation): the settings and the buffer sfm_batch_observe_vehicles fills; nothing a
+// tick reads or writes.  Dropped with the boxes they refer to.
+struct BatchVehObsDev {
+    bool on = false;           // (not "buf is allocated": a batch without vehicles can be observed and has no buffer)
+    int k = 0;
+    int frame = 0;
+    DevBuf<float> range2;      // [B] sense_range^2
+    DevBuf<float2> goal;       // [M]
+    DevBuf<uint8_t> mask;      // [M]; not allocated: every vehicle is observed
+    DevBuf<float> buf;         // [M][16 + 4 k]
+};
+
 struct BatchRecordDev {        // grow-only device buffers of the recording calls
     DevBuf<float4> frames;     // sfm_batch_run_recorded
     DevBuf<float2> zframes;
@@ -216,7 +239,10 @@ struct SfmBatch {
     sfm::BatchNoiseDev noise;
     sfm::BatchGridDev grid;
     sfm::BatchReplayDev replay;
-    std::vector<int32_t> scene_off_h;       // the scene offsets [B+1] of the last sfm_batch_upload_state, on the host
+    sfm::BatchDriveDev drive;
+    sfm::BatchVehObsDev vobs;
+    sfm::Event v_done;                      // created by the first sfm_batch_set_vehicle_driving with vehicles; outlives every drop of the driving
+    std::vector<int32_t> scene_off_h;      // the scene offsets [B+1] of the last sfm_batch_upload_state, on the host
     std::vector<float> dt_h;                // [B] the scenes' step lengths (sfm_batch_create, sfm_batch_set_params)
     sfm::Event c_done;                      // created by the first sfm_batch_set_steering with rows; outlives every drop of the steering
     std::string err;
@@ -247,7 +273,12 @@ constexpr const char* NOISE_OFF = "restart noise is off: call sfm_batch_set_rest
 constexpr const char* SCANS_OFF = "scans are off: call sfm_batch_set_scan first (sfm_batch_upload_state drops them)";
 constexpr const char* OBSERVED_OFF = "observed tracks are off: call sfm_batch_set_observed first (sfm_batch_upload_state, setting modes or a "
                                      "spawn schedule and switching steering off drop them)";
-constexpr const char* GRIDS_OFF = "grids are off: call sfm_batch_set_grid first (sfm_batch_upload_state drops them)";
+constexpr const char* DRIVING_OFF = "vehicle driving is off: call sfm_batch_set_vehicle_driving first (sfm_batch_set_dynamic_boxes and "
+                                    "sfm_batch_set_dynamic_obstacles drop it)";
+constexpr const char* VEHICLE_OBS_OFF = "vehicle observations are off: call sfm_batch_set_vehicle_observation first "
+                                        "(sfm_batch_set_dynamic_boxes and sfm_batch_set_dynamic_obstacles drop them)";
+constexpr const char* NO_BOXES = "this needs device-side vehicles: call sfm_batch_set_dynamic_boxes first";
+constexpr const char* GRIDS_OFF ="grids are off: call sfm_batch_set_grid first (sfm_batch_upload_state drops them)";
 
 // one kind of the scenes' geometry as the kernels take it, and what the sensors see of the scenes
 inline BatchGeo batch_geo(const SfmBatch* b, int k) { return BatchGeo{b->geo_item_off[k], b->geo[k].off, b->geo[k].pts, b->geo[k].ctr}; }

@@ -222,6 +222,10 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_restart_noise_kernel(const Re
         for (int k = k0 + wave; k < k1; k += WAVES_PER_BLOCK) {        // wave-uniform
             const int D = a.delay[k];
             if (D <= 0 || a.trk.off[k + 1] == a.trk.off[k]) continue;
+            if (a.veh_cmd) {                                           // a driven vehicle stays at its snapshot pose
+                const float kind = a.veh_cmd[k].w;
+                if (kind == 1.0f || kind == 2.0f) continue;
+            }
             const uint32_t h = reset_word(seed, (uint32_t)(k - k0), e, 0u, 4u);
             const int add = (int)(((unsigned long long)h * (unsigned long long)((uint32_t)D + 1u)) >> 32);   // 0 .. D
             const int f0 = a.first[k];

@@ -32,7 +32,8 @@ int sfm::batch_restart_noise(SfmBatch* b, const int* d_list, const uint8_t* d_ma
         a.veh_local = b->boxes.local;
         a.veh_ctr = b->geo[2].ctr;
         a.veh_pts = b->geo[2].pts;
-        b->tracks.first_stale = true;                              // how far a first tick moved is known on the device only
+        if (b->drive.on) a.veh_cmd = b->drive.cmd;                 // (driven vehicles keep their snapshot pose)
+        b->tracks.first_stale = true;                             // how far a first tick moved is known on the device only
     }
     HIP_TRY(b, launch_batch_restart_noise(a, scenes, b->stream));
     return SFM_OK;

@@ -20,7 +20,7 @@ static int check_frame(SfmBatch* b, int frame) {
 
 // One lookup for the device buffers a caller may see: which = SFM_BATCH_PTR_*, or PTR_OBSERVATIONS for sfm_batch_observation_ptr's.
 // off: why there is none (its feature is off, no state was uploaded), else p and bytes -- both 0 where the buffer has no element.
-constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_SCENE_SCORES + 1;     // (not part of the ABI: sfm_batch_device_ptr refuses it)
+constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_VEHICLE_OBS + 1;    // (not part of the ABI: sfm_batch_device_ptr refuses it)
 struct BatchBuffer { const char* off; void* p; size_t bytes; };
 static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     const size_t n = (size_t)b->n_total, B = (size_t)b->B;
@@ -46,6 +46,12 @@ static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     case SFM_BATCH_PTR_SCENE_SCORES:
         if (!b->replay.on) return {OBSERVED_OFF, nullptr, 0};
         return which == SFM_BATCH_PTR_ROW_SCORES ? have(b->replay.score, sizeof(float4) * n) : have(b->replay.scene, 5 * sizeof(float) * B);
+    case SFM_BATCH_PTR_VEHICLE_COMMANDS:
+        if (!b->drive.on) return {DRIVING_OFF, nullptr, 0};
+        return have(b->drive.cmd, sizeof(float4) * (size_t)b->geo[2].K);
+    case SFM_BATCH_PTR_VEHICLE_OBS:
+        if (!b->vobs.on) return {VEHICLE_OBS_OFF, nullptr, 0};
+        return have(b->vobs.buf, sizeof(float) * (size_t)b->geo[2].K * (size_t)(SFM_BATCH_OBS_HEADER + 4 * b->vobs.k));
     }
     if (!b->have_state) return {NO_STATE, nullptr, 0};
     if (which == SFM_BATCH_PTR_COMMANDS) {
@@ -83,10 +89,12 @@ void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes) {
     if (!b) return nullptr;
     // SFM_BATCH_PTR_RESETS came without an ABI bump: while restart noise is off it is refused as the unknown value it was, word for
     // word, so a caller of ABI 17 as it was sees no difference
-    // (SFM_BATCH_PTR_GRID likewise, while grids are off, and SFM_BATCH_PTR_ROW_SCORES / _SCENE_SCORES while observed tracks are off)
+    // (SFM_BATCH_PTR_GRID likewise, while grids are off, SFM_BATCH_PTR_ROW_SCORES / _SCENE_SCORES while observed tracks are off, and
+    //  SFM_BATCH_PTR_VEHICLE_COMMANDS / _VEHICLE_OBS while driving / vehicle observations are off)
     const bool known = (which >= SFM_BATCH_PTR_COMMANDS && which <= SFM_BATCH_PTR_SCAN) || (which == SFM_BATCH_PTR_RESETS && b->noise.on) ||
                        (which == SFM_BATCH_PTR_GRID && b->grid.on) ||
-                       ((which == SFM_BATCH_PTR_ROW_SCORES || which == SFM_BATCH_PTR_SCENE_SCORES) && b->replay.on);
+                       ((which == SFM_BATCH_PTR_ROW_SCORES || which == SFM_BATCH_PTR_SCENE_SCORES) && b->replay.on) ||
+                       (which == SFM_BATCH_PTR_VEHICLE_COMMANDS && b->drive.on) || (which == SFM_BATCH_PTR_VEHICLE_OBS && b->vobs.on);
     if (!known) { bfail(b, SFM_ERR_INVALID, "which must be SFM_BATCH_PTR_COMMANDS, _STATE, _ZSTATE, _EPISODES, _DONE or _SCAN"); return nullptr; }
     return buffer_ptr(b, which, which == SFM_BATCH_PTR_SCAN ? ", so which = SFM_BATCH_PTR_SCAN has no buffer" :
                                 which == SFM_BATCH_PTR_EPISODES || which == SFM_BATCH_PTR_DONE ? ", so which = SFM_BATCH_PTR_EPISODES / _DONE has no buffer" : "", bytes);

@@ -61,6 +61,7 @@ hipError_t launch_batch_scan(const ScanArgs& a, int B, hipStream_t st);
 hipError_t launch_batch_grid(const GridArgs& a, int B, hipStream_t st);
 hipError_t launch_batch_replay(const ReplayArgs& a, int B, hipStream_t st);
 hipError_t launch_batch_score(const ScoreArgs& a, int B, hipStream_t st);
+hipError_t launch_batch_vehicle_observe(const VehicleObserveArgs& a, int B, hipStream_t st);
 hipError_t launch_dynamic_boxes(float4* ctr, const int* off, const float2* local, const float2* rot, float2* pts, int M,
                                 float dt, int advance, hipStream_t st);
 

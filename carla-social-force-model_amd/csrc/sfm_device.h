@@ -331,6 +331,12 @@ struct BatchArgs {
     // {ux, uy, uz, kind} with kind 0 not steered, 1 velocity command, 2 preferred velocity (held as a float; any other value: 0).
     // Read by the lane that owns the row, never written by a tick -- the caller may write it on the batch's stream
     const float4* cmd;        // [N_total]
+    // driven vehicles (sfm_batch_set_vehicle_driving; appended last for the same reason): the command of every vehicle {a, b, c, kind}
+    // with kind 0 not driven, 1 velocity, 2 unicycle (held as a float; any other value: 0), read in the vehicle prologue by the wave
+    // that moves the vehicle and never written by a tick -- the caller may write it on the batch's stream.  veh_head is veh_rot's
+    // array, writable: the wave that drives vehicle k reads its heading there and lane 0 stores the new one in place
+    const float4* veh_cmd;    // [M]; null: nobody is driven
+    float2* veh_head;         // [M] {cos, sin}
 };
 
 // Restart of chosen scenes from the batch's snapshot (sfm_batch_restart, sfm_batch_restart_kernel): every array a tick can change,
@@ -365,6 +371,8 @@ struct BatchRestart {
     // while episodes are off
     int* age;                 // [B]
     float* prev_goal_d2;      // [B]
+    // the vehicles' headings (state since vehicles can be driven, sfm_batch_set_vehicle_driving); null without device-side vehicles
+    float2* rot;        const float2* s_rot;
 };
 
 // What the batch's read-only sensors (observations, episode ends, range scans) see of the scenes: the common head of their arguments.
@@ -430,6 +438,19 @@ struct GridArgs : BatchSceneView {
 };
 static_assert(sizeof(GridArgs) == 120 + 32, "the grid kernel's arguments follow the view without padding");
 
+// Vehicle observations of a batch (sfm_batch_observe_vehicles, sfm_batch_vehicle_observe_kernel in sfm_batch_vehicle_observe.hip):
+// everything but obs is read only.  The vehicles are geo[2]'s items (device-side vehicles: the half the next tick reads).
+struct VehicleObserveArgs : BatchSceneView {
+    const float2* rot;        // [M] the vehicles' headings {cos, sin}, as the next tick reads them
+    const float* range2;      // [B] sense_range^2, formed in double and rounded once
+    const float2* goal;       // [M]
+    const uint8_t* mask;      // [M] nonzero: the vehicle is observed; null: every vehicle
+    float* obs;               // [M][16 + 4 k]
+    int k;                    // neighbour slots per vehicle, 1 .. SFM_BATCH_MAX_OBS_NEIGHBOURS
+    int frame;                // 0 world axes, 1 the vehicle's heading frame
+};
+static_assert(sizeof(VehicleObserveArgs) == 120 + 48, "the vehicle observation kernel's arguments follow the view without padding");
+
 // Restart noise of a batch (sfm_batch_set_restart_noise, sfm_batch_restart_noise_kernel in sfm_batch_reset.hip): launched behind
 // sfm_batch_restart_kernel with the same choice of scenes (list / mask as in BatchRestart); the rule is specified in include/sfm_hip.h.
 constexpr int RESET_MAX_TRIES = 32;
@@ -453,6 +474,7 @@ struct RestartNoiseArgs {
     const float2* veh_local;  // [P] ring points in the vehicle frame
     float4* veh_ctr;          // [M] the half of the ping-pong the next tick reads
     float2* veh_pts;          // [P]
+    const float4* veh_cmd;    // [M] the driving commands (BatchArgs::veh_cmd); a driven vehicle stays at its snapshot pose.  null: none
 };
 
 // Observed tracks of a batch (sfm_batch_set_observed, sfm_batch_replay_kernel and sfm_batch_score_kernel in sfm_batch_replay.hip;

@@ -104,6 +104,40 @@ __device__ __forceinline__ void track_vehicle(const BatchTracks& t, int k, int l
     }
 }
 
+// One wave moves vehicle k as its command u = {a, b, c, kind} says (sfm_batch_set_vehicle_driving; the caller has found kind 1 or 2,
+// k is wave-uniform): the single definition of the rule in include/sfm_hip.h.  Kind 1, velocity: v' = (a, b), the heading turns to
+// v' / |v'| unless v' = 0.  Kind 2, unicycle: the heading is turned by the caller's (b, c) = (cos, sin) of this tick's turn and
+// normalised again, v' = a h' (a < 0 reverses).  Then centre' = centre + dt v', the ring p = centre' + R(h') u as advance_vehicle forms
+// it.  Every line is one correctly rounded fp32 operation or an fmaf.  A vehicle whose centre is not finite stays ABSENT as
+// track_vehicle leaves one: centre and ring +inf, velocity 0, the heading kept.  The heading is read from head[k] by every lane and
+// stored there by lane 0 of this wave, the only one that touches head[k] in the launch; centre and ring go to the other half.
+__device__ __forceinline__ void drive_vehicle(const float4 u, float dt, const float4* ctr, const int* off, const float2* local, float2* head,
+                                              float4* ctr_out, float2* pts_out, int k, int lane) {
+    const float4 c = ctr[k];
+    const float2 h = head[k];
+    float hx = h.x, hy = h.y, vx, vy;
+    if (u.w == 1.0f) {                                                  // uniform
+        const float s2 = fmaf(u.x, u.x, u.y * u.y);
+        if (s2 > 0.0f) { const float s = sqrtf(s2); hx = u.x / s; hy = u.y / s; }
+        vx = u.x; vy = u.y;
+    } else {
+        const float gx = fmaf(u.y, h.x, -(u.z * h.y)), gy = fmaf(u.z, h.x, u.y * h.y);
+        const float n2 = fmaf(gx, gx, gy * gy);
+        if (n2 > 0.0f) { const float n = sqrtf(n2); hx = gx / n; hy = gy / n; }
+        vx = u.x * hx; vy = u.x * hy;
+    }
+    const float inf = __builtin_inff();
+    const bool present = fabsf(c.x) < inf && fabsf(c.y) < inf;          // (a NaN fails it)
+    float4 o = make_float4(fmaf(dt, vx, c.x), fmaf(dt, vy, c.y), vx, vy);
+    if (!present) { o = make_float4(inf, inf, 0.0f, 0.0f); hx = h.x; hy = h.y; }
+    if (lane == 0) { ctr_out[k] = o; head[k] = make_float2(hx, hy); }
+    const int o1 = off[k + 1];
+    for (int p = off[k] + lane; p < o1; p += WAVE) {
+        const float2 q = local[p];
+        pts_out[p] = present ? make_float2(fmaf(hx, q.x, fmaf(-hy, q.y, o.x)), fmaf(hy, q.x, fmaf(hx, q.y, o.y))) : make_float2(inf, inf);
+    }
+}
+
 // The tile-box rule (the operands of tiles_negligible): a row counts unless it is parked far away (a despawned pedestrian or
 // padding), and its speed bound is rounded up so that it stays a bound.  A tile's box and bound are the union over its rows:
 // the callers start from an empty box (+inf / -inf, 0), put in each row that counts, then tile_box_reduce over the wave.

@@ -182,3 +182,108 @@ def observe_scene(scene, k, sense_range, frame=0, state=None, vehicles=None, veh
         with np.errstate(over="ignore", invalid="ignore"):
             rec = rotate_record(rec, heading(rec)).astype(np.float32)
     return rec
+
+
+def rotate_vehicle_record(rec0, h):
+    """Frame 1 of a vehicle record from its frame-0 record and the stored headings ``h`` (M,2) float32, bit for bit: every 2-vector
+    (p, q) except floats 4-5 becomes (fmaf(hx, p, hy * q), fmaf(hx, q, -(hy * p))) -- floats 0-1, 2-3, 10-11, 12-13 and both halves
+    of every slot; floats 4 .. 9, 14 and 15 stay.  A pure function of the frame-0 record and ``h``."""
+    from .scan import _fma32
+    out = np.array(rec0, dtype=np.float32, copy=True)
+    h = np.asarray(h, dtype=np.float32).reshape(-1, 2)
+    hx, hy = h[:, 0], h[:, 1]
+    with np.errstate(over="ignore", invalid="ignore"):
+        for c in [0, 2, 10, 12] + list(range(OBS_HEADER, out.shape[1], 2)):
+            p, q = out[:, c].copy(), out[:, c + 1].copy()
+            out[:, c] = _fma32(hx, p, hy * q)
+            out[:, c + 1] = _fma32(hx, q, -(hy * p))
+    out[rec0[:, 6] == 0] = 0.0                                         # (absent or masked out: the whole record is zeros)
+    return out
+
+
+def observe_vehicles_scene(scene, k, sense_range, frame=0, goals=None, mask=None, state=None, vehicles=None, vehicle_vel=None,
+                           headings=None):
+    """The vehicle observation record of one scene, (M, 16 + 4k) float32, as ``SfmBatch.vehicle_observations()`` returns it -- bit
+    for bit in both frames (include/sfm_hip.h specifies the record; every decision is taken on fp32 squared distances formed as the
+    kernel forms them, and frame 1's rotation is written in exact fused multiply-adds).
+
+    ``scene``: a scene dict as ``SfmBatch.upload`` takes it (or a ``scenarios.Scenario``).  ``goals`` (M,2) or None (zeros);
+    ``mask`` (M,) or None (every vehicle).  What has changed on the device since the upload is fed in: ``state`` = (loc, vel) of
+    the rows, ``vehicles`` = the scene's list of (center, ring), ``vehicle_vel`` (M,2), ``headings`` (M,2) fp32 {cos, sin}
+    (default: ``scenarios.vehicle_headings(scene)``)."""
+    from .scan import _fma32
+    from .scenarios import vehicle_headings
+    k = int(k)
+    if not 1 <= k <= MAX_OBS_NEIGHBOURS:
+        raise ValueError(f"k must be 1 .. {MAX_OBS_NEIGHBOURS}, got {k}")
+    if frame not in (0, 1):
+        raise ValueError(f"frame must be 0 or 1, got {frame!r}")
+    R2 = range2(sense_range)
+    veh = (_get(scene, "dynamic_obstacles") or []) if vehicles is None else vehicles
+    M = len(veh)
+    rec = np.zeros((M, OBS_HEADER + 4 * k), np.float32)
+    if M == 0:
+        return rec
+    loc, vel = (_get(scene, "loc"), _get(scene, "vel")) if state is None else state
+    loc, vel = np.asarray(loc, dtype=np.float64), np.asarray(vel, dtype=np.float64)
+    n = loc.reshape(-1, loc.shape[-1]).shape[0] if loc.size else 0
+    loc, vel = (loc.reshape(n, -1), vel.reshape(n, -1)) if n else (np.zeros((0, 3)),) * 2
+    x, y = (_f32(loc[:, 0], 0), _f32(loc[:, 1], 0)) if n else (np.zeros(0, np.float32),) * 2
+    vx, vy = (_f32(vel[:, 0], 0), _f32(vel[:, 1], 0)) if n else (np.zeros(0, np.float32),) * 2
+    alive = live(x, y)
+    vv = _get(scene, "dynamic_vel") if vehicle_vel is None else vehicle_vel
+    vv = np.zeros((M, 2), np.float32) if vv is None else _f32(vv, 2)
+    h = _f32(vehicle_headings(scene) if headings is None else headings, 2)
+    g = np.zeros((M, 2), np.float32) if goals is None else _f32(goals, 2)
+    mk = np.ones(M, bool) if mask is None else np.asarray(mask).reshape(M) != 0
+    ctr = np.stack([_f32(c, 0) for c, _ in veh])
+    bpts, _ = _polylines(_get(scene, "borders") or [], False)
+    spts, _ = _polylines(_get(scene, "static_obstacles") or [], True)
+    inf = np.float32(np.inf)
+    with np.errstate(over="ignore", invalid="ignore"):
+        present = live(ctr[:, 0], ctr[:, 1])
+        for v in range(M):
+            if not (mk[v] and present[v]):
+                continue
+            cx, cy = ctr[v]
+            r = rec[v]
+            r[0], r[1] = g[v, 0] - cx, g[v, 1] - cy
+            r[2], r[3] = vv[v]
+            r[4], r[5] = h[v]
+            r[6] = 1.0
+            # neighbours: the first k live rows with d2 < R2 in ascending (d2, j) order -- a stable sort over ascending j
+            d2 = _d2(x - cx, y - cy)
+            cand = alive & (d2 < R2)
+            order = np.argsort(np.where(cand, d2, inf), kind="stable")[:k]
+            m = min(int(cand.sum()), k)
+            r[7] = m
+            for s in range(m):
+                j = order[s]
+                r[OBS_HEADER + 4 * s:OBS_HEADER + 4 * s + 4] = (x[j] - cx, y[j] - cy, vx[j] - vv[v, 0], vy[j] - vv[v, 1])
+            # clear_d2: ring points x live rows; a NaN distance is no candidate
+            ring = _f32(veh[v][1], 2)
+            clear = inf
+            if ring.shape[0] and alive.any():
+                dd = _d2(x[alive][:, None] - ring[None, :, 0], y[alive][:, None] - ring[None, :, 1])
+                dd = dd[~np.isnan(dd)]
+                clear = dd.min() if dd.size else inf
+            r[8] = clear
+            others = present & (np.arange(M) != v)
+            od = _d2(ctr[others, 0] - cx, ctr[others, 1] - cy)
+            od = od[~np.isnan(od)]
+            r[9] = od.min() if od.size else inf
+            flags = 0
+            for bit, col, pts in ((1, 10, bpts), (2, 12, spts)):
+                if pts.shape[0] == 0:
+                    continue
+                pd = _d2(pts[:, 0] - cx, pts[:, 1] - cy)
+                pd = np.where(np.isnan(pd), inf, pd)
+                i = int(np.argmin(pd))                                 # the first minimum: polylines in order, points in order
+                if pd[i] < R2:
+                    r[col], r[col + 1] = pts[i, 0] - cx, pts[i, 1] - cy
+                    flags += bit
+            r[14] = flags
+            r[15] = _fma32(vv[v, 0], h[v, 0], vv[v, 1] * h[v, 1])
+    if frame == 1:
+        rec = rotate_vehicle_record(rec, h)
+    return rec

@@ -249,6 +249,118 @@ def place_tracked(sc, tracks, tau, dt=None):
     return sc
 
 
+def vehicle_headings(sc):
+    """The vehicles' headings (M,2) float32 {cos, sin} as the device holds them: ``dynamic_heading`` once ``drive_vehicles`` has
+    stored it, else the fp32 cos / sin of the float64 ``dynamic_yaw`` (what ``batch.pack_boxes`` sends)."""
+    get, _ = _accessors(sc)
+    h = get("dynamic_heading")
+    if h is not None:
+        return np.array(h, dtype=np.float32).reshape(-1, 2)
+    yaw = np.asarray(get("dynamic_yaw") if get("dynamic_yaw") is not None else [], dtype=np.float64).reshape(-1)
+    return np.column_stack((np.cos(yaw), np.sin(yaw))).astype(np.float32)
+
+
+def place_ring_heading_f32(center, heading, local):
+    """``place_ring_f32`` from a stored fp32 heading {cos, sin}: p = (fmaf(hx, ux, fmaf(-hy, uy, cx)), fmaf(hy, ux, fmaf(hx, uy, cy)))
+    with exact fused multiply-adds (``scan._fma32``), float64 values of fp32 numbers."""
+    from .scan import _fma32
+    c = np.asarray(center, dtype=np.float32)
+    h = np.asarray(heading, dtype=np.float32)
+    u = np.asarray(local, dtype=np.float32).reshape(-1, 2)
+    px = _fma32(h[0], u[:, 0], _fma32(-h[1], u[:, 1], c[0]))
+    py = _fma32(h[1], u[:, 0], _fma32(h[0], u[:, 1], c[1]))
+    return np.column_stack((px, py)).astype(np.float64)
+
+
+def drive_command(kind, command, heading):
+    """The rule of a driven vehicle (drive_vehicle in sfm_interaction.h; include/sfm_hip.h states it) without the move: kind 1 or 2,
+    the fp32 command (a, b, c) and heading (hx, hy) -> (heading' (2,), velocity' (2,)) float32, every line one correctly rounded
+    fp32 operation or an exact fmaf."""
+    from .scan import _fma32
+    a, b, c = (np.float32(v) for v in command)
+    hx, hy = (np.float32(v) for v in heading)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        if int(kind) == 1:
+            s2 = _fma32(a, a, b * b)
+            if s2 > 0:
+                s = np.sqrt(s2)
+                hx, hy = a / s, b / s
+            return np.array([hx, hy], np.float32), np.array([a, b], np.float32)
+        gx = _fma32(b, hx, -(c * hy))
+        gy = _fma32(c, hx, b * hy)
+        n2 = _fma32(gx, gx, gy * gy)
+        if n2 > 0:
+            n = np.sqrt(n2)
+            hx, hy = gx / n, gy / n
+        return np.array([hx, hy], np.float32), np.array([a * hx, a * hy], np.float32)
+
+
+def drive_vehicles(sc, kinds, commands, dt, tracks=None, tau=None):
+    """The host twin of the batch's driven vehicles for ONE scene (a Scenario or a scene dict) and ONE integrating tick of step
+    ``dt``: moves ``dynamic_obstacles`` (centres and rings), ``dynamic_vel`` and the headings ``dynamic_heading`` (M,2) float32 the
+    way the device does, bit for bit (include/sfm_hip.h states the rule; every operation is fp32, fused multiply-adds are exact).
+
+    ``kinds`` (M,) or one value: 1 velocity, 2 unicycle, anything else not driven; ``commands`` (M,3) or one (3,) command: (a, b, c).
+    A vehicle that is not driven does what it does without driving: with ``tracks`` (one entry per vehicle, None or a track dict)
+    and ``tau`` (the tick this call arrives at), a vehicle that has keyframes is placed by ``place_tracked``'s rule -- its stored
+    heading stays what it was -- and any other moves by ``dt`` times its velocity, its ring placed at its stored heading.  A driven
+    vehicle ignores its keyframes; one whose centre is not finite stays absent (centre and ring +inf, velocity 0, heading kept).
+    Sets ``dynamic_present`` (M,) bool and keeps ``dynamic_yaw`` in step with the headings (float64, for readers; the device holds
+    no angle).  Returns ``sc``."""
+    from .scan import _fma32
+    get, put = _accessors(sc)
+    dyn = list(get("dynamic_obstacles") or [])
+    M = len(dyn)
+    kd = np.broadcast_to(np.asarray(kinds, dtype=np.float64), (M,)) if np.ndim(kinds) == 0 else np.asarray(kinds, dtype=np.float64).reshape(M)
+    cmd = np.asarray(commands, dtype=np.float32)
+    cmd = np.broadcast_to(cmd, (M, 3)) if cmd.ndim == 1 else cmd.reshape(M, 3)
+    tracks = [None] * M if tracks is None else list(tracks)
+    if len(tracks) != M:
+        raise ValueError(f"{len(tracks)} tracks for {M} vehicles")
+    vel = get("dynamic_vel")
+    vel = np.zeros((M, 2), np.float32) if vel is None else np.array(vel, dtype=np.float64).reshape(M, 2).astype(np.float32)
+    head = vehicle_headings(sc).copy()
+    ext = np.asarray(get("dynamic_extent"), dtype=np.float64).reshape(M, 2)
+    yaws = np.array(get("dynamic_yaw"), dtype=np.float64).reshape(M)
+    dt32 = np.float32(dt)
+    tracked = None
+    if any(t is not None for t in tracks):                              # the keyframe rule, taken from its one definition
+        if tau is None:
+            raise ValueError("drive_vehicles: tracks need tau, the tick this call arrives at")
+        tracked = place_tracked({"dynamic_obstacles": dyn, "dynamic_vel": vel.astype(np.float64), "dynamic_yaw": yaws.copy(),
+                                 "dynamic_extent": ext}, tracks, tau, dt)
+    present = np.ones(M, dtype=bool)
+    new = []
+    for k, (c, _) in enumerate(dyn):
+        local = ring_local_offsets(*ext[k])
+        c32 = np.asarray(c, dtype=np.float64).astype(np.float32)
+        if kd[k] in (1.0, 2.0):
+            h2, v2 = drive_command(kd[k], cmd[k], head[k])
+            if np.isfinite(c32).all():
+                head[k], vel[k] = h2, v2
+                c2 = np.array([_fma32(dt32, v2[0], c32[0]), _fma32(dt32, v2[1], c32[1])], np.float32)
+                new.append((c2.astype(np.float64), place_ring_heading_f32(c2, h2, local)))
+                yaws[k] = np.arctan2(np.float64(h2[1]), np.float64(h2[0]))
+            else:
+                present[k] = False
+                vel[k] = 0.0
+                new.append((np.full(2, np.inf), np.full((len(local), 2), np.inf)))
+        elif tracks[k] is not None:
+            new.append(tracked["dynamic_obstacles"][k])
+            vel[k] = tracked["dynamic_vel"][k]
+            yaws[k] = tracked["dynamic_yaw"][k]
+            present[k] = tracked["dynamic_present"][k]
+        else:
+            c2 = np.array([_fma32(dt32, vel[k, 0], c32[0]), _fma32(dt32, vel[k, 1], c32[1])], np.float32)
+            new.append((c2.astype(np.float64), place_ring_heading_f32(c2, head[k], local)))
+    put("dynamic_obstacles", new)
+    put("dynamic_vel", vel.astype(np.float64))
+    put("dynamic_yaw", yaws)
+    put("dynamic_heading", head)
+    put("dynamic_present", present)
+    return sc
+
+
 def make_track_plan(sc, seed, ticks, dt=0.05, max_speed=1.4):
     """A synthetic track plan for one scene (a Scenario or a scene dict), the recipe of the batch track tests: every vehicle drives
     a gentle arc (constant turn rate, up to +-0.6 rad over the run) that passes through the crowd's centre of mass half-way; the

@@ -939,6 +939,95 @@ int sfm_batch_score(SfmBatch* b);
  * buffers on the device, valid until the next sfm_batch_set_observed or a call that drops the tracks; while observed tracks are off
  * the values are refused as the unknown `which` they were before. */
 int sfm_batch_download_scores(SfmBatch* b, float* row_scores, float* scene_scores);
+/* Driven vehicles: device-side vehicles (sfm_batch_set_dynamic_boxes) whose motion is decided while the batch runs -- a driving
+ * policy being trained against the crowd, a planner under test, a braking controller.  The reference reads each vehicle's transform
+ * and velocity from the simulator every tick, whoever drives it (obstacles.py:314-317); here the command lives in a device buffer
+ * that the tick's one launch reads.  These entry points, the vehicle observations below and SFM_BATCH_PTR_VEHICLE_COMMANDS /
+ * _VEHICLE_OBS were added WITHOUT a bump of SFM_ABI_VERSION (it stays 17), like the restart noise, the grids and the observed
+ * tracks: additions only, and a build that has them is recognised by the symbols.
+ *
+ * Command.  Vehicle k (an index into the M vehicles of all scenes, as in sfm_batch_set_dynamic_boxes) has a command {a, b, c, kind},
+ * [M] float4 with the kind held as a float.  Every tick with SFM_TICK_INTEGRATE reads it and never writes it; a tick without the
+ * flag moves no vehicle and reads no command.  sfm_batch_run, sfm_batch_run_recorded and sfm_batch_run_recorded_forces hold the
+ * commands for all their ticks (for kind 2 the turn applies every tick).
+ *
+ * Heading.  Each vehicle has a heading h = (cos, sin): the yaw sfm_batch_set_dynamic_boxes gave it.  A driven tick rewrites it, so
+ * it is state: sfm_batch_snapshot holds it, and sfm_batch_restart, sfm_batch_restart_device and the auto restart put back the chosen
+ * scenes' centres, rings, velocities and headings (other scenes are left bit for bit).  Restart noise leaves a driven vehicle at its
+ * snapshot pose (its traffic-timing delay is not applied while its kind is 1 or 2).
+ *
+ * The rule (drive_vehicle, the one definition).  Every line is one correctly rounded fp32 operation or an fmaf, sqrtf and / are the
+ * correctly rounded forms; dt is the scene's step_length and (cx, cy, vx, vy) the vehicle as this tick reads it.
+ *   kind 0, or any value other than 1 and 2: not driven -- the vehicle runs free or follows its track exactly as without driving.
+ *   kind 1, velocity: s2 = fmaf(a, a, b * b); h' = (a / s, b / s) with s = sqrtf(s2) when s2 > 0, else h' = h (a stopped vehicle
+ *     keeps its heading); v' = (a, b); c is ignored.
+ *   kind 2, unicycle: signed speed a and this tick's turn (b, c) = (cos dpsi, sin dpsi), supplied by the caller -- the kernel does
+ *     no trigonometry.  g = (fmaf(b, hx, -(c * hy)), fmaf(c, hx, b * hy)); n2 = fmaf(gx, gx, gy * gy); h' = (gx / n, gy / n) with
+ *     n = sqrtf(n2) when n2 > 0, else h' = h; v' = (a * h'x, a * h'y).  A negative a reverses.
+ *   Both: centre' = (fmaf(dt, v'x, cx), fmaf(dt, v'y, cy)); the stored velocity becomes v' -- what the dynamic obstacle force and
+ *     gap acceptance see from the next tick on; ring point p = (fmaf(h'x, ux, fmaf(-h'y, uy, cx')), fmaf(h'y, ux, fmaf(h'x, uy, cy')))
+ *     for the ring-local offset (ux, uy), as every vehicle's ring is formed.
+ *   A driven vehicle with keyframes (sfm_batch_set_vehicle_tracks) ignores them while its kind is 1 or 2; the tracks' tick counter
+ *     goes on counting, and when the kind goes back to 0 the track takes over at that tick.
+ *   A driven vehicle whose centre is not finite stays absent as an absent tracked vehicle is: centre and ring +inf, velocity 0, the
+ *     heading kept.
+ *
+ * sfm_batch_set_vehicle_driving: kind [M] uint8 and a, b, c [M] float; kind = NULL switches driving off.  Refused with nothing
+ * changed: no device-side vehicles (SFM_ERR_STATE); a kind above 2; a NULL a, b or c; a command of a driven vehicle that is not
+ * finite.  sfm_batch_set_dynamic_boxes and sfm_batch_set_dynamic_obstacles drop driving (and the vehicle observations), because the
+ * vehicles may differ; every other call keeps it.  Commands are an input, like pedestrian steering: a snapshot neither holds nor
+ * restores them.
+ * sfm_batch_set_vehicle_commands: new a, b, c for the kinds of the last sfm_batch_set_vehicle_driving -- ONE copy from pinned memory,
+ * ordered on the batch's stream, like sfm_batch_set_commands.  SFM_ERR_STATE while driving is off.
+ * sfm_batch_download_vehicle_driving: synchronises the stream; kind as the tick takes it (0, 1 or 2), the command, and the headings
+ * and velocities as the next tick reads them; NULL skips a column.  SFM_ERR_STATE while driving is off.
+ * SFM_BATCH_PTR_VEHICLE_COMMANDS (sfm_batch_device_ptr): the command buffer on the device, [M] float4, valid until driving is set
+ * again or dropped.  Values written on the device are not validated; a kind other than 1 or 2 counts as 0.  While driving is off
+ * the value is refused as the unknown `which` it was before. */
+#define SFM_BATCH_PTR_VEHICLE_COMMANDS 10
+#define SFM_BATCH_PTR_VEHICLE_OBS 11
+#define SFM_DRIVE_NONE 0
+#define SFM_DRIVE_VELOCITY 1
+#define SFM_DRIVE_UNICYCLE 2
+int sfm_batch_set_vehicle_driving(SfmBatch* b, const uint8_t* kind, const float* a, const float* b_, const float* c);
+int sfm_batch_set_vehicle_commands(SfmBatch* b, const float* a, const float* b_, const float* c);
+int sfm_batch_download_vehicle_driving(SfmBatch* b, uint8_t* kind, float* a, float* b_, float* c, float* hx, float* hy, float* vx,
+                                       float* vy);
+/* Vehicle observations: what a driving policy and its reward read per vehicle, by ONE launch of sfm_batch_vehicle_observe_kernel (a
+ * workgroup per scene, a wave per vehicle, lanes striding over pedestrians and points; every reduction a lexicographic (d2, index)
+ * minimum by shuffles; no atomics) over the buffers the next tick would read.  It writes only its own buffer.
+ *
+ * Settings (sfm_batch_set_vehicle_observation): k neighbour slots, 1 .. SFM_BATCH_MAX_OBS_NEIGHBOURS, for the batch; sense_range
+ * [B], validated and squared as sfm_batch_set_observation does it (R2 below); frame 0 or 1; goal_x, goal_y [M], finite (NULL, both:
+ * zeros); mask [M] (NULL: every vehicle) -- a vehicle outside the mask costs nothing and reads zeros.  sense_range = NULL switches
+ * the observations off.  The call zero-fills the buffer and waits for the stream.  Refused with nothing changed: no state
+ * (SFM_ERR_STATE); no device-side vehicles (SFM_ERR_STATE); k, frame, a range or a goal out of bounds.
+ *
+ * Record: [M][SFM_BATCH_OBS_HEADER + 4 k] floats, for a vehicle with centre c, velocity v and heading h (d2 of a point q from c:
+ * dx = q.x - cx, dy = q.y - cy, fmaf(dx, dx, dy * dy)):
+ *   0-1   goal - centre                         2-3   velocity                      4-5   heading h, always in world axes
+ *   6     present: 1.0 iff the centre is finite and |cx|, |cy| < 1e12; otherwise the WHOLE record is zeros
+ *   7     m, the number of filled neighbour slots
+ *   8     clear_d2: the minimum over this vehicle's ring points p and the scene's live rows j of fmaf(dx, dx, dy * dy) with
+ *         dx = x_j - px; +inf with no live row or an empty ring; not limited by the range (collisions, near-miss rewards)
+ *   9     other_d2: the minimum over the OTHER present vehicles of the scene of the squared centre distance; +inf when none
+ *   10-11 nearest border point - centre: the first minimum over all border points of the scene in polyline order, then point
+ *         order; present iff d2 < R2, else zeros          12-13 nearest static-obstacle point - centre, likewise
+ *   14    flags: 1 border point present + 2 static point present
+ *   15    signed speed along the heading, fmaf(vx, hx, vy * hy)
+ *   16+4s slot s: (x_j - cx, y_j - cy, vx_j - vx, vy_j - vy) -- the slots hold the first k live rows with d2 < R2 (strict) in
+ *         ascending (d2, j) order; empty slots are zeros.  "Live" is sfm_batch_observe's test.
+ * Frame 1 decides everything in frame 0 first and then replaces every 2-vector (p, q) except slots 4-5 by
+ * (fmaf(hx, p, hy * q), fmaf(hx, q, -(hy * p))); the heading is used as stored.  Both frames are defined bit for bit.
+ * A tracked vehicle that is not driven is observed with the heading sfm_batch_set_dynamic_boxes gave it, not its keyframe's yaw: a
+ * policy observes the vehicle it drives.
+ * sfm_batch_observe_vehicles: the launch, on the batch's stream; the host does not wait.  sfm_batch_download_vehicle_observations
+ * synchronises the stream and copies the buffer (zeros before the first launch).  SFM_BATCH_PTR_VEHICLE_OBS (sfm_batch_device_ptr):
+ * the buffer on the device.  All SFM_ERR_STATE while the observations are off (the pointer value: refused as unknown). */
+int sfm_batch_set_vehicle_observation(SfmBatch* b, int k, const float* sense_range, int frame, const float* goal_x, const float* goal_y,
+                                      const uint8_t* mask);
+int sfm_batch_observe_vehicles(SfmBatch* b);
+int sfm_batch_download_vehicle_observations(SfmBatch* b, float* out);
 /* Current state of every scene (synchronises the batch's stream); NULL skips a column.  A planar batch leaves z alone and
  * writes vz = 0. */
 int sfm_batch_download_state(SfmBatch* b, float* x, float* y, float* z, float* vx, float* vy, float* vz);
