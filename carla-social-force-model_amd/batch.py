@@ -146,6 +146,14 @@ frame, goals, mask)`` and ``observe_vehicles()`` are the sensor centred on a veh
 ``vehicle_observation_tensor()`` aliases it.  ``upload`` and ``set_dynamic_boxes`` drop both, every other call keeps them.
 ``scenarios.drive_vehicles`` and ``observe.observe_vehicles_scene`` are the host twins, bit for bit (the exact rules:
 include/sfm_hip.h): examples/batch_av_loop.py.
+
+Range scans from the vehicles (ABI 17, added without a bump): the lidar of a driving policy.  ``set_vehicle_scan(max_range,
+ped_radius, point_radius, R=..., mask=..., frame=..., mount=...)`` chooses up to 256 rays from a sensor mounted at ``mount`` in the
+vehicle frame; ``scan_vehicles()`` fills, per vehicle, ``2R`` floats in one launch -- ranges, then kinds as for ``scan()`` -- with
+every pedestrian, border, static obstacle and OTHER vehicle of the scene as candidates and the vehicle's own ring left out.
+Frame 1 turns the rays by the stored heading.  ``vehicle_scans()`` downloads per scene, ``vehicle_scan_tensor()`` aliases the
+buffer, ``scan.scan_vehicles_scene`` is the host twin, bit for bit in both frames.  ``upload`` and ``set_dynamic_boxes`` drop it,
+every other call keeps it: examples/batch_av_lidar_loop.py.
 """
 from __future__ import annotations
 
@@ -730,6 +738,21 @@ def vehicle_observation_arrays(item_off, k, sense_range, frame=0, goals=None, ma
     return int(k), r, frame, gx, gy, mk
 
 
+PTR_VEHICLE_SCAN = 12            # SFM_BATCH_PTR_VEHICLE_SCAN: the vehicle scan record [M][2R] (while the vehicle scan is on)
+
+
+def vehicle_scan_arrays(item_off, max_range, ped_radius, point_radius=_scan.POINT_RADIUS, frame=0, mask=None, mount=(0.0, 0.0)):
+    """Vehicle scan settings -> the arguments of sfm_batch_set_vehicle_scan behind the directions: (max_range, ped_radius,
+    point_radius float32 [B], mask uint8 [M] or None, frame int, mount_x, mount_y float32).  The three lengths as for
+    ``scan.scan_arrays``; ``mask``: None (every vehicle) or bools as for ``vehicle_observation_arrays``; ``mount``: the sensor's (x, y)
+    in the vehicle frame, metres, x forward.  Pure NumPy; raises ValueError on what the library would refuse."""
+    io = np.asarray(item_off)
+    rm, rp, rq, frame = _scan.scan_arrays(len(io) - 1, max_range, ped_radius, point_radius, frame)
+    mx, my = _scan.check_mount(mount)
+    mk = None if mask is None else np.ascontiguousarray(_per_vehicle(mask, io, 0, "mask") != 0, dtype=np.uint8)
+    return rm, rp, rq, mk, frame, mx, my
+
+
 PTR_RESETS = 6                   # SFM_BATCH_PTR_RESETS: the restart counters [B] uint32 (while restart noise is on)
 MAX_RESTART_TRIES = 32           # SFM_BATCH_MAX_RESTART_TRIES
 
@@ -928,6 +951,7 @@ class SfmBatch:
         self._boxes = False               # the vehicles last set move on the device (set_dynamic_boxes with at least one vehicle)
         self.driving = False              # set_vehicle_driving has been called and no later call has dropped it
         self.vobs_k = None                # pedestrian slots of set_vehicle_observation (None: vehicle observations are off)
+        self.vscan_rays = None            # rays per vehicle of set_vehicle_scan (None: the vehicle scan is off)
 
     def _check(self, rc, what):
         if rc != 0:
@@ -997,6 +1021,7 @@ class SfmBatch:
                           "sfm_batch_set_dynamic_obstacles")
         self._dyn = (dy[0].copy(), dy[1].copy())
         self._boxes, self.driving, self.vobs_k = False, False, None    # (the vehicles were replaced: driving and their observations go)
+        self.vscan_rays = None            # ... and their scans
         z, vz =(None, None) if planar else (pk["z"], pk["vz"])
         self._check_drops(L.sfm_batch_upload_state(self._b, iptr(so), fptr(pk["x"]), fptr(pk["y"]), fptr(z), fptr(pk["vx"]),
                                                    fptr(pk["vy"]), fptr(vz), fptr(pk["wx"]), fptr(pk["wy"]),
@@ -1023,6 +1048,7 @@ class SfmBatch:
                                                                 *(fptr(a) for a in boxes[2:])), "sfm_batch_set_dynamic_boxes")
         self._dyn = (boxes[0].copy(), boxes[1].copy())
         self._boxes, self.driving, self.vobs_k = int(boxes[0][-1]) > 0, False, None    # (new vehicles: driving and their observations go)
+        self.vscan_rays = None            # ... and their scans
 
     def dynamic_obstacles(self):
         """Per scene, its vehicles as the next tick sees them: a list of (center (2,), ring (P,2)) float64 like
@@ -1422,6 +1448,60 @@ class SfmBatch:
         if self.vobs_k is None:
             raise SfmLibraryError("SfmBatch.vehicle_observation_tensor: vehicle observations are off (set_vehicle_observation)")
         return self._vehicle_tensor(PTR_VEHICLE_OBS, obs_width(self.vobs_k), device)
+
+    def set_vehicle_scan(self, max_range, ped_radius=None, point_radius=_scan.POINT_RADIUS, R=None, angles=None, directions=None,
+                         mask=None, frame=0, mount=(0.0, 0.0)):
+        """What ``scan_vehicles`` computes (sfm_batch_set_vehicle_scan; see ``vehicle_scan_arrays`` and the module docstring): per
+        scanned vehicle R rays (up to 256) from a sensor at ``mount`` = (x, y) in the vehicle frame (x forward), each the distance to
+        the first disc it meets -- every pedestrian a disc of ``ped_radius``, every border, static-obstacle and OTHER vehicle's ring
+        point a disc of ``point_radius`` (0 switches a kind off); the vehicle's own ring is left out -- up to ``max_range``; the
+        three lengths one value or one per scene, in metres.  The rays as for ``set_scan``: ``R``, ``angles`` or ``directions``.
+        ``mask``: which vehicles are scanned, as for ``set_vehicle_observation``.  ``frame``: 0 world axes, 1 the vehicle's heading
+        frame.  ``max_range=None`` switches the scan off and frees the buffer.  Needs ``upload`` and device-side vehicles;
+        ``upload`` and ``set_dynamic_boxes`` drop it, every other call keeps it, and it keeps the snapshot.  Allocates and
+        zero-fills the buffer (``vehicle_scan_tensor()`` must be taken again)."""
+        L = self._lib
+        if max_range is None:
+            self._check(L.sfm_batch_set_vehicle_scan(self._b, 0, None, None, None, None, None, None, 0, 0.0, 0.0), "sfm_batch_set_vehicle_scan")
+            self.vscan_rays = None
+            return
+        self._need_upload("set_vehicle_scan")
+        if ped_radius is None:
+            raise ValueError("set_vehicle_scan needs a ped_radius (metres; 0: pedestrians are not seen)")
+        if sum(v is not None for v in (R, angles, directions)) != 1:
+            raise ValueError("set_vehicle_scan takes exactly one of R, angles and directions")
+        lim = _scan.MAX_VEHICLE_SCAN_RAYS
+        if directions is not None:
+            dx, dy = _scan.check_directions(directions, lim)
+        else:
+            dx, dy = _scan.ray_directions(_scan.default_angles(R, lim) if angles is None else angles, lim)
+        rm, rp, rq, mk, frame, mx, my = vehicle_scan_arrays(self._vehicle_off("set_vehicle_scan"), max_range, ped_radius, point_radius,
+                                                            frame, mask, mount)
+        self._check(L.sfm_batch_set_vehicle_scan(self._b, int(dx.shape[0]), fptr(dx), fptr(dy), fptr(rm), fptr(rp), fptr(rq), u8ptr(mk),
+                                                 frame, float(mx), float(my)), "sfm_batch_set_vehicle_scan")
+        self.vscan_rays = int(dx.shape[0])
+
+    def scan_vehicles(self):
+        """Scan from every scanned vehicle as the batch is now (sfm_batch_scan_vehicles): one launch on the batch's stream, ordered
+        with the ticks and restarts around it; the host does not wait.  Raises SfmLibraryError while the vehicle scan is off."""
+        self._check(self._lib.sfm_batch_scan_vehicles(self._b), "sfm_batch_scan_vehicles")
+
+    def vehicle_scans(self):
+        """``scan_vehicles()`` and a download: a list of B float32 arrays (M_b, 2R) in scene order -- ranges, then kinds
+        (synchronises the batch's stream)."""
+        self.scan_vehicles()
+        io = self._dyn[0]
+        buf = np.zeros((int(io[-1]), 2 * (self.vscan_rays or 0)), np.float32)
+        self._check(self._lib.sfm_batch_download_vehicle_scan(self._b, fptr(buf)), "sfm_batch_download_vehicle_scan")
+        return _split_rows(io, buf)
+
+    def vehicle_scan_tensor(self, device=None):
+        """The vehicle scan buffer as a torch tensor (M, 2R) float32 that aliases device memory (no copy): what a driving policy
+        reads after ``scan_vehicles()``.  Put torch and the batch on one stream.  Take it again after ``set_vehicle_scan``.  Raises
+        SfmLibraryError while the vehicle scan is off."""
+        if self.vscan_rays is None:
+            raise SfmLibraryError("SfmBatch.vehicle_scan_tensor: the vehicle scan is off (set_vehicle_scan)")
+        return self._vehicle_tensor(PTR_VEHICLE_SCAN, 2 * self.vscan_rays, device)
 
     def set_scan(self, max_range, ped_radius=None, point_radius=_scan.POINT_RADIUS, R=None, angles=None, mask=None, frame=0,
                  directions=None):

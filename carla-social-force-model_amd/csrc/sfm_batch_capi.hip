@@ -66,6 +66,7 @@ static void drop_batch_boxes(SfmBatch* b) {
     b->tracks = {};
     b->drive = {};                                                // (the commands and the vehicle observations are per vehicle)
     b->vobs = {};
+    b->vscan = {};                                                // (... and so are the vehicles' range scans)
     b->boxes = {};
 }
 
@@ -433,6 +434,7 @@ int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x
     b->noise = {};                                                // ... and its restart noise (the boxes are per row)
     b->grid = {};                                                 // ... and its grids (the slots are per row)
     b->replay = {};                                               // ... and its observed tracks (the roles are per row)
+    b->vscan = {};                                                // ... and the vehicles' scans of it
     b->snap.on = false;                                           // ... and so is its snapshot
     b->have_state = false;
     if (n > 0) {

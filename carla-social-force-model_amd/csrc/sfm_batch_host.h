@@ -2,7 +2,7 @@
 // features), its error plumbing, and the messages for a feature that is off.  sfm_batch_capi.hip holds the ticks and everything they
 // read or write; sfm_batch_sense_capi.hip the read-only sensors (observations, episode ends, range scans, occupancy grids) and the device pointers;
 // sfm_batch_reset_capi.hip the restart noise; sfm_batch_replay_capi.hip the observed tracks; sfm_batch_drive_capi.hip the driven
-// vehicles and the vehicle observations.
+// vehicles and the vehicle observations (the vehicles' range scans are a sensor: sfm_batch_sense_capi.hip).
 #pragma once
 #include "sfm_capi_common.h"
 #include "sfm_metres.h"
@@ -199,6 +199,19 @@ struct BatchVehObsDev {
     DevBuf<float> buf;         // [M][16 + 4 k]
 };
 
+// range scans from the vehicles (sfm_batch_set_vehicle_scan): the settings and the buffer sfm_batch_scan_vehicles fills; nothing a
+// tick reads or writes.  Dropped with the boxes they refer to, and by sfm_batch_upload_state.
+struct BatchVehScanDev {
+    bool on = false;
+    int R = 0;
+    int frame = 0;
+    float mount_x = 0.f, mount_y = 0.f;
+    DevBuf<BatchVehicleScanScene> set;   // [B]
+    DevBuf<float2> dir;        // [R]
+    DevBuf<uint8_t> mask;      // [M]; not allocated: every vehicle is scanned
+    DevBuf<float> buf;         // [M][2 R]
+};
+
 struct BatchRecordDev {        // grow-only device buffers of the recording calls
     DevBuf<float4> frames;     // sfm_batch_run_recorded
     DevBuf<float2> zframes;
@@ -241,6 +254,7 @@ struct SfmBatch {
     sfm::BatchReplayDev replay;
     sfm::BatchDriveDev drive;
     sfm::BatchVehObsDev vobs;
+    sfm::BatchVehScanDev vscan;
     sfm::Event v_done;                      // created by the first sfm_batch_set_vehicle_driving with vehicles; outlives every drop of the driving
     std::vector<int32_t> scene_off_h;      // the scene offsets [B+1] of the last sfm_batch_upload_state, on the host
     std::vector<float> dt_h;                // [B] the scenes' step lengths (sfm_batch_create, sfm_batch_set_params)
@@ -277,6 +291,8 @@ constexpr const char* DRIVING_OFF = "vehicle driving is off: call sfm_batch_set_
                                     "sfm_batch_set_dynamic_obstacles drop it)";
 constexpr const char* VEHICLE_OBS_OFF = "vehicle observations are off: call sfm_batch_set_vehicle_observation first "
                                         "(sfm_batch_set_dynamic_boxes and sfm_batch_set_dynamic_obstacles drop them)";
+constexpr const char* VEHICLE_SCAN_OFF = "vehicle scans are off: call sfm_batch_set_vehicle_scan first (sfm_batch_upload_state, "
+                                         "sfm_batch_set_dynamic_boxes and sfm_batch_set_dynamic_obstacles drop them)";
 constexpr const char* NO_BOXES = "this needs device-side vehicles: call sfm_batch_set_dynamic_boxes first";
 constexpr const char* GRIDS_OFF ="grids are off: call sfm_batch_set_grid first (sfm_batch_upload_state drops them)";
 
@@ -302,6 +318,8 @@ int batch_launch(SfmBatch* b, uint32_t flags, float4* frame = nullptr, float2* z
 // Observed tracks (sfm_batch_replay_capi.hip): inv_h follows the step lengths (sfm_batch_set_params calls it with the stream
 // synchronised and b->dt_h current; it refuses what sfm_batch_set_observed refuses).
 int batch_replay_step_lengths(SfmBatch* b, const float* dt);
+// The vehicle scan's one launch (sfm_batch_vehicle_scan.hip).
+hipError_t launch_batch_vehicle_scan(const VehicleScanArgs& a, int B, hipStream_t st);
 // The delays go with the tracks they refer to (the caller synchronised the stream).
 inline void drop_noise_delays(SfmBatch* b) { b->noise.delay = {}; b->noise.max_delay = 0; }
 

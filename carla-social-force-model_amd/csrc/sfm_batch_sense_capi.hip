@@ -1,5 +1,5 @@
-// sfm_batch_sense_capi.hip -- host side of the batch's read-only sensors (ABI 15 to 17): observations, episode ends, range scans and
-// occupancy grids, and the device pointers a caller shares with them.  Each sensor reads the scenes through one BatchSceneView and writes only its own
+// sfm_batch_sense_capi.hip -- host side of the batch's read-only sensors (ABI 15 to 17): observations, episode ends, range scans (from
+// the rows and from the vehicles) and occupancy grids, and the device pointers a caller shares with them.  Each sensor reads the scenes through one BatchSceneView and writes only its own
 // buffers -- nothing a tick reads or writes.  The batch's types are in sfm_batch_host.h; the ticks, the restarts and everything else
 // in sfm_batch_capi.hip.
 #include "sfm_batch_host.h"
@@ -20,7 +20,7 @@ static int check_frame(SfmBatch* b, int frame) {
 
 // One lookup for the device buffers a caller may see: which = SFM_BATCH_PTR_*, or PTR_OBSERVATIONS for sfm_batch_observation_ptr's.
 // off: why there is none (its feature is off, no state was uploaded), else p and bytes -- both 0 where the buffer has no element.
-constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_VEHICLE_OBS + 1;    // (not part of the ABI: sfm_batch_device_ptr refuses it)
+constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_VEHICLE_SCAN + 1;    // (not part of the ABI: sfm_batch_device_ptr refuses it)
 struct BatchBuffer { const char* off; void* p; size_t bytes; };
 static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     const size_t n = (size_t)b->n_total, B = (size_t)b->B;
@@ -52,6 +52,9 @@ static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     case SFM_BATCH_PTR_VEHICLE_OBS:
         if (!b->vobs.on) return {VEHICLE_OBS_OFF, nullptr, 0};
         return have(b->vobs.buf, sizeof(float) * (size_t)b->geo[2].K * (size_t)(SFM_BATCH_OBS_HEADER + 4 * b->vobs.k));
+    case SFM_BATCH_PTR_VEHICLE_SCAN:
+        if (!b->vscan.on) return {VEHICLE_SCAN_OFF, nullptr, 0};
+        return have(b->vscan.buf, sizeof(float) * (size_t)b->geo[2].K * (size_t)(2 * b->vscan.R));
     }
     if (!b->have_state) return {NO_STATE, nullptr, 0};
     if (which == SFM_BATCH_PTR_COMMANDS) {
@@ -90,11 +93,13 @@ void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes) {
     // SFM_BATCH_PTR_RESETS came without an ABI bump: while restart noise is off it is refused as the unknown value it was, word for
     // word, so a caller of ABI 17 as it was sees no difference
     // (SFM_BATCH_PTR_GRID likewise, while grids are off, SFM_BATCH_PTR_ROW_SCORES / _SCENE_SCORES while observed tracks are off, and
-    //  SFM_BATCH_PTR_VEHICLE_COMMANDS / _VEHICLE_OBS while driving / vehicle observations are off)
+    //  SFM_BATCH_PTR_VEHICLE_COMMANDS / _VEHICLE_OBS while driving / vehicle observations are off; SFM_BATCH_PTR_VEHICLE_SCAN is
+    //  specified as SFM_ERR_STATE while the vehicle scan is off, so it is always known)
     const bool known = (which >= SFM_BATCH_PTR_COMMANDS && which <= SFM_BATCH_PTR_SCAN) || (which == SFM_BATCH_PTR_RESETS && b->noise.on) ||
                        (which == SFM_BATCH_PTR_GRID && b->grid.on) ||
                        ((which == SFM_BATCH_PTR_ROW_SCORES || which == SFM_BATCH_PTR_SCENE_SCORES) && b->replay.on) ||
-                       (which == SFM_BATCH_PTR_VEHICLE_COMMANDS && b->drive.on) || (which == SFM_BATCH_PTR_VEHICLE_OBS && b->vobs.on);
+                       (which == SFM_BATCH_PTR_VEHICLE_COMMANDS && b->drive.on) || (which == SFM_BATCH_PTR_VEHICLE_OBS && b->vobs.on) ||
+                       which == SFM_BATCH_PTR_VEHICLE_SCAN;
     if (!known) { bfail(b, SFM_ERR_INVALID, "which must be SFM_BATCH_PTR_COMMANDS, _STATE, _ZSTATE, _EPISODES, _DONE or _SCAN"); return nullptr; }
     return buffer_ptr(b, which, which == SFM_BATCH_PTR_SCAN ? ", so which = SFM_BATCH_PTR_SCAN has no buffer" :
                                 which == SFM_BATCH_PTR_EPISODES || which == SFM_BATCH_PTR_DONE ? ", so which = SFM_BATCH_PTR_EPISODES / _DONE has no buffer" : "", bytes);
@@ -280,6 +285,77 @@ int sfm_batch_scan(SfmBatch* b) {
 }
 
 int sfm_batch_download_scan(SfmBatch* b, float* out) { return download_buffer(b, SFM_BATCH_PTR_SCAN, out); }
+
+// Range scans from the vehicles (ABI 17, added without a bump).  Everything is checked before anything is allocated or freed.
+int sfm_batch_set_vehicle_scan(SfmBatch* b, int R, const float* dir_x, const float* dir_y, const float* max_range, const float* ped_radius,
+                               const float* point_radius, const uint8_t* mask, int frame, float mount_x, float mount_y) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!max_range) {
+        HIP_TRY(b, hipStreamSynchronize(b->stream));             // a scan in flight may still write the buffer
+        b->vscan = {};
+        return SFM_OK;
+    }
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, NO_STATE);
+    if (!b->boxes.on) return bfail(b, SFM_ERR_STATE, std::string("vehicle scans: ") + NO_BOXES);
+    if (R < 1 || R > SFM_BATCH_MAX_VEHICLE_SCAN_RAYS)
+        return bfail(b, SFM_ERR_INVALID, "R must be 1 .. " + std::to_string(SFM_BATCH_MAX_VEHICLE_SCAN_RAYS) + " rays per vehicle, got " + std::to_string(R));
+    if (frame != SFM_OBS_FRAME_WORLD && frame != SFM_OBS_FRAME_HEADING)
+        return bfail(b, SFM_ERR_INVALID, "frame must be 0 (world axes) or 1 (the vehicle's heading frame), got " + std::to_string(frame));
+    if (!dir_x || !dir_y) return bfail(b, SFM_ERR_INVALID, "dir_x or dir_y is NULL");
+    if (!ped_radius || !point_radius) return bfail(b, SFM_ERR_INVALID, "ped_radius or point_radius is NULL");
+    if (!std::isfinite(mount_x) || !std::isfinite(mount_y) || std::fabs(mount_x) > SFM_BATCH_MAX_SENSE_RANGE || std::fabs(mount_y) > SFM_BATCH_MAX_SENSE_RANGE)
+        return bfail(b, SFM_ERR_INVALID, "the mount must be finite and within 1e6 metres of the vehicle's centre");
+    std::vector<float2> dir((size_t)R);
+    for (int q = 0; q < R; ++q) {
+        if (!std::isfinite(dir_x[q]) || !std::isfinite(dir_y[q]))
+            return bfail(b, SFM_ERR_INVALID, "ray " + std::to_string(q) + ": its direction is not finite");
+        dir[q] = make_float2(dir_x[q], dir_y[q]);
+    }
+    const size_t B = (size_t)b->B;
+    std::vector<BatchVehicleScanScene> set(B);
+    for (size_t s = 0; s < B; ++s) {
+        set[s] = BatchVehicleScanScene{max_range[s], 0.f, 0.f, 0.f};    // (the range goes to the kernel as the fp32 value given)
+        if ((rc = batch_metres(b, s, "max_range", max_range[s], true, nullptr))) return rc;
+        if ((rc = batch_metres(b, s, "ped_radius", ped_radius[s], false, &set[s].ped_r2))) return rc;
+        if ((rc = batch_metres(b, s, "point_radius", point_radius[s], false, &set[s].point_r2))) return rc;
+    }
+    const size_t M = (size_t)b->geo[2].K, vals = M * (size_t)(2 * R);
+    BatchVehScanDev o;
+    HIP_TRY(b, o.set.alloc(B));
+    HIP_TRY(b, o.dir.alloc((size_t)R));
+    HIP_TRY(b, hipMemcpy(o.set, set.data(), sizeof(BatchVehicleScanScene) * B, hipMemcpyHostToDevice));
+    HIP_TRY(b, hipMemcpy(o.dir, dir.data(), sizeof(float2) * (size_t)R, hipMemcpyHostToDevice));
+    if (mask && M > 0) {
+        HIP_TRY(b, o.mask.alloc(M));
+        HIP_TRY(b, hipMemcpy(o.mask, mask, M, hipMemcpyHostToDevice));
+    }
+    if (vals > 0) {
+        HIP_TRY(b, o.buf.alloc(vals));
+        HIP_TRY(b, hipMemsetAsync(o.buf, 0, sizeof(float) * vals, b->stream));
+    }
+    o.R = R;
+    o.frame = frame;
+    o.mount_x = mount_x;
+    o.mount_y = mount_y;
+    o.on = true;
+    HIP_TRY(b, hipStreamSynchronize(b->stream));                 // the zero fill; and a scan in flight may still write the old buffer
+    b->vscan = std::move(o);
+    return SFM_OK;
+}
+
+int sfm_batch_scan_vehicles(SfmBatch* b) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->vscan.on) return bfail(b, SFM_ERR_STATE, VEHICLE_SCAN_OFF);
+    if (b->geo[2].K == 0) return SFM_OK;                         // no vehicle: nothing to write
+    const VehicleScanArgs a{batch_scene_view(b), b->boxes.rot, b->vscan.set, b->vscan.dir, b->vscan.mask /* null: every vehicle */,
+                            b->vscan.buf, b->vscan.R, b->vscan.frame, b->vscan.mount_x, b->vscan.mount_y};
+    HIP_TRY(b, launch_batch_vehicle_scan(a, b->B, b->stream));
+    return SFM_OK;
+}
+
+int sfm_batch_download_vehicle_scan(SfmBatch* b, float* out) { return download_buffer(b, SFM_BATCH_PTR_VEHICLE_SCAN, out); }
 
 // Occupancy grids (ABI 17, added without a bump).  Everything is checked before anything is allocated or freed.
 int sfm_batch_set_grid(SfmBatch* b, int G, const float* cell, const uint8_t* mask, int frame) {

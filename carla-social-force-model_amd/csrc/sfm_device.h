@@ -451,6 +451,27 @@ struct VehicleObserveArgs : BatchSceneView {
 };
 static_assert(sizeof(VehicleObserveArgs) == 120 + 48, "the vehicle observation kernel's arguments follow the view without padding");
 
+// Range scans from the vehicles of a batch (sfm_batch_scan_vehicles, sfm_batch_vehicle_scan_kernel in sfm_batch_vehicle_scan.hip):
+// everything but out is read only.  The vehicles are geo[2]'s items; a vehicle's own ring is no candidate of its rays.
+constexpr int VEHICLE_SCAN_MAX_RAYS = 256;
+struct BatchVehicleScanScene {    // one scene's settings (sfm_batch_set_vehicle_scan): BatchScanScene's
+    float max_range;          // Rmax, the fp32 value as given
+    float ped_r2, point_r2;   // radius^2, each formed in double and rounded once; 0: the kind is never hit
+    float pad;
+};
+struct VehicleScanArgs : BatchSceneView {
+    const float2* rot;        // [M] the vehicles' headings {cos, sin}, as the next tick reads them
+    const BatchVehicleScanScene* set;   // [B]
+    const float2* dir;        // [R] ray directions, used as given
+    const uint8_t* mask;      // [M] nonzero: the vehicle is scanned; null: every vehicle
+    float* out;               // [M][2 R]: ranges, then kinds
+    int R;                    // rays per vehicle, 1 .. VEHICLE_SCAN_MAX_RAYS
+    int frame;                // 0 world axes, 1 the vehicle's heading frame
+    float mount_x, mount_y;   // the sensor in the vehicle frame (x forward), one pair for the batch
+};
+static_assert(sizeof(VehicleScanArgs) == 120 + 56, "the vehicle scan kernel's arguments follow the view without padding");
+static_assert(VEHICLE_SCAN_MAX_RAYS <= BLOCK, "the direction table is staged by one pass of the workgroup");
+
 // Restart noise of a batch (sfm_batch_set_restart_noise, sfm_batch_restart_noise_kernel in sfm_batch_reset.hip): launched behind
 // sfm_batch_restart_kernel with the same choice of scenes (list / mask as in BatchRestart); the rule is specified in include/sfm_hip.h.
 constexpr int RESET_MAX_TRIES = 32;

@@ -16,6 +16,7 @@ from ._args import MAX_METRES as MAX_SCAN_RANGE, check_frame, per_scene_metres
 from .observe import _f32, _get, _polylines, live as _live
 
 MAX_SCAN_RAYS = 64                   # SFM_BATCH_MAX_SCAN_RAYS
+MAX_VEHICLE_SCAN_RAYS = 256          # SFM_BATCH_MAX_VEHICLE_SCAN_RAYS
 KIND_NONE, KIND_PEDESTRIAN, KIND_BORDER, KIND_STATIC, KIND_VEHICLE = range(5)
 POINT_RADIUS = 0.1                   # the reference's sampling resolution of borders and rings
 
@@ -46,31 +47,32 @@ def radius2(r):
     return np.float32(r * r)
 
 
-def default_angles(R):
-    """The default ray angles: 2 pi q / R, q = 0 .. R-1, float64."""
+def default_angles(R, limit=MAX_SCAN_RAYS):
+    """The default ray angles: 2 pi q / R, q = 0 .. R-1, float64.  ``limit``: the most rays the sensor takes (64 for the rows' scan,
+    ``MAX_VEHICLE_SCAN_RAYS`` for the vehicles')."""
     R = int(R)
-    if not 1 <= R <= MAX_SCAN_RAYS:
-        raise ValueError(f"R must be 1 .. {MAX_SCAN_RAYS} rays, got {R}")
+    if not 1 <= R <= limit:
+        raise ValueError(f"R must be 1 .. {limit} rays, got {R}")
     return 2.0 * np.pi * np.arange(R) / R
 
 
-def ray_directions(angles):
-    """Ray angles (radians, 1 .. 64 of them) -> (dir_x, dir_y) float32 [R]: cos and sin formed in double and rounded once.  Pure
-    NumPy; raises ValueError on a shape that does not fit and on an angle that is not finite."""
+def ray_directions(angles, limit=MAX_SCAN_RAYS):
+    """Ray angles (radians, 1 .. ``limit`` of them, 64 unless said otherwise) -> (dir_x, dir_y) float32 [R]: cos and sin formed in
+    double and rounded once.  Pure NumPy; raises ValueError on a shape that does not fit and on an angle that is not finite."""
     a = np.asarray(angles)
     if a.dtype.kind not in "iuf":
         raise ValueError(f"angles must be numbers, got {a.dtype}")
     a = a.astype(np.float64)
-    if a.ndim != 1 or not 1 <= a.shape[0] <= MAX_SCAN_RAYS:
-        raise ValueError(f"angles: expected 1 .. {MAX_SCAN_RAYS} values, got shape {a.shape}")
+    if a.ndim != 1 or not 1 <= a.shape[0] <= limit:
+        raise ValueError(f"angles: expected 1 .. {limit} values, got shape {a.shape}")
     if not np.isfinite(a).all():
         raise ValueError("angles must be finite")
     return np.ascontiguousarray(np.cos(a), dtype=np.float32), np.ascontiguousarray(np.sin(a), dtype=np.float32)
 
 
-def check_directions(directions):
+def check_directions(directions, limit=MAX_SCAN_RAYS):
     """(dir_x, dir_y) given directly -> both as float32 [R], used as given (not renormalised).  Raises ValueError on shapes that do
-    not fit, R outside 1 .. 64 and values that are not finite in float32."""
+    not fit, R outside 1 .. ``limit`` (64 unless said otherwise) and values that are not finite in float32."""
     try:
         dx, dy = directions
     except (TypeError, ValueError):
@@ -78,8 +80,8 @@ def check_directions(directions):
     dx, dy = np.asarray(dx), np.asarray(dy)
     if dx.dtype.kind not in "iuf" or dy.dtype.kind not in "iuf":
         raise ValueError("directions must be numbers")
-    if dx.ndim != 1 or dx.shape != dy.shape or not 1 <= dx.shape[0] <= MAX_SCAN_RAYS:
-        raise ValueError(f"directions: expected two arrays of 1 .. {MAX_SCAN_RAYS} values, got shapes {dx.shape} and {dy.shape}")
+    if dx.ndim != 1 or dx.shape != dy.shape or not 1 <= dx.shape[0] <= limit:
+        raise ValueError(f"directions: expected two arrays of 1 .. {limit} values, got shapes {dx.shape} and {dy.shape}")
     with np.errstate(over="ignore"):
         dx, dy = np.ascontiguousarray(dx, dtype=np.float32), np.ascontiguousarray(dy, dtype=np.float32)
     if not (np.isfinite(dx).all() and np.isfinite(dy).all()):
@@ -266,3 +268,140 @@ def range_census(scene, angles, max_range, ped_radius, point_radius, frame=0, ma
             out[k, 0] += int(((vk >= lo) & (vk < Rmax)).sum())
             out[k, 1] += int(((vk >= Rmax) & (vk <= hi)).sum())
     return out
+
+
+# What follows is the vehicles' scan.  ``_walk`` above stays one self-contained function (its tests read its source), so the four
+# helpers below restate its checks, its pruning test, its per-disc arithmetic and its choice of the first minimum; the reduction of
+# ``scan_vehicles_scene`` to ``scan_scene`` in tests/test_batch_vehicle_scan_host.py holds the two statements to each other bit for bit.
+
+def _check_radii(max_range, ped_radius, point_radius):
+    """The scan's three lengths as the library takes them -> (Rmax, ped_r2, point_r2) float32; raises ValueError."""
+    Rmax = np.float32(max_range)
+    if not (np.isfinite(Rmax) and 0 < Rmax <= np.float32(MAX_SCAN_RANGE)):
+        raise ValueError(f"max_range must be finite, > 0 and <= {MAX_SCAN_RANGE:g} metres")
+    for name, r in (("ped_radius", ped_radius), ("point_radius", point_radius)):
+        if not (np.isfinite(np.float32(r)) and 0 <= np.float32(r) <= np.float32(MAX_SCAN_RANGE)):
+            raise ValueError(f"{name} must be finite, >= 0 and <= {MAX_SCAN_RANGE:g} metres")
+    return Rmax, radius2(ped_radius), radius2(point_radius)
+
+
+def _far(ax, ay, r2, Rmax):
+    """``scan_scene``'s pruning test: which candidates (offsets ax, ay from the origin, radius^2 r2) lie further than
+    1.001 (Rmax + 2 r) from it."""
+    d = np.sqrt(ax.astype(np.float64) ** 2 + ay.astype(np.float64) ** 2)
+    return d > 1.001 * (np.float64(Rmax) + 2.0 * np.sqrt(r2.astype(np.float64))) + 1e-30
+
+
+def _disc_ranges(ax, ay, r2, rx, ry):
+    """The per-disc rules of include/sfm_hip.h for P discs (offsets ax, ay from the origin and r2, each (P,)) against R rays
+    (rx, ry, each (R,)): (R, P) float32, the range of every candidate and +inf where the disc is no candidate of the ray."""
+    A, Bv = ax[None, :], ay[None, :]
+    U, V = rx[:, None], ry[:, None]
+    t = _fma32(A, U, Bv * V)
+    c = _fma32(A, V, -(Bv * U))
+    q = _fma32(-c, c, r2[None, :])
+    w = np.sqrt(q)
+    cand = (q > 0) & ((t + w) > 0)
+    s = t - w
+    return np.where(cand, np.where(s > 0, s, np.float32(0.0)), np.float32(np.inf)).astype(np.float32)
+
+
+def _first_minimum(val, kind, Rmax):
+    """A ray's value from its candidates' ranges val (R, P) in the fixed order: (ranges (R,), kinds (R,)) float32."""
+    R = val.shape[0]
+    if val.shape[1] == 0:
+        return np.full(R, Rmax, np.float32), np.zeros(R, np.float32)
+    idx = np.argmin(val, axis=1)                                       # the first minimum in the fixed order
+    best = val[np.arange(R), idx]
+    hit = best < Rmax
+    return np.where(hit, best, Rmax).astype(np.float32), np.where(hit, kind[idx].astype(np.float32), np.float32(0.0))
+
+
+def check_mount(mount):
+    """The sensor's place in the vehicle frame (x forward), metres -> (mx, my) float32; finite, |m| <= 1e6.  Raises ValueError."""
+    try:
+        mx, my = mount
+        with np.errstate(over="ignore", invalid="ignore"):
+            mx, my = np.float32(mx), np.float32(my)
+    except (TypeError, ValueError):
+        raise ValueError("mount must be a pair (x, y) of numbers") from None
+    if not (np.isfinite(mx) and np.isfinite(my) and abs(mx) <= np.float32(MAX_SCAN_RANGE) and abs(my) <= np.float32(MAX_SCAN_RANGE)):
+        raise ValueError(f"mount must be finite and within {MAX_SCAN_RANGE:g} metres of the vehicle's centre")
+    return mx, my
+
+
+def vehicle_scan_origin(center, heading, mount):
+    """The sensor's origin by the rule of include/sfm_hip.h, all fp32: (cx + fmaf(hx, mx, -(hy my)), cy + fmaf(hy, mx, hx my))."""
+    cx, cy = np.float32(center[0]), np.float32(center[1])
+    hx, hy = np.float32(heading[0]), np.float32(heading[1])
+    mx, my = np.float32(mount[0]), np.float32(mount[1])
+    with np.errstate(over="ignore", invalid="ignore"):
+        rx = _fma32(hx, mx, -(hy * my))[()]
+        ry = _fma32(hy, mx, hx * my)[()]
+        return np.float32(cx + rx), np.float32(cy + ry)
+
+
+def scan_vehicles_scene(scene, angles, max_range, ped_radius, point_radius, frame=0, mask=None, mount=(0.0, 0.0), state=None,
+                        vehicles=None, headings=None, directions=None, prune=True):
+    """The vehicle scan record of one scene, (M_b, 2R) float32, as ``SfmBatch.vehicle_scans()`` returns it -- bit for bit in both
+    frames (include/sfm_hip.h specifies the record): floats 0 .. R-1 the ranges, R .. 2R-1 the kinds.  Per scanned present vehicle R
+    rays from the sensor's origin (the centre plus the mount turned by the stored heading); the candidates in the fixed order are
+    EVERY pedestrian row, the border points, the static-obstacle points and the ring points of the scene's OTHER vehicles.
+
+    ``scene``, ``angles`` / ``directions`` (1 .. 256 rays), ``max_range``, ``ped_radius``, ``point_radius``, ``frame`` and
+    ``prune`` as for ``scan_scene``; ``mask`` (M_b,) bool, the vehicles that are scanned (None: all); ``mount`` = (x, y) in the
+    vehicle frame.  What has changed on the device since the upload is fed in: ``state`` = (loc, vel) of the rows, ``vehicles`` =
+    the scene's list of (center, ring), ``headings`` (M_b, 2) fp32 {cos, sin} (default: ``scenarios.vehicle_headings(scene)``, what
+    the upload derives from ``dynamic_yaw``)."""
+    from .scenarios import vehicle_headings
+    if frame not in (0, 1):
+        raise ValueError(f"frame must be 0 or 1, got {frame!r}")
+    ux, uy = (ray_directions(angles, MAX_VEHICLE_SCAN_RAYS) if directions is None
+              else check_directions(directions, MAX_VEHICLE_SCAN_RAYS))
+    R = ux.shape[0]
+    Rmax, pr2, qr2 = _check_radii(max_range, ped_radius, point_radius)
+    mount = check_mount(mount)
+    veh = list((_get(scene, "dynamic_obstacles") or []) if vehicles is None else vehicles)
+    M = len(veh)
+    if mask is None:
+        scanned = np.ones(M, bool)
+    else:
+        scanned = np.asarray(mask)
+        if scanned.shape != (M,):
+            raise ValueError(f"a mask of shape {scanned.shape} for {M} vehicles")
+        scanned = scanned != 0
+    rec = np.zeros((M, 2 * R), np.float32)
+    if M == 0:
+        return rec
+    h = _f32(vehicle_headings(scene) if headings is None else headings, 2)
+    if h.shape != (M, 2):
+        raise ValueError(f"headings of shape {h.shape} for {M} vehicles")
+    loc = np.asarray(_get(scene, "loc") if state is None else state[0], dtype=np.float64)
+    n = loc.reshape(-1, loc.shape[-1]).shape[0] if loc.size else 0
+    loc = loc.reshape(n, -1) if n else np.zeros((0, 3))
+    x, y = _f32(loc[:, 0], 0), _f32(loc[:, 1], 0)
+    ctr = np.stack([_f32(c, 0)[:2] for c, _ in veh])
+    rings = [_f32(r, 2) for _, r in veh]
+    bpts = _polylines(_get(scene, "borders") or [], False)[0]
+    spts = _polylines(_get(scene, "static_obstacles") or [], True)[0]
+    can_prune = bool(prune) and bool((np.abs(ux.astype(np.float64) ** 2 + uy.astype(np.float64) ** 2 - 1.0) < 1e-6).all())
+    with np.errstate(over="ignore", invalid="ignore"):
+        for k in np.flatnonzero(scanned & _live(ctr[:, 0], ctr[:, 1])):
+            ox, oy = vehicle_scan_origin(ctr[k], h[k], mount)
+            other = [rings[v] for v in range(M) if v != k] + [np.zeros((0, 2), np.float32)]
+            geo = [bpts, spts, np.concatenate(other, axis=0)]
+            px = np.concatenate([x] + [g[:, 0] for g in geo])
+            py = np.concatenate([y] + [g[:, 1] for g in geo])
+            r2 = np.concatenate([np.full(n, pr2, np.float32), np.full(len(px) - n, qr2, np.float32)])
+            kind = np.concatenate([np.full(n, KIND_PEDESTRIAN, np.int64)] + [np.full(len(g), KIND_BORDER + q, np.int64) for q, g in enumerate(geo)])
+            ax, ay = px - ox, py - oy
+            keep = r2 > 0                                              # (radius 0: q = -c^2 <= 0, never a candidate)
+            if can_prune:
+                keep &= ~_far(ax, ay, r2, Rmax)
+            if frame == 1:
+                rx = _fma32(h[k, 0], ux, -(h[k, 1] * uy))
+                ry = _fma32(h[k, 1], ux, h[k, 0] * uy)
+            else:
+                rx, ry = ux, uy
+            rec[k, :R], rec[k, R:] = _first_minimum(_disc_ranges(ax[keep], ay[keep], r2[keep], rx, ry), kind[keep], Rmax)
+    return rec

@@ -1028,6 +1028,62 @@ int sfm_batch_set_vehicle_observation(SfmBatch* b, int k, const float* sense_ran
                                       const uint8_t* mask);
 int sfm_batch_observe_vehicles(SfmBatch* b);
 int sfm_batch_download_vehicle_observations(SfmBatch* b, float* out);
+/* Range scans from the vehicles: the lidar of a driving policy, by ONE launch of sfm_batch_vehicle_scan_kernel (a workgroup per
+ * scene, a lane per (vehicle, ray) pair; no atomics) over the buffers the next tick would read.  It writes only its own buffer.
+ * sfm_batch_scan casts from pedestrian rows, offers 64 rays and counts every vehicle ring as an obstacle; this casts from a sensor
+ * mounted on a device-side vehicle (sfm_batch_set_dynamic_boxes), offers 256 rays and leaves the vehicle's OWN ring out.
+ * These three entry points and SFM_BATCH_PTR_VEHICLE_SCAN were added WITHOUT a bump of SFM_ABI_VERSION (it stays 17), like the
+ * driven vehicles: additions only, and a build that has them is recognised by the symbols.
+ *
+ * Settings (sfm_batch_set_vehicle_scan), for the whole batch unless marked per scene.  R: rays per vehicle, 1 ..
+ * SFM_BATCH_MAX_VEHICLE_SCAN_RAYS.  dir_x, dir_y [R]: fp32, finite, used as given and NOT renormalised.  max_range[b]: per scene,
+ * finite, 0 < Rmax <= SFM_BATCH_MAX_SENSE_RANGE, the fp32 value as given.  ped_radius[b], point_radius[b]: per scene, finite,
+ * 0 <= r <= 1e6; the kernel uses r2 = float32(double(r) * r), and a radius of 0 switches that kind off.  mask [M] uint8_t, or NULL
+ * for every vehicle, M the number of device-side vehicles (the items of sfm_batch_set_dynamic_boxes): a vehicle outside the mask
+ * costs nothing and reads zeros.  frame: SFM_OBS_FRAME_WORLD (0) or SFM_OBS_FRAME_HEADING (1, the vehicle's heading frame).
+ * mount_x, mount_y: where the sensor sits in the vehicle frame, metres, x forward; fp32, finite, |m| <= 1e6; one pair for the batch.
+ *
+ * Record: [M][2R] floats in the vehicles' concatenated order.  Floats 0 .. R-1: the ranges.  Floats R .. 2R-1: the kind hit, the
+ * SFM_SCAN_* values (0 none, 1 pedestrian, 2 border, 3 static, 4 vehicle).
+ *
+ * Rules for vehicle k of scene b, all exact: every value is one correctly rounded fp32 operation or an fmaf.  (cx, cy) is the
+ * vehicle's centre, (hx, hy) its stored heading {cos, sin} as sfm_batch_observe_vehicles reads it -- used as stored, never
+ * renormalised, and for a tracked vehicle that is not driven the heading sfm_batch_set_dynamic_boxes gave it, not its keyframe's yaw.
+ *   Present: iff |cx| < 1e12 and |cy| < 1e12 (sfm_batch_observe's live test; NaN fails it).  Otherwise the WHOLE record is zeros: an
+ *     absent tracked vehicle sits at +inf and fails the test.
+ *   Origin:  rx = fmaf(hx, mx, -(hy * my));  ry = fmaf(hy, mx, hx * my);  ox = cx + rx;  oy = cy + ry     (m the mount)
+ *   Ray:     frame 0: (ux, uy) as given.  frame 1: (fmaf(hx, ux, -(hy * uy)), fmaf(hy, ux, hx * uy)) -- sfm_batch_scan's rule with
+ *     the stored heading in place of the derived one.
+ *   Per disc at (px, py) with r2, sfm_batch_scan's rules unchanged:
+ *     ax = px - ox;  ay = py - oy;  t = fmaf(ax, ux, ay * uy);  c = fmaf(ax, uy, -(ay * ux));  q = fmaf(-c, c, r2)
+ *     candidate iff q > 0 and (t + w) > 0 with w = sqrtf(q) correctly rounded;  range = max(t - w, 0)
+ *   Ray value: the first minimum under strict `<` in this fixed order: the scene's pedestrians j ascending (EVERY row is walked,
+ *     none is excluded: ghosts, NaN positions and rings at +inf fail q > 0 by themselves), then the border points, then the
+ *     static-obstacle points, then the ring points of the scene's vehicles OTHER than k; within a kind polylines in order, points in
+ *     order.  A minimum below Rmax is stored with its kind; otherwise the ray stores Rmax and kind 0.
+ * Vehicles are read as the next tick would read them, from the current half of the ping-pong.  Only x and y of the state are used:
+ * a 3-D batch gives the planar record.  A scene with vehicles and no pedestrians still scans its geometry.
+ * The kernel uses no atomics and every order is a function of the scene alone: a scene's record is bitwise the same alone or
+ * anywhere in any batch.
+ *
+ * sfm_batch_set_vehicle_scan allocates and zero-fills the buffer and waits for the batch's stream; max_range = NULL switches the
+ * scan off and frees the buffer.  Refused with nothing changed: no state, or no device-side vehicles (SFM_ERR_STATE); R or frame
+ * out of bounds; a direction, range, radius or mount that is not finite or out of bounds; a NULL dir_x, dir_y, ped_radius or
+ * point_radius.  sfm_batch_upload_state drops the scan, and so do sfm_batch_set_dynamic_boxes and sfm_batch_set_dynamic_obstacles,
+ * exactly as they drop the vehicle observations (the buffer and the mask are per vehicle); every other call keeps it, and it keeps
+ * the snapshot.  A snapshot neither holds nor restores the scan.
+ * sfm_batch_scan_vehicles: ONE launch on the batch's stream, ordered with the ticks, the other sensors and the restarts around it;
+ * the host does not wait.  With no vehicles it launches nothing and succeeds.  sfm_batch_download_vehicle_scan synchronises the
+ * stream and copies the buffer ([M][2R] floats; zeros before the first launch).  SFM_BATCH_PTR_VEHICLE_SCAN (sfm_batch_device_ptr):
+ * the buffer on the device, valid until the next sfm_batch_set_vehicle_scan or a call that drops the scan.  All three give
+ * SFM_ERR_STATE while the scan is off. */
+#define SFM_BATCH_PTR_VEHICLE_SCAN 12
+#define SFM_BATCH_MAX_VEHICLE_SCAN_RAYS 256
+int sfm_batch_set_vehicle_scan(SfmBatch* b, int R, const float* dir_x, const float* dir_y, const float* max_range,
+                               const float* ped_radius, const float* point_radius, const uint8_t* mask, int frame,
+                               float mount_x, float mount_y);
+int sfm_batch_scan_vehicles(SfmBatch* b);
+int sfm_batch_download_vehicle_scan(SfmBatch* b, float* out);
 /* Current state of every scene (synchronises the batch's stream); NULL skips a column.  A planar batch leaves z alone and
  * writes vz = 0. */
 int sfm_batch_download_state(SfmBatch* b, float* x, float* y, float* z, float* vx, float* vy, float* vz);
