@@ -43,7 +43,9 @@ SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_
                             "sfm_batch_download_vehicle_driving", "sfm_batch_set_vehicle_observation",
                             "sfm_batch_observe_vehicles", "sfm_batch_download_vehicle_observations",
                             "sfm_batch_set_vehicle_scan", "sfm_batch_scan_vehicles",
-                            "sfm_batch_download_vehicle_scan")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
+                            "sfm_batch_download_vehicle_scan",
+                            "sfm_batch_set_routes", "sfm_batch_plan_routes", "sfm_batch_plan_routes_device",
+                            "sfm_batch_download_routes")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
 UNBUMPED = ("sfm_batch_set_restart_noise", "sfm_batch_download_restart_noise",
             "sfm_batch_set_grid", "sfm_batch_grid", "sfm_batch_download_grid",
             "sfm_batch_set_observed", "sfm_batch_run_observed", "sfm_batch_score",
@@ -51,7 +53,9 @@ UNBUMPED = ("sfm_batch_set_restart_noise", "sfm_batch_download_restart_noise",
             "sfm_batch_set_vehicle_driving", "sfm_batch_set_vehicle_commands", "sfm_batch_download_vehicle_driving",
             "sfm_batch_set_vehicle_observation", "sfm_batch_observe_vehicles",
             "sfm_batch_download_vehicle_observations",
-            "sfm_batch_set_vehicle_scan", "sfm_batch_scan_vehicles", "sfm_batch_download_vehicle_scan")   # ... and those a build of the SAME number may lack
+            "sfm_batch_set_vehicle_scan", "sfm_batch_scan_vehicles", "sfm_batch_download_vehicle_scan",
+            "sfm_batch_set_routes", "sfm_batch_plan_routes", "sfm_batch_plan_routes_device",
+            "sfm_batch_download_routes")   # ... and those a build of the SAME number may lack
 
 FORCE_NAMES = ("acceleration_force", "pedestrian_force", "border_force",
                "static_obstacle_force", "dynamic_obstacle_force")
@@ -203,6 +207,11 @@ SYMBOLS = {
     "sfm_batch_set_vehicle_scan": (C.c_int, [_H, C.c_int, _F, _F, _F, _F, _F, _U8, C.c_int, C.c_float, C.c_float]),
     "sfm_batch_scan_vehicles": (C.c_int, [_H]),
     "sfm_batch_download_vehicle_scan": (C.c_int, [_H, _F]),
+    # batch routes over walk graphs (ABI 17, added without a bump)
+    "sfm_batch_set_routes": (C.c_int, [_H, _I, _F, _F, _I, _I, _F, _U8, _U8, _F, _F, C.c_int]),
+    "sfm_batch_plan_routes": (C.c_int, [_H, _U8]),
+    "sfm_batch_plan_routes_device": (C.c_int, [_H, C.c_void_p]),
+    "sfm_batch_download_routes": (C.c_int, [_H, _I, _I, _I, _F, _I, _I, _F, _F, _U8]),
 }
 
 _lib = None

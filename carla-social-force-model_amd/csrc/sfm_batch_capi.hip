@@ -73,6 +73,7 @@ static void drop_batch_boxes(SfmBatch* b) {
 static void drop_batch_modes(SfmBatch* b) {
     b->spawns = {};
     b->spawn_used = false;
+    b->routes = {};                                               // (a route is walked as a mode queue)
     b->modes = {};
 }
 
@@ -275,7 +276,8 @@ int sfm::batch_restart_device(SfmBatch* b, const uint8_t* d_mask, long long shif
     r.mask = d_mask;
     HIP_TRY(b, launch_batch_restart(r, b->B, b->stream));
     if (b->tracks.on) b->tracks.first_stale = true;                     // who was chosen is known on the device only
-    return batch_restart_noise(b, nullptr, d_mask, b->B);
+    const int rc = batch_restart_noise(b, nullptr, d_mask, b->B);
+    return rc ? rc : batch_plan_routes(b, nullptr, d_mask, b->B);       // (routes: from where the rows were placed)
 }
 
 // sfm_batch_run_recorded, and with want_forces also the [F][K][N_total][C] force record of every recorded tick
@@ -1007,7 +1009,8 @@ int sfm_batch_restart(SfmBatch* b, const uint8_t* mask) {
             for (int v = b->boxes.item_off_h[k]; v < b->boxes.item_off_h[k + 1]; ++v)
                 b->tracks.first_h[v] = b->tracks.off_h[v + 1] > b->tracks.off_h[v] ? (int32_t)((long long)b->snap.first_h[v] + shift) : b->snap.first_h[v];
         }
-    return batch_restart_noise(b, r.list, nullptr, chosen);
+    rc = batch_restart_noise(b, r.list, nullptr, chosen);
+    return rc ? rc : batch_plan_routes(b, r.list, nullptr, chosen);     // (routes: from where the rows were placed)
 }
 
 // The restart with its mask on the device (ABI 16): no copy, no host scan, no event wait, no pinned list.

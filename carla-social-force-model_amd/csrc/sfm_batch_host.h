@@ -2,7 +2,8 @@
 // features), its error plumbing, and the messages for a feature that is off.  sfm_batch_capi.hip holds the ticks and everything they
 // read or write; sfm_batch_sense_capi.hip the read-only sensors (observations, episode ends, range scans, occupancy grids) and the device pointers;
 // sfm_batch_reset_capi.hip the restart noise; sfm_batch_replay_capi.hip the observed tracks; sfm_batch_drive_capi.hip the driven
-// vehicles and the vehicle observations (the vehicles' range scans are a sensor: sfm_batch_sense_capi.hip).
+// vehicles and the vehicle observations (the vehicles' range scans are a sensor: sfm_batch_sense_capi.hip); sfm_batch_route_capi.hip
+// the routes over walk graphs.
 #pragma once
 #include "sfm_capi_common.h"
 #include "sfm_metres.h"
@@ -212,6 +213,23 @@ struct BatchVehScanDev {
     DevBuf<float> buf;         // [M][2 R]
 };
 
+// routes (sfm_batch_set_routes): the scenes' walk graphs, each row's graph type and goal, and what the plan kernel leaves per row;
+// the ticks read and write none of it (they see the waypoints, modes and queues the plan kernel wrote).  Dropped with the modes.
+struct BatchRoutesDev {
+    bool on = false;
+    int capacity = 0;
+    DevBuf<int> node_off;      // [B+1]
+    DevBuf<float2> node_xy;    // [V_total]
+    DevBuf<int> adj_off;       // [V_total+1]
+    DevBuf<uint2> adj;         // [A] {neighbour | type << 16, bits of the weight}
+    DevBuf<uint8_t> gtype;     // [N_total]
+    DevBuf<float2> goal;       // [N_total]
+    DevBuf<int> status;        // [N_total]
+    DevBuf<int4> info;         // [N_total] {s, t, L, bits of D[s]}
+    std::vector<int32_t> wp_off_h;     // the queue CSR [N_total+1] as sfm_batch_set_routes rebuilt it
+    int v_cap = 64, a_cap = 0;         // the plan kernel's LDS: nodes (a multiple of 64) and staged adjacency entries (RouteArgs)
+};
+
 struct BatchRecordDev {        // grow-only device buffers of the recording calls
     DevBuf<float4> frames;     // sfm_batch_run_recorded
     DevBuf<float2> zframes;
@@ -255,7 +273,8 @@ struct SfmBatch {
     sfm::BatchDriveDev drive;
     sfm::BatchVehObsDev vobs;
     sfm::BatchVehScanDev vscan;
-    sfm::Event v_done;                      // created by the first sfm_batch_set_vehicle_driving with vehicles; outlives every drop of the driving
+    sfm::BatchRoutesDev routes;
+    sfm::Event v_done;                     // created by the first sfm_batch_set_vehicle_driving with vehicles; outlives every drop of the driving
     std::vector<int32_t> scene_off_h;      // the scene offsets [B+1] of the last sfm_batch_upload_state, on the host
     std::vector<float> dt_h;                // [B] the scenes' step lengths (sfm_batch_create, sfm_batch_set_params)
     sfm::Event c_done;                      // created by the first sfm_batch_set_steering with rows; outlives every drop of the steering
@@ -294,6 +313,7 @@ constexpr const char* VEHICLE_OBS_OFF = "vehicle observations are off: call sfm_
 constexpr const char* VEHICLE_SCAN_OFF = "vehicle scans are off: call sfm_batch_set_vehicle_scan first (sfm_batch_upload_state, "
                                          "sfm_batch_set_dynamic_boxes and sfm_batch_set_dynamic_obstacles drop them)";
 constexpr const char* NO_BOXES = "this needs device-side vehicles: call sfm_batch_set_dynamic_boxes first";
+constexpr const char* ROUTES_OFF = "routes are off: call sfm_batch_set_routes first (sfm_batch_upload_state and sfm_batch_set_mode_fsm drop them)";
 constexpr const char* GRIDS_OFF ="grids are off: call sfm_batch_set_grid first (sfm_batch_upload_state drops them)";
 
 // one kind of the scenes' geometry as the kernels take it, and what the sensors see of the scenes
@@ -310,6 +330,11 @@ int batch_restart_device(SfmBatch* b, const uint8_t* d_mask, long long shift);
 // The noise launch of a restart (sfm_batch_reset_capi.hip), right behind launch_batch_restart on the batch's stream with the same
 // choice of scenes; nothing while the noise is off.  With delays set it marks the host's copy of the tracks' first ticks stale.
 int batch_restart_noise(SfmBatch* b, const int* d_list, const uint8_t* d_mask, int scenes);
+// The route launch of a restart (sfm_batch_route_capi.hip), behind batch_restart_noise with the same choice of scenes; nothing
+// while routes are off.
+int batch_plan_routes(SfmBatch* b, const int* d_list, const uint8_t* d_mask, int scenes);
+hipError_t launch_batch_plan_routes(const RouteArgs& a, int scenes, hipStream_t st);
+size_t route_lds_bytes(int v_cap, int a_cap);
 // What sfm_batch_run_observed shares with sfm_batch_run (sfm_batch_capi.hip, where both are described): the check of a tick's
 // flags, and the launch of one tick of the whole batch.
 int check_batch_flags(SfmBatch* b, uint32_t flags, const char* what);

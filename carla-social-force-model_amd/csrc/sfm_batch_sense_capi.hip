@@ -20,7 +20,7 @@ static int check_frame(SfmBatch* b, int frame) {
 
 // One lookup for the device buffers a caller may see: which = SFM_BATCH_PTR_*, or PTR_OBSERVATIONS for sfm_batch_observation_ptr's.
 // off: why there is none (its feature is off, no state was uploaded), else p and bytes -- both 0 where the buffer has no element.
-constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_VEHICLE_SCAN + 1;    // (not part of the ABI: sfm_batch_device_ptr refuses it)
+constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_ROUTE_STATUS + 1;    // (not part of the ABI: sfm_batch_device_ptr refuses it)
 struct BatchBuffer { const char* off; void* p; size_t bytes; };
 static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     const size_t n = (size_t)b->n_total, B = (size_t)b->B;
@@ -55,6 +55,10 @@ static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     case SFM_BATCH_PTR_VEHICLE_SCAN:
         if (!b->vscan.on) return {VEHICLE_SCAN_OFF, nullptr, 0};
         return have(b->vscan.buf, sizeof(float) * (size_t)b->geo[2].K * (size_t)(2 * b->vscan.R));
+    case SFM_BATCH_PTR_ROUTE_GOALS:
+    case SFM_BATCH_PTR_ROUTE_STATUS:
+        if (!b->routes.on) return {ROUTES_OFF, nullptr, 0};
+        return which == SFM_BATCH_PTR_ROUTE_GOALS ? have(b->routes.goal, sizeof(float2) * n) : have(b->routes.status, sizeof(int) * n);
     }
     if (!b->have_state) return {NO_STATE, nullptr, 0};
     if (which == SFM_BATCH_PTR_COMMANDS) {
@@ -99,7 +103,8 @@ void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes) {
                        (which == SFM_BATCH_PTR_GRID && b->grid.on) ||
                        ((which == SFM_BATCH_PTR_ROW_SCORES || which == SFM_BATCH_PTR_SCENE_SCORES) && b->replay.on) ||
                        (which == SFM_BATCH_PTR_VEHICLE_COMMANDS && b->drive.on) || (which == SFM_BATCH_PTR_VEHICLE_OBS && b->vobs.on) ||
-                       which == SFM_BATCH_PTR_VEHICLE_SCAN;
+                       which == SFM_BATCH_PTR_VEHICLE_SCAN ||
+                       ((which == SFM_BATCH_PTR_ROUTE_GOALS || which == SFM_BATCH_PTR_ROUTE_STATUS) && b->routes.on);
     if (!known) { bfail(b, SFM_ERR_INVALID, "which must be SFM_BATCH_PTR_COMMANDS, _STATE, _ZSTATE, _EPISODES, _DONE or _SCAN"); return nullptr; }
     return buffer_ptr(b, which, which == SFM_BATCH_PTR_SCAN ? ", so which = SFM_BATCH_PTR_SCAN has no buffer" :
                                 which == SFM_BATCH_PTR_EPISODES || which == SFM_BATCH_PTR_DONE ? ", so which = SFM_BATCH_PTR_EPISODES / _DONE has no buffer" : "", bytes);
