@@ -45,7 +45,9 @@ SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_
                             "sfm_batch_set_vehicle_scan", "sfm_batch_scan_vehicles",
                             "sfm_batch_download_vehicle_scan",
                             "sfm_batch_set_routes", "sfm_batch_plan_routes", "sfm_batch_plan_routes_device",
-                            "sfm_batch_download_routes")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
+                            "sfm_batch_download_routes",
+                            "sfm_batch_set_vehicle_autopilot", "sfm_batch_download_vehicle_autopilot",
+                            "sfm_batch_vehicle_autopilot_launches")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
 UNBUMPED = ("sfm_batch_set_restart_noise", "sfm_batch_download_restart_noise",
             "sfm_batch_set_grid", "sfm_batch_grid", "sfm_batch_download_grid",
             "sfm_batch_set_observed", "sfm_batch_run_observed", "sfm_batch_score",
@@ -55,7 +57,9 @@ UNBUMPED = ("sfm_batch_set_restart_noise", "sfm_batch_download_restart_noise",
             "sfm_batch_download_vehicle_observations",
             "sfm_batch_set_vehicle_scan", "sfm_batch_scan_vehicles", "sfm_batch_download_vehicle_scan",
             "sfm_batch_set_routes", "sfm_batch_plan_routes", "sfm_batch_plan_routes_device",
-            "sfm_batch_download_routes")   # ... and those a build of the SAME number may lack
+            "sfm_batch_download_routes",
+            "sfm_batch_set_vehicle_autopilot", "sfm_batch_download_vehicle_autopilot",
+            "sfm_batch_vehicle_autopilot_launches")   # ... and those a build of the SAME number may lack
 
 FORCE_NAMES = ("acceleration_force", "pedestrian_force", "border_force",
                "static_obstacle_force", "dynamic_obstacle_force")
@@ -203,6 +207,10 @@ SYMBOLS = {
     "sfm_batch_set_vehicle_observation": (C.c_int, [_H, C.c_int, _F, C.c_int, _F, _F, _U8]),
     "sfm_batch_observe_vehicles": (C.c_int, [_H]),
     "sfm_batch_download_vehicle_observations": (C.c_int, [_H, _F]),
+    # batch vehicle autopilot (ABI 17, added without a bump)
+    "sfm_batch_set_vehicle_autopilot": (C.c_int, [_H, _I, _F, _F, _F, _U8]),
+    "sfm_batch_download_vehicle_autopilot": (C.c_int, [_H, _I, _F]),
+    "sfm_batch_vehicle_autopilot_launches": (C.c_int, [_H, C.POINTER(C.c_longlong)]),
     # batch range scans from the vehicles (ABI 17, added without a bump)
     "sfm_batch_set_vehicle_scan": (C.c_int, [_H, C.c_int, _F, _F, _F, _F, _F, _U8, C.c_int, C.c_float, C.c_float]),
     "sfm_batch_scan_vehicles": (C.c_int, [_H]),

@@ -179,6 +179,10 @@ int sfm::batch_launch(SfmBatch* b, uint32_t flags, float4* frame, float2* zframe
     const bool steer = b->steer.on && b->n_total > 0;            // (no rows: no command buffer, and nobody to steer)
     if (steer) a.cmd = b->steer.cmd;
     const bool ext = (flags & SFM_TICK_REDRAW_WAYPOINTS) || frame || force_rec;
+    if (move && b->drive.ap.on) {                                // the autopilot writes this tick's commands from what this tick reads
+        const int rc = batch_autopilot_launch(b);
+        if (rc) return rc;
+    }
     HIP_TRY(b, launch_batch_tick(b->z3, ext, b->modes.on, b->modes.on && b->spawns.on, steer, a, b->B, b->stream));
     if (move) {                                          // the moved half is what the next tick sees
         swap(b->geo[2].ctr, b->boxes.ctr_alt);
@@ -276,8 +280,9 @@ int sfm::batch_restart_device(SfmBatch* b, const uint8_t* d_mask, long long shif
     r.mask = d_mask;
     HIP_TRY(b, launch_batch_restart(r, b->B, b->stream));
     if (b->tracks.on) b->tracks.first_stale = true;                     // who was chosen is known on the device only
-    const int rc = batch_restart_noise(b, nullptr, d_mask, b->B);
-    return rc ? rc : batch_plan_routes(b, nullptr, d_mask, b->B);       // (routes: from where the rows were placed)
+    int rc = batch_restart_noise(b, nullptr, d_mask, b->B);
+    if (!rc) rc = batch_plan_routes(b, nullptr, d_mask, b->B);          // (routes: from where the rows were placed)
+    return rc ? rc : batch_autopilot_restart(b, nullptr, d_mask, b->B); // (the autopilot's cursors)
 }
 
 // sfm_batch_run_recorded, and with want_forces also the [F][K][N_total][C] force record of every recorded tick
@@ -960,6 +965,7 @@ int sfm_batch_snapshot(SfmBatch* b) {
         b->snap.first_h = b->tracks.first_h;
         b->snap.tick = b->tracks.tick;
     }
+    if ((rc = batch_autopilot_snapshot(b))) return rc;              // the autopilot's cursors
     b->snap.on = true;
     return SFM_OK;
 }
@@ -1010,7 +1016,8 @@ int sfm_batch_restart(SfmBatch* b, const uint8_t* mask) {
                 b->tracks.first_h[v] = b->tracks.off_h[v + 1] > b->tracks.off_h[v] ? (int32_t)((long long)b->snap.first_h[v] + shift) : b->snap.first_h[v];
         }
     rc = batch_restart_noise(b, r.list, nullptr, chosen);
-    return rc ? rc : batch_plan_routes(b, r.list, nullptr, chosen);     // (routes: from where the rows were placed)
+    if (!rc) rc = batch_plan_routes(b, r.list, nullptr, chosen);        // (routes: from where the rows were placed)
+    return rc ? rc : batch_autopilot_restart(b, r.list, nullptr, chosen);   // (the autopilot's cursors)
 }
 
 // The restart with its mask on the device (ABI 16): no copy, no host scan, no event wait, no pinned list.

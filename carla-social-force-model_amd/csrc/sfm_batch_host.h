@@ -181,11 +181,26 @@ struct BatchReplayDev {
 // driven vehicles (sfm_batch_set_vehicle_driving): the command of every vehicle {a, b, c, kind}, an input the ticks only read, and
 // its pinned host copy, kept and sent as the steering's (sfm_batch_set_vehicle_commands; SfmBatch::v_done is recorded behind the
 // copy).  The headings the driven ticks turn are BatchBoxesDev::rot.  Dropped with the boxes they refer to.
+// The autopilot (sfm_batch_set_vehicle_autopilot) is a part of the driving: a controller on the device that writes the commands of
+// the autopiloted vehicles in front of every integrating tick.  Its lifetime is the driving's -- whatever drops the driving drops it,
+// and so does every sfm_batch_set_vehicle_driving -- which is why it lives inside BatchDriveDev.  The cursors are state: the
+// snapshot holds them in s_cursor (valid while SfmBatch::snap is; setting the autopilot drops the snapshot).
+struct BatchAutopilotDev {
+    bool on = false;
+    DevBuf<int> path_off;      // [M+1]
+    DevBuf<float2> path;       // [P]
+    DevBuf<AutopilotVehicle> set;   // [M]
+    DevBuf<int> cursor;        // [M]
+    DevBuf<int> s_cursor;      // [M] the snapshot's copy
+    DevBuf<float> record;      // [M][8]
+    long long launches = 0;    // controller launches since the autopilot was set (sfm_batch_vehicle_autopilot_launches)
+};
 struct BatchDriveDev {
     bool on = false;           // (not "cmd is allocated": a batch without vehicles can be driven and has no buffers)
     DevBuf<float4> cmd;        // [M] on the device
     PinnedBuf<float4> cmd_h;
     bool pending = false;
+    BatchAutopilotDev ap;
 };
 
 // vehicle observations (sfm_batch_set_vehicle_observation): the settings and the buffer sfm_batch_observe_vehicles fills; nothing a
@@ -345,6 +360,18 @@ int batch_launch(SfmBatch* b, uint32_t flags, float4* frame = nullptr, float2* z
 int batch_replay_step_lengths(SfmBatch* b, const float* dt);
 // The vehicle scan's one launch (sfm_batch_vehicle_scan.hip).
 hipError_t launch_batch_vehicle_scan(const VehicleScanArgs& a, int B, hipStream_t st);
+// The autopilot (sfm_batch_autopilot_capi.hip, sfm_batch_autopilot.hip).  batch_autopilot_launch: the controller launch batch_launch
+// puts in front of an integrating tick while the autopilot is on.  batch_autopilot_snapshot: the cursors into the snapshot, with
+// the other arrays of sfm_batch_snapshot.  batch_autopilot_restart: the cursors of the chosen scenes back, one small launch behind
+// the restart's own (and the noise and the routes) with the same choice of scenes; nothing while the autopilot is off.
+int batch_autopilot_launch(SfmBatch* b);
+int batch_autopilot_snapshot(SfmBatch* b);
+int batch_autopilot_restart(SfmBatch* b, const int* d_list, const uint8_t* d_mask, int scenes);
+hipError_t launch_batch_vehicle_autopilot(const AutopilotArgs& a, int B, hipStream_t st);
+hipError_t launch_batch_autopilot_restart(const int* list, const uint8_t* mask, const int* item_off, int* cursor, const int* s_cursor,
+                                          int scenes, hipStream_t st);
+constexpr const char* AUTOPILOT_OFF = "the vehicle autopilot is off: call sfm_batch_set_vehicle_autopilot first (sfm_batch_set_vehicle_driving, "
+                                      "sfm_batch_set_dynamic_boxes and sfm_batch_set_dynamic_obstacles drop it)";
 // The delays go with the tracks they refer to (the caller synchronised the stream).
 inline void drop_noise_delays(SfmBatch* b) { b->noise.delay = {}; b->noise.max_delay = 0; }
 

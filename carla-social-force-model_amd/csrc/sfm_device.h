@@ -472,6 +472,33 @@ struct VehicleScanArgs : BatchSceneView {
 static_assert(sizeof(VehicleScanArgs) == 120 + 56, "the vehicle scan kernel's arguments follow the view without padding");
 static_assert(VEHICLE_SCAN_MAX_RAYS <= BLOCK, "the direction table is staged by one pass of the workgroup");
 
+// The vehicle autopilot of a batch (sfm_batch_set_vehicle_autopilot, sfm_batch_vehicle_autopilot_kernel in sfm_batch_autopilot.hip):
+// launched in front of every integrating tick; it reads what that tick will read and writes the commands of the autopiloted vehicles,
+// their cursors and their records.  The rule is specified in include/sfm_hip.h.
+constexpr uint32_t AUTOPILOT_LOOP = 1u, AUTOPILOT_IGNORE_WALKERS = 2u;
+constexpr int AUTOPILOT_INDEX_BITS = 28;               // the leader's key is kind << 28 | index (checked on the host to fit)
+struct AutopilotVehicle {     // one vehicle's settings, validated on the host
+    float v0, T, s0, acc, dec, brake;
+    float half_width, front, look;
+    float reach2;             // reach^2, formed in double and rounded once
+    float ped_margin;
+    float cos_max, sin_max;   // the turn limit per tick
+    uint32_t flags;           // AUTOPILOT_*
+    float pad[2];
+};
+static_assert(sizeof(AutopilotVehicle) == 64, "one vehicle's settings are four 16-byte loads");
+struct AutopilotArgs : BatchSceneView {
+    const BatchParams* prm;   // [B] the scenes' step lengths
+    const float2* rot;        // [M] the vehicles' headings {cos, sin}, as the next tick reads them
+    const int* path_off;      // [M+1] CSR of the paths; an empty path: the vehicle is not autopiloted
+    const float2* path;       // [P]
+    const AutopilotVehicle* set;  // [M]
+    int* cursor;              // [M] the waypoint each vehicle steers for: the only state
+    float4* cmd;              // [M] the vehicle commands (BatchArgs::veh_cmd); only autopiloted vehicles' entries are written
+    float* record;            // [M][8]
+};
+static_assert(sizeof(AutopilotArgs) == 120 + 64, "the autopilot kernel's arguments follow the view without padding");
+
 // Restart noise of a batch (sfm_batch_set_restart_noise, sfm_batch_restart_noise_kernel in sfm_batch_reset.hip): launched behind
 // sfm_batch_restart_kernel with the same choice of scenes (list / mask as in BatchRestart); the rule is specified in include/sfm_hip.h.
 constexpr int RESET_MAX_TRIES = 32;

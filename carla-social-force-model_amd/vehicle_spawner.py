@@ -22,6 +22,7 @@ of speeds while they still have transforms).  The mirror gives each vehicle its 
 
 Only the scripted keys are taken.  ``auto_pilot`` (traffic manager or BehaviorAgent), ``spawn_point`` (a map's recommended spawn
 points) and ``destination`` need the simulator and its map: they are refused.  Pure NumPy; nothing here touches the GPU.
+(Traffic that drives itself on a batch -- a path, a gap to the car in front, braking for walkers -- is ``SfmBatch.set_vehicle_autopilot``.)
 """
 from __future__ import annotations
 

@@ -993,6 +993,82 @@ int sfm_batch_set_vehicle_driving(SfmBatch* b, const uint8_t* kind, const float*
 int sfm_batch_set_vehicle_commands(SfmBatch* b, const float* a, const float* b_, const float* c);
 int sfm_batch_download_vehicle_driving(SfmBatch* b, uint8_t* kind, float* a, float* b_, float* c, float* hx, float* hy, float* vx,
                                        float* vy);
+/* The vehicle autopilot: traffic that yields.  A controller on the device writes the unicycle command (kind 2 above) of every
+ * autopiloted vehicle by ONE launch of sfm_batch_vehicle_autopilot_kernel (a workgroup per scene, a wave per vehicle, lanes striding
+ * over pedestrians and ring points; the leader a lexicographic minimum by shuffles; no atomics) in front of every tick that has
+ * SFM_TICK_INTEGRATE -- in sfm_batch_tick, sfm_batch_run, sfm_batch_run_recorded, sfm_batch_run_recorded_forces and
+ * sfm_batch_run_observed alike.  A tick without the flag launches no controller, and a batch that never sets the autopilot launches
+ * exactly what it launched before.  Each autopiloted vehicle follows a path of waypoints under a bounded turn per tick and sets its
+ * speed by the Intelligent Driver Model (IDM; Treiber, Hennecke and Helbing 2000) against the nearest thing in its corridor: a
+ * pedestrian, a ring point of another vehicle, or the end of its path.  This is what the reference's default traffic does
+ * (vehicle_spawner.py spawns with auto_pilot = True; ignore_walkers_percentage is the flag below).  These entry points were added
+ * WITHOUT a bump of SFM_ABI_VERSION (it stays 17), like the driven vehicles: additions only, recognised by the symbols.
+ *
+ * Settings per vehicle, [M][SFM_BATCH_AUTOPILOT_SETTINGS] floats in this order, all finite: v0 > 0 (desired speed), T >= 0 (time
+ * headway), s0 > 0 (standstill gap), acc > 0, dec > 0 (comfortable deceleration), brake >= dec (hard limit), half_width >= 0 (of the
+ * corridor), front >= 0 (centre to bumper), look > 0 (how far ahead of the bumper a leader counts), reach > 0 (used as reach2 =
+ * float32(double(reach) * reach)), ped_margin >= 0, and the turn limit per tick cos_max, sin_max with 0 < cos_max <= 1, sin_max >= 0.
+ * flags [M] uint8: SFM_AUTOPILOT_LOOP (the path is closed), SFM_AUTOPILOT_IGNORE_WALKERS.
+ * Path and cursor.  path_off [M+1] is the CSR of the paths into px, py; P_k = path_off[k+1] - path_off[k] >= 1 points, and P_k = 0
+ * means vehicle k is not autopiloted.  The cursor c_k, the waypoint the vehicle steers for, is the only new state; it starts at 0.
+ *
+ * The rule (one controller launch; the one definition).  Every line is one correctly rounded fp32 operation or an fmaf, sqrtf and /
+ * are the correctly rounded forms, nothing is contracted; max(x, y) stands for x > y ? x : y (so max(-0, 0) = +0 and a NaN x gives
+ * y).  The launch reads what the tick behind it reads: centre (cx, cy) and velocity (vx, vy) from the current half of the vehicles,
+ * the stored heading h, the pedestrians' rows; dt is the scene's step_length.  d2 of a point q: dx = q.x - cx, dy = q.y - cy,
+ * fmaf(dx, dx, dy * dy).  For vehicle k with P_k >= 1:
+ *   1. Absent.  If not (|cx| < 1e12 and |cy| < 1e12) the command becomes {0, 1, 0, 2}, the cursor is left alone and the record is
+ *      zeros; the tick keeps the vehicle absent as stated above for driven vehicles.
+ *   2. Cursor.  At most P_k times: while d2(path[c]) < reach2 (strict), on a SFM_AUTOPILOT_LOOP path c = c + 1, wrapping to 0; on
+ *      an open path c = c + 1 while c < P_k - 1, and if the test holds at c = P_k - 1 the vehicle is FINISHED: the cursor stays, the
+ *      command is {0, 1, 0, 2} and the record {c, 0, 0, 0, 0, 0, 0, 1}, in every launch from then on (it stands inside reach).
+ *   3. Turn.  t = path[c] - centre, n2 = fmaf(tx, tx, ty * ty) (the d2 above); g = (tx / n, ty / n) with n = sqrtf(n2) when n2 > 0,
+ *      else g = h.  cosphi = fmaf(gx, hx, gy * hy), sinphi = fmaf(gy, hx, -(gx * hy)).  If cosphi < cos_max the turn becomes
+ *      (cos_max, sinphi < 0 ? -sin_max : sin_max): a target exactly behind turns left.  The kernel does no trigonometry.
+ *   4. Leader.  For a candidate point q: rx = q.x - cx, ry = q.y - cy, al = fmaf(rx, hx, ry * hy), ac = fmaf(rx, hy, -(ry * hx)).
+ *      Pedestrian (kind 1; none under SFM_AUTOPILOT_IGNORE_WALKERS): every row j of the scene with |x| < 1e12 and |y| < 1e12 (the
+ *      live test of the observations) is a candidate iff al > 0, |ac| < (half_width + ped_margin) and al < (front + look), with
+ *      gap = (al - front) - ped_margin, u = fmaf(vx_j, hx, vy_j * hy) and index j (the row inside the scene).
+ *      Vehicle (kind 2): every ring point of every OTHER vehicle v of the scene whose centre passes the live test, with
+ *      |ac| < half_width in place of the second test, gap = al - front, u = fmaf(vx_v, hx, vy_v * hy) and index v (the vehicle
+ *      inside the scene).  End of path (kind 3): on an open path with c = P_k - 1, gap = sqrtf(n2), u = 0, index 0, no corridor test.
+ *      The leader is the minimum of (gap, kind, index) in lexicographic order; a NaN gap is no candidate.
+ *   5. Speed.  s = max(fmaf(vx, hx, vy * hy), 0); q = s / v0; q2 = q * q; r4 = q2 * q2.  With a leader: g = max(gap,
+ *      SFM_AUTOPILOT_GAP_FLOOR); dv = s - u; k2 = 2 * sqrtf(acc * dec); dyn = fmaf(s, T, (s * dv) / k2); sstar = s0 + max(dyn, 0);
+ *      ratio = sstar / g; inter = ratio * ratio.  With no leader inter = 0.  araw = acc * ((1 - r4) - inter); a = max(araw, -brake);
+ *      s' = max(fmaf(dt, a, s), 0).
+ *   6. Output.  The vehicle's command becomes {s', cosphi, sinphi, 2}, its cursor c, and its record [8] {c, leader kind (0: none),
+ *      leader index, gap, u, a, s', 0} (index, gap and u are 0 with no leader; the last entry is 1 for a finished vehicle).
+ * Commands, cursors and records of vehicles that are not autopiloted are not touched: a caller's policy keeps writing the commands
+ * of its own vehicles.  An autopiloted vehicle's command is rewritten by every controller launch, whatever the caller put there.
+ * Determinism: a vehicle's command, cursor and record are bitwise the same alone or anywhere in any batch.
+ *
+ * sfm_batch_set_vehicle_autopilot: needs device-side vehicles.  If driving is off it is switched on with every command of kind 0;
+ * if it is on, its commands stay.  Either way the command of every autopiloted vehicle becomes {0, 1, 0, 2} at once (what the
+ * controller writes for a vehicle that stands), so it counts as driven from the call on, not from the first controller launch.
+ * Allocates cursors and records, zero-fills them and waits for the stream.  It drops the snapshot
+ * (which does not hold the new cursors).  path_off = NULL switches the autopilot off and frees them; driving stays as it is.
+ * Refused with nothing changed: no state, or no device-side vehicles (SFM_ERR_STATE); path_off[0] != 0 or decreasing; more than
+ * SFM_BATCH_MAX_AUTOPILOT_POINTS points on one path; a point or a setting that is not finite; a bound above violated; flags above 3;
+ * a NULL array that is needed.
+ * The cursor is state: sfm_batch_snapshot holds it, and sfm_batch_restart, sfm_batch_restart_device and the auto restart put back the
+ * chosen scenes' cursors by one small launch behind the restart's own (other scenes are left bit for bit).  Restart noise leaves an
+ * autopiloted vehicle at its snapshot pose, as any vehicle whose command has kind 2.
+ * Lifetime: the autopilot goes wherever driving goes (sfm_batch_set_dynamic_boxes, sfm_batch_set_dynamic_obstacles), and EVERY
+ * sfm_batch_set_vehicle_driving drops it, because the kinds may differ: set driving first and the autopilot second.  A refused call
+ * drops nothing.
+ * sfm_batch_download_vehicle_autopilot: synchronises the stream; cursor [M] int32 and record [M][8] as the last controller launch
+ * left them (NULL skips one).  SFM_ERR_STATE while the autopilot is off.
+ * sfm_batch_vehicle_autopilot_launches: controller launches since the autopilot was set; 0 while it is off. */
+#define SFM_BATCH_AUTOPILOT_SETTINGS 13
+#define SFM_BATCH_MAX_AUTOPILOT_POINTS 4096
+#define SFM_AUTOPILOT_GAP_FLOOR 0.01f
+#define SFM_AUTOPILOT_LOOP 1
+#define SFM_AUTOPILOT_IGNORE_WALKERS 2
+int sfm_batch_set_vehicle_autopilot(SfmBatch* b, const int32_t* path_off, const float* px, const float* py, const float* settings,
+                                    const uint8_t* flags);
+int sfm_batch_download_vehicle_autopilot(SfmBatch* b, int32_t* cursor, float* record);
+int sfm_batch_vehicle_autopilot_launches(SfmBatch* b, long long* launches);
 /* Vehicle observations: what a driving policy and its reward read per vehicle, by ONE launch of sfm_batch_vehicle_observe_kernel (a
  * workgroup per scene, a wave per vehicle, lanes striding over pedestrians and points; every reduction a lexicographic (d2, index)
  * minimum by shuffles; no atomics) over the buffers the next tick would read.  It writes only its own buffer.
