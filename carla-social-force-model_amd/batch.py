@@ -872,6 +872,16 @@ def observation_arrays(B, k, sense_range, frame=0):
     return int(k), per_scene_metres(sense_range, "sense_range", int(B), True), frame
 
 
+def _scan_rays(R, angles, directions, limit, name):
+    """A scan's rays, given as exactly one of ``R``, ``angles`` and ``directions`` (at most ``limit`` of them) -> (dir_x, dir_y)
+    float32.  ``name``: the caller's, for the message."""
+    if sum(v is not None for v in (R, angles, directions)) != 1:
+        raise ValueError(f"{name} takes exactly one of R, angles and directions")
+    if directions is not None:
+        return _scan.check_directions(directions, limit)
+    return _scan.ray_directions(_scan.default_angles(R, limit) if angles is None else angles, limit)
+
+
 def _split_rows(scene_off, *cols):
     """Arrays over the concatenated rows -> per scene, in scene order, its rows of each (views): a list of B arrays for one array,
     of B tuples for several."""
@@ -1567,13 +1577,7 @@ class SfmBatch:
         self._need_upload("set_vehicle_scan")
         if ped_radius is None:
             raise ValueError("set_vehicle_scan needs a ped_radius (metres; 0: pedestrians are not seen)")
-        if sum(v is not None for v in (R, angles, directions)) != 1:
-            raise ValueError("set_vehicle_scan takes exactly one of R, angles and directions")
-        lim = _scan.MAX_VEHICLE_SCAN_RAYS
-        if directions is not None:
-            dx, dy = _scan.check_directions(directions, lim)
-        else:
-            dx, dy = _scan.ray_directions(_scan.default_angles(R, lim) if angles is None else angles, lim)
+        dx, dy = _scan_rays(R, angles, directions, _scan.MAX_VEHICLE_SCAN_RAYS, "set_vehicle_scan")
         rm, rp, rq, mk, frame, mx, my = vehicle_scan_arrays(self._vehicle_off("set_vehicle_scan"), max_range, ped_radius, point_radius,
                                                             frame, mask, mount)
         self._check(L.sfm_batch_set_vehicle_scan(self._b, int(dx.shape[0]), fptr(dx), fptr(dy), fptr(rm), fptr(rp), fptr(rq), u8ptr(mk),
@@ -1621,12 +1625,7 @@ class SfmBatch:
         self._need_upload("set_scan")
         if ped_radius is None:
             raise ValueError("set_scan needs a ped_radius (metres; 0: pedestrians are not seen)")
-        if sum(v is not None for v in (R, angles, directions)) != 1:
-            raise ValueError("set_scan takes exactly one of R, angles and directions")
-        if directions is not None:
-            dx, dy = _scan.check_directions(directions)
-        else:
-            dx, dy = _scan.ray_directions(_scan.default_angles(R) if angles is None else angles)
+        dx, dy = _scan_rays(R, angles, directions, _scan.MAX_SCAN_RAYS, "set_scan")
         rm, rp, rq, frame = _scan.scan_arrays(self.B, max_range, ped_radius, point_radius, frame)
         m = _scan.scan_mask(mask, self.scene_off)
         if m is not None and m.shape[0] == 0:

@@ -79,36 +79,15 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_grid_kernel(const GridArgs a)
     for (int base = 0; base < n; base += BLOCK) {                      // uniform
         const int t = base + tid;
         const bool want = t < n && (!a.slot || a.slot[s0 + t] >= 0);
-        const unsigned long long m = __ballot(want);
-        if (lane == 0) sh.wcount[wave] = __popcll(m);
-        __syncthreads();
-        int before = n_grid, all = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES_PER_BLOCK; ++w) {
-            const int cw = sh.wcount[w];
-            before += w < wave ? cw : 0;
-            all += cw;
-        }
-        if (want) sh.rows[before + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)t;
-        n_grid += all;
-        __syncthreads();                                               // the list; and wcount is rewritten by the next pass
+        n_grid += block_compact(want, sh.wcount, lane, wave, n_grid, [&](int p) { sh.rows[p] = (unsigned short)t; });
     }
     if (n_grid == 0) return;                                           // uniform
 
-    // the scene's points per kind: one contiguous run of the kind's CSR (an empty kind's arrays are not read)
-    const int bk0 = a.geo[0].item_off[b], bk1 = a.geo[0].item_off[b + 1];
-    const int sk0 = a.geo[1].item_off[b], sk1 = a.geo[1].item_off[b + 1];
-    const int vk0 = a.geo[2].item_off[b], vk1 = a.geo[2].item_off[b + 1];
-    const int bp0 = bk1 > bk0 ? a.geo[0].off[bk0] : 0, nb = bk1 > bk0 ? a.geo[0].off[bk1] - bp0 : 0;
-    const int sp0 = sk1 > sk0 ? a.geo[1].off[sk0] : 0, ns = sk1 > sk0 ? a.geo[1].off[sk1] - sp0 : 0;
-    const int vp0 = vk1 > vk0 ? a.geo[2].off[vk0] : 0, nv = vk1 > vk0 ? a.geo[2].off[vk1] - vp0 : 0;
-    const int P = nb + ns + nv;                                        // virtual index e: borders, static, vehicles
+    const SceneRun run(a.geo, b);
+    const int nb = run.nb, ns = run.ns, P = run.total();               // virtual index e: borders, static, vehicles
     const bool one_tile = P <= GRID_TILE;
-    auto point = [&](int e) {
-        return e < nb ? a.geo[0].pts[bp0 + e] : e < nb + ns ? a.geo[1].pts[sp0 + (e - nb)] : a.geo[2].pts[vp0 + (e - nb - ns)];
-    };
     if (one_tile && P > 0) {                                           // the whole scene's geometry fits: staged once
-        for (int e = tid; e < P; e += BLOCK) sh.tile[e] = point(e);
+        for (int e = tid; e < P; e += BLOCK) sh.tile[e] = run.point(e);
         __syncthreads();
     }
 
@@ -129,10 +108,9 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_grid_kernel(const GridArgs a)
         float hx = 1.0f, hy = 0.0f;
         if (rot) {                                                     // the scan kernel's heading, fp32 throughout
             const float4 o = a.own[s0 + row];
-            const float gx = o.x - x, gy = o.y - y;
-            const float vv = fmaf(vx, vx, vy * vy), gg = fmaf(gx, gx, gy * gy);
-            if (vv > 0.0f) { const float l = sqrtf(vv); hx = vx / l; hy = vy / l; }
-            else if (gg > 0.0f) { const float l = sqrtf(gg); hx = gx / l; hy = gy / l; }
+            const float2 h = row_heading(vx, vy, o.x - x, o.y - y);
+            hx = h.x;
+            hy = h.y;
         }
 
         // (a) the pedestrians inside the grid, ascending, with their cells and relative velocities
@@ -151,28 +129,15 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_grid_kernel(const GridArgs a)
                     grid_rotate(rot, hx, hy, rx, ry);
                 }
             }
-            const bool in = cell >= 0;
-            const unsigned long long m = __ballot(in);
-            if (lane == 0) sh.wcount[wave] = __popcll(m);
-            __syncthreads();                                           // (also: everyone is done with the list of the row before)
-            int before = n_src, all = 0;
-#pragma unroll
-            for (int w = 0; w < WAVES_PER_BLOCK; ++w) {
-                const int cw = sh.wcount[w];
-                before += w < wave ? cw : 0;
-                all += cw;
-            }
-            if (in) {
-                const int k = before + __popcll(m & ((1ull << lane) - 1ull));
+            // (behind the compaction's first barrier everyone is done with the list of the row before)
+            n_src += block_compact(cell >= 0, sh.wcount, lane, wave, n_src, [&](int k) {
                 sh.cid[k] = (unsigned short)cell;
                 sh.rv[k] = make_float2(rx, ry);
-            }
-            n_src += all;
-            __syncthreads();                                           // the list; and wcount is rewritten by the next pass
+            });
         }
         // ... and the geometry points per kind and cell (behind the barriers above: the counts of the row before were cleared)
         for (int e = tid; e < P; e += BLOCK) {
-            const float2 p = one_tile ? sh.tile[e] : point(e);
+            const float2 p = one_tile ? sh.tile[e] : run.point(e);
             const int cell = grid_cell(p.x - x, p.y - y, rot, hx, hy, c, half, g, G);
             if (cell >= 0) atomicAdd(&sh.cnt[e < nb ? 0 : e < nb + ns ? 1 : 2][cell], 1);
         }

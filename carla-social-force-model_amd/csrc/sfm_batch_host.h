@@ -125,15 +125,18 @@ struct BatchEpisodeDev {
     DevBuf<uint8_t> done;              // [B]
 };
 
-// range scans (sfm_batch_set_scan, ABI 17): the settings and the buffer sfm_batch_scan fills; nothing a tick reads or writes
+// range scans, from the rows (SfmBatch::scan: sfm_batch_set_scan, ABI 17) and from the vehicles (SfmBatch::vscan:
+// sfm_batch_set_vehicle_scan): the settings and the buffer sfm_batch_scan / sfm_batch_scan_vehicles fills, one record per item -- a
+// row, or a vehicle; nothing a tick reads or writes.  sfm_batch_upload_state drops both; the vehicles' goes with the boxes it refers to too.
 struct BatchScanDev {
-    bool on = false;           // (not "buf is allocated": a batch without rows can be scanned and has no buffer)
+    bool on = false;           // (not "buf is allocated": a batch without items can be scanned and has no buffer)
     int R = 0;
     int frame = 0;
+    float mount_x = 0.f, mount_y = 0.f;    // the vehicles' sensor in the vehicle frame; the rows' rays start at the row: 0
     DevBuf<BatchScanScene> set;    // [B]
     DevBuf<float2> dir;        // [R]
-    DevBuf<uint8_t> mask;      // [N_total]; not allocated: every row is scanned
-    DevBuf<float> buf;         // [N_total][2 R]
+    DevBuf<uint8_t> mask;      // [items]; not allocated: every item is scanned
+    DevBuf<float> buf;         // [items][2 R]
 };
 
 // occupancy grids (sfm_batch_set_grid): the settings and the buffer sfm_batch_grid fills; nothing a tick reads or writes
@@ -215,19 +218,6 @@ struct BatchVehObsDev {
     DevBuf<float> buf;         // [M][16 + 4 k]
 };
 
-// range scans from the vehicles (sfm_batch_set_vehicle_scan): the settings and the buffer sfm_batch_scan_vehicles fills; nothing a
-// tick reads or writes.  Dropped with the boxes they refer to, and by sfm_batch_upload_state.
-struct BatchVehScanDev {
-    bool on = false;
-    int R = 0;
-    int frame = 0;
-    float mount_x = 0.f, mount_y = 0.f;
-    DevBuf<BatchVehicleScanScene> set;   // [B]
-    DevBuf<float2> dir;        // [R]
-    DevBuf<uint8_t> mask;      // [M]; not allocated: every vehicle is scanned
-    DevBuf<float> buf;         // [M][2 R]
-};
-
 // routes (sfm_batch_set_routes): the scenes' walk graphs, each row's graph type and goal, and what the plan kernel leaves per row;
 // the ticks read and write none of it (they see the waypoints, modes and queues the plan kernel wrote).  Dropped with the modes.
 struct BatchRoutesDev {
@@ -287,7 +277,7 @@ struct SfmBatch {
     sfm::BatchReplayDev replay;
     sfm::BatchDriveDev drive;
     sfm::BatchVehObsDev vobs;
-    sfm::BatchVehScanDev vscan;
+    sfm::BatchScanDev vscan;
     sfm::BatchRoutesDev routes;
     sfm::Event v_done;                     // created by the first sfm_batch_set_vehicle_driving with vehicles; outlives every drop of the driving
     std::vector<int32_t> scene_off_h;      // the scene offsets [B+1] of the last sfm_batch_upload_state, on the host

@@ -113,12 +113,12 @@ __device__ __forceinline__ void observe_store(const ObserveArgs& a, const Observ
     float4 h0 = make_float4(o.x - x, o.y - y, vx, vy);
     float4 h2 = hv ? make_float4(nv.p.x - x, nv.p.y - y, nv.v.x - vx, nv.v.y - vy) : make_float4(0.f, 0.f, 0.f, 0.f);
     float4 h3 = make_float4(hb ? nb.p.x - x : 0.f, hb ? nb.p.y - y : 0.f, hs ? ns.p.x - x : 0.f, hs ? ns.p.y - y : 0.f);
-    // frame 1: the heading is v / |v|, else the goal's direction, else (1, 0); decided on the fp32 squared lengths
+    // frame 1: the heading is v / |v|, else the goal's direction, else (1, 0) (row_heading)
     float hx = 1.0f, hy = 0.0f;
     if (a.frame) {                                                     // uniform
-        const float vv = fmaf(vx, vx, vy * vy), gg = fmaf(h0.x, h0.x, h0.y * h0.y);
-        if (vv > 0.0f) { const float l = sqrtf(vv); hx = vx / l; hy = vy / l; }
-        else if (gg > 0.0f) { const float l = sqrtf(gg); hx = h0.x / l; hy = h0.y / l; }
+        const float2 h = row_heading(vx, vy, h0.x, h0.y);
+        hx = h.x;
+        hy = h.y;
     }
     auto rot = [&](float& p, float& q) {
         const float rp = fmaf(hx, p, hy * q), rq = fmaf(-hy, p, hx * q);

@@ -12,9 +12,59 @@ static int batch_metres(SfmBatch* b, size_t s, const char* name, float r, bool s
     return why.empty() ? SFM_OK : bfail(b, SFM_ERR_INVALID, why);
 }
 
-static int check_frame(SfmBatch* b, int frame) {
+static int check_frame(SfmBatch* b, int frame, const char* whose = "row") {
     if (frame != SFM_OBS_FRAME_WORLD && frame != SFM_OBS_FRAME_HEADING)
-        return bfail(b, SFM_ERR_INVALID, "frame must be 0 (world axes) or 1 (the row's heading frame), got " + std::to_string(frame));
+        return bfail(b, SFM_ERR_INVALID, std::string("frame must be 0 (world axes) or 1 (the ") + whose + "'s heading frame), got " + std::to_string(frame));
+    return SFM_OK;
+}
+
+// What sfm_batch_set_scan and sfm_batch_set_vehicle_scan share: every check from R on, then the settings and the zero-filled buffer of
+// `items` records (rows, or vehicles) in *o.  `whose`: "row" or "vehicle", for the messages; mount: the vehicles' {x, y}, checked
+// where sfm_batch_set_vehicle_scan always checked it, null for the rows.  Everything is checked before anything is allocated; the
+// caller synchronises the stream (the zero fill) before it moves *o into the batch.
+static int build_scan(SfmBatch* b, size_t items, int max_rays, const char* whose, int R, const float* dir_x, const float* dir_y,
+                      const float* max_range, const float* ped_radius, const float* point_radius, const uint8_t* mask, int frame,
+                      const float* mount, BatchScanDev* o) {
+    int rc;
+    if (R < 1 || R > max_rays)
+        return bfail(b, SFM_ERR_INVALID, "R must be 1 .. " + std::to_string(max_rays) + " rays per " + whose + ", got " + std::to_string(R));
+    if ((rc = check_frame(b, frame, whose))) return rc;
+    if (!dir_x || !dir_y) return bfail(b, SFM_ERR_INVALID, "dir_x or dir_y is NULL");
+    if (!ped_radius || !point_radius) return bfail(b, SFM_ERR_INVALID, "ped_radius or point_radius is NULL");
+    if (mount && (!std::isfinite(mount[0]) || !std::isfinite(mount[1]) || std::fabs(mount[0]) > SFM_BATCH_MAX_SENSE_RANGE ||
+                  std::fabs(mount[1]) > SFM_BATCH_MAX_SENSE_RANGE))
+        return bfail(b, SFM_ERR_INVALID, "the mount must be finite and within 1e6 metres of the vehicle's centre");
+    std::vector<float2> dir((size_t)R);
+    for (int q = 0; q < R; ++q) {
+        if (!std::isfinite(dir_x[q]) || !std::isfinite(dir_y[q]))
+            return bfail(b, SFM_ERR_INVALID, "ray " + std::to_string(q) + ": its direction is not finite");
+        dir[q] = make_float2(dir_x[q], dir_y[q]);
+    }
+    const size_t B = (size_t)b->B;
+    std::vector<BatchScanScene> set(B);
+    for (size_t s = 0; s < B; ++s) {
+        set[s] = BatchScanScene{max_range[s], 0.f, 0.f, 0.f};    // (the range goes to the kernel as the fp32 value given)
+        if ((rc = batch_metres(b, s, "max_range", max_range[s], true, nullptr))) return rc;
+        if ((rc = batch_metres(b, s, "ped_radius", ped_radius[s], false, &set[s].ped_r2))) return rc;
+        if ((rc = batch_metres(b, s, "point_radius", point_radius[s], false, &set[s].point_r2))) return rc;
+    }
+    const size_t vals = items * (size_t)(2 * R);
+    HIP_TRY(b, o->set.alloc(B));
+    HIP_TRY(b, o->dir.alloc((size_t)R));
+    HIP_TRY(b, hipMemcpy(o->set, set.data(), sizeof(BatchScanScene) * B, hipMemcpyHostToDevice));
+    HIP_TRY(b, hipMemcpy(o->dir, dir.data(), sizeof(float2) * (size_t)R, hipMemcpyHostToDevice));
+    if (mask && items > 0) {
+        HIP_TRY(b, o->mask.alloc(items));
+        HIP_TRY(b, hipMemcpy(o->mask, mask, items, hipMemcpyHostToDevice));
+    }
+    if (vals > 0) {
+        HIP_TRY(b, o->buf.alloc(vals));
+        HIP_TRY(b, hipMemsetAsync(o->buf, 0, sizeof(float) * vals, b->stream));
+    }
+    o->R = R;
+    o->frame = frame;
+    if (mount) { o->mount_x = mount[0]; o->mount_y = mount[1]; }
+    o->on = true;
     return SFM_OK;
 }
 
@@ -238,42 +288,10 @@ int sfm_batch_set_scan(SfmBatch* b, int R, const float* dir_x, const float* dir_
         return SFM_OK;
     }
     if (!b->have_state) return bfail(b, SFM_ERR_STATE, NO_STATE);
-    if (R < 1 || R > SFM_BATCH_MAX_SCAN_RAYS)
-        return bfail(b, SFM_ERR_INVALID, "R must be 1 .. " + std::to_string(SFM_BATCH_MAX_SCAN_RAYS) + " rays per row, got " + std::to_string(R));
-    if ((rc = check_frame(b, frame))) return rc;
-    if (!dir_x || !dir_y) return bfail(b, SFM_ERR_INVALID, "dir_x or dir_y is NULL");
-    if (!ped_radius || !point_radius) return bfail(b, SFM_ERR_INVALID, "ped_radius or point_radius is NULL");
-    std::vector<float2> dir((size_t)R);
-    for (int q = 0; q < R; ++q) {
-        if (!std::isfinite(dir_x[q]) || !std::isfinite(dir_y[q]))
-            return bfail(b, SFM_ERR_INVALID, "ray " + std::to_string(q) + ": its direction is not finite");
-        dir[q] = make_float2(dir_x[q], dir_y[q]);
-    }
-    const size_t B = (size_t)b->B;
-    std::vector<BatchScanScene> set(B);
-    for (size_t s = 0; s < B; ++s) {
-        set[s] = BatchScanScene{max_range[s], 0.f, 0.f, 0.f};    // (the range goes to the kernel as the fp32 value given)
-        if ((rc = batch_metres(b, s, "max_range", max_range[s], true, nullptr))) return rc;
-        if ((rc = batch_metres(b, s, "ped_radius", ped_radius[s], false, &set[s].ped_r2))) return rc;
-        if ((rc = batch_metres(b, s, "point_radius", point_radius[s], false, &set[s].point_r2))) return rc;
-    }
-    const size_t n = (size_t)b->n_total, vals = n * (size_t)(2 * R);
     BatchScanDev o;
-    HIP_TRY(b, o.set.alloc(B));
-    HIP_TRY(b, o.dir.alloc((size_t)R));
-    HIP_TRY(b, hipMemcpy(o.set, set.data(), sizeof(BatchScanScene) * B, hipMemcpyHostToDevice));
-    HIP_TRY(b, hipMemcpy(o.dir, dir.data(), sizeof(float2) * (size_t)R, hipMemcpyHostToDevice));
-    if (mask && n > 0) {
-        HIP_TRY(b, o.mask.alloc(n));
-        HIP_TRY(b, hipMemcpy(o.mask, mask, n, hipMemcpyHostToDevice));
-    }
-    if (vals > 0) {
-        HIP_TRY(b, o.buf.alloc(vals));
-        HIP_TRY(b, hipMemsetAsync(o.buf, 0, sizeof(float) * vals, b->stream));
-    }
-    o.R = R;
-    o.frame = frame;
-    o.on = true;
+    if ((rc = build_scan(b, (size_t)b->n_total, SFM_BATCH_MAX_SCAN_RAYS, "row", R, dir_x, dir_y, max_range, ped_radius, point_radius, mask,
+                         frame, nullptr, &o)))
+        return rc;
     HIP_TRY(b, hipStreamSynchronize(b->stream));                 // the zero fill; and a scan in flight may still write the old buffer
     b->scan = std::move(o);
     return SFM_OK;
@@ -303,47 +321,11 @@ int sfm_batch_set_vehicle_scan(SfmBatch* b, int R, const float* dir_x, const flo
     }
     if (!b->have_state) return bfail(b, SFM_ERR_STATE, NO_STATE);
     if (!b->boxes.on) return bfail(b, SFM_ERR_STATE, std::string("vehicle scans: ") + NO_BOXES);
-    if (R < 1 || R > SFM_BATCH_MAX_VEHICLE_SCAN_RAYS)
-        return bfail(b, SFM_ERR_INVALID, "R must be 1 .. " + std::to_string(SFM_BATCH_MAX_VEHICLE_SCAN_RAYS) + " rays per vehicle, got " + std::to_string(R));
-    if (frame != SFM_OBS_FRAME_WORLD && frame != SFM_OBS_FRAME_HEADING)
-        return bfail(b, SFM_ERR_INVALID, "frame must be 0 (world axes) or 1 (the vehicle's heading frame), got " + std::to_string(frame));
-    if (!dir_x || !dir_y) return bfail(b, SFM_ERR_INVALID, "dir_x or dir_y is NULL");
-    if (!ped_radius || !point_radius) return bfail(b, SFM_ERR_INVALID, "ped_radius or point_radius is NULL");
-    if (!std::isfinite(mount_x) || !std::isfinite(mount_y) || std::fabs(mount_x) > SFM_BATCH_MAX_SENSE_RANGE || std::fabs(mount_y) > SFM_BATCH_MAX_SENSE_RANGE)
-        return bfail(b, SFM_ERR_INVALID, "the mount must be finite and within 1e6 metres of the vehicle's centre");
-    std::vector<float2> dir((size_t)R);
-    for (int q = 0; q < R; ++q) {
-        if (!std::isfinite(dir_x[q]) || !std::isfinite(dir_y[q]))
-            return bfail(b, SFM_ERR_INVALID, "ray " + std::to_string(q) + ": its direction is not finite");
-        dir[q] = make_float2(dir_x[q], dir_y[q]);
-    }
-    const size_t B = (size_t)b->B;
-    std::vector<BatchVehicleScanScene> set(B);
-    for (size_t s = 0; s < B; ++s) {
-        set[s] = BatchVehicleScanScene{max_range[s], 0.f, 0.f, 0.f};    // (the range goes to the kernel as the fp32 value given)
-        if ((rc = batch_metres(b, s, "max_range", max_range[s], true, nullptr))) return rc;
-        if ((rc = batch_metres(b, s, "ped_radius", ped_radius[s], false, &set[s].ped_r2))) return rc;
-        if ((rc = batch_metres(b, s, "point_radius", point_radius[s], false, &set[s].point_r2))) return rc;
-    }
-    const size_t M = (size_t)b->geo[2].K, vals = M * (size_t)(2 * R);
-    BatchVehScanDev o;
-    HIP_TRY(b, o.set.alloc(B));
-    HIP_TRY(b, o.dir.alloc((size_t)R));
-    HIP_TRY(b, hipMemcpy(o.set, set.data(), sizeof(BatchVehicleScanScene) * B, hipMemcpyHostToDevice));
-    HIP_TRY(b, hipMemcpy(o.dir, dir.data(), sizeof(float2) * (size_t)R, hipMemcpyHostToDevice));
-    if (mask && M > 0) {
-        HIP_TRY(b, o.mask.alloc(M));
-        HIP_TRY(b, hipMemcpy(o.mask, mask, M, hipMemcpyHostToDevice));
-    }
-    if (vals > 0) {
-        HIP_TRY(b, o.buf.alloc(vals));
-        HIP_TRY(b, hipMemsetAsync(o.buf, 0, sizeof(float) * vals, b->stream));
-    }
-    o.R = R;
-    o.frame = frame;
-    o.mount_x = mount_x;
-    o.mount_y = mount_y;
-    o.on = true;
+    const float mount[2] = {mount_x, mount_y};
+    BatchScanDev o;
+    if ((rc = build_scan(b, (size_t)b->geo[2].K, SFM_BATCH_MAX_VEHICLE_SCAN_RAYS, "vehicle", R, dir_x, dir_y, max_range, ped_radius,
+                         point_radius, mask, frame, mount, &o)))
+        return rc;
     HIP_TRY(b, hipStreamSynchronize(b->stream));                 // the zero fill; and a scan in flight may still write the old buffer
     b->vscan = std::move(o);
     return SFM_OK;

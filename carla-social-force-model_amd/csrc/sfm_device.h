@@ -386,6 +386,62 @@ struct BatchSceneView {
 // A live row: not a ghost parked far away, not a NaN position (which fails the comparison).
 __device__ __forceinline__ bool row_live(float x, float y) { return fabsf(x) < NEAR_LIMIT && fabsf(y) < NEAR_LIMIT; }
 
+// Frame 1's heading of a row with velocity v and goal offset g (own - position): v / |v|, else g / |g|, else (1, 0); decided on the
+// fp32 squared lengths, every operation rounded once.  (Nothing here can contract, so the includer's `fp contract` does not matter.)
+__device__ __forceinline__ float2 row_heading(float vx, float vy, float gx, float gy) {
+    const float vv = fmaf(vx, vx, vy * vy), gg = fmaf(gx, gx, gy * gy);
+    float hx = 1.0f, hy = 0.0f;
+    if (vv > 0.0f) { const float l = sqrtf(vv); hx = vx / l; hy = vy / l; }
+    else if (gg > 0.0f) { const float l = sqrtf(gg); hx = gx / l; hy = gy / l; }
+    return make_float2(hx, hy);
+}
+
+// Scene b's geometry points as one virtual run g = 0 .. total()-1: borders, static obstacles, vehicles.  The scene's points of one
+// kind are one contiguous run of the kind's CSR (polylines in order, points in order); an empty kind's arrays are not read.
+struct SceneRun {
+    const BatchGeo* geo;
+    int nb, ns, nv;           // points per kind
+    int bp0, sp0, vp0;        // each kind's first point in its pts
+    __device__ __forceinline__ SceneRun(const BatchGeo* geo_, int b) : geo(geo_) {
+        const int bk0 = geo[0].item_off[b], bk1 = geo[0].item_off[b + 1];
+        const int sk0 = geo[1].item_off[b], sk1 = geo[1].item_off[b + 1];
+        const int vk0 = geo[2].item_off[b], vk1 = geo[2].item_off[b + 1];
+        bp0 = bk1 > bk0 ? geo[0].off[bk0] : 0; nb = bk1 > bk0 ? geo[0].off[bk1] - bp0 : 0;
+        sp0 = sk1 > sk0 ? geo[1].off[sk0] : 0; ns = sk1 > sk0 ? geo[1].off[sk1] - sp0 : 0;
+        vp0 = vk1 > vk0 ? geo[2].off[vk0] : 0; nv = vk1 > vk0 ? geo[2].off[vk1] - vp0 : 0;
+    }
+    __device__ __forceinline__ int total() const { return nb + ns + nv; }
+    __device__ __forceinline__ float2 point(int g) const {
+        return g < nb ? geo[0].pts[bp0 + g] : g < nb + ns ? geo[1].pts[sp0 + (g - nb)] : geo[2].pts[vp0 + (g - nb - ns)];
+    }
+    // points [g0, g0 + cnt) into the LDS tile, by the whole workgroup (the caller's barriers stand around it).  One 8-byte load and one
+    // LDS store per lane and step: left as written, the two-wide form only adds set-up in front of the first load
+    __device__ __forceinline__ void stage(float2* tile, int g0, int cnt) const {
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+        for (int e = threadIdx.x; e < cnt; e += BLOCK) tile[e] = point(g0 + e);
+    }
+};
+
+// Ordered compaction of a workgroup's lanes: the lanes with `pred` get the slots base, base + 1, .. in thread order, put(slot) stores
+// a lane's entry, and the number of such lanes comes back.  Two barriers: wcount is written before the first; the entries are
+// visible, and wcount may be written again, behind the second.  Every lane of the workgroup must call it.
+template <class Put>
+__device__ __forceinline__ int block_compact(bool pred, int* wcount, int lane, int wave, int base, Put&& put) {
+    const unsigned long long m = __ballot(pred);
+    if (lane == 0) wcount[wave] = __popcll(m);
+    __syncthreads();
+    int before = base, all = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES_PER_BLOCK; ++w) {
+        const int cw = wcount[w];
+        before += w < wave ? cw : 0;
+        all += cw;
+    }
+    if (pred) put(before + __popcll(m & ((1ull << lane) - 1ull)));
+    __syncthreads();
+    return all;
+}
+
 // Observations of a batch (sfm_batch_observe, sfm_batch_observe_kernel in sfm_batch_observe.hip): everything but obs is read only.
 struct ObserveArgs : BatchSceneView {
     const float* range2;      // [B] sense_range^2, formed in double and rounded once
@@ -411,7 +467,7 @@ struct EpisodeArgs : BatchSceneView {
 
 // Range scans of a batch (sfm_batch_scan, sfm_batch_scan_kernel in sfm_batch_scan.hip): everything but out is read only.
 constexpr int SCAN_MAX_RAYS = 64;
-struct BatchScanScene {       // one scene's scan settings (sfm_batch_set_scan)
+struct BatchScanScene {       // one scene's scan settings (sfm_batch_set_scan, sfm_batch_set_vehicle_scan)
     float max_range;          // Rmax, the fp32 value as given
     float ped_r2, point_r2;   // radius^2, each formed in double and rounded once like R2; 0: the kind is never hit
     float pad;
@@ -454,14 +510,9 @@ static_assert(sizeof(VehicleObserveArgs) == 120 + 48, "the vehicle observation k
 // Range scans from the vehicles of a batch (sfm_batch_scan_vehicles, sfm_batch_vehicle_scan_kernel in sfm_batch_vehicle_scan.hip):
 // everything but out is read only.  The vehicles are geo[2]'s items; a vehicle's own ring is no candidate of its rays.
 constexpr int VEHICLE_SCAN_MAX_RAYS = 256;
-struct BatchVehicleScanScene {    // one scene's settings (sfm_batch_set_vehicle_scan): BatchScanScene's
-    float max_range;          // Rmax, the fp32 value as given
-    float ped_r2, point_r2;   // radius^2, each formed in double and rounded once; 0: the kind is never hit
-    float pad;
-};
 struct VehicleScanArgs : BatchSceneView {
     const float2* rot;        // [M] the vehicles' headings {cos, sin}, as the next tick reads them
-    const BatchVehicleScanScene* set;   // [B]
+    const BatchScanScene* set;    // [B] (sfm_batch_set_vehicle_scan)
     const float2* dir;        // [R] ray directions, used as given
     const uint8_t* mask;      // [M] nonzero: the vehicle is scanned; null: every vehicle
     float* out;               // [M][2 R]: ranges, then kinds

@@ -151,128 +151,9 @@ def heading32(x, y, vx, vy, wx, wy):
     return hx, hy
 
 
-def _walk(scene, angles, max_range, ped_radius, point_radius, frame, mask, state, vehicles, waypoints, directions, prune):
-    """The shared walk of ``scan_scene`` and ``range_census``: validates, then yields first (n, R, Rmax) and after it, per scanned
-    live row in ascending order, (i, val, kind): val (R, P) float32 the range of every candidate in the fixed order (+inf where
-    the disc is no candidate of the ray), kind (P,) int64."""
-    if frame not in (0, 1):
-        raise ValueError(f"frame must be 0 or 1, got {frame!r}")
-    ux, uy = ray_directions(angles) if directions is None else check_directions(directions)
-    R = ux.shape[0]
-    Rmax = np.float32(max_range)
-    if not (np.isfinite(Rmax) and 0 < Rmax <= np.float32(MAX_SCAN_RANGE)):
-        raise ValueError(f"max_range must be finite, > 0 and <= {MAX_SCAN_RANGE:g} metres")
-    for name, r in (("ped_radius", ped_radius), ("point_radius", point_radius)):
-        if not (np.isfinite(np.float32(r)) and 0 <= np.float32(r) <= np.float32(MAX_SCAN_RANGE)):
-            raise ValueError(f"{name} must be finite, >= 0 and <= {MAX_SCAN_RANGE:g} metres")
-    pr2, qr2 = radius2(ped_radius), radius2(point_radius)
-    loc, vel = (_get(scene, "loc"), _get(scene, "vel")) if state is None else state
-    loc, vel = np.asarray(loc, dtype=np.float64), np.asarray(vel, dtype=np.float64)
-    n = loc.reshape(-1, loc.shape[-1]).shape[0] if loc.size else 0
-    yield n, R, Rmax
-    if n == 0:
-        return
-    loc, vel = loc.reshape(n, -1), vel.reshape(n, -1)
-    x, y = _f32(loc[:, 0], 0), _f32(loc[:, 1], 0)
-    vx, vy = _f32(vel[:, 0], 0), _f32(vel[:, 1], 0)
-    scanned = np.ones(n, bool) if mask is None else np.asarray(mask).astype(bool).reshape(n)
-    live = _live(x, y)
-    if frame == 1:
-        wp = np.asarray(_get(scene, "waypoint") if waypoints is None else waypoints, dtype=np.float64).reshape(n, -1)
-        hx, hy = heading32(x, y, vx, vy, _f32(wp[:, 0], 0), _f32(wp[:, 1], 0))
-
-    borders = _get(scene, "borders") or []
-    statics = _get(scene, "static_obstacles") or []
-    veh = (_get(scene, "dynamic_obstacles") or []) if vehicles is None else vehicles
-    geo = [_polylines(borders, False)[0], _polylines(statics, True)[0], _polylines(veh, True)[0]]
-    gx = np.concatenate([g[:, 0] for g in geo])
-    gy = np.concatenate([g[:, 1] for g in geo])
-    gkind = np.concatenate([np.full(len(g), KIND_BORDER + q, np.int64) for q, g in enumerate(geo)])
-    can_prune = bool(prune) and bool((np.abs(ux.astype(np.float64) ** 2 + uy.astype(np.float64) ** 2 - 1.0) < 1e-6).all())
-    inf = np.float32(np.inf)
-
-    with np.errstate(over="ignore", invalid="ignore"):
-        for i in np.flatnonzero(scanned & live):
-            others = np.arange(n) != i
-            px = np.concatenate([x[others], gx])
-            py = np.concatenate([y[others], gy])
-            r2 = np.concatenate([np.full(n - 1, pr2, np.float32), np.full(len(gx), qr2, np.float32)])
-            kind = np.concatenate([np.full(n - 1, KIND_PEDESTRIAN, np.int64), gkind])
-            ax, ay = px - x[i], py - y[i]
-            keep = r2 > 0                                              # (radius 0: q = -c^2 <= 0, never a candidate)
-            if can_prune:
-                d = np.sqrt(ax.astype(np.float64) ** 2 + ay.astype(np.float64) ** 2)
-                far = d > 1.001 * (np.float64(Rmax) + 2.0 * np.sqrt(r2.astype(np.float64))) + 1e-30
-                keep &= ~far
-            ax, ay, r2, kind = ax[keep], ay[keep], r2[keep], kind[keep]
-            if frame == 1:
-                rx = _fma32(hx[i], ux, -(hy[i] * uy))
-                ry = _fma32(hy[i], ux, hx[i] * uy)
-            else:
-                rx, ry = ux, uy
-            A, Bv = ax[None, :], ay[None, :]
-            U, V = rx[:, None], ry[:, None]
-            t = _fma32(A, U, Bv * V)
-            c = _fma32(A, V, -(Bv * U))
-            q = _fma32(-c, c, r2[None, :])
-            w = np.sqrt(q)
-            cand = (q > 0) & ((t + w) > 0)
-            s = t - w
-            yield i, np.where(cand, np.where(s > 0, s, np.float32(0.0)), inf).astype(np.float32), kind
-
-
-def scan_scene(scene, angles, max_range, ped_radius, point_radius, frame=0, mask=None, state=None, vehicles=None, waypoints=None,
-               directions=None, prune=True):
-    """The scan record of one scene, (N, 2R) float32, as ``SfmBatch.scans()`` returns it: floats 0 .. R-1 the ranges, R .. 2R-1
-    the kinds (0 nothing, 1 pedestrian, 2 border, 3 static obstacle, 4 vehicle).
-
-    ``scene``: a scene dict as ``SfmBatch.upload`` takes it (or a ``scenarios.Scenario``).  ``angles``: the R ray angles (see
-    ``ray_directions``; ``default_angles(R)`` is ``set_scan``'s default), or None with ``directions`` = (dir_x, dir_y) used as
-    given.  ``max_range``, ``ped_radius``, ``point_radius``: metres, this scene's.  ``frame``: 0 world axes, 1 heading frame.
-    ``mask``: bool (N,), the rows that are scanned (None: all).  What has changed on the device since the upload is fed in as for
-    ``observe.observe_scene``: ``state`` = (loc, vel), ``vehicles`` = the scene's list of (center, ring), ``waypoints`` (N,2|3).
-
-    Chunked per row: the largest block is R x (N - 1 + points).  ``prune``: candidates further than 1.001 (Rmax + 2 r) from the row
-    are left out before the ray arithmetic when every direction has | |u|^2 - 1 | < 1e-6.  That cannot change the record: a
-    candidate needs q > 0, so |c| <= r up to rounding and t >= |a||u| - r up to rounding (2^-22 |a| each), hence its range
-    t - w >= |a| (1 - 1.3e-6) - 2.0000002 r > Rmax, and a range >= Rmax is never stored (if it is the minimum the ray is a miss;
-    if it is not, it is not the minimum).  ``prune=False`` evaluates everything."""
-    walk = _walk(scene, angles, max_range, ped_radius, point_radius, frame, mask, state, vehicles, waypoints, directions, prune)
-    n, R, Rmax = next(walk)
-    rec = np.zeros((n, 2 * R), np.float32)
-    for i, val, kind in walk:
-        if val.shape[1] == 0:
-            rec[i, :R] = Rmax
-            continue
-        idx = np.argmin(val, axis=1)                                   # the first minimum in the fixed order
-        best = val[np.arange(R), idx]
-        hit = best < Rmax
-        rec[i, :R] = np.where(hit, best, Rmax)
-        rec[i, R:] = np.where(hit, kind[idx].astype(np.float32), np.float32(0.0))
-    return rec
-
-
-def range_census(scene, angles, max_range, ped_radius, point_radius, frame=0, mask=None, state=None, vehicles=None, waypoints=None,
-                 directions=None, band=0.01):
-    """How hard a scene tests the range limit: an int64 array (5, 2), per kind the number of (row, ray, candidate) triples whose
-    range lies in [(1 - band) Rmax, Rmax) and in [Rmax, (1 + band) Rmax] -- just inside and just outside the limit.  Arguments as
-    for ``scan_scene``; nothing is pruned."""
-    walk = _walk(scene, angles, max_range, ped_radius, point_radius, frame, mask, state, vehicles, waypoints, directions, False)
-    _, _, Rmax = next(walk)
-    lo, hi = np.float64(Rmax) * (1.0 - band), np.float64(Rmax) * (1.0 + band)
-    out = np.zeros((5, 2), np.int64)
-    for _, val, kind in walk:
-        v = val.astype(np.float64)
-        for k in range(1, 5):
-            vk = v[:, kind == k]
-            out[k, 0] += int(((vk >= lo) & (vk < Rmax)).sum())
-            out[k, 1] += int(((vk >= Rmax) & (vk <= hi)).sum())
-    return out
-
-
-# What follows is the vehicles' scan.  ``_walk`` above stays one self-contained function (its tests read its source), so the four
-# helpers below restate its checks, its pruning test, its per-disc arithmetic and its choice of the first minimum; the reduction of
-# ``scan_vehicles_scene`` to ``scan_scene`` in tests/test_batch_vehicle_scan_host.py holds the two statements to each other bit for bit.
+# The rules of the two scans, each stated once: the three lengths (_check_radii), the pruning test (_far), the per-disc arithmetic
+# (_disc_ranges) and the choice of the first minimum (_first_minimum).  ``_walk`` casts from the rows, ``scan_vehicles_scene`` from
+# the vehicles.
 
 def _check_radii(max_range, ped_radius, point_radius):
     """The scan's three lengths as the library takes them -> (Rmax, ped_r2, point_r2) float32; raises ValueError."""
@@ -316,6 +197,102 @@ def _first_minimum(val, kind, Rmax):
     hit = best < Rmax
     return np.where(hit, best, Rmax).astype(np.float32), np.where(hit, kind[idx].astype(np.float32), np.float32(0.0))
 
+
+def _walk(scene, angles, max_range, ped_radius, point_radius, frame, mask, state, vehicles, waypoints, directions, prune):
+    """The shared walk of ``scan_scene`` and ``range_census``: validates, then yields first (n, R, Rmax) and after it, per scanned
+    live row in ascending order, (i, val, kind): val (R, P) float32 the range of every candidate in the fixed order (+inf where
+    the disc is no candidate of the ray), kind (P,) int64."""
+    if frame not in (0, 1):
+        raise ValueError(f"frame must be 0 or 1, got {frame!r}")
+    ux, uy = ray_directions(angles) if directions is None else check_directions(directions)
+    R = ux.shape[0]
+    Rmax, pr2, qr2 = _check_radii(max_range, ped_radius, point_radius)
+    loc, vel = (_get(scene, "loc"), _get(scene, "vel")) if state is None else state
+    loc, vel = np.asarray(loc, dtype=np.float64), np.asarray(vel, dtype=np.float64)
+    n = loc.reshape(-1, loc.shape[-1]).shape[0] if loc.size else 0
+    yield n, R, Rmax
+    if n == 0:
+        return
+    loc, vel = loc.reshape(n, -1), vel.reshape(n, -1)
+    x, y = _f32(loc[:, 0], 0), _f32(loc[:, 1], 0)
+    vx, vy = _f32(vel[:, 0], 0), _f32(vel[:, 1], 0)
+    scanned = np.ones(n, bool) if mask is None else np.asarray(mask).astype(bool).reshape(n)
+    live = _live(x, y)
+    if frame == 1:
+        wp = np.asarray(_get(scene, "waypoint") if waypoints is None else waypoints, dtype=np.float64).reshape(n, -1)
+        hx, hy = heading32(x, y, vx, vy, _f32(wp[:, 0], 0), _f32(wp[:, 1], 0))
+
+    borders = _get(scene, "borders") or []
+    statics = _get(scene, "static_obstacles") or []
+    veh = (_get(scene, "dynamic_obstacles") or []) if vehicles is None else vehicles
+    geo = [_polylines(borders, False)[0], _polylines(statics, True)[0], _polylines(veh, True)[0]]
+    gx = np.concatenate([g[:, 0] for g in geo])
+    gy = np.concatenate([g[:, 1] for g in geo])
+    gkind = np.concatenate([np.full(len(g), KIND_BORDER + q, np.int64) for q, g in enumerate(geo)])
+    can_prune = bool(prune) and bool((np.abs(ux.astype(np.float64) ** 2 + uy.astype(np.float64) ** 2 - 1.0) < 1e-6).all())
+
+    with np.errstate(over="ignore", invalid="ignore"):
+        for i in np.flatnonzero(scanned & live):
+            others = np.arange(n) != i
+            px = np.concatenate([x[others], gx])
+            py = np.concatenate([y[others], gy])
+            r2 = np.concatenate([np.full(n - 1, pr2, np.float32), np.full(len(gx), qr2, np.float32)])
+            kind = np.concatenate([np.full(n - 1, KIND_PEDESTRIAN, np.int64), gkind])
+            ax, ay = px - x[i], py - y[i]
+            keep = r2 > 0                                              # (radius 0: q = -c^2 <= 0, never a candidate)
+            if can_prune:
+                keep &= ~_far(ax, ay, r2, Rmax)
+            if frame == 1:
+                rx = _fma32(hx[i], ux, -(hy[i] * uy))
+                ry = _fma32(hy[i], ux, hx[i] * uy)
+            else:
+                rx, ry = ux, uy
+            yield i, _disc_ranges(ax[keep], ay[keep], r2[keep], rx, ry), kind[keep]
+
+
+def scan_scene(scene, angles, max_range, ped_radius, point_radius, frame=0, mask=None, state=None, vehicles=None, waypoints=None,
+               directions=None, prune=True):
+    """The scan record of one scene, (N, 2R) float32, as ``SfmBatch.scans()`` returns it: floats 0 .. R-1 the ranges, R .. 2R-1
+    the kinds (0 nothing, 1 pedestrian, 2 border, 3 static obstacle, 4 vehicle).
+
+    ``scene``: a scene dict as ``SfmBatch.upload`` takes it (or a ``scenarios.Scenario``).  ``angles``: the R ray angles (see
+    ``ray_directions``; ``default_angles(R)`` is ``set_scan``'s default), or None with ``directions`` = (dir_x, dir_y) used as
+    given.  ``max_range``, ``ped_radius``, ``point_radius``: metres, this scene's.  ``frame``: 0 world axes, 1 heading frame.
+    ``mask``: bool (N,), the rows that are scanned (None: all).  What has changed on the device since the upload is fed in as for
+    ``observe.observe_scene``: ``state`` = (loc, vel), ``vehicles`` = the scene's list of (center, ring), ``waypoints`` (N,2|3).
+
+    Chunked per row: the largest block is R x (N - 1 + points).  ``prune``: candidates further than 1.001 (Rmax + 2 r) from the row
+    are left out before the ray arithmetic when every direction has | |u|^2 - 1 | < 1e-6.  That cannot change the record: a
+    candidate needs q > 0, so |c| <= r up to rounding and t >= |a||u| - r up to rounding (2^-22 |a| each), hence its range
+    t - w >= |a| (1 - 1.3e-6) - 2.0000002 r > Rmax, and a range >= Rmax is never stored (if it is the minimum the ray is a miss;
+    if it is not, it is not the minimum).  ``prune=False`` evaluates everything."""
+    walk = _walk(scene, angles, max_range, ped_radius, point_radius, frame, mask, state, vehicles, waypoints, directions, prune)
+    n, R, Rmax = next(walk)
+    rec = np.zeros((n, 2 * R), np.float32)
+    for i, val, kind in walk:
+        rec[i, :R], rec[i, R:] = _first_minimum(val, kind, Rmax)
+    return rec
+
+
+def range_census(scene, angles, max_range, ped_radius, point_radius, frame=0, mask=None, state=None, vehicles=None, waypoints=None,
+                 directions=None, band=0.01):
+    """How hard a scene tests the range limit: an int64 array (5, 2), per kind the number of (row, ray, candidate) triples whose
+    range lies in [(1 - band) Rmax, Rmax) and in [Rmax, (1 + band) Rmax] -- just inside and just outside the limit.  Arguments as
+    for ``scan_scene``; nothing is pruned."""
+    walk = _walk(scene, angles, max_range, ped_radius, point_radius, frame, mask, state, vehicles, waypoints, directions, False)
+    _, _, Rmax = next(walk)
+    lo, hi = np.float64(Rmax) * (1.0 - band), np.float64(Rmax) * (1.0 + band)
+    out = np.zeros((5, 2), np.int64)
+    for _, val, kind in walk:
+        v = val.astype(np.float64)
+        for k in range(1, 5):
+            vk = v[:, kind == k]
+            out[k, 0] += int(((vk >= lo) & (vk < Rmax)).sum())
+            out[k, 1] += int(((vk >= Rmax) & (vk <= hi)).sum())
+    return out
+
+
+# What follows is the vehicles' scan, built from the same pieces.
 
 def check_mount(mount):
     """The sensor's place in the vehicle frame (x forward), metres -> (mx, my) float32; finite, |m| <= 1e6.  Raises ValueError."""

@@ -284,11 +284,11 @@ OLD_HOST_TESTS = ("test_a_disc_dead_ahead_and_the_same_disc_behind", "test_insid
 
 def _mutant(name):
     old, new = MUTATIONS[name]
-    src = inspect.getsource(S._walk)
+    src = inspect.getsource(S._disc_ranges)
     assert src.count(old) == 1, name
     ns = dict(vars(S))
-    exec(compile(src.replace(old, new), f"<scan._walk: {name}>", "exec"), ns)
-    return ns["_walk"]
+    exec(compile(src.replace(old, new), f"<scan._disc_ranges: {name}>", "exec"), ns)
+    return ns["_disc_ranges"]
 
 
 def _old_tests_pass():
@@ -317,6 +317,6 @@ def test_a_twin_with_one_line_changed_is_refused(name, monkeypatch):
     """Every changed copy must leave the envelope on the smallest crowd (frame 0 at the origin, frame 1 shifted) while the analytic
     cases and the pruning test of test_batch_scan_host.py still pass."""
     assert _old_tests_pass() and _new_tests_pass()                       # the twin itself passes both
-    monkeypatch.setattr(S, "_walk", _mutant(name))
+    monkeypatch.setattr(S, "_disc_ranges", _mutant(name))
     assert not _new_tests_pass(), f"{name}: inside the envelope"
     assert _old_tests_pass(), f"{name}: refused by test_batch_scan_host.py already"
