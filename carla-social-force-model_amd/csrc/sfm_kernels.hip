@@ -760,7 +760,9 @@ __global__ __launch_bounds__(BLOCK) void sfm_tick_kernel(const TickArgs a) {
                     float cx = 0.0f, cy = 0.0f, cz = 0.0f, rinv;
                     moussaid<Z3, RAD, Z3>(a.ped, pj.x - xi[k], pj.y - yi[k], zj - zi[k], vxi[k] - pj.z,
                                           vyi[k] - pj.w, vzi[k] - vzj, ri[k] + rj, cx, cy, cz, rinv);
-                    const bool valid = (j < N) & (j != ibase + k);   // all_diffs drops j == i (stateutils.py:41-49)
+                    // all_diffs drops j == i (stateutils.py:41-49); a tail slot holds a copy of row i_end - 1, which would meet that
+                    // row at distance 0 and send the wave into the coincidence pass below for nothing
+                    const bool valid = (j < N) & (j != ibase + k) & (ibase + k < a.i_end);
                     gx[k] += valid ? cx : 0.0f;                       // select, so a NaN on the diagonal never leaks
                     gy[k] += valid ? cy : 0.0f;
                     if (Z3) gz[k] += valid ? cz : 0.0f;

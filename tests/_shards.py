@@ -176,21 +176,31 @@ class ShardReplay:
     handles.  Every ``resort_every`` ticks: the ``row_data()`` exchange, ``resort()`` on every handle, then new bounds from
     ``balanced_bounds`` over each rank's ``work()`` -- or, where the ordered kernel measured nothing, over a lopsided cost so that the
     bounds move all the same.  The packing is held to ``pack_order`` at every re-pack.  Needs SFM_RESORT_EVERY=0 in the
-    environment: the whole-crowd handle must re-pack when the ranks do, not by itself."""
+    environment: the whole-crowd handle must re-pack when the ranks do, not by itself.
 
-    def __init__(self, cfg, sc, world, layout=None, split=False, resort_every=4, whole=True):
+    ``bounds``: explicit row bounds instead of the equal split (they need not be whole tiles: a rank whose rows are not takes the
+    ordered kernel); ``partition=False``: no rank blocks, the plain strip packing of an upload; ``resort_every=0``: no re-pack;
+    ``dt``, ``redraw``: the ticks' step length and whether they redraw waypoints; ``exchange_buffers``: which of the ``packed()``
+    buffers the exchange carries (None: all of them -- anything else computes a wrong crowd, for a test that shows it would be
+    noticed); ``recorded_tick()``: a tick that records its forces and does not integrate, on every rank."""
+
+    def __init__(self, cfg, sc, world, layout=None, split=False, resort_every=4, whole=True, bounds=None, partition=True, dt=DT,
+                 redraw=True, exchange_buffers=None):
         import torch
         from carla_social_force_model_amd.stepper import HipShardEngine, block_layout, equal_bounds
         self.torch = torch
         self.world, self.split, self.resort_every = world, split, resort_every
-        self.layout = block_layout(world, layout)
-        self.ranks = [HipShardEngine(cfg, DT) for _ in range(world)]
-        self.whole = HipShardEngine(cfg, DT) if whole else None
+        self.redraw, self.exchange_buffers = redraw, exchange_buffers
+        self.layout = block_layout(world, layout) if partition else None
+        self.ranks = [HipShardEngine(cfg, dt) for _ in range(world)]
+        self.whole = HipShardEngine(cfg, dt) if whole else None
         for e in self._handles():
-            e.set_partition(*self.layout)
+            if self.layout:
+                e.set_partition(*self.layout)
             self.n, self.n_pad = e.load(sc)
         self.aspect = crowd_aspect(sc.loc[:, 0], sc.loc[:, 1])        # the handles' pack aspect, fixed at upload
-        self.bounds = equal_bounds(self.n, self.n_pad, world)
+        self.bounds = equal_bounds(self.n, self.n_pad, world) if bounds is None else [int(b) for b in bounds]
+        assert len(self.bounds) == world + 1 and self.bounds[0] == 0 and self.bounds[-1] == self.n, self.bounds
         self._apply_bounds()
         self.pending = False
         self.since_resort = 0
@@ -204,10 +214,12 @@ class ShardReplay:
 
     def _apply_bounds(self):
         self.shard_set = True                              # (set_shard drops geometry forces a rank had launched ahead)
+        blocks = self.layout and all(b % TILE == 0 for b in self.bounds[:-1])      # (rank blocks are whole tiles)
         for r, e in enumerate(self.ranks):
             e.set_shard(self.bounds[r], self.bounds[r + 1])
-            e.set_partition(*self.layout, self.bounds)
-        if self.whole:
+            if blocks:
+                e.set_partition(*self.layout, self.bounds)
+        if self.whole and blocks:
             self.whole.set_partition(*self.layout, self.bounds)
 
     def synchronize(self):
@@ -229,9 +241,13 @@ class ShardReplay:
                     dst[lo * w:hi * w].copy_(src[lo * w:hi * w])
         self.synchronize()
 
+    def _packed(self, e):
+        bufs = e.packed()
+        return bufs if self.exchange_buffers is None else [b for k, b in enumerate(bufs) if k in self.exchange_buffers]
+
     def _flush(self):
         if self.pending:
-            self.exchange(lambda e: e.packed())
+            self.exchange(self._packed)
             self.pending = False
 
     def repack(self):
@@ -272,22 +288,34 @@ class ShardReplay:
             self.repack()
         if self.split:
             for e in self.ranks:
-                e.begin()
+                e.begin(redraw=self.redraw)
             self._flush()                                  # the previous tick's rows arrive between the two halves
             for e in self.ranks:
-                e.end()
+                e.end(redraw=self.redraw)
         else:
             self._flush()
             for e in self.ranks:
-                e.run(1)
+                e.run(1, redraw=self.redraw)
         self.pending = True
         if self.whole:
-            self.whole.run(1)
+            self.whole.run(1, redraw=self.redraw)
         self.synchronize()
         self.launches.append([e.engine.timing()[2] for e in self.ranks])
         self.after_set_shard.append(self.shard_set)
         self.shard_set = False
         self.since_resort += 1
+
+    def recorded_tick(self, which="pedestrian_force"):
+        """The exchange, then a tick on every rank that records its forces and does not integrate.  Returns force ``which`` of the
+        whole crowd, every pedestrian's from the rank that owns it (no row may be left out, none come from two ranks)."""
+        self._flush()
+        for e in self.ranks:
+            e.engine.tick(record=True)
+        self.synchronize()
+        got = np.stack([e.engine.forces(which) for e in self.ranks])
+        own = ~np.isnan(got[:, :, 0])
+        assert (own.sum(axis=0) == 1).all(), "every pedestrian's force must come from exactly one rank"
+        return np.choose(np.argmax(own, axis=0)[:, None], list(got))
 
     def merged(self):
         """(loc, vel, wp, draws) of the whole crowd, every pedestrian from the rank that owns it."""

@@ -1,12 +1,14 @@
 """Crowds with ONE FAST ROW PER TILE, for the speed bound of the tile-pair cutoff (tests/test_speed_bound_host.py on the CPU,
-tests/test_speed_bound_gpu.py on the GPU; DESIGN.md sections 3.5 and 4).  No GPU code here, and no call into the library.
+tests/test_speed_bound_gpu.py on the GPU; on sharded ranks tests/test_speed_bound_shards_host.py and
+tests/test_speed_bound_shards_gpu.py, whose shard specs, roles and cells stand at the end of this file; DESIGN.md sections 3.5 and 4).
+No GPU code here, and no call into the library.
 
 The cutoff drops a tile pair whose boxes are farther apart than  gamma 41 ln2 1.001 (1 + lambda (vmax_a + vmax_b)) (+ 2 r_max 1.001),
 vmax the largest speed of a tile.  Every other crowd that runs under the cutoff walks at <= 1.6 m/s, evenly over the tiles, with its
 partners within 3 m -- inside the reach even at vmax = 0 -- so a wrong vmax changes nothing there.  Here:
 
   * a tile is 64 consecutive device rows on an 8 x 8 grid of 8 m pitch (a 56 m box of its own);
-  * a FAST tile holds exactly one fast row -- planar v = (5, 0.125, 0), 3-D v = (0.125, 0.03125, 6) -- and otherwise rows of at most
+  * a FAST tile holds exactly one fast row -- planar v = (5, 0.125, 0), 3-D v = (0.1875, 0.03125, 6) -- and otherwise rows of at most
     0.25 m/s (3-D: 0.1875); a SLOW tile holds only such rows;
   * the fast row stands in the column of its box that faces a slow tile, its PARTNER -- v = (-0.25, 0, 0), 3-D (-0.125, 0, 0) -- in
     the facing column of that tile, GAP = 30 m (3-D: 20 m) away: between the reach without the fast row (19.9 m, 3-D 17.4 m, + 0.9 m
@@ -15,7 +17,7 @@ partners within 3 m -- inside the reach even at vmax = 0 -- so a wrong vmax chan
   * a pair never has a fast row on both sides: it could not show which tile's bound was wrong.
 
 Two layouts.  'units' (uploaded with SFM_REORDER=0: the device's tiles are the caller's): each designed pair of tiles alone on a
-site of a 512 m lattice, the tile indices and the fast row's lane chosen freely.  'stacks' (uploaded WITH the spatial packing):
+site of a 512 m lattice (each site 3 m higher in y than the last), the tile indices and the fast row's lane chosen freely.  'stacks' (uploaded WITH the spatial packing):
 strips side by side in x, GAP apart, each a stack of tiles 24 m apart in y, rows of a tile in (y, x) order -- the sort-tile-
 recursive packing (sort by x, strips of strip_rows rows, each sorted by y) then leaves exactly these tiles whatever the caller's
 order, which ``packing`` restates and the host file asserts; a strip holds at most ONE fast tile where its strip bound is at stake.
@@ -41,8 +43,9 @@ PITCH, GRID, WAVE = 8.0, 8, 64
 SIDE = PITCH * (GRID - 1)                     # 56 m: a tile's box
 STACK = SIDE + 24.0                           # y pitch of stacked tiles: 24 m apart, beyond the reach of two slow tiles (20.8 m)
 SITE = 512.0                                  # 'units': one designed pair of tiles per site
+SITE_RISE = 3.0                               # ... each 3 m higher in y than the last: no two sites share a row's y (see ``build``)
 GAP = {False: 30.0, True: 20.0}               # [3-D]
-V_FAST = {False: (5.0, 0.125, 0.0), True: (0.125, 0.03125, 6.0)}
+V_FAST = {False: (5.0, 0.125, 0.0), True: (0.1875, 0.03125, 6.0)}
 V_PARTNER = {False: (-0.25, 0.0, 0.0), True: (-0.125, 0.0, 0.0)}
 SLOW = {False: 0.25, True: 0.1875}            # largest speed of every other row
 ROW = 3                                       # grid row of the fast row and of its partner
@@ -173,11 +176,11 @@ def _tile_origins(spec):
         for k, (f, s, _, _) in enumerate(spec.pairs):
             sd = 1 if k % 2 == 0 else -1
             lo, hi = (f, s) if sd > 0 else (s, f)
-            org[lo], org[hi] = (k * SITE, 0.0), (k * SITE + SIDE + gap, 0.0)
+            org[lo], org[hi] = (k * SITE, k * SITE_RISE), (k * SITE + SIDE + gap, k * SITE_RISE)
             side.append(sd)
             seen |= {f, s}
         for j, t in enumerate(sorted(set(range(n_t)) - seen)):
-            org[t] = ((len(spec.pairs) + j) * SITE, 0.0)
+            org[t] = ((len(spec.pairs) + j) * SITE, (len(spec.pairs) + j) * SITE_RISE)
     else:
         strips, tps = spec.shape
         assert strips * tps == n_t
@@ -210,10 +213,15 @@ def build(spec):
     slot = (rows % WAVE + rot[rows // WAVE]) % WAVE
     loc = np.zeros((n, 3))
     loc[:, 0], loc[:, 1] = org[rows // WAVE, 0] + PITCH * (slot % GRID), org[rows // WAVE, 1] + PITCH * (slot // GRID)
-    lim = 11 if not z3 else 7                                  # / 64 per component: norm <= 0.243 (3-D with v_z <= 2 / 64: 0.158)
+    lim = 11 if not z3 else 7                                  # / 64 per component: norm <= 0.243 (3-D with v_z <= 2 / 64: 0.158), + 0.003
     vel = np.zeros((n, 3))
     vel[:, :2] = rng.integers(-lim, lim + 1, (n, 2)) / 64.0
     vel[(vel[:, 0] == 0) & (vel[:, 1] == 0), 0] = 1.0 / 64.0
+    # ... and off the 1 / 64 lattice by up to 1 / 512 a component, every row its own way: rows on a lattice of positions with a lattice
+    # of velocities meet at theta = 0 exactly -- a row dead ahead with D_y = 0 -- which is an exposure on the row (1e-59 m/s^2 from
+    # another site, 5e-4 within a tile), and a shard decides BOTH rows of a designed pair on their own.  (Designed rows: SITE_RISE.)
+    vel[:, 0] += ((rows * 0.9068996821171) % 1.0 - 0.5) / 256.0
+    vel[:, 1] += ((rows * 0.2915026221292) % 1.0 - 0.5) / 256.0
     if z3:
         vel[:, 2] = rng.integers(-2, 3, n) / 64.0
         loc[:, 2] = rng.integers(0, 4, n) * 0.5
@@ -264,7 +272,22 @@ def moved(crowd, loc, vel):
 _A = ((0, 5, 0, 40), (1, 6, 1, 63), (7, 2, 31, 0), (4, 3, 32, 17))
 _B = ((5, 0, 63, 9), (6, 1, 32, 31), (2, 7, 31, 32), (3, 4, 1, 62))          # the roles exchanged: every tile is the fast one somewhere
 _R = ((8, 3, 16, 5), (0, 5, 63, 1), (1, 6, 0, 33), (7, 2, 32, 60))          # N = 64 * 8 + 17: the fast row at the last index
+# sharded ranks (below): four disjoint pairs of tiles whose partner lies 2 above / 6 above / 1 below / 5 below the fast tile -- with the
+# fast tile on one rank and the partner on another that is every direction (remote tile below / above the own one) and distance
+# (within / beyond n_t / 2 ahead of it) on both ranks -- the four lanes dealt over them as a Latin square
+_LANES, _TYPES, _PARTNER_LANES = (0, 31, 32, 63), ((1, 3), (0, 6), (5, 4), (7, 2)), (40, 9, 0, 63)
+_S = tuple(tuple((f, s, _LANES[(j + k) % 4], _PARTNER_LANES[(j + k) % 4]) for j, (f, s) in enumerate(_TYPES)) for k in range(4))
+# ragged bounds: a cut at row 200 goes through tile 3 (lanes 0-7 | 8-63), cuts at rows 100 and 300 through tiles 1 (lanes 0-35 | 36-63)
+# and 4 (0-43 | 44-63); the fast row of a cut tile on the side of the rank that owns the partner, or on the other rank's
+_C2A = ((3, 6, 0, 40), (0, 1, 31, 9), (7, 5, 32, 0), (4, 2, 63, 17))
+_C2B = ((3, 6, 63, 40), (0, 1, 32, 9), (7, 5, 0, 0), (4, 2, 31, 17))
+_C3 = ((1, 2, 63, 5), (4, 7, 0, 33), (0, 6, 32, 60), (5, 3, 31, 1))
 SPECS = {s.name: s for s in (
+    Spec("s0", "units", 512, False, _S[0]), Spec("s1", "units", 512, False, _S[1]), Spec("s2", "units", 512, False, _S[2]),
+    Spec("s3", "units", 512, False, _S[3]), Spec("s0z", "units", 512, True, _S[0]), Spec("s1z", "units", 512, True, _S[1]),
+    Spec("s2z", "units", 512, True, _S[2]), Spec("s3z", "units", 512, True, _S[3]),
+    Spec("c2a", "units", 512, False, _C2A), Spec("c2bz", "units", 512, True, _C2B), Spec("c3", "units", 512, False, _C3),
+    Spec("c3z", "units", 512, True, _C3),
     Spec("a", "units", 512, False, _A), Spec("b", "units", 512, False, _B), Spec("ragged", "units", 529, False, _R),
     Spec("a3", "units", 512, True, _A), Spec("b3", "units", 512, True, _B), Spec("ragged3", "units", 529, True, _R),
     # 'stacks', 2 strips of 16 tiles (cross-strip pairs are listed under the tile of strip 0: strip 1's bound is the one at stake, and
@@ -320,3 +343,141 @@ CARRY_FORCES = ("acceleration_force", "pedestrian_force")
 def carry_dt(spec):
     """Step length of a carried-bounds cell."""
     return DT_CARRY if spec.starters else DT_CARRY_3D
+
+
+# ---- sharded ranks (tests/test_speed_bound_shards_host.py, tests/test_speed_bound_shards_gpu.py) -----------------------------------------------
+# A rank owns the device rows [bounds[r], bounds[r + 1]).  ROLE of a rank in a designed pair, by the rows it owns:
+#   'oo'               it owns the fast row and its partner: one decision serves both ends, as in a whole crowd;
+#   'fo' + dir + dist  it owns the FAST row, the partner is another rank's: it decides the fast row's end alone (one-sided);
+#   'fr' + dir + dist  the fast row is another rank's (its tile's speed comes from rows that arrived by the exchange), it owns the
+#                      PARTNER and decides the partner's end alone;
+#   dir  '+' / '-'     the remote row's tile index lies above / below the own row's,
+#   dist 'w' / 'b'     within / beyond n_t / 2 ahead of it (2 ((remote - own) mod n_t) < n_t).
+# Every role must occur with the fast row at lanes 0, 31, 32 and 63 over the cells (the host file asserts it).
+ONE_SIDED = tuple(k + d + w for k in ("fo", "fr") for d in "+-" for w in "wb")
+ROLES = ("oo",) + ONE_SIDED
+ROLE_LANES = (0, 31, 32, 63)
+
+
+@dataclass(frozen=True)
+class ShardSpec:
+    crowd: str
+    world: int
+    bounds: tuple              # row bounds of the ranks, bounds[0] = 0, bounds[world] = N
+    roles: tuple               # per designed pair: ((rank, role), ...) of the one or two ranks that own one of its rows
+    cut: tuple = ()            # ragged bounds, per designed pair: the fast TILE is cut by a bound and the rank that owns the partner owns rows
+    #                            of it -- 'own': the fast row among them, 'other': the fast row is the other rank's; '': neither
+    partition: tuple = ()      # (gx, gy) rank blocks (sfm_set_partition); (): the plain packing of an upload
+    tag: str = ""
+
+    @property
+    def name(self):
+        return f"{self.crowd}-w{self.world}{self.tag}"
+
+    @property
+    def aligned(self):
+        return all(b % WAVE == 0 for b in self.bounds[:-1])
+
+
+def _eq(n, world):
+    return tuple(n * k // world // WAVE * WAVE for k in range(world)) + (n,)
+
+
+_ROLES_S = {       # the pairs of _TYPES: (1, 3), (0, 6), (5, 4), (7, 2)
+    2: ((((0, "oo"),), ((0, "fo+b"), (1, "fr-w")), ((1, "oo"),), ((0, "fr+b"), (1, "fo-w")))),
+    4: ((((0, "fo+w"), (1, "fr-b")), ((0, "fo+b"), (3, "fr-w")), ((2, "oo"),), ((1, "fr+b"), (3, "fo-w")))),
+    8: ((((1, "fo+w"), (3, "fr-b")), ((0, "fo+b"), (6, "fr-w")), ((4, "fr+w"), (5, "fo-b")), ((2, "fr+b"), (7, "fo-w")))),
+}
+_ROLES_R = {       # _R: (8, 3), (0, 5), (1, 6), (7, 2) at N = 529, nine tiles
+    2: ((0, 256, 529), (((0, "fr+b"), (1, "fo-w")), ((0, "fo+b"), (1, "fr-w")), ((0, "fo+b"), (1, "fr-w")), ((0, "fr+b"), (1, "fo-w")))),
+    4: ((0, 128, 256, 384, 529), (((1, "fr+b"), (3, "fo-w")), ((0, "fo+b"), (2, "fr-w")), ((0, "fo+b"), (3, "fr-w")), ((1, "fr+b"), (3, "fo-w")))),
+    8: ((0, 64, 128, 192, 256, 320, 384, 448, 529),
+        (((3, "fr+b"), (7, "fo-w")), ((0, "fo+b"), (5, "fr-w")), ((1, "fo+b"), (6, "fr-w")), ((2, "fr+b"), (7, "fo-w")))),
+}
+_ROLES_A = {       # _A: (0, 5), (1, 6), (7, 2), (4, 3)
+    2: (((0, "fo+b"), (1, "fr-w")), ((0, "fo+b"), (1, "fr-w")), ((0, "fr+b"), (1, "fo-w")), ((0, "fr+w"), (1, "fo-b"))),
+    4: (((0, "fo+b"), (2, "fr-w")), ((0, "fo+b"), (3, "fr-w")), ((1, "fr+b"), (3, "fo-w")), ((1, "fr+w"), (2, "fo-b"))),
+}
+_ROLES_B = {       # _B: (5, 0), (6, 1), (2, 7), (3, 4)
+    2: (((0, "fr+b"), (1, "fo-w")), ((0, "fr+b"), (1, "fo-w")), ((0, "fo+b"), (1, "fr-w")), ((0, "fo+w"), (1, "fr-b"))),
+    4: (((0, "fr+b"), (2, "fo-w")), ((0, "fr+b"), (3, "fo-w")), ((1, "fo+b"), (3, "fr-w")), ((1, "fo+w"), (2, "fr-b"))),
+}
+_ROLES_C3 = (((1, "oo"),), ((1, "fo+w"), (2, "fr-b")), ((0, "fo+b"), (2, "fr-w")), ((1, "fr+w"), (2, "fo-b")))
+_ROLES_MID = {     # two strips of sixteen tiles: a pair's tiles are n_t / 2 apart
+    2: (((0, "fr+b"), (1, "fo-b")), ((0, "fo+b"), (1, "fr-b")), ((0, "fo+b"), (1, "fr-b"))),
+    4: (((0, "fr+b"), (2, "fo-b")), ((0, "fo+b"), (2, "fr-b")), ((1, "fo+b"), (3, "fr-b"))),
+}
+_ROLES_W15 = {
+    2: (((0, "fr+b"), (1, "fo-b")), ((0, "fo+b"), (1, "fr-b"))),
+    4: (((1, "fr+b"), (3, "fo-b")), ((0, "fo+b"), (2, "fr-b"))),
+}
+SHARDS = {s.name: s for s in (
+    # units, whole tiles: 4 | 4, two each, one each (no own-own pair: every designed pair is one-sided on both ranks)
+    [ShardSpec(c + z, w, _eq(512, w), _ROLES_S[w]) for c in ("s0", "s1", "s2", "s3") for z in ("", "z") for w in (2, 4, 8)]
+    + [ShardSpec(c, w, *_ROLES_R[w]) for c in ("ragged", "ragged3") for w in (2, 4, 8)]
+    + [ShardSpec("starters", w, _eq(512, w), _ROLES_A[w]) for w in (2, 4)] + [ShardSpec("carry3", w, _eq(512, w), _ROLES_B[w]) for w in (2, 4)]
+    # units, ragged bounds: every rank takes the ordered kernel, whose keep mask then works on tiles it owns only part of
+    + [ShardSpec("c2a", 2, (0, 200, 512), (((0, "fo+w"), (1, "fr-b")), ((0, "oo"),), ((1, "oo"),), ((0, "fr+w"), (1, "fo-b"))),
+                 cut=("other", "", "", "")),
+       ShardSpec("c2bz", 2, (0, 200, 512), (((1, "oo"),), ((0, "oo"),), ((1, "oo"),), ((0, "fr+w"), (1, "fo-b"))), cut=("own", "", "", "")),
+       ShardSpec("c3", 3, (0, 100, 300, 512), _ROLES_C3, cut=("own", "other", "", "")),
+       ShardSpec("c3z", 3, (0, 100, 300, 512), _ROLES_C3, cut=("own", "other", "", ""))]
+    # stacks: one strip per rank (every cross-strip pair is remote on both sides), half a strip each
+    + [ShardSpec(c + z, w, _eq(2048, w), r[w]) for c, r in (("strip-mid", _ROLES_MID), ("strip-w15", _ROLES_W15)) for z in ("", "3")
+       for w in (2, 4)]
+    # rank blocks: two columns by x of two blocks by y -- a block is half a strip, and the block packing leaves the designed tiles
+    + [ShardSpec("strip-mid", 4, _eq(2048, 4), _ROLES_MID[4], partition=(2, 2), tag="-2x2")]
+)}
+
+
+@dataclass(frozen=True)
+class ShardCell:
+    kind: str                  # 'plain' | 'ragged' | 'split' | 'starters'
+    shard: str
+    rad: bool
+    env: tuple
+    split: bool = False        # the integrating tick as begin / exchange / end (else run(1))
+
+    @property
+    def spec(self):
+        return SHARDS[self.shard]
+
+    @property
+    def id(self):
+        knobs = "-".join(f"{k[4:].lower()}{v}" for k, v in self.env if k in ("SFM_STRIPS", "SFM_IPW", "SFM_TEAM"))
+        return f"{self.kind}-{self.shard}-{'rad' if self.rad else 'norad'}" + (f"-{knobs}" if knobs else "") + ("-split" if self.split else "")
+
+
+def _shard_env(crowd_, strips=0, **more):
+    """SFM_SYM=1 throughout: a rank takes the ordered kernel because of its bounds, not because of a knob."""
+    reorder = 1 if SPECS[crowd_].packed else 0
+    return (("SFM_SYM", 1), ("SFM_CUTOFF", 1), ("SFM_FUSED", 0), ("SFM_REORDER", reorder), ("SFM_STRIPS", strips),
+            ("SFM_RESORT_EVERY", 0)) + tuple(more.items())
+
+
+def _plain(crowd_, world, rad, strips=0, tag=""):
+    return ShardCell("plain", f"{crowd_}-w{world}{tag}", rad, _shard_env(crowd_, strips))
+
+
+_STACKS = ("strip-mid", "strip-w15", "strip-mid3", "strip-w153")
+SHARD_CELLS = (
+    [_plain(c, 8, rad) for c, rad in (("s0", False), ("s1z", True), ("s2", True), ("s3z", False), ("ragged", False), ("ragged3", True))]
+    + [_plain(c, 2, rad) for c, rad in (("s0z", False), ("s1", True), ("ragged", False), ("ragged3", True))]
+    + [_plain(c, 4, rad) for c, rad in (("s2z", True), ("s3", False), ("ragged", True), ("ragged3", False))]
+    + [ShardCell("ragged", f"{c}-w{w}", rad, _shard_env(c, SFM_IPW=ipw, SFM_TEAM=team))
+       for c, w, rad, ipw, team in (("c2a", 2, False, 4, 1), ("c2bz", 2, True, 4, 1), ("c3", 3, True, 8, 4), ("c3z", 3, False, 8, 4))]
+    + [_plain(c, w, (k + w // 2 + strips) % 2 == 1, strips) for k, c in enumerate(_STACKS) for w in (2, 4) for strips in (0, 1)]
+    + [_plain("strip-mid", 4, True, 1, tag="-2x2")]
+    + [ShardCell("split", s, rad, _shard_env(SHARDS[s].crowd, strips), split=True)
+       for s, rad, strips in (("s0-w2", False, 0), ("s1z-w4", True, 0), ("strip-mid-w2", True, 1), ("strip-w153-w4", False, 1),
+                              ("carry3-w2", True, 0), ("carry3-w4", False, 0))]
+    + [ShardCell("starters", f"{c}-w{w}", rad, _shard_env(c), split=split)
+       for c, rad in (("starters", True), ("carry3", False)) for w in (2, 4) for split in (False, True)]
+)
+# The integrating split-tick cells, dt = DT_SPLIT: the designed term moves the partner's v' by >= VELOCITY_FACTOR allowances of
+# check_velocity (at dt = 0.05 by 40-60).  The allowance is 1e-5 |v'|, and the fast row's own |v'| is 20-40 times its partner's (5 m/s;
+# in 3-D the cap, 1.3 x its planar target speed, takes the v_z off it and most of the term's effect with it): on the fast row's end the
+# term moves v' by 25-60 allowances, held to VELOCITY_FACTOR_FAST -- a dropped end still misses check_velocity twentyfold -- and to
+# VELOCITY_FACTOR in the 3-D crowd whose fast rows no cap touches, 'carry3'.
+DT_SPLIT = DT_CARRY
+VELOCITY_FACTOR, VELOCITY_FACTOR_FAST = 100.0, 20.0
