@@ -44,6 +44,8 @@ SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_
                             "sfm_batch_observe_vehicles", "sfm_batch_download_vehicle_observations",
                             "sfm_batch_set_vehicle_scan", "sfm_batch_scan_vehicles",
                             "sfm_batch_download_vehicle_scan",
+                            "sfm_batch_set_vehicle_grid", "sfm_batch_grid_vehicles",
+                            "sfm_batch_download_vehicle_grid",
                             "sfm_batch_set_routes", "sfm_batch_plan_routes", "sfm_batch_plan_routes_device",
                             "sfm_batch_download_routes",
                             "sfm_batch_set_vehicle_autopilot", "sfm_batch_download_vehicle_autopilot",
@@ -56,6 +58,7 @@ UNBUMPED = ("sfm_batch_set_restart_noise", "sfm_batch_download_restart_noise",
             "sfm_batch_set_vehicle_observation", "sfm_batch_observe_vehicles",
             "sfm_batch_download_vehicle_observations",
             "sfm_batch_set_vehicle_scan", "sfm_batch_scan_vehicles", "sfm_batch_download_vehicle_scan",
+            "sfm_batch_set_vehicle_grid", "sfm_batch_grid_vehicles", "sfm_batch_download_vehicle_grid",
             "sfm_batch_set_routes", "sfm_batch_plan_routes", "sfm_batch_plan_routes_device",
             "sfm_batch_download_routes",
             "sfm_batch_set_vehicle_autopilot", "sfm_batch_download_vehicle_autopilot",
@@ -215,6 +218,10 @@ SYMBOLS = {
     "sfm_batch_set_vehicle_scan": (C.c_int, [_H, C.c_int, _F, _F, _F, _F, _F, _U8, C.c_int, C.c_float, C.c_float]),
     "sfm_batch_scan_vehicles": (C.c_int, [_H]),
     "sfm_batch_download_vehicle_scan": (C.c_int, [_H, _F]),
+    # batch bird's-eye grids around the vehicles (ABI 17, added without a bump)
+    "sfm_batch_set_vehicle_grid": (C.c_int, [_H, C.c_int, C.c_int, _F, _U8, C.c_int, C.c_float, C.c_float]),
+    "sfm_batch_grid_vehicles": (C.c_int, [_H]),
+    "sfm_batch_download_vehicle_grid": (C.c_int, [_H, _F]),
     # batch routes over walk graphs (ABI 17, added without a bump)
     "sfm_batch_set_routes": (C.c_int, [_H, _I, _F, _F, _I, _I, _F, _U8, _U8, _F, _F, C.c_int]),
     "sfm_batch_plan_routes": (C.c_int, [_H, _U8]),

@@ -67,7 +67,7 @@ static void drop_batch_boxes(SfmBatch* b) {
     b->drive = {};                                                // (the commands and the vehicle observations are per vehicle)
     b->vobs = {};
     b->vscan = {};                                                // (... and so are the vehicles' range scans)
-    b->boxes = {};
+    b->boxes = {};                                                // (with the vehicles' grids, which live inside)
 }
 
 static void drop_batch_modes(SfmBatch* b) {
@@ -442,6 +442,7 @@ int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x
     b->grid = {};                                                 // ... and its grids (the slots are per row)
     b->replay = {};                                               // ... and its observed tracks (the roles are per row)
     b->vscan = {};                                                // ... and the vehicles' scans of it
+    b->boxes.vgrid = {};                                          // ... and the vehicles' grids of it
     b->snap.on = false;                                           // ... and so is its snapshot
     b->have_state = false;
     if (n > 0) {

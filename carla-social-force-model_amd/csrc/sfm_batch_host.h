@@ -21,6 +21,20 @@ struct BatchGeoDev {           // one kind of polylines over all scenes
     int P = 0;
 };
 
+// bird's-eye grids around the vehicles (sfm_batch_set_vehicle_grid): the settings and the buffer sfm_batch_grid_vehicles fills;
+// nothing a tick reads or writes.  They live inside the boxes they refer to (BatchBoxesDev::vgrid: slots and buffer are per
+// vehicle), so whatever replaces or drops the boxes drops them with no line of its own; sfm_batch_upload_state drops them too.
+struct BatchVehGridDev {
+    bool on = false;           // (not "buf is allocated": a batch without gridded vehicles can be gridded and has no buffer)
+    int GU = 0, GV = 0;
+    int frame = 0;
+    float centre_x = 0.f, centre_y = 0.f;  // the middle of the window in the vehicle frame
+    size_t M = 0;              // gridded vehicles: the slots of buf
+    DevBuf<float> cell;        // [B]
+    DevBuf<int> slot;          // [M]; not allocated: every vehicle is gridded, slot = vehicle
+    DevBuf<float> buf;         // [M'][8][GV][GU]
+};
+
 // device-side vehicles (sfm_batch_set_dynamic_boxes): geo[2].ctr / .pts hold the vehicles the next tick sees, ctr_alt / pts_alt
 // (the same sizes) the half an integrating tick writes; batch_launch swaps them after each such launch
 struct BatchBoxesDev {
@@ -30,6 +44,7 @@ struct BatchBoxesDev {
     DevBuf<float4> ctr_alt;
     DevBuf<float2> pts_alt;
     std::vector<int32_t> item_off_h;   // the vehicles' scene_item_off [B+1] on the host
+    BatchVehGridDev vgrid;     // the bird's-eye grids around these vehicles (sfm_batch_set_vehicle_grid)
 };
 
 // scripted vehicle tracks (sfm_batch_set_vehicle_tracks, ABI 12): read-only on the device; dropped with the boxes they refer to
@@ -317,6 +332,8 @@ constexpr const char* VEHICLE_OBS_OFF = "vehicle observations are off: call sfm_
                                         "(sfm_batch_set_dynamic_boxes and sfm_batch_set_dynamic_obstacles drop them)";
 constexpr const char* VEHICLE_SCAN_OFF = "vehicle scans are off: call sfm_batch_set_vehicle_scan first (sfm_batch_upload_state, "
                                          "sfm_batch_set_dynamic_boxes and sfm_batch_set_dynamic_obstacles drop them)";
+constexpr const char* VEHICLE_GRID_OFF = "vehicle grids are off: call sfm_batch_set_vehicle_grid first (sfm_batch_upload_state, "
+                                         "sfm_batch_set_dynamic_boxes and sfm_batch_set_dynamic_obstacles drop them)";
 constexpr const char* NO_BOXES = "this needs device-side vehicles: call sfm_batch_set_dynamic_boxes first";
 constexpr const char* ROUTES_OFF = "routes are off: call sfm_batch_set_routes first (sfm_batch_upload_state and sfm_batch_set_mode_fsm drop them)";
 constexpr const char* GRIDS_OFF ="grids are off: call sfm_batch_set_grid first (sfm_batch_upload_state drops them)";
@@ -350,6 +367,8 @@ int batch_launch(SfmBatch* b, uint32_t flags, float4* frame = nullptr, float2* z
 int batch_replay_step_lengths(SfmBatch* b, const float* dt);
 // The vehicle scan's one launch (sfm_batch_vehicle_scan.hip).
 hipError_t launch_batch_vehicle_scan(const VehicleScanArgs& a, int B, hipStream_t st);
+// The vehicle grid's one launch (sfm_batch_vehicle_grid.hip).
+hipError_t launch_batch_vehicle_grid(const VehicleGridArgs& a, int B, hipStream_t st);
 // The autopilot (sfm_batch_autopilot_capi.hip, sfm_batch_autopilot.hip).  batch_autopilot_launch: the controller launch batch_launch
 // puts in front of an integrating tick while the autopilot is on.  batch_autopilot_snapshot: the cursors into the snapshot, with
 // the other arrays of sfm_batch_snapshot.  batch_autopilot_restart: the cursors of the chosen scenes back, one small launch behind

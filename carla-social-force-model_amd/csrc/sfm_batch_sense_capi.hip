@@ -70,7 +70,7 @@ static int build_scan(SfmBatch* b, size_t items, int max_rays, const char* whose
 
 // One lookup for the device buffers a caller may see: which = SFM_BATCH_PTR_*, or PTR_OBSERVATIONS for sfm_batch_observation_ptr's.
 // off: why there is none (its feature is off, no state was uploaded), else p and bytes -- both 0 where the buffer has no element.
-constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_ROUTE_STATUS + 1;    // (not part of the ABI: sfm_batch_device_ptr refuses it)
+constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_VEHICLE_GRID + 1;   // (not part of the ABI: sfm_batch_device_ptr refuses it)
 struct BatchBuffer { const char* off; void* p; size_t bytes; };
 static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     const size_t n = (size_t)b->n_total, B = (size_t)b->B;
@@ -105,6 +105,9 @@ static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     case SFM_BATCH_PTR_VEHICLE_SCAN:
         if (!b->vscan.on) return {VEHICLE_SCAN_OFF, nullptr, 0};
         return have(b->vscan.buf, sizeof(float) * (size_t)b->geo[2].K * (size_t)(2 * b->vscan.R));
+    case SFM_BATCH_PTR_VEHICLE_GRID:
+        if (!b->boxes.vgrid.on) return {VEHICLE_GRID_OFF, nullptr, 0};
+        return have(b->boxes.vgrid.buf, sizeof(float) * b->boxes.vgrid.M * (size_t)SFM_BATCH_VEHICLE_GRID_CHANNELS * (size_t)b->boxes.vgrid.GU * (size_t)b->boxes.vgrid.GV);
     case SFM_BATCH_PTR_ROUTE_GOALS:
     case SFM_BATCH_PTR_ROUTE_STATUS:
         if (!b->routes.on) return {ROUTES_OFF, nullptr, 0};
@@ -153,7 +156,7 @@ void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes) {
                        (which == SFM_BATCH_PTR_GRID && b->grid.on) ||
                        ((which == SFM_BATCH_PTR_ROW_SCORES || which == SFM_BATCH_PTR_SCENE_SCORES) && b->replay.on) ||
                        (which == SFM_BATCH_PTR_VEHICLE_COMMANDS && b->drive.on) || (which == SFM_BATCH_PTR_VEHICLE_OBS && b->vobs.on) ||
-                       which == SFM_BATCH_PTR_VEHICLE_SCAN ||
+                       which == SFM_BATCH_PTR_VEHICLE_SCAN || (which == SFM_BATCH_PTR_VEHICLE_GRID && b->boxes.vgrid.on) ||
                        ((which == SFM_BATCH_PTR_ROUTE_GOALS || which == SFM_BATCH_PTR_ROUTE_STATUS) && b->routes.on);
     if (!known) { bfail(b, SFM_ERR_INVALID, "which must be SFM_BATCH_PTR_COMMANDS, _STATE, _ZSTATE, _EPISODES, _DONE or _SCAN"); return nullptr; }
     return buffer_ptr(b, which, which == SFM_BATCH_PTR_SCAN ? ", so which = SFM_BATCH_PTR_SCAN has no buffer" :
@@ -394,5 +397,68 @@ int sfm_batch_grid(SfmBatch* b) {
 }
 
 int sfm_batch_download_grid(SfmBatch* b, float* out) { return download_buffer(b, SFM_BATCH_PTR_GRID, out); }
+
+// Bird's-eye grids around the vehicles (ABI 17, added without a bump).  Everything is checked before anything is allocated or freed.
+int sfm_batch_set_vehicle_grid(SfmBatch* b, int GU, int GV, const float* cell, const uint8_t* mask, int frame, float centre_x,
+                               float centre_y) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!cell) {
+        HIP_TRY(b, hipStreamSynchronize(b->stream));             // a grid launch in flight may still write the buffer
+        b->boxes.vgrid = {};
+        return SFM_OK;
+    }
+    if (!b->have_state) return bfail(b, SFM_ERR_STATE, NO_STATE);
+    if (!b->boxes.on) return bfail(b, SFM_ERR_STATE, std::string("vehicle grids: ") + NO_BOXES);
+    const int side = SFM_BATCH_MAX_VEHICLE_GRID_SIDE;
+    if (GU < 1 || GU > side || GV < 1 || GV > side)
+        return bfail(b, SFM_ERR_INVALID, "GU and GV must be 1 .. " + std::to_string(side) + " cells, got " + std::to_string(GU) + " x " + std::to_string(GV));
+    if (GU * GV > VEHICLE_GRID_MAX_CELLS)
+        return bfail(b, SFM_ERR_INVALID, "GU * GV must be at most " + std::to_string(VEHICLE_GRID_MAX_CELLS) + " cells, got " + std::to_string(GU * GV));
+    if ((rc = check_frame(b, frame, "vehicle"))) return rc;
+    if (!std::isfinite(centre_x) || !std::isfinite(centre_y) || std::fabs(centre_x) > SFM_BATCH_MAX_SENSE_RANGE ||
+        std::fabs(centre_y) > SFM_BATCH_MAX_SENSE_RANGE)
+        return bfail(b, SFM_ERR_INVALID, "the centre must be finite and within 1e6 metres of the vehicle's centre");
+    const size_t B = (size_t)b->B, K = (size_t)b->geo[2].K;
+    for (size_t s = 0; s < B; ++s)
+        if ((rc = batch_metres(b, s, "cell", cell[s], true, nullptr))) return rc;   // (the size goes to the kernel as the fp32 value given)
+    BatchVehGridDev o;
+    o.M = K;                                                     // no mask: every vehicle, slot = vehicle
+    if (mask && K > 0) {
+        std::vector<int32_t> slot(K);
+        o.M = pack_grid_slots(mask, K, slot.data());
+        HIP_TRY(b, o.slot.alloc(K));
+        HIP_TRY(b, hipMemcpy(o.slot, slot.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice));
+    }
+    const size_t vals = o.M * (size_t)SFM_BATCH_VEHICLE_GRID_CHANNELS * (size_t)GU * (size_t)GV;    // (64 bits)
+    HIP_TRY(b, o.cell.alloc(B));
+    HIP_TRY(b, hipMemcpy(o.cell, cell, sizeof(float) * B, hipMemcpyHostToDevice));
+    if (vals > 0) {
+        HIP_TRY(b, o.buf.alloc(vals));
+        HIP_TRY(b, hipMemsetAsync(o.buf, 0, sizeof(float) * vals, b->stream));
+    }
+    o.GU = GU;
+    o.GV = GV;
+    o.frame = frame;
+    o.centre_x = centre_x;
+    o.centre_y = centre_y;
+    o.on = true;
+    HIP_TRY(b, hipStreamSynchronize(b->stream));                 // the zero fill; and a grid launch in flight may still write the old buffer
+    b->boxes.vgrid = std::move(o);
+    return SFM_OK;
+}
+
+int sfm_batch_grid_vehicles(SfmBatch* b) {
+    int rc = bbind(b);
+    if (rc) return rc;
+    if (!b->boxes.vgrid.on) return bfail(b, SFM_ERR_STATE, VEHICLE_GRID_OFF);
+    if (b->boxes.vgrid.M == 0) return SFM_OK;                          // no gridded vehicle: nothing to write
+    const VehicleGridArgs a{batch_scene_view(b), b->boxes.rot, b->boxes.vgrid.cell, b->boxes.vgrid.slot /* null: every vehicle */, b->boxes.vgrid.buf,
+                            b->boxes.vgrid.GU, b->boxes.vgrid.GV, b->boxes.vgrid.frame, b->boxes.vgrid.centre_x, b->boxes.vgrid.centre_y, 0};
+    HIP_TRY(b, launch_batch_vehicle_grid(a, b->B, b->stream));
+    return SFM_OK;
+}
+
+int sfm_batch_download_vehicle_grid(SfmBatch* b, float* out) { return download_buffer(b, SFM_BATCH_PTR_VEHICLE_GRID, out); }
 
 }  // extern "C"

@@ -523,6 +523,24 @@ struct VehicleScanArgs : BatchSceneView {
 static_assert(sizeof(VehicleScanArgs) == 120 + 56, "the vehicle scan kernel's arguments follow the view without padding");
 static_assert(VEHICLE_SCAN_MAX_RAYS <= BLOCK, "the direction table is staged by one pass of the workgroup");
 
+// Bird's-eye grids around the vehicles of a batch (sfm_batch_grid_vehicles, sfm_batch_vehicle_grid_kernel in
+// sfm_batch_vehicle_grid.hip): everything but out is read only.  The vehicles are geo[2]'s items; a vehicle's own ring is no source.
+constexpr int VEHICLE_GRID_MAX_SIDE = 64;              // cells along one axis
+constexpr int VEHICLE_GRID_MAX_CELLS = 1024;           // GU * GV: a lane of the workgroup owns at most four cells
+constexpr int VEHICLE_GRID_CHANNELS = 8;
+struct VehicleGridArgs : BatchSceneView {
+    const float2* rot;        // [M] the vehicles' headings {cos, sin}, as the next tick reads them
+    const float* cell;        // [B] the cell size, the fp32 value as given
+    const int* slot;          // [M] the vehicle's slot in out, -1: the vehicle is not gridded; null: every vehicle, slot = vehicle
+    float* out;               // [M'][8][GV][GU]
+    int GU, GV;               // cells along x (frame 1: forward) and along y, 1 .. VEHICLE_GRID_MAX_SIDE, GU * GV <= VEHICLE_GRID_MAX_CELLS
+    int frame;                // 0 world axes, 1 the vehicle's heading frame
+    float centre_x, centre_y; // the middle of the window in the vehicle frame (x forward), one pair for the batch
+    int pad;
+};
+static_assert(sizeof(VehicleGridArgs) == 120 + 56, "the vehicle grid kernel's arguments follow the view without padding");
+static_assert(VEHICLE_GRID_MAX_CELLS <= 4 * BLOCK, "a lane owns at most four cells");
+
 // The vehicle autopilot of a batch (sfm_batch_set_vehicle_autopilot, sfm_batch_vehicle_autopilot_kernel in sfm_batch_autopilot.hip):
 // launched in front of every integrating tick; it reads what that tick will read and writes the commands of the autopiloted vehicles,
 // their cursors and their records.  The rule is specified in include/sfm_hip.h.

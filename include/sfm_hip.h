@@ -1160,6 +1160,62 @@ int sfm_batch_set_vehicle_scan(SfmBatch* b, int R, const float* dir_x, const flo
                                float mount_x, float mount_y);
 int sfm_batch_scan_vehicles(SfmBatch* b);
 int sfm_batch_download_vehicle_scan(SfmBatch* b, float* out);
+/* Bird's-eye grids around the vehicles: the raster a CNN driving policy or a planner consumes, by ONE launch of
+ * sfm_batch_vehicle_grid_kernel (a workgroup per scene, which loops over the scene's gridded vehicles; no float atomics) over the
+ * buffers the next tick would read.  It writes only its own buffer.  sfm_batch_grid is centred on a pedestrian row, square, turned by
+ * the row's derived heading, counts every vehicle ring and records no vehicle velocity; this is centred on a device-side vehicle
+ * (sfm_batch_set_dynamic_boxes), GU x GV with the window's middle anywhere in the vehicle frame, turned by the STORED heading,
+ * leaves the vehicle's OWN ring out and records the other vehicles' velocities per cell.
+ * These three entry points and SFM_BATCH_PTR_VEHICLE_GRID were added WITHOUT a bump of SFM_ABI_VERSION (it stays 17), like the
+ * vehicles' range scans: additions only, and a build that has them is recognised by the symbols.
+ *
+ * Settings (sfm_batch_set_vehicle_grid), for the whole batch unless marked per scene.  GU: cells along x (frame 1: forward), GV:
+ * cells along y; each 1 .. SFM_BATCH_MAX_VEHICLE_GRID_SIDE and GU * GV <= 1024.  cell[b]: the cell size in metres, per scene,
+ * finite, 0 < c <= SFM_BATCH_MAX_SENSE_RANGE, used as the fp32 value.  mask [M] uint8_t, or NULL for every vehicle, M the number of
+ * device-side vehicles in concatenated order: the masked vehicles get compact slots in ascending order, a vehicle outside the mask
+ * costs nothing and has no record.  frame: SFM_OBS_FRAME_WORLD (0) or SFM_OBS_FRAME_HEADING (1, the vehicle's stored heading
+ * frame).  centre_x, centre_y: where the middle of the window lies in the vehicle frame, metres, x forward; fp32, finite,
+ * |.| <= 1e6; one pair for the batch.  (GU = 48, 0.5 m cells, centre = (8, 0): the window spans 4 m behind to 20 m ahead.)
+ *
+ * Record: [M'][SFM_BATCH_VEHICLE_GRID_CHANNELS][GV][GU] floats for M' gridded vehicles, slot-major: cell [cv][cu] of channel ch
+ * of a slot is float ((slot * 8 + ch) * GV + cv) * GU + cu.  For vehicle k with centre (cx, cy) and velocity (vx_k, vy_k) -- its
+ * ctr entry, as sfm_batch_observe_vehicles reads them -- and stored heading (hx, hy), used as stored and never renormalised:
+ *   0     the number of live pedestrians in the cell: every live row counts, none is excluded
+ *   1, 2  the sum of their velocities relative to the vehicle, (vx_j - vx_k, vy_j - vy_k), in ascending j, by fp32 adds from 0.0f
+ *   3     the number of border points            4     the number of static-obstacle ring points
+ *   5     the number of ring points of the scene's OTHER vehicles: vehicle k's own ring is skipped by its index range
+ *   6, 7  the sum over those ring points of the owning vehicle's velocity relative to vehicle k (every point of one vehicle adds
+ *         the same term), in ascending (vehicle, point) order, by fp32 adds from 0.0f
+ * Frame 1 rotates the velocities of channels 1, 2, 6 and 7 like the positions.  Counts are exact.
+ * Rules, all exact: every value is one correctly rounded fp32 operation or an fmaf.
+ *   Present: iff |cx| < 1e12 and |cy| < 1e12 (sfm_batch_observe's live test; NaN fails it).  Otherwise the WHOLE record is zeros.
+ *   Origin:  the vehicle scan's rule with the centre (mx, my) as the mount: rx = fmaf(hx, mx, -(hy * my));
+ *            ry = fmaf(hy, mx, hx * my);  ox = cx + rx;  oy = cy + ry
+ *   Per source at (px, py):  ax = px - ox;  ay = py - oy.  Frame 0: fx = ax, fy = ay.  Frame 1: fx = fmaf(hx, ax, hy * ay),
+ *            fy = fmaf(hx, ay, -(hy * ax)).  pu = fx / c + 0.5f * GU;  pv = fy / c + 0.5f * GV  (the division is rounded first).
+ *            Inside iff 0 <= pu < GU and 0 <= pv < GV by float compares -- NaN and a ring at +inf fail by themselves --; then
+ *            cu = (int)pu, cv = (int)pv.
+ * Only {x, y, vx, vy} of the state is used: a 3-D batch gives the planar record.  A scene with vehicles and no pedestrians still
+ * grids its geometry.  There are no float atomics and every order is a function of the scene alone: a scene's record is bitwise
+ * the same alone or anywhere in any batch.
+ *
+ * Lifetime, the vehicle scan's: sfm_batch_set_vehicle_grid allocates and zero-fills the buffer (its size computed in 64 bits) and
+ * waits for the batch's stream; cell = NULL switches the grid off and frees the buffer.  Refused with nothing changed: no state, or
+ * no device-side vehicles (SFM_ERR_STATE); GU or GV out of bounds or a product over 1024; frame outside {0, 1}; a cell size or a
+ * centre that is not finite or out of bounds.  sfm_batch_upload_state, sfm_batch_set_dynamic_boxes and
+ * sfm_batch_set_dynamic_obstacles drop it; every other call keeps it, snapshot and restart included.
+ * sfm_batch_grid_vehicles: ONE launch on the batch's stream; the host does not wait.  With no gridded vehicle it launches nothing
+ * and succeeds.  sfm_batch_download_vehicle_grid synchronises the stream and copies the buffer (zeros before the first launch).
+ * SFM_BATCH_PTR_VEHICLE_GRID (sfm_batch_device_ptr): the buffer on the device, valid until the next sfm_batch_set_vehicle_grid or
+ * a call that drops the grid.  While the grid is off the launch and the download give SFM_ERR_STATE, and the pointer value is
+ * refused as the unknown value it was. */
+#define SFM_BATCH_PTR_VEHICLE_GRID 15
+#define SFM_BATCH_VEHICLE_GRID_CHANNELS 8
+#define SFM_BATCH_MAX_VEHICLE_GRID_SIDE 64
+int sfm_batch_set_vehicle_grid(SfmBatch* b, int GU, int GV, const float* cell, const uint8_t* mask, int frame, float centre_x,
+                               float centre_y);
+int sfm_batch_grid_vehicles(SfmBatch* b);
+int sfm_batch_download_vehicle_grid(SfmBatch* b, float* out);
 /* Routes planned on the device over walk graphs: what path_planner.PedPathPlanner.generate_route gives a pedestrian at spawn time
  * -- its waypoint queue and the crossing flag of each leg -- by ONE launch of sfm_batch_plan_routes_kernel (a workgroup per chosen
  * scene, a wave per routed row; no atomics), from where each row stands to a goal read from a device buffer.  Route SEARCH over a
