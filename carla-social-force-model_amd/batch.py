@@ -1362,10 +1362,10 @@ class SfmBatch:
         ptr = self._lib.sfm_batch_device_ptr(self._b, int(which), C.byref(nbytes))
         if not ptr and which in (PTR_EPISODES, PTR_DONE):
             self._check(-1, "sfm_batch_device_ptr")                    # (episodes are off: the library's message)
-        if not ptr and which == PTR_GRID and self.grid_cells is not None and len(self._grid_rows) == 0:
-            return 0, 0                                                # (grids are on and no row is gridded: no buffer)
-        if not ptr and which == PTR_VEHICLE_GRID and self.vgrid_window is not None and len(self._vgrid_items) == 0:
-            return 0, 0                                                # (likewise without a gridded vehicle)
+        if not ptr and which in (PTR_GRID, PTR_VEHICLE_GRID):
+            on, items = (self.grid_cells, self._grid_rows) if which == PTR_GRID else (self.vgrid_window, self._vgrid_items)
+            if on is not None and len(items) == 0:
+                return 0, 0                                            # (the grid is on and no row, or vehicle, is gridded: no buffer)
         if not ptr and int(self.scene_off[-1]) > 0 and not (which == PTR_ZSTATE and self.planar):
             self._check(-1, "sfm_batch_device_ptr")                    # (without rows, and {z, vz} of a planar batch: no buffer)
         return int(ptr or 0), int(nbytes.value)
@@ -1648,10 +1648,38 @@ class SfmBatch:
                     "sfm_batch_set_vehicle_grid")
         self.vgrid_window, self._vgrid_items, self._vgrid_counts = (GU, GV), items, counts
 
-    def _need_vehicle_grid(self, name):
-        if self.vgrid_window is None:
-            self._check(self._lib.sfm_batch_grid_vehicles(self._b), "sfm_batch_grid_vehicles")    # (the library's message)
-            raise SfmLibraryError(f"SfmBatch.{name}: the vehicle grid is off (set_vehicle_grid)")
+    def _grid_kind(self, vehicles, name):
+        """What the two grids' readers share: the grid around the rows (``vehicles`` false) or around the vehicles as (GU, GV, the
+        item of every slot, slots per scene, channels, PTR_*, the download call).  Raises SfmLibraryError while that grid is off."""
+        if vehicles:
+            window, items, counts, rest = self.vgrid_window, self._vgrid_items, self._vgrid_counts, (
+                _grid.VEHICLE_GRID_CHANNELS, PTR_VEHICLE_GRID, "sfm_batch_download_vehicle_grid")
+            compute, off = "sfm_batch_grid_vehicles", "the vehicle grid is off (set_vehicle_grid)"
+        else:
+            window, items, counts, rest = self.grid_cells, self._grid_rows, self._grid_counts, (
+                _grid.GRID_CHANNELS, PTR_GRID, "sfm_batch_download_grid")
+            window, compute, off = window and (window, window), "sfm_batch_grid", "grids are off"
+        if window is None:
+            self._check(getattr(self._lib, compute)(self._b), compute)   # (the library's message, from the call itself)
+            raise SfmLibraryError(f"SfmBatch.{name}: {off}")
+        return (*window, items, counts, *rest)
+
+    def _grid_records(self, vehicles, name):
+        """The grid's whole buffer, downloaded and split by the scenes' slot counts."""
+        GU, GV, items, counts, channels, _, download = self._grid_kind(vehicles, name)
+        buf = np.zeros((len(items), channels, GV, GU), np.float32)
+        self._check(getattr(self._lib, download)(self._b, fptr(buf) if len(items) else None), download)
+        cut = np.concatenate([[0], np.cumsum(counts)])
+        return [buf[cut[b]:cut[b + 1]] for b in range(self.B)]
+
+    def _grid_alias(self, vehicles, name, device):
+        """The grid's buffer as a torch tensor (slots, channels, GV, GU) that aliases device memory."""
+        GU, GV, items, _, channels, which, _ = self._grid_kind(vehicles, name)
+        nbytes = C.c_int64(0)
+        ptr = self._lib.sfm_batch_device_ptr(self._b, which, C.byref(nbytes))
+        if not ptr and len(items) > 0:
+            self._check(-1, "sfm_batch_device_ptr")
+        return self._alias(ptr, (int(nbytes.value) // (4 * channels * GU * GV), channels, GV, GU), device)
 
     def grid_vehicles(self):
         """Compute the vehicle grids as the batch is now (sfm_batch_grid_vehicles): one launch on the batch's stream, ordered with
@@ -1660,31 +1688,19 @@ class SfmBatch:
 
     def vehicle_grid_items(self):
         """The vehicle (its index over the vehicles of all scenes, in concatenated order) of every slot, int64 (M',), ascending."""
-        self._need_vehicle_grid("vehicle_grid_items")
-        return self._vgrid_items.copy()
+        return self._grid_kind(True, "vehicle_grid_items")[2].copy()
 
     def vehicle_grids(self):
         """``grid_vehicles()`` and a download: a list of B float32 arrays (m_b, 8, GV, GU) in scene order, m_b the scene's gridded
         vehicles in ascending order (synchronises the batch's stream)."""
-        self._need_vehicle_grid("vehicle_grids")
         self.grid_vehicles()
-        (GU, GV), M = self.vgrid_window, len(self._vgrid_items)
-        buf = np.zeros((M, _grid.VEHICLE_GRID_CHANNELS, GV, GU), np.float32)
-        self._check(self._lib.sfm_batch_download_vehicle_grid(self._b, fptr(buf) if M else None), "sfm_batch_download_vehicle_grid")
-        cut = np.concatenate([[0], np.cumsum(self._vgrid_counts)])
-        return [buf[cut[b]:cut[b + 1]] for b in range(self.B)]
+        return self._grid_records(True, "vehicle_grids")
 
     def vehicle_grid_tensor(self, device=None):
         """The vehicle grid buffer as a torch tensor (M', 8, GV, GU) float32 that aliases device memory (no copy): what a conv layer
         reads after ``grid_vehicles()``.  Put torch and the batch on one stream.  Take it again after ``set_vehicle_grid``.  Raises
         SfmLibraryError while the vehicle grid is off."""
-        self._need_vehicle_grid("vehicle_grid_tensor")
-        nbytes = C.c_int64(0)
-        ptr = self._lib.sfm_batch_device_ptr(self._b, PTR_VEHICLE_GRID, C.byref(nbytes))
-        if not ptr and len(self._vgrid_items) > 0:
-            self._check(-1, "sfm_batch_device_ptr")
-        GU, GV = self.vgrid_window
-        return self._alias(ptr, (int(nbytes.value) // (4 * _grid.VEHICLE_GRID_CHANNELS * GU * GV), _grid.VEHICLE_GRID_CHANNELS, GV, GU), device)
+        return self._grid_alias(True, "vehicle_grid_tensor", device)
 
     def set_scan(self, max_range, ped_radius=None, point_radius=_scan.POINT_RADIUS, R=None, angles=None, mask=None, frame=0,
                  directions=None):
@@ -1761,11 +1777,6 @@ class SfmBatch:
         self._check(L.sfm_batch_set_grid(self._b, G, fptr(c), u8ptr(m), frame), "sfm_batch_set_grid")
         self.grid_cells, self._grid_rows, self._grid_counts = G, rows, counts
 
-    def _need_grid(self, name):
-        if self.grid_cells is None:                                    # (the library's message, from the call itself)
-            self._check(self._lib.sfm_batch_grid(self._b), "sfm_batch_grid")
-            raise SfmLibraryError(f"SfmBatch.{name}: grids are off")
-
     def grid(self):
         """Compute the grids as the state is now (sfm_batch_grid): one launch on the batch's stream, ordered with the ticks and
         restarts around it; the host does not wait.  Raises SfmLibraryError while grids are off."""
@@ -1773,31 +1784,19 @@ class SfmBatch:
 
     def grid_rows(self):
         """The global (concatenated) row of every slot of the grid buffer, int64 [M], ascending."""
-        self._need_grid("grid_rows")
-        return self._grid_rows.copy()
+        return self._grid_kind(False, "grid_rows")[2].copy()
 
     def grids(self):
         """``grid()`` and a download: a list of B float32 arrays (m_b, 6, G, G) in scene order, m_b the scene's gridded rows in
         ascending order (synchronises the batch's stream)."""
         self.grid()
-        self._need_grid("grids")
-        G, M = self.grid_cells, len(self._grid_rows)
-        buf = np.zeros((M, _grid.GRID_CHANNELS, G, G), np.float32)
-        self._check(self._lib.sfm_batch_download_grid(self._b, fptr(buf) if M else None), "sfm_batch_download_grid")
-        cut = np.concatenate([[0], np.cumsum(self._grid_counts)])
-        return [buf[cut[s]:cut[s + 1]] for s in range(self.B)]
+        return self._grid_records(False, "grids")
 
     def grid_tensor(self, device=None):
         """The grid buffer as a torch tensor (M, 6, G, G) float32 that aliases device memory (no copy): what a conv policy reads
         after ``grid()``.  Put torch and the batch on one stream.  Take it again after ``upload`` or ``set_grid``.  Raises
         SfmLibraryError while grids are off."""
-        self._need_grid("grid_tensor")
-        nbytes = C.c_int64(0)
-        ptr = self._lib.sfm_batch_device_ptr(self._b, PTR_GRID, C.byref(nbytes))
-        if not ptr and len(self._grid_rows) > 0:
-            self._check(-1, "sfm_batch_device_ptr")
-        G = self.grid_cells
-        return self._alias(ptr, (int(nbytes.value) // (4 * _grid.GRID_CHANNELS * G * G), _grid.GRID_CHANNELS, G, G), device)
+        return self._grid_alias(False, "grid_tensor", device)
 
     def set_observed(self, tracks, roles=None, every=1, v0=None):
         """The recording every scene is calibrated against (sfm_batch_set_observed; see ``replay.pack_observed`` and the module

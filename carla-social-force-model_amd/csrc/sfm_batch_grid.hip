@@ -11,19 +11,23 @@
 //   2. the rows that have a slot are compacted, in ascending order, into an LDS list by ballots and per-wave counts; when the
 //      scene's geometry fits one tile of GRID_TILE points it is staged in LDS once, else every row reads it from memory (a point
 //      is used once per row, by one lane);
-//   3. per gridded row, in list order (a row that is not live gets its zeros and is done):
-//      (a) lane t takes pedestrians t, t + BLOCK, ..: the cell of each and its relative velocity; the sources that fall inside
-//          the grid are compacted, by ballots again and so in ascending j, into an LDS list {cell, relative velocity};
-//          every lane takes geometry points e, e + BLOCK, .. of the three kinds' contiguous runs and counts the cell of each with an
+//   3. per gridded row, in list order (a row that is not live gets its zeros and is done): the window is the row's -- G x G cells
+//      around its position, in frame 1 turned by the scan kernel's heading (GridWindow, sfm_grid_cells.h: the rotation and the cell
+//      rule live there);
+//      (a) the OTHER live pedestrians are offered to the shared loop (GRID_OFFER): lane t takes pedestrians t, t + BLOCK, .., the
+//          sources inside the grid are compacted in ascending j into the LDS list {cell, relative velocity}, and the list -- it holds
+//          a whole scene, so once, at the end -- is walked in order into the cells tid, tid + BLOCK, .. the lane owns (G^2 <= 1024: up
+//          to 4; GRID_WALK and GRID_ADD, with the order and the wave test described there);
+//      (b) every lane takes geometry points e, e + BLOCK, .. of the three kinds' contiguous runs and counts the cell of each with an
 //          integer LDS add (the result of integer adds does not depend on their order);
-//      (b) a lane owns the cells tid, tid + BLOCK, .. (G^2 <= 1024: up to 4) and walks the source list in order -- broadcast LDS
-//          reads -- counting its matches and adding their velocities: ascending j, fp32 adds from 0.0f, no float atomic;
 //   4. the lane stores the 6 channels of its cells (consecutive lanes store consecutive floats) and clears the geometry counts it
 //      read; the next row's adds come behind the barriers of its phase (a).
+// What is this kernel's own: the list of gridded rows, the one-line staging of the tile (SceneRun::stage costs set-up here, as in the
+// scan kernel), that a source is a live row other than the gridded one, and the store with its three kinds of counts.
 // No register array is indexed at run time, so nothing goes to scratch.
 // Determinism: no float atomics, every order is a function of the scene alone -- a scene's record is bitwise the same alone or
 // anywhere in any batch.
-#include "sfm_device.h"
+#include "sfm_grid_cells.h"
 
 #pragma clang fp contract(off)     // every operation of the rules is a single rounding, or an explicit fmaf
 
@@ -41,24 +45,6 @@ struct GridShared {
     int wcount[WAVES_PER_BLOCK];
 };
 static_assert(sizeof(GridShared) <= 80 * 1024, "two workgroups share a CU's 160 KiB of LDS");
-
-// the rotation into the heading frame: the rules of include/sfm_hip.h
-__device__ __forceinline__ void grid_rotate(bool rot, float hx, float hy, float& a, float& b) {
-    if (rot) {
-        const float ra = fmaf(hx, a, hy * b), rb = fmaf(hx, b, -(hy * a));
-        a = ra;
-        b = rb;
-    }
-}
-
-// the cell [cv][cu] of a source at (ax, ay) relative to the row, as cv * G + cu; -1: outside (NaN and +-inf fail the compares)
-__device__ __forceinline__ int grid_cell(float ax, float ay, bool rot, float hx, float hy, float c, float half, float g, int G) {
-    grid_rotate(rot, hx, hy, ax, ay);
-    const float pu = ax / c + half;                                    // the division is rounded first (correctly: hipcc's default
-    const float pv = ay / c + half;                                    // for fp32 divide), then the sum
-    const bool in = pu >= 0.0f && pu < g && pv >= 0.0f && pv < g;
-    return in ? (int)pv * G + (int)pu : -1;
-}
 
 __global__ __launch_bounds__(BLOCK) void sfm_batch_grid_kernel(const GridArgs a) {
     __shared__ GridShared sh;
@@ -91,8 +77,7 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_grid_kernel(const GridArgs a)
         __syncthreads();
     }
 
-    const float c = a.cell[b], g = (float)G, half = 0.5f * g;          // (both exact)
-    const bool rot = a.frame != 0;                                     // uniform
+    GridWindow w(a.cell[b], G, G, a.frame != 0);                       // (rot: uniform)
     const size_t per_row = (size_t)GRID_CHANNELS * (size_t)cells;
 #pragma unroll 1
     for (int pos = 0; pos < n_grid; ++pos) {                           // uniform
@@ -104,76 +89,38 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_grid_kernel(const GridArgs a)
             for (int q = tid; q < (int)per_row; q += BLOCK) out[q] = 0.0f;
             continue;
         }
-        const float x = s.x, y = s.y, vx = s.z, vy = s.w;
-        float hx = 1.0f, hy = 0.0f;
-        if (rot) {                                                     // the scan kernel's heading, fp32 throughout
+        const float vx = s.z, vy = s.w;
+        w.ox = s.x;
+        w.oy = s.y;
+        w.hx = 1.0f;
+        w.hy = 0.0f;
+        if (w.rot) {                                                   // the scan kernel's heading, fp32 throughout
             const float4 o = a.own[s0 + row];
-            const float2 h = row_heading(vx, vy, o.x - x, o.y - y);
-            hx = h.x;
-            hy = h.y;
+            const float2 h = row_heading(vx, vy, o.x - s.x, o.y - s.y);
+            w.hx = h.x;
+            w.hy = h.y;
         }
 
-        // (a) the pedestrians inside the grid, ascending, with their cells and relative velocities
-        int n_src = 0;
-#pragma unroll 1
-        for (int base = 0; base < n; base += BLOCK) {                  // uniform
-            const int t = base + tid;
-            int cell = -1;
-            float rx = 0.0f, ry = 0.0f;
-            if (t < n && t != row) {
-                const float4 p = sh.pk[t];
-                if (row_live(p.x, p.y)) {
-                    cell = grid_cell(p.x - x, p.y - y, rot, hx, hy, c, half, g, G);
-                    rx = p.z - vx;
-                    ry = p.w - vy;
-                    grid_rotate(rot, hx, hy, rx, ry);
-                }
-            }
-            // (behind the compaction's first barrier everyone is done with the list of the row before)
-            n_src += block_compact(cell >= 0, sh.wcount, lane, wave, n_src, [&](int k) {
-                sh.cid[k] = (unsigned short)cell;
-                sh.rv[k] = make_float2(rx, ry);
-            });
-        }
+        // (a), (b) the other live pedestrians inside the grid, ascending, with their cells and relative velocities: the list holds
+        // them all, so it is walked once, at the end
+        int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+        float x0 = 0.0f, x1 = 0.0f, x2 = 0.0f, x3 = 0.0f, y0 = 0.0f, y1 = 0.0f, y2 = 0.0f, y3 = 0.0f;
+        auto other = [&](int t, int& cell, float& rx, float& ry) {
+            const float4 p = sh.pk[t];
+            if (t == row || !row_live(p.x, p.y)) return;
+            cell = w.cell(p.x, p.y);
+            rx = p.z - vx;
+            ry = p.w - vy;
+            w.rotate(rx, ry);
+        };
+        GRID_OFFER(BATCH_MAX_N, 0, n, other, c, x, y);
         // ... and the geometry points per kind and cell (behind the barriers above: the counts of the row before were cleared)
         for (int e = tid; e < P; e += BLOCK) {
             const float2 p = one_tile ? sh.tile[e] : run.point(e);
-            const int cell = grid_cell(p.x - x, p.y - y, rot, hx, hy, c, half, g, G);
+            const int cell = w.cell(p.x, p.y);
             if (cell >= 0) atomicAdd(&sh.cnt[e < nb ? 0 : e < nb + ns ? 1 : 2][cell], 1);
         }
         if (P > 0) __syncthreads();                                    // uniform
-
-        // (b) a lane owns cells tid + q BLOCK and walks the sources in order
-        int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-        float x0 = 0.0f, x1 = 0.0f, x2 = 0.0f, x3 = 0.0f, y0 = 0.0f, y1 = 0.0f, y2 = 0.0f, y3 = 0.0f;
-        // one source, in its turn (a macro: the accumulators stay plain registers)
-#define GRID_ADD(cell, v)                                                                                      \
-        do {                                                                                                   \
-            const int cid_ = __builtin_amdgcn_readfirstlane(cell);                                             \
-            const bool mine_ = (cid_ & (BLOCK - 1)) == tid;                                                    \
-            const int q_ = cid_ / BLOCK; /* uniform */                                                         \
-            if (q_ == 0) { c0 += mine_; x0 = mine_ ? x0 + (v).x : x0; y0 = mine_ ? y0 + (v).y : y0; }          \
-            else if (q_ == 1) { c1 += mine_; x1 = mine_ ? x1 + (v).x : x1; y1 = mine_ ? y1 + (v).y : y1; }     \
-            else if (q_ == 2) { c2 += mine_; x2 = mine_ ? x2 + (v).x : x2; y2 = mine_ ? y2 + (v).y : y2; }     \
-            else { c3 += mine_; x3 = mine_ ? x3 + (v).x : x3; y3 = mine_ ? y3 + (v).y : y3; }                  \
-        } while (0)
-        int k = 0;
-#pragma unroll 1
-        for (; k + 4 <= n_src; k += 4) {                               // uniform: the LDS reads are broadcasts, four in flight
-            const int e0 = sh.cid[k], e1 = sh.cid[k + 1], e2 = sh.cid[k + 2], e3 = sh.cid[k + 3];
-            const float2 v0 = sh.rv[k], v1 = sh.rv[k + 1], v2 = sh.rv[k + 2], v3 = sh.rv[k + 3];
-            GRID_ADD(e0, v0);
-            GRID_ADD(e1, v1);
-            GRID_ADD(e2, v2);
-            GRID_ADD(e3, v3);
-        }
-#pragma unroll 1
-        for (; k < n_src; ++k) {
-            const int e = sh.cid[k];
-            const float2 v = sh.rv[k];
-            GRID_ADD(e, v);
-        }
-#undef GRID_ADD
 
         // 4. the row's 6 G^2 floats
         auto store = [&](int cell, int count, float sx, float sy) {

@@ -21,18 +21,20 @@ struct BatchGeoDev {           // one kind of polylines over all scenes
     int P = 0;
 };
 
-// bird's-eye grids around the vehicles (sfm_batch_set_vehicle_grid): the settings and the buffer sfm_batch_grid_vehicles fills;
-// nothing a tick reads or writes.  They live inside the boxes they refer to (BatchBoxesDev::vgrid: slots and buffer are per
+// grids, around the rows (SfmBatch::grid: sfm_batch_set_grid) and around the vehicles (BatchBoxesDev::vgrid:
+// sfm_batch_set_vehicle_grid): the settings and the buffer sfm_batch_grid / sfm_batch_grid_vehicles fills, one slot per gridded item
+// -- a row, or a vehicle; nothing a tick reads or writes.  The vehicles' live inside the boxes they refer to (slots and buffer are per
 // vehicle), so whatever replaces or drops the boxes drops them with no line of its own; sfm_batch_upload_state drops them too.
-struct BatchVehGridDev {
-    bool on = false;           // (not "buf is allocated": a batch without gridded vehicles can be gridded and has no buffer)
-    int GU = 0, GV = 0;
+struct BatchGridDev {
+    bool on = false;           // (not "buf is allocated": a batch without gridded items can be gridded and has no buffer)
+    int GU = 0, GV = 0;        // the rows' grid: both G
     int frame = 0;
-    float centre_x = 0.f, centre_y = 0.f;  // the middle of the window in the vehicle frame
-    size_t M = 0;              // gridded vehicles: the slots of buf
+    float centre_x = 0.f, centre_y = 0.f;  // the middle of the window in the vehicle frame; the rows' window is centred on the row: 0
+    size_t M = 0;              // gridded items: the slots of buf
     DevBuf<float> cell;        // [B]
-    DevBuf<int> slot;          // [M]; not allocated: every vehicle is gridded, slot = vehicle
-    DevBuf<float> buf;         // [M'][8][GV][GU]
+    DevBuf<int> slot;          // [items]; not allocated: every item is gridded, slot = item
+    DevBuf<float> buf;         // [M][channels][GV][GU]: 6 channels for a row, 8 for a vehicle
+    size_t vals(int channels) const { return M * (size_t)channels * (size_t)GU * (size_t)GV; }    // (64 bits)
 };
 
 // device-side vehicles (sfm_batch_set_dynamic_boxes): geo[2].ctr / .pts hold the vehicles the next tick sees, ctr_alt / pts_alt
@@ -44,7 +46,7 @@ struct BatchBoxesDev {
     DevBuf<float4> ctr_alt;
     DevBuf<float2> pts_alt;
     std::vector<int32_t> item_off_h;   // the vehicles' scene_item_off [B+1] on the host
-    BatchVehGridDev vgrid;     // the bird's-eye grids around these vehicles (sfm_batch_set_vehicle_grid)
+    BatchGridDev vgrid;        // the bird's-eye grids around these vehicles (sfm_batch_set_vehicle_grid)
 };
 
 // scripted vehicle tracks (sfm_batch_set_vehicle_tracks, ABI 12): read-only on the device; dropped with the boxes they refer to
@@ -152,17 +154,6 @@ struct BatchScanDev {
     DevBuf<float2> dir;        // [R]
     DevBuf<uint8_t> mask;      // [items]; not allocated: every item is scanned
     DevBuf<float> buf;         // [items][2 R]
-};
-
-// occupancy grids (sfm_batch_set_grid): the settings and the buffer sfm_batch_grid fills; nothing a tick reads or writes
-struct BatchGridDev {
-    bool on = false;           // (not "buf is allocated": a batch without gridded rows can be gridded and has no buffer)
-    int G = 0;
-    int frame = 0;
-    size_t M = 0;              // gridded rows: the slots of buf
-    DevBuf<float> cell;        // [B]
-    DevBuf<int> slot;          // [N_total]; not allocated: every row is gridded, slot = row
-    DevBuf<float> buf;         // [M][6][G][G]
 };
 
 // restart noise (sfm_batch_set_restart_noise): how a restarted scene may differ from the snapshot, and the two per-scene counters the

@@ -68,6 +68,43 @@ static int build_scan(SfmBatch* b, size_t items, int max_rays, const char* whose
     return SFM_OK;
 }
 
+// What sfm_batch_set_grid and sfm_batch_set_vehicle_grid share: every check from the frame on, then the settings and the zero-filled
+// buffer of the gridded ones of `items` rows, or vehicles, in *o -- GU x GV cells in `channels` channels each.  `whose` as for
+// build_scan; centre: the middle of the vehicles' window {x, y}, checked where sfm_batch_set_vehicle_grid always checked it, null for
+// the rows.  Everything is checked before anything is allocated; the caller synchronises the stream (the zero fill) before it moves
+// *o into the batch.
+static int build_grid(SfmBatch* b, size_t items, int channels, const char* whose, int GU, int GV, const float* cell, const uint8_t* mask,
+                      int frame, const float* centre, BatchGridDev* o) {
+    int rc;
+    if ((rc = check_frame(b, frame, whose))) return rc;
+    if (centre && (!std::isfinite(centre[0]) || !std::isfinite(centre[1]) || std::fabs(centre[0]) > SFM_BATCH_MAX_SENSE_RANGE ||
+                   std::fabs(centre[1]) > SFM_BATCH_MAX_SENSE_RANGE))
+        return bfail(b, SFM_ERR_INVALID, "the centre must be finite and within 1e6 metres of the vehicle's centre");
+    const size_t B = (size_t)b->B;
+    for (size_t s = 0; s < B; ++s)
+        if ((rc = batch_metres(b, s, "cell", cell[s], true, nullptr))) return rc;   // (the size goes to the kernel as the fp32 value given)
+    o->GU = GU;
+    o->GV = GV;
+    o->M = items;                                                // no mask: every item, slot = item
+    if (mask && items > 0) {
+        std::vector<int32_t> slot(items);
+        o->M = pack_grid_slots(mask, items, slot.data());
+        HIP_TRY(b, o->slot.alloc(items));
+        HIP_TRY(b, hipMemcpy(o->slot, slot.data(), sizeof(int32_t) * items, hipMemcpyHostToDevice));
+    }
+    const size_t vals = o->vals(channels);
+    HIP_TRY(b, o->cell.alloc(B));
+    HIP_TRY(b, hipMemcpy(o->cell, cell, sizeof(float) * B, hipMemcpyHostToDevice));
+    if (vals > 0) {
+        HIP_TRY(b, o->buf.alloc(vals));
+        HIP_TRY(b, hipMemsetAsync(o->buf, 0, sizeof(float) * vals, b->stream));
+    }
+    o->frame = frame;
+    if (centre) { o->centre_x = centre[0]; o->centre_y = centre[1]; }
+    o->on = true;
+    return SFM_OK;
+}
+
 // One lookup for the device buffers a caller may see: which = SFM_BATCH_PTR_*, or PTR_OBSERVATIONS for sfm_batch_observation_ptr's.
 // off: why there is none (its feature is off, no state was uploaded), else p and bytes -- both 0 where the buffer has no element.
 constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_VEHICLE_GRID + 1;   // (not part of the ABI: sfm_batch_device_ptr refuses it)
@@ -91,7 +128,7 @@ static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
         return have(b->noise.resets, sizeof(uint32_t) * B);
     case SFM_BATCH_PTR_GRID:
         if (!b->grid.on) return {GRIDS_OFF, nullptr, 0};
-        return have(b->grid.buf, sizeof(float) * b->grid.M * (size_t)(SFM_BATCH_GRID_CHANNELS * b->grid.G * b->grid.G));
+        return have(b->grid.buf, sizeof(float) * b->grid.vals(SFM_BATCH_GRID_CHANNELS));
     case SFM_BATCH_PTR_ROW_SCORES:
     case SFM_BATCH_PTR_SCENE_SCORES:
         if (!b->replay.on) return {OBSERVED_OFF, nullptr, 0};
@@ -107,7 +144,7 @@ static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
         return have(b->vscan.buf, sizeof(float) * (size_t)b->geo[2].K * (size_t)(2 * b->vscan.R));
     case SFM_BATCH_PTR_VEHICLE_GRID:
         if (!b->boxes.vgrid.on) return {VEHICLE_GRID_OFF, nullptr, 0};
-        return have(b->boxes.vgrid.buf, sizeof(float) * b->boxes.vgrid.M * (size_t)SFM_BATCH_VEHICLE_GRID_CHANNELS * (size_t)b->boxes.vgrid.GU * (size_t)b->boxes.vgrid.GV);
+        return have(b->boxes.vgrid.buf, sizeof(float) * b->boxes.vgrid.vals(SFM_BATCH_VEHICLE_GRID_CHANNELS));
     case SFM_BATCH_PTR_ROUTE_GOALS:
     case SFM_BATCH_PTR_ROUTE_STATUS:
         if (!b->routes.on) return {ROUTES_OFF, nullptr, 0};
@@ -359,28 +396,8 @@ int sfm_batch_set_grid(SfmBatch* b, int G, const float* cell, const uint8_t* mas
     if (!b->have_state) return bfail(b, SFM_ERR_STATE, NO_STATE);
     if (G < 1 || G > SFM_BATCH_MAX_GRID)
         return bfail(b, SFM_ERR_INVALID, "G must be 1 .. " + std::to_string(SFM_BATCH_MAX_GRID) + " cells per side, got " + std::to_string(G));
-    if ((rc = check_frame(b, frame))) return rc;
-    const size_t B = (size_t)b->B, n = (size_t)b->n_total;
-    for (size_t s = 0; s < B; ++s)
-        if ((rc = batch_metres(b, s, "cell", cell[s], true, nullptr))) return rc;   // (the size goes to the kernel as the fp32 value given)
     BatchGridDev o;
-    o.M = n;                                                     // no mask: every row, slot = row
-    if (mask && n > 0) {
-        std::vector<int32_t> slot(n);
-        o.M = pack_grid_slots(mask, n, slot.data());
-        HIP_TRY(b, o.slot.alloc(n));
-        HIP_TRY(b, hipMemcpy(o.slot, slot.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
-    }
-    const size_t vals = o.M * (size_t)SFM_BATCH_GRID_CHANNELS * (size_t)G * (size_t)G;
-    HIP_TRY(b, o.cell.alloc(B));
-    HIP_TRY(b, hipMemcpy(o.cell, cell, sizeof(float) * B, hipMemcpyHostToDevice));
-    if (vals > 0) {
-        HIP_TRY(b, o.buf.alloc(vals));
-        HIP_TRY(b, hipMemsetAsync(o.buf, 0, sizeof(float) * vals, b->stream));
-    }
-    o.G = G;
-    o.frame = frame;
-    o.on = true;
+    if ((rc = build_grid(b, (size_t)b->n_total, SFM_BATCH_GRID_CHANNELS, "row", G, G, cell, mask, frame, nullptr, &o))) return rc;
     HIP_TRY(b, hipStreamSynchronize(b->stream));                 // the zero fill; and a grid launch in flight may still write the old buffer
     b->grid = std::move(o);
     return SFM_OK;
@@ -391,7 +408,7 @@ int sfm_batch_grid(SfmBatch* b) {
     if (rc) return rc;
     if (!b->grid.on) return bfail(b, SFM_ERR_STATE, GRIDS_OFF);
     if (b->grid.M == 0) return SFM_OK;                           // no gridded row: nothing to write
-    const GridArgs a{batch_scene_view(b), b->grid.cell, b->grid.slot /* null: every row */, b->grid.buf, b->grid.G, b->grid.frame};
+    const GridArgs a{batch_scene_view(b), b->grid.cell, b->grid.slot /* null: every row */, b->grid.buf, b->grid.GU, b->grid.frame};
     HIP_TRY(b, launch_batch_grid(a, b->B, b->stream));
     return SFM_OK;
 }
@@ -415,34 +432,10 @@ int sfm_batch_set_vehicle_grid(SfmBatch* b, int GU, int GV, const float* cell, c
         return bfail(b, SFM_ERR_INVALID, "GU and GV must be 1 .. " + std::to_string(side) + " cells, got " + std::to_string(GU) + " x " + std::to_string(GV));
     if (GU * GV > VEHICLE_GRID_MAX_CELLS)
         return bfail(b, SFM_ERR_INVALID, "GU * GV must be at most " + std::to_string(VEHICLE_GRID_MAX_CELLS) + " cells, got " + std::to_string(GU * GV));
-    if ((rc = check_frame(b, frame, "vehicle"))) return rc;
-    if (!std::isfinite(centre_x) || !std::isfinite(centre_y) || std::fabs(centre_x) > SFM_BATCH_MAX_SENSE_RANGE ||
-        std::fabs(centre_y) > SFM_BATCH_MAX_SENSE_RANGE)
-        return bfail(b, SFM_ERR_INVALID, "the centre must be finite and within 1e6 metres of the vehicle's centre");
-    const size_t B = (size_t)b->B, K = (size_t)b->geo[2].K;
-    for (size_t s = 0; s < B; ++s)
-        if ((rc = batch_metres(b, s, "cell", cell[s], true, nullptr))) return rc;   // (the size goes to the kernel as the fp32 value given)
-    BatchVehGridDev o;
-    o.M = K;                                                     // no mask: every vehicle, slot = vehicle
-    if (mask && K > 0) {
-        std::vector<int32_t> slot(K);
-        o.M = pack_grid_slots(mask, K, slot.data());
-        HIP_TRY(b, o.slot.alloc(K));
-        HIP_TRY(b, hipMemcpy(o.slot, slot.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice));
-    }
-    const size_t vals = o.M * (size_t)SFM_BATCH_VEHICLE_GRID_CHANNELS * (size_t)GU * (size_t)GV;    // (64 bits)
-    HIP_TRY(b, o.cell.alloc(B));
-    HIP_TRY(b, hipMemcpy(o.cell, cell, sizeof(float) * B, hipMemcpyHostToDevice));
-    if (vals > 0) {
-        HIP_TRY(b, o.buf.alloc(vals));
-        HIP_TRY(b, hipMemsetAsync(o.buf, 0, sizeof(float) * vals, b->stream));
-    }
-    o.GU = GU;
-    o.GV = GV;
-    o.frame = frame;
-    o.centre_x = centre_x;
-    o.centre_y = centre_y;
-    o.on = true;
+    const float centre[2] = {centre_x, centre_y};
+    BatchGridDev o;
+    if ((rc = build_grid(b, (size_t)b->geo[2].K, SFM_BATCH_VEHICLE_GRID_CHANNELS, "vehicle", GU, GV, cell, mask, frame, centre, &o)))
+        return rc;
     HIP_TRY(b, hipStreamSynchronize(b->stream));                 // the zero fill; and a grid launch in flight may still write the old buffer
     b->boxes.vgrid = std::move(o);
     return SFM_OK;

@@ -14,27 +14,25 @@
 //      once, else every vehicle reads it from memory (a point is used once per vehicle, by one lane);
 //   2. the scene's vehicles are walked in ascending order by the whole workgroup (the loop is uniform: mask and presence are the
 //      same for every lane).  A vehicle without a slot is passed over; a gridded vehicle that is not present gets its zeros;
-//   3. per gridded present vehicle:
-//      (a) lane t takes pedestrians t, t + BLOCK, ..: the cell of each and its relative velocity; the sources inside the window are
-//          compacted, by ballots and so in ascending j, into an LDS list {cell, relative velocity}, which is walked as in (b)
-//          whenever VGRID_LIST rows have been offered and at the end; every lane takes border and static points e, e + BLOCK, ..
-//          and counts the cell of each with an integer LDS add (order does not matter);
-//      (b) a lane owns the cells tid, tid + BLOCK, .. (GU GV <= 1024: up to 4) and walks the list in order -- broadcast LDS reads --
-//          counting its matches and adding their velocities: ascending j, fp32 adds from 0.0f, no float atomic.  An entry's cell
-//          is uniform, so the three waves that do not hold its owning lane pass over it on a scalar test;
-//      (c) the ring points of the OTHER vehicles, BLOCK at a time in ascending (vehicle, point) order -- the own ring is skipped by
-//          its index range in the geometry's virtual run; the lane that holds a point inside the window finds the owning vehicle
-//          by bisection of the ring offsets -- are compacted into the same list, now {cell, the owner's relative velocity}.  The
-//          list is walked as in (b), into a second set of accumulators, whenever VGRID_LIST points have been offered and at the
-//          end: the order holds at any number of points;
+//   3. per gridded present vehicle: the window is GU x GV cells around `centre`, turned by the stored heading (GridWindow,
+//      sfm_grid_cells.h: the rotation and the cell rule live there);
+//      (a) the live pedestrians are offered to the shared loop (GRID_OFFER): lane t takes pedestrians t, t + BLOCK, .., the sources
+//          inside the window are compacted in ascending j into an LDS list {cell, relative velocity} of VGRID_LIST entries, which is
+//          walked in order whenever VGRID_LIST rows have been offered and at the end, into the cells tid, tid + BLOCK, .. the lane
+//          owns (GU GV <= 1024: up to 4; GRID_WALK and GRID_ADD, with the order and the wave test described there);
+//      (b) every lane takes border and static points e, e + BLOCK, .. and counts the cell of each with an integer LDS add (order
+//          does not matter);
+//      (c) the ring points of the OTHER vehicles go through the same loop in ascending (vehicle, point) order, into a second set of
+//          accumulators -- the own ring is skipped by its index range in the geometry's virtual run; the lane that holds a point
+//          inside the window finds the owning vehicle by bisection of the ring offsets; the list now holds {cell, the owner's
+//          relative velocity}, and the order holds at any number of points;
 //   4. the lane stores the 8 channels of its cells (consecutive lanes store consecutive floats) and clears the counts it read.
+// What is this kernel's own: the walk over the scene's vehicles with its barrier, the list's size, what a source is (every live
+// pedestrian; every ring point but the own ring's, with its owner's velocity), and the store with its two sets of sums.
 // No register array is indexed at run time, so nothing goes to scratch.
 // Determinism: no float atomics, every order is a function of the scene alone -- a scene's record is bitwise the same alone or
 // anywhere in any batch.
-//
-// The cell rule, the rotation and the accumulation macro are sfm_batch_grid.hip's, restated here for a window of two sides: that
-// kernel keeps its own copies, so its code and registers are what they were.
-#include "sfm_device.h"
+#include "sfm_grid_cells.h"
 
 #pragma clang fp contract(off)     // every operation of the rules is a single rounding, or an explicit fmaf
 
@@ -54,32 +52,6 @@ struct VehicleGridShared {
 };
 static_assert(sizeof(VehicleGridShared) <= 80 * 1024, "two workgroups share a CU's 160 KiB of LDS");
 static_assert(sizeof(VehicleGridShared) <= 40 * 1024, "... and four do: 1 024 scenes are resident on 256 CUs at once");
-
-// the rotation into the heading frame: the rules of include/sfm_hip.h
-__device__ __forceinline__ void vgrid_rotate(bool rot, float hx, float hy, float& a, float& b) {
-    if (rot) {
-        const float ra = fmaf(hx, a, hy * b), rb = fmaf(hx, b, -(hy * a));
-        a = ra;
-        b = rb;
-    }
-}
-
-// the window of one vehicle
-struct VehicleGridWindow {
-    float ox, oy, hx, hy;      // the window's middle in world axes; the stored heading
-    float c, halfu, halfv, gu, gv;
-    int GU;
-    bool rot;
-    // the cell [cv][cu] of a source at (px, py), as cv * GU + cu; -1: outside (NaN and +-inf fail the compares)
-    __device__ __forceinline__ int cell(float px, float py) const {
-        float ax = px - ox, ay = py - oy;
-        vgrid_rotate(rot, hx, hy, ax, ay);
-        const float pu = ax / c + halfu;                               // the division is rounded first (correctly: hipcc's default
-        const float pv = ay / c + halfv;                               // for fp32 divide), then the sum
-        const bool in = pu >= 0.0f && pu < gu && pv >= 0.0f && pv < gv;
-        return in ? (int)pv * GU + (int)pu : -1;
-    }
-};
 
 __global__ __launch_bounds__(BLOCK) void sfm_batch_vehicle_grid_kernel(const VehicleGridArgs a) {
     __shared__ VehicleGridShared sh;
@@ -102,14 +74,7 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_vehicle_grid_kernel(const Veh
 
     const int ring0 = nbs - run.vp0;                                   // vehicle v's ring in the run: ring0 + off[v] .. ring0 + off[v + 1]
     const int* __restrict__ voff = a.geo[2].off;
-    VehicleGridWindow w;
-    w.c = a.cell[b];
-    w.gu = (float)GU;                                                  // (exact, and so are the halves)
-    w.gv = (float)GV;
-    w.halfu = 0.5f * w.gu;
-    w.halfv = 0.5f * w.gv;
-    w.GU = GU;
-    w.rot = a.frame != 0;                                              // uniform
+    GridWindow w(a.cell[b], GU, GV, a.frame != 0);                     // (rot: uniform)
     const float mx = a.centre_x, my = a.centre_y;
     const size_t per_slot = (size_t)VEHICLE_GRID_CHANNELS * (size_t)cells;
 #pragma unroll 1
@@ -140,66 +105,17 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_vehicle_grid_kernel(const Veh
         float x0 = 0.0f, x1 = 0.0f, x2 = 0.0f, x3 = 0.0f, y0 = 0.0f, y1 = 0.0f, y2 = 0.0f, y3 = 0.0f;
         int d0 = 0, d1 = 0, d2 = 0, d3 = 0;
         float u0 = 0.0f, u1 = 0.0f, u2 = 0.0f, u3 = 0.0f, z0 = 0.0f, z1 = 0.0f, z2 = 0.0f, z3 = 0.0f;
-        // one source, in its turn (a macro: the accumulators stay plain registers)
-#define VGRID_ADD(cell, v, C, X, Y)                                                                                            \
-        do {                                                                                                                   \
-            const int cid_ = __builtin_amdgcn_readfirstlane(cell);                                                             \
-            if (((cid_ / WAVE) & (WAVES_PER_BLOCK - 1)) != wave) break; /* uniform: the owning lane sits in another wave */     \
-            const bool mine_ = (cid_ & (BLOCK - 1)) == tid;                                                                    \
-            const int q_ = cid_ / BLOCK; /* uniform */                                                                         \
-            if (q_ == 0) { C##0 += mine_; X##0 = mine_ ? X##0 + (v).x : X##0; Y##0 = mine_ ? Y##0 + (v).y : Y##0; }            \
-            else if (q_ == 1) { C##1 += mine_; X##1 = mine_ ? X##1 + (v).x : X##1; Y##1 = mine_ ? Y##1 + (v).y : Y##1; }       \
-            else if (q_ == 2) { C##2 += mine_; X##2 = mine_ ? X##2 + (v).x : X##2; Y##2 = mine_ ? Y##2 + (v).y : Y##2; }       \
-            else { C##3 += mine_; X##3 = mine_ ? X##3 + (v).x : X##3; Y##3 = mine_ ? Y##3 + (v).y : Y##3; }                    \
-        } while (0)
-#define VGRID_WALK(count, C, X, Y)                                                                                             \
-        do {                                                                                                                   \
-            int k_ = 0;                                                                                                        \
-            _Pragma("unroll 1")                                                                                                \
-            for (; k_ + 4 <= (count); k_ += 4) { /* uniform: the LDS reads are broadcasts, four in flight */                   \
-                const int e0 = sh.cid[k_], e1 = sh.cid[k_ + 1], e2 = sh.cid[k_ + 2], e3 = sh.cid[k_ + 3];                      \
-                const float2 v0 = sh.rv[k_], v1 = sh.rv[k_ + 1], v2 = sh.rv[k_ + 2], v3 = sh.rv[k_ + 3];                       \
-                VGRID_ADD(e0, v0, C, X, Y);                                                                                    \
-                VGRID_ADD(e1, v1, C, X, Y);                                                                                    \
-                VGRID_ADD(e2, v2, C, X, Y);                                                                                    \
-                VGRID_ADD(e3, v3, C, X, Y);                                                                                    \
-            }                                                                                                                  \
-            _Pragma("unroll 1")                                                                                                \
-            for (; k_ < (count); ++k_) {                                                                                       \
-                const int e_ = sh.cid[k_];                                                                                     \
-                const float2 v_ = sh.rv[k_];                                                                                   \
-                VGRID_ADD(e_, v_, C, X, Y);                                                                                    \
-            }                                                                                                                  \
-        } while (0)
 
-        // (a), (b) the pedestrians inside the window, ascending, with their cells and relative velocities: offered BLOCK at a time,
-        // walked per chunk
-        int n_src = 0, offered = 0;
-#pragma unroll 1
-        for (int base = 0; base < n; base += BLOCK) {                  // uniform
-            const int t = base + tid;
-            int cell = -1;
-            float rx = 0.0f, ry = 0.0f;
-            if (t < n) {
-                const float4 p = sh.pk[t];
-                if (row_live(p.x, p.y)) {
-                    cell = w.cell(p.x, p.y);
-                    rx = p.z - vxk;
-                    ry = p.w - vyk;
-                    vgrid_rotate(w.rot, w.hx, w.hy, rx, ry);
-                }
-            }
-            n_src += block_compact(cell >= 0, sh.wcount, lane, wave, n_src, [&](int p) {
-                sh.cid[p] = (unsigned short)cell;
-                sh.rv[p] = make_float2(rx, ry);
-            });
-            offered += BLOCK;
-            if (offered == VGRID_LIST || base + BLOCK >= n) {          // uniform: the chunk is full, or the rows are over
-                VGRID_WALK(n_src, c, x, y);
-                n_src = 0;
-                offered = 0;
-            }
-        }
+        // (a), (b) the live pedestrians inside the window, ascending, with their cells and relative velocities
+        auto walker = [&](int t, int& cell, float& rx, float& ry) {
+            const float4 p = sh.pk[t];
+            if (!row_live(p.x, p.y)) return;
+            cell = w.cell(p.x, p.y);
+            rx = p.z - vxk;
+            ry = p.w - vyk;
+            w.rotate(rx, ry);
+        };
+        GRID_OFFER(VGRID_LIST, 0, n, walker, c, x, y);
         // ... and the border and static points per cell
         for (int e = tid; e < nbs; e += BLOCK) {
             const float2 p = one_tile ? sh.tile[e] : run.point(e);
@@ -208,44 +124,24 @@ __global__ __launch_bounds__(BLOCK) void sfm_batch_vehicle_grid_kernel(const Veh
         }
         __syncthreads();
 
-
-        // (c) the ring points of the other vehicles, ascending (vehicle, point): offered BLOCK at a time, walked per chunk
-        int n_pts = 0;
-#pragma unroll 1
-        for (int base = nbs; base < P; base += BLOCK) {                // uniform
-            const int e = base + tid;
-            int cell = -1;
-            float rx = 0.0f, ry = 0.0f;
-            if (e < P && (e < own_lo || e >= own_hi)) {
-                const float2 p = one_tile ? sh.tile[e] : run.point(e);
-                cell = w.cell(p.x, p.y);
-                if (cell >= 0) {
-                    const int pidx = e - ring0;                        // the point's index in the rings' array
-                    int lo = vk0, hi = vk1 - 1;                        // the owner: the last vehicle whose ring begins at or before it
-                    while (lo < hi) {
-                        const int mid = (lo + hi + 1) >> 1;
-                        if (voff[mid] <= pidx) lo = mid; else hi = mid - 1;
-                    }
-                    const float4 cv = a.geo[2].ctr[lo];
-                    rx = cv.z - vxk;
-                    ry = cv.w - vyk;
-                    vgrid_rotate(w.rot, w.hx, w.hy, rx, ry);
-                }
+        // (c) the ring points of the other vehicles, ascending (vehicle, point), each with its owner's relative velocity
+        auto ring = [&](int e, int& cell, float& rx, float& ry) {
+            if (e >= own_lo && e < own_hi) return;
+            const float2 p = one_tile ? sh.tile[e] : run.point(e);
+            cell = w.cell(p.x, p.y);
+            if (cell < 0) return;
+            const int pidx = e - ring0;                                // the point's index in the rings' array
+            int lo = vk0, hi = vk1 - 1;                                // the owner: the last vehicle whose ring begins at or before it
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (voff[mid] <= pidx) lo = mid; else hi = mid - 1;
             }
-            // (behind the compaction's first barrier everyone is done with the list walked before)
-            n_pts += block_compact(cell >= 0, sh.wcount, lane, wave, n_pts, [&](int p) {
-                sh.cid[p] = (unsigned short)cell;
-                sh.rv[p] = make_float2(rx, ry);
-            });
-            offered += BLOCK;
-            if (offered == VGRID_LIST || base + BLOCK >= P) {          // uniform: the chunk is full, or the run is over
-                VGRID_WALK(n_pts, d, u, z);
-                n_pts = 0;
-                offered = 0;
-            }
-        }
-#undef VGRID_WALK
-#undef VGRID_ADD
+            const float4 cv = a.geo[2].ctr[lo];
+            rx = cv.z - vxk;
+            ry = cv.w - vyk;
+            w.rotate(rx, ry);
+        };
+        GRID_OFFER(VGRID_LIST, nbs, P, ring, d, u, z);
 
         // 4. the vehicle's 8 GU GV floats
         auto store = [&](int cell, int peds, float sx, float sy, int pts, float tx, float ty) {

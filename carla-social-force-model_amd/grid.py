@@ -40,6 +40,13 @@ def grid_arrays(B, G, cell, frame=0):
     return G, per_scene_metres(cell, "cell", B, True), frame
 
 
+def _slots(m, off):
+    """(items int64 [M], counts int64 [B]): the items a bool mask ``m`` over them keeps (None: all), ascending, and how many of them
+    lie between each pair of the ascending offsets ``off``."""
+    items = np.arange(int(off[-1]), dtype=np.int64) if m is None else np.flatnonzero(m).astype(np.int64)
+    return items, np.diff(np.searchsorted(items, off)).astype(np.int64)
+
+
 def grid_slots(mask, scene_off):
     """Which rows are gridded -> (rows int64 [M], counts int64 [B]): the global row of every slot -- the slots are the masked rows
     of the whole batch in ascending order -- and how many slots each scene owns.  ``mask`` as ``scan.scan_mask`` takes it (None:
@@ -47,21 +54,36 @@ def grid_slots(mask, scene_off):
     so = np.asarray(scene_off, dtype=np.int64)
     if so.ndim != 1 or so.shape[0] < 1 or (np.diff(so) < 0).any():
         raise ValueError("scene_off must be B + 1 ascending offsets")
-    m = scan_mask(mask, so)
-    rows = np.arange(int(so[-1]), dtype=np.int64) if m is None else np.flatnonzero(m).astype(np.int64)
-    return rows, np.diff(np.searchsorted(rows, so)).astype(np.int64)
+    return _slots(scan_mask(mask, so), so)
 
 
-def _cells(fx, fy, c, half, G):
-    """(inside, cell id) of sources at (fx, fy) in the grid's frame: pu = fx / c + half, the division rounded first."""
+def _window_cells(fx, fy, c, GU, GV):
+    """(inside, cell id cv * GU + cu) of sources at (fx, fy) in the window's frame: pu = fx / c + 0.5f GU, the division rounded
+    first; pv likewise with GV."""
     with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
-        pu = ((fx / c).astype(np.float32) + half).astype(np.float32)
-        pv = ((fy / c).astype(np.float32) + half).astype(np.float32)
-        g = np.float32(G)
-        inside = (pu >= 0) & (pu < g) & (pv >= 0) & (pv < g)           # float compares: NaN and +-inf fail by themselves
+        gu, gv = np.float32(GU), np.float32(GV)
+        pu = ((fx / c).astype(np.float32) + np.float32(0.5) * gu).astype(np.float32)
+        pv = ((fy / c).astype(np.float32) + np.float32(0.5) * gv).astype(np.float32)
+        inside = (pu >= 0) & (pu < gu) & (pv >= 0) & (pv < gv)         # float compares: NaN and +-inf fail by themselves
     cu = np.where(inside, pu, np.float32(0)).astype(np.int32)          # (int)pu
     cv = np.where(inside, pv, np.float32(0)).astype(np.int32)
-    return inside, cv * G + cu
+    return inside, cv * GU + cu
+
+
+def _ordered_sums(cid, vx, vy, cells):
+    """Per cell the count of the sources and the sums of (vx, vy) by fp32 adds from 0.0f in the order given: the q-th source of
+    every cell is added in round q."""
+    count = np.bincount(cid, minlength=cells).astype(np.float32)
+    order = np.argsort(cid, kind="stable")
+    sk = cid[order]
+    rank = np.arange(len(sk)) - np.searchsorted(sk, sk, side="left")
+    sx, sy = np.zeros(cells, np.float32), np.zeros(cells, np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for q in range(int(rank.max()) + 1 if len(rank) else 0):
+            pick = order[rank == q]
+            sx[cid[pick]] = sx[cid[pick]] + vx[pick]
+            sy[cid[pick]] = sy[cid[pick]] + vy[pick]
+    return count, sx, sy
 
 
 def _rotate(hx, hy, a, b):
@@ -80,7 +102,6 @@ def grid_scene(scene, G, cell, frame=0, mask=None, state=None, vehicles=None, wa
     ``scan.scan_scene``: ``state`` = (loc, vel), ``vehicles`` = the scene's list of (center, ring), ``waypoints`` (N,2|3)."""
     G, c, frame = grid_arrays(1, G, cell, frame)
     c = c[0]
-    half = np.float32(0.5) * np.float32(G)
     loc, vel = (_get(scene, "loc"), _get(scene, "vel")) if state is None else state
     loc, vel = np.asarray(loc, dtype=np.float64), np.asarray(vel, dtype=np.float64)
     n = loc.reshape(-1, loc.shape[-1]).shape[0] if loc.size else 0
@@ -112,28 +133,18 @@ def grid_scene(scene, G, cell, frame=0, mask=None, state=None, vehicles=None, wa
             rot = (lambda a, b: _rotate(hx[i][:, None], hy[i][:, None], a, b)) if frame == 1 else (lambda a, b: (a, b))
             fx, fy = rot(x[None, :] - xi, y[None, :] - yi)
             rvx, rvy = rot(vx[None, :] - vx[i][:, None], vy[None, :] - vy[i][:, None])
-            inside, cid = _cells(fx, fy, c, half, G)
+            inside, cid = _window_cells(fx, fy, c, G, G)
             # a source: a live row j != i; a gridded row that is not live reads zeros
             inside &= alive[None, :] & alive[i][:, None] & (np.arange(n)[None, :] != i[:, None])
             key = (slot * C2 + cid)[inside]                            # row-major: per gridded row, ascending j
-            rvx, rvy = rvx[inside], rvy[inside]
             flat = rec[lo:lo + m]
-            flat[:, CH_COUNT] = np.bincount(key, minlength=m * C2).reshape(m, C2)
-            # the sums: fp32 adds in ascending j from 0.0f -- the q-th source of every cell is added in round q
-            order = np.argsort(key, kind="stable")
-            sk = key[order]
-            rank = np.arange(len(sk)) - np.searchsorted(sk, sk, side="left")
-            sx, sy = np.zeros(m * C2, np.float32), np.zeros(m * C2, np.float32)
-            for q in range(int(rank.max()) + 1 if len(rank) else 0):
-                pick = order[rank == q]
-                sx[key[pick]] = sx[key[pick]] + rvx[pick]
-                sy[key[pick]] = sy[key[pick]] + rvy[pick]
-            flat[:, CH_VX], flat[:, CH_VY] = sx.reshape(m, C2), sy.reshape(m, C2)
+            for ch, v in zip((CH_COUNT, CH_VX, CH_VY), _ordered_sums(key, rvx[inside], rvy[inside], m * C2)):
+                flat[:, ch] = v.reshape(m, C2)
             for ch, pts in zip((CH_BORDER, CH_STATIC, CH_VEHICLE), geo):
                 if len(pts) == 0:
                     continue
                 fx, fy = rot(pts[None, :, 0] - xi, pts[None, :, 1] - yi)
-                inside, cid = _cells(fx, fy, c, half, G)
+                inside, cid = _window_cells(fx, fy, c, G, G)
                 inside &= alive[i][:, None]
                 flat[:, ch] = np.bincount((slot * C2 + cid)[inside], minlength=m * C2).reshape(m, C2)
     return rec.reshape(len(rows), GRID_CHANNELS, G, G)
@@ -215,39 +226,7 @@ def vehicle_grid_slots(mask, item_off):
     """Which vehicles are gridded -> (vehicles int64 [M'], counts int64 [B]): the vehicle (in concatenated order) of every slot --
     the slots are the masked vehicles of the whole batch in ascending order -- and how many slots each scene owns.  ``mask`` as
     for ``vehicle_grid_arrays``.  Pure NumPy; raises ValueError."""
-    m = _vehicle_mask(mask, item_off)
-    io = np.asarray(item_off, dtype=np.int64)
-    veh = np.arange(int(io[-1]), dtype=np.int64) if m is None else np.flatnonzero(m).astype(np.int64)
-    return veh, np.diff(np.searchsorted(veh, io)).astype(np.int64)
-
-
-def _window_cells(fx, fy, c, GU, GV):
-    """(inside, cell id cv * GU + cu) of sources at (fx, fy) in the window's frame: pu = fx / c + 0.5f GU, the division rounded
-    first; pv likewise with GV."""
-    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
-        gu, gv = np.float32(GU), np.float32(GV)
-        pu = ((fx / c).astype(np.float32) + np.float32(0.5) * gu).astype(np.float32)
-        pv = ((fy / c).astype(np.float32) + np.float32(0.5) * gv).astype(np.float32)
-        inside = (pu >= 0) & (pu < gu) & (pv >= 0) & (pv < gv)         # float compares: NaN and +-inf fail by themselves
-    cu = np.where(inside, pu, np.float32(0)).astype(np.int32)          # (int)pu
-    cv = np.where(inside, pv, np.float32(0)).astype(np.int32)
-    return inside, cv * GU + cu
-
-
-def _ordered_sums(cid, vx, vy, cells):
-    """Per cell the count of the sources and the sums of (vx, vy) by fp32 adds from 0.0f in the order given: the q-th source of
-    every cell is added in round q."""
-    count = np.bincount(cid, minlength=cells).astype(np.float32)
-    order = np.argsort(cid, kind="stable")
-    sk = cid[order]
-    rank = np.arange(len(sk)) - np.searchsorted(sk, sk, side="left")
-    sx, sy = np.zeros(cells, np.float32), np.zeros(cells, np.float32)
-    with np.errstate(over="ignore", invalid="ignore"):
-        for q in range(int(rank.max()) + 1 if len(rank) else 0):
-            pick = order[rank == q]
-            sx[cid[pick]] = sx[cid[pick]] + vx[pick]
-            sy[cid[pick]] = sy[cid[pick]] + vy[pick]
-    return count, sx, sy
+    return _slots(_vehicle_mask(mask, item_off), np.asarray(item_off, dtype=np.int64))
 
 
 def grid_vehicles_scene(scene, GU, GV, cell, frame=0, mask=None, centre=(0.0, 0.0), state=None, vehicles=None, headings=None,

@@ -137,6 +137,35 @@ def masks(kind, sizes=SIZES):
     return out
 
 
+# ---- one source per owning wave: the accumulation's wave test ---------------------------------------------------------------------
+BLOCK, WAVE = 256, 64                # sfm_device.h: a lane owns the cells tid + q BLOCK; cell id's owning wave is (id / WAVE) % 4
+BIG = 2.0 ** 25
+ORDER_VALUES = (1.0, -BIG, BIG)      # (_vehicle_grid_cases.ORDER_VALUES) added in this order the fp32 sum is 0; with the 1 last it is 1
+WAVE_CELLS = {32: ([WAVE * w + BLOCK * q + l for w in range(4) for q in range(4) for l in (0, WAVE - 1)], [WAVE * w for w in range(4)]),
+              8: ([0, 7, 27, 36, 56, 63], [27])}       # G: (the cells that are hit, those of them that hold the order triple)
+
+
+def wave_scene(G):
+    """(scene, expected): row 0 stands at the fp32 origin, goal straight ahead along +x, and is the one gridded row; every cell of
+    WAVE_CELLS[G][0] of its 1 m grid holds one source at the cell's centre with a velocity of its own, and the cells of
+    WAVE_CELLS[G][1] three, a quarter cell apart, whose x-velocities are ORDER_VALUES in row order.  ``expected``:
+    {cell: (count, sum vx, sum vy)}, stated by hand.  Every coordinate is a multiple of 1/4 and so exact in fp32; with heading
+    (1, 0) frame 1 is frame 0."""
+    hit, triple = WAVE_CELLS[G]
+    loc, vel, expected = [(0.0, 0.0)], [(0.0, 0.0)], {}
+    for cid in hit:
+        x, y = cid % G - G / 2 + 0.5, cid // G - G / 2 + 0.5
+        if cid in triple:
+            loc += [(x - 0.25, y - 0.25), (x, y), (x + 0.25, y + 0.25)]
+            vel += [(v, 0.0) for v in ORDER_VALUES]
+            expected[cid] = (3.0, 0.0, 0.0)
+        else:
+            loc.append((x, y))
+            vel.append((cid / 8.0, -1.0 - cid))
+            expected[cid] = (1.0, cid / 8.0, -1.0 - cid)
+    return tiny(loc, vel, waypoint=[(1.0, 0.0)] + loc[1:]), expected
+
+
 # ---- float64 truth --------------------------------------------------------------------------------------------------------------
 
 def _heading64(x, y, vx, vy, wx, wy):

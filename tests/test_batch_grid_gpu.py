@@ -136,6 +136,33 @@ def test_every_slot_is_written_whole_and_nothing_else():
         b.close()
 
 
+@pytest.mark.parametrize("G", sorted(K.WAVE_CELLS))
+def test_one_source_per_owning_wave_lands_in_its_cell(G):
+    """The accumulation passes over an entry in every wave but the one that holds the cell's owning lane: sources in the first and
+    the last cell of every wave and quarter (G = 32), an order triple in one cell of each wave, and a grid whose cells all belong
+    to wave 0 (G = 8).  The buffer holds NaN before the launch; the device is the twin bit for bit in both frames."""
+    import torch
+    sc, expected = K.wave_scene(G)
+    mask = [np.arange(len(sc["loc"])) == 0]
+    for frame in (0, 1):
+        b = _batch([sc])
+        try:
+            b.set_stream(torch.cuda.current_stream().cuda_stream)
+            b.set_grid(1.0, G=G, mask=mask, frame=frame)
+            t = b.grid_tensor()
+            assert t.shape == (1, 6, G, G)
+            t.fill_(float("nan"))
+            b.grid()
+            seen = t.cpu().numpy()
+        finally:
+            b.close()
+        _same(seen, grid_scene(sc, G, 1.0, frame=frame, mask=mask[0]), f"G = {G}, frame {frame}")
+        flat = seen[0, :3].reshape(3, -1)
+        assert sorted(np.flatnonzero(flat[0]).tolist()) == sorted(expected)
+        for c, v in expected.items():
+            assert tuple(flat[:, c]) == v, (G, frame, c)
+
+
 # ---- 3. independence ------------------------------------------------------------------------------------------------------------
 
 def test_a_scene_does_not_depend_on_the_rest_of_the_batch():

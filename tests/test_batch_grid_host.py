@@ -130,6 +130,32 @@ def test_velocity_sums_are_formed_in_ascending_order():
     assert rec[CH_VX, 2, 2] == 1.0 and rec[CH_VY, 2, 2] == 4.0 and rec[CH_COUNT, 2, 2] == 2
 
 
+@pytest.mark.parametrize("G", sorted(K.WAVE_CELLS))
+def test_one_source_per_owning_wave_lands_in_its_cell(G):
+    """The scene of the device's wave test, from the twin alone: the cells and the sums are the ones stated by hand, in both
+    frames, and the order triple sums to 0 -- which no other order of the three adds gives."""
+    sc, expected = K.wave_scene(G)
+    hit, triple = K.WAVE_CELLS[G]
+    if G == 32:
+        owners = {((c // K.WAVE) % 4, c // K.BLOCK, c % K.WAVE) for c in hit}
+        assert owners == {(w, q, l) for w in range(4) for q in range(4) for l in (0, 63)}
+        assert sorted((c // K.WAVE) % 4 for c in triple) == [0, 1, 2, 3]
+    else:
+        assert G * G <= K.WAVE                                          # waves 1 to 3 own no cell
+    assert 36 <= len(sc["loc"]) <= 44 or G == 8
+    mask = np.arange(len(sc["loc"])) == 0
+    want = np.zeros((3, G * G), np.float32)
+    for c, v in expected.items():
+        want[:, c] = v
+    for frame in (0, 1):
+        rec = grid_scene(sc, G, 1.0, frame=frame, mask=mask)
+        assert rec.shape == (1, 6, G, G) and not rec[0, CH_BORDER:].any()
+        assert np.array_equal(rec[0, :3].reshape(3, -1).view(np.uint32), want.view(np.uint32)), (G, frame)
+    ordered = lambda vs: np.float32(np.float32(np.float32(vs[0]) + np.float32(vs[1])) + np.float32(vs[2]))
+    assert ordered(K.ORDER_VALUES) == 0.0 and ordered(K.ORDER_VALUES[1:] + K.ORDER_VALUES[:1]) == 1.0     # the order shows
+    assert all(want[1, c] == 0.0 and want[0, c] == 3.0 for c in triple)
+
+
 def test_cell_size_scales_before_the_shift():
     """pu = fx / c + half, not (fx + half) / c: with c = 0.25 a source 0.5 away is two cells from the centre."""
     rec = grid_scene(K.tiny([[0, 0], [0.5, -0.25]]), 6, 0.25, mask=[True, False])[0]
