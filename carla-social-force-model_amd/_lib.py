@@ -49,7 +49,9 @@ SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_
                             "sfm_batch_set_routes", "sfm_batch_plan_routes", "sfm_batch_plan_routes_device",
                             "sfm_batch_download_routes",
                             "sfm_batch_set_vehicle_autopilot", "sfm_batch_download_vehicle_autopilot",
-                            "sfm_batch_vehicle_autopilot_launches")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
+                            "sfm_batch_vehicle_autopilot_launches",
+            "sfm_batch_set_row_episodes", "sfm_batch_end_row_step", "sfm_batch_download_row_episodes",
+            "sfm_batch_respawn_rows_device", "sfm_batch_download_row_respawns")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
 UNBUMPED = ("sfm_batch_set_restart_noise", "sfm_batch_download_restart_noise",
             "sfm_batch_set_grid", "sfm_batch_grid", "sfm_batch_download_grid",
             "sfm_batch_set_observed", "sfm_batch_run_observed", "sfm_batch_score",
@@ -62,7 +64,9 @@ UNBUMPED = ("sfm_batch_set_restart_noise", "sfm_batch_download_restart_noise",
             "sfm_batch_set_routes", "sfm_batch_plan_routes", "sfm_batch_plan_routes_device",
             "sfm_batch_download_routes",
             "sfm_batch_set_vehicle_autopilot", "sfm_batch_download_vehicle_autopilot",
-            "sfm_batch_vehicle_autopilot_launches")   # ... and those a build of the SAME number may lack
+            "sfm_batch_vehicle_autopilot_launches",
+            "sfm_batch_set_row_episodes", "sfm_batch_end_row_step", "sfm_batch_download_row_episodes",
+            "sfm_batch_respawn_rows_device", "sfm_batch_download_row_respawns")   # ... and those a build of the SAME number may lack
 
 FORCE_NAMES = ("acceleration_force", "pedestrian_force", "border_force",
                "static_obstacle_force", "dynamic_obstacle_force")
@@ -227,6 +231,12 @@ SYMBOLS = {
     "sfm_batch_plan_routes": (C.c_int, [_H, _U8]),
     "sfm_batch_plan_routes_device": (C.c_int, [_H, C.c_void_p]),
     "sfm_batch_download_routes": (C.c_int, [_H, _I, _I, _I, _F, _I, _I, _F, _F, _U8]),
+    # batch row episodes and row respawns (ABI 17, added without a bump)
+    "sfm_batch_set_row_episodes": (C.c_int, [_H, _U8, _F, _F, _F, _I]),
+    "sfm_batch_end_row_step": (C.c_int, [_H, C.c_uint32]),
+    "sfm_batch_download_row_episodes": (C.c_int, [_H, _F, _U8, _I, _F]),
+    "sfm_batch_respawn_rows_device": (C.c_int, [_H, C.c_void_p]),
+    "sfm_batch_download_row_respawns": (C.c_int, [_H, _U32, _U32]),
 }
 
 _lib = None

@@ -105,6 +105,15 @@ later -- all keyed by the scene's seed and its restart counter, so reproducible 
 ``reset_count_tensor()`` aliases the first, and ``reset.resample_scene`` is the host twin, bit for bit (the exact rule:
 include/sfm_hip.h): examples/batch_rl_loop_randomised.py.
 
+Row episodes (ABI 17, added without a bump): many agents per scene.  ``set_row_episodes(agents, goal_radius, ped_radius, veh_radius,
+max_steps)`` marks any set of ROWS as agents, each with its own goal, collision test and time limit (the radii and the limit are
+per scene); ``end_row_step()`` fills, by one launch, a record of 8 floats per row -- the slots of the scene record, for this agent
+row, ``ped_d2`` over all other live rows -- and the mask ``row_done``; ``respawn_rows_device(mask=None)`` puts the chosen rows back from
+the snapshot by one more launch while their scenes go on (with restart noise set: placed by its rounds, clear of the crowd as it
+stands now), and ``end_row_step(auto_respawn=True)`` is the two in a row.  ``row_episode_tensor()`` / ``row_done_tensor()`` alias the
+buffers, ``row_episodes()`` / ``row_respawns()`` download, and ``episode.row_episode_scene`` / ``reset.respawn_rows_scene`` are the
+host twins, bit for bit (the exact rules: include/sfm_hip.h): examples/batch_multiagent_loop.py.
+
 Occupancy grids (ABI 17, added without a bump): the local map of a CNN policy, computed on the device by one launch per call.
 ``set_grid(cell, G=..., mask=..., frame=...)`` chooses a G x G grid (G <= 32) of ``cell`` metres per cell (one value, or one per
 scene) centred on every gridded row, in world axes or in the row's heading frame (x forward).  ``grid()`` fills, per gridded row,
@@ -918,6 +927,9 @@ EPISODE_WIDTH = 8                # SFM_BATCH_EPISODE_WIDTH: floats of a scene's 
 EP_DONE, EP_REASON, EP_AGE, EP_GOAL_D2, EP_PREV_GOAL_D2, EP_PED_D2, EP_VEH_D2, EP_WALL_D2 = range(8)     # its slots
 REASON_ARRIVED, REASON_TIME_LIMIT, REASON_PED_HIT, REASON_VEH_HIT, REASON_NOT_LIVE = 1, 2, 4, 8, 16     # SFM_EPISODE_*: bits of slot 1
 END_STEP_AUTO_RESTART = 1        # SFM_END_STEP_AUTO_RESTART
+END_ROW_STEP_AUTO_RESPAWN = 1    # SFM_END_ROW_STEP_AUTO_RESPAWN
+PTR_ROW_EPISODES, PTR_ROW_DONE = 16, 17       # SFM_BATCH_PTR_ROW_*: the row record [N_total][8] and row_done [N_total] (while row episodes are on)
+PTR_ROW_RESETS = 18              # SFM_BATCH_PTR_ROW_RESETS: the rows' respawn counters [N_total] uint32 (while restart noise is on)
 PTR_ROUTE_GOALS, PTR_ROUTE_STATUS = 13, 14    # SFM_BATCH_PTR_ROUTE_*: the goals [N_total][2] and the status [N_total] int32 (while routes are on)
 
 
@@ -937,6 +949,25 @@ def episode_arrays(B, agent, goal_radius=0.0, ped_radius=0.0, veh_radius=0.0, ma
     if (ms < 0).any() or (ms >= 2**31).any():
         raise ValueError("max_steps must be >= 0 (0: no time limit) and fit int32")
     return (np.ascontiguousarray(ag, dtype=np.int32), *radii, np.ascontiguousarray(ms, dtype=np.int32))
+
+
+def row_episode_arrays(scene_off, agents, goal_radius=0.0, ped_radius=0.0, veh_radius=0.0, max_steps=0):
+    """Row-episode settings -> the arguments of sfm_batch_set_row_episodes: (agents uint8 [N_total], goal_radius, ped_radius,
+    veh_radius float32 [B], max_steps int32 [B]).  ``agents``: which rows are agents -- True / False for every row, an array of
+    N_total values (nonzero = agent) or a list of B per-scene arrays.  The other arguments as for ``episode_arrays``: per scene.
+    Pure NumPy; raises ValueError on a shape that does not fit and on every value the library would refuse."""
+    so = np.asarray(scene_off)
+    B, n = so.shape[0] - 1, int(so[-1])
+    if isinstance(agents, (bool, np.bool_)):
+        ag = np.full(n, bool(agents))
+    else:
+        if isinstance(agents, (list, tuple)) and len(agents) == B and all(np.ndim(a) == 1 for a in agents):
+            agents = np.concatenate([np.asarray(a).reshape(-1) for a in agents]) if B else np.zeros(0)
+        ag = np.asarray(agents).reshape(-1) != 0
+        if ag.shape[0] != n:
+            raise ValueError(f"agents must hold one value per row, {n} in all, got {ag.shape[0]}")
+    _, rg, rp, rv, ms = episode_arrays(B, -1, goal_radius, ped_radius, veh_radius, max_steps)
+    return np.ascontiguousarray(ag, dtype=np.uint8), rg, rp, rv, ms
 
 
 class _DeviceSpan:
@@ -1020,6 +1051,7 @@ class SfmBatch:
         self.has_snapshot = False         # snapshot() has been taken and no later call has dropped it
         self.obs_k = None                 # neighbour slots of set_observation (None: observations are off)
         self.has_episodes = False         # set_episodes has been called and no later call has dropped it
+        self.has_row_episodes = False     # set_row_episodes has been called and no later call has dropped it
         self.scan_rays = None             # rays per row of set_scan (None: scans are off)
         self.grid_cells = None            # cells per side of set_grid (None: grids are off)
         self._grid_rows = self._grid_counts = None
@@ -1114,6 +1146,7 @@ class SfmBatch:
         self.scene_off = so.copy()
         self.obs_k = None                 # (the upload dropped the observations with the rows)
         self.has_episodes = False         # ... and the episodes
+        self.has_row_episodes = False     # ... and the row episodes
         self.scan_rays = None             # ... and the scans
         self.grid_cells = None            # ... and the grids
         self._grid_rows = self._grid_counts = None
@@ -1309,6 +1342,100 @@ class SfmBatch:
     def done_tensor(self, device=None):
         """The mask ``done`` as a torch tensor (B,) uint8 (0 / 1) that aliases device memory: what ``restart_device`` takes."""
         return self._alias(self.device_ptr(PTR_DONE)[0], (self.B,), device, "|u1")
+
+    def set_row_episodes(self, agents, goal_radius=0.0, ped_radius=0.0, veh_radius=0.0, max_steps=0):
+        """Which ROWS are agents and what ends an agent's episode (sfm_batch_set_row_episodes; see ``row_episode_arrays``): many
+        agents per scene, each with its own goal, collision test and time limit.  ``agents=None`` switches row episodes off and
+        frees the buffers.  Independent of ``set_episodes``; both may be set at once.  Needs ``upload`` first, which also drops
+        them; every other call keeps them, and they keep the snapshot.  Allocates and fills the record, the mask and the per-row
+        episode state (``row_episode_tensor()`` / ``row_done_tensor()`` must be taken again)."""
+        L = self._lib
+        if agents is None:
+            self._check(L.sfm_batch_set_row_episodes(self._b, None, None, None, None, None), "sfm_batch_set_row_episodes")
+            self.has_row_episodes = False
+            return
+        self._need_upload("set_row_episodes")
+        ag, rg, rp, rv, ms = row_episode_arrays(self.scene_off, agents, goal_radius, ped_radius, veh_radius, max_steps)
+        if ag.shape[0] == 0:                                           # (no rows: still a call, so that row episodes are on)
+            ag = np.zeros(1, np.uint8)
+        self._check(L.sfm_batch_set_row_episodes(self._b, u8ptr(ag), fptr(rg), fptr(rp), fptr(rv), iptr(ms)), "sfm_batch_set_row_episodes")
+        self.has_row_episodes = True
+
+    def end_row_step(self, auto_respawn=False):
+        """Decide which agent rows' episodes are over (sfm_batch_end_row_step): one launch on the batch's stream fills the row
+        record and ``row_done``; the host does not wait.  ``auto_respawn=True``: a second launch puts the rows that are done back
+        from the snapshot (``respawn_rows_device()``), the record keeping the terminal values.  Raises SfmLibraryError while row
+        episodes are off and, with ``auto_respawn``, whenever ``respawn_rows_device`` would."""
+        self._check(self._lib.sfm_batch_end_row_step(self._b, END_ROW_STEP_AUTO_RESPAWN if auto_respawn else 0), "sfm_batch_end_row_step")
+
+    def row_episodes(self):
+        """(record (N_total, 8) float32, done (N_total,) bool, age (N_total,) int32, prev_goal_d2 (N_total,) float32) as the last
+        ``end_row_step`` left them (synchronises the batch's stream).  Rows that are not agents hold zeros (prev_goal_d2: NaN)."""
+        self._need_upload("row_episodes")
+        n = int(self.scene_off[-1])
+        rec, done = np.zeros((max(n, 1), EPISODE_WIDTH), np.float32), np.zeros(max(n, 1), np.uint8)
+        age, prev = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float32)
+        self._check(self._lib.sfm_batch_download_row_episodes(self._b, fptr(rec), u8ptr(done), iptr(age), fptr(prev)),
+                    "sfm_batch_download_row_episodes")
+        return rec[:n], done[:n].astype(bool), age[:n], prev[:n]
+
+    def _row_ptr(self, which, name):
+        if not self.has_row_episodes:
+            raise SfmLibraryError(f"SfmBatch.{name}: row episodes are off (set_row_episodes; upload drops them)")
+        nbytes = C.c_int64(0)
+        ptr = self._lib.sfm_batch_device_ptr(self._b, which, C.byref(nbytes))
+        if not ptr and int(self.scene_off[-1]) > 0:
+            self._check(-1, "sfm_batch_device_ptr")
+        return ptr
+
+    def row_episode_tensor(self, device=None):
+        """The row record as a torch tensor (N_total, 8) float32 that aliases device memory (no copy): what a per-agent reward
+        reads after ``end_row_step()``.  Put torch and the batch on one stream.  Take it again after ``upload`` or
+        ``set_row_episodes``.  Raises SfmLibraryError while row episodes are off."""
+        return self._alias(self._row_ptr(PTR_ROW_EPISODES, "row_episode_tensor"), (int(self.scene_off[-1]), EPISODE_WIDTH), device)
+
+    def row_done_tensor(self, device=None):
+        """``row_done`` as a torch tensor (N_total,) uint8 (0 / 1) that aliases device memory: what ``respawn_rows_device`` takes."""
+        return self._alias(self._row_ptr(PTR_ROW_DONE, "row_done_tensor"), (int(self.scene_off[-1]),), device, "|u1")
+
+    def respawn_rows_device(self, mask=None):
+        """Put chosen ROWS back to the snapshot with one launch while their scenes go on (sfm_batch_respawn_rows_device); rows that
+        are not chosen, the vehicles, the clocks and every counter of a scene are not touched.  ``mask``: None -- the batch's own
+        ``row_done`` as the last ``end_row_step`` left it; or a torch tensor of N_total one-byte elements (bool, uint8 or int8) on
+        the batch's device, contiguous, nonzero = respawn.  With restart noise set the respawned rows are placed by its rounds
+        against the scene as it stands now (``reset.respawn_rows_scene`` is the host twin).  Raises SfmLibraryError without a
+        snapshot, with ``mask=None`` while row episodes are off, and while a spawn schedule or routes are set: re-planning single
+        rows and re-entering the birth machine are out of scope, such batches restart whole scenes."""
+        self._need_upload("respawn_rows_device")
+        if mask is None:
+            ptr = None
+        else:
+            import torch
+            n = int(self.scene_off[-1])
+            if not isinstance(mask, torch.Tensor):
+                raise ValueError("respawn_rows_device takes a torch tensor on the device (or None: the batch's row_done)")
+            if not mask.is_cuda:
+                raise ValueError("the mask of respawn_rows_device must be on the device")
+            if mask.element_size() != 1 or mask.dtype not in (torch.bool, torch.uint8, torch.int8):
+                raise ValueError(f"the mask of respawn_rows_device must be bool, uint8 or int8, got {mask.dtype}")
+            if mask.numel() != n or not mask.is_contiguous():
+                raise ValueError(f"the mask of respawn_rows_device must hold {n} contiguous elements, got shape {tuple(mask.shape)}"
+                                 f"{'' if mask.is_contiguous() else ' (not contiguous)'}")
+            if n == 0:
+                return
+            ptr = mask.data_ptr()
+        self._check(self._lib.sfm_batch_respawn_rows_device(self._b, C.c_void_p(ptr or None)), "sfm_batch_respawn_rows_device")
+
+    def row_respawns(self):
+        """(row_resets (N_total,) uint32, fallbacks (B,) uint32): how often each row has been respawned since ``set_restart_noise``,
+        and how many chosen rows of each scene's latest respawn no try could place.  Synchronises the batch's stream; raises
+        SfmLibraryError while restart noise is off."""
+        self._need_upload("row_respawns")
+        n = int(self.scene_off[-1])
+        resets, fallbacks = np.zeros(max(n, 1), np.uint32), np.zeros(self.B, np.uint32)
+        self._check(self._lib.sfm_batch_download_row_respawns(self._b, resets.ctypes.data, fallbacks.ctypes.data),
+                    "sfm_batch_download_row_respawns")
+        return resets[:n], fallbacks
 
     def set_steering(self, kinds, commands=None):
         """Which rows the caller steers, and their first commands (sfm_batch_set_steering; see ``pack_steering``): kind 1 rows take

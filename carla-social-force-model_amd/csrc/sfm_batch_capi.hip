@@ -282,7 +282,8 @@ int sfm::batch_restart_device(SfmBatch* b, const uint8_t* d_mask, long long shif
     if (b->tracks.on) b->tracks.first_stale = true;                     // who was chosen is known on the device only
     int rc = batch_restart_noise(b, nullptr, d_mask, b->B);
     if (!rc) rc = batch_plan_routes(b, nullptr, d_mask, b->B);          // (routes: from where the rows were placed)
-    return rc ? rc : batch_autopilot_restart(b, nullptr, d_mask, b->B); // (the autopilot's cursors)
+    if (!rc) rc = batch_autopilot_restart(b, nullptr, d_mask, b->B);    // (the autopilot's cursors)
+    return rc ? rc : batch_row_restart(b, nullptr, d_mask, b->B);       // (the row episodes start over)
 }
 
 // sfm_batch_run_recorded, and with want_forces also the [F][K][N_total][C] force record of every recorded tick
@@ -436,7 +437,7 @@ int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x
     drop_batch_modes(b);                                          // a new crowd: its modes are set anew
     b->steer = {};                                                // ... and so are its commands (the rows may differ)
     b->obs = {};                                                  // ... and its observations
-    b->ep = {};                                                   // ... and its episodes (the agents are rows)
+    b->ep = {};                                                   // ... and its episodes, per scene and per row (the agents are rows)
     b->scan = {};                                                 // ... and its scans (the mask is per row)
     b->noise = {};                                                // ... and its restart noise (the boxes are per row)
     b->grid = {};                                                 // ... and its grids (the slots are per row)
@@ -1018,7 +1019,8 @@ int sfm_batch_restart(SfmBatch* b, const uint8_t* mask) {
         }
     rc = batch_restart_noise(b, r.list, nullptr, chosen);
     if (!rc) rc = batch_plan_routes(b, r.list, nullptr, chosen);        // (routes: from where the rows were placed)
-    return rc ? rc : batch_autopilot_restart(b, r.list, nullptr, chosen);   // (the autopilot's cursors)
+    if (!rc) rc = batch_autopilot_restart(b, r.list, nullptr, chosen);  // (the autopilot's cursors)
+    return rc ? rc : batch_row_restart(b, r.list, nullptr, chosen);     // (the row episodes start over)
 }
 
 // The restart with its mask on the device (ABI 16): no copy, no host scan, no event wait, no pinned list.

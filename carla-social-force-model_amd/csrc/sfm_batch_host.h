@@ -3,7 +3,7 @@
 // read or write; sfm_batch_sense_capi.hip the read-only sensors (observations, episode ends, range scans, occupancy grids) and the device pointers;
 // sfm_batch_reset_capi.hip the restart noise; sfm_batch_replay_capi.hip the observed tracks; sfm_batch_drive_capi.hip the driven
 // vehicles and the vehicle observations (the vehicles' range scans are a sensor: sfm_batch_sense_capi.hip); sfm_batch_route_capi.hip
-// the routes over walk graphs.
+// the routes over walk graphs; sfm_batch_row_episode_capi.hip the row episodes and the row respawns.
 #pragma once
 #include "sfm_capi_common.h"
 #include "sfm_metres.h"
@@ -131,8 +131,23 @@ struct BatchObsDev {
     DevBuf<float> buf;         // [N_total][16 + 4 k]
 };
 
+// row episodes (sfm_batch_set_row_episodes): the episodes per ROW -- the settings, the scenes' agent lists, the per-row episode
+// state, and the record and mask sfm_batch_end_row_step fills; nothing a tick reads or writes
+struct BatchRowEpisodeDev {
+    bool on = false;           // (not "record is allocated": a batch without rows can have row episodes and has no buffers)
+    DevBuf<BatchEpisodeScene> set;     // [B] (agent = -1: not read)
+    DevBuf<int> agent_off;             // [B+1]
+    DevBuf<int> agent_rows;            // [agents] row indices inside their scenes, ascending per scene
+    DevBuf<int> age;                   // [N_total]
+    DevBuf<float> prev;                // [N_total] row_prev_goal_d2
+    DevBuf<float> record;              // [N_total][8]
+    DevBuf<uint8_t> done;              // [N_total]
+};
+
 // episodes (sfm_batch_set_episodes, ABI 16): the settings, the per-scene episode state, and the record and mask sfm_batch_end_step
-// fills; nothing a tick reads or writes
+// fills; nothing a tick reads or writes.  The row episodes are the second half of the same block (`rows`), set and dropped by their
+// own call: sfm_batch_upload_state drops both halves with one line, sfm_batch_set_episodes keeps `rows` and
+// sfm_batch_set_row_episodes keeps the rest.
 struct BatchEpisodeDev {
     bool on = false;
     DevBuf<BatchEpisodeScene> set;     // [B]
@@ -140,6 +155,7 @@ struct BatchEpisodeDev {
     DevBuf<float> prev;                // [B] prev_goal_d2
     DevBuf<float> record;              // [B][8]
     DevBuf<uint8_t> done;              // [B]
+    BatchRowEpisodeDev rows;           // the row episodes (sfm_batch_set_row_episodes)
 };
 
 // range scans, from the rows (SfmBatch::scan: sfm_batch_set_scan, ABI 17) and from the vehicles (SfmBatch::vscan:
@@ -168,6 +184,8 @@ struct BatchNoiseDev {
     DevBuf<float2> pos_box;        // [N_total] {hx, hy}
     DevBuf<float2> goal_box;       // [N_total]; not allocated: the goals stay
     DevBuf<int> delay;             // [M]; not allocated: no traffic timing
+    DevBuf<uint32_t> row_resets;   // [N_total] respawns of the row since the noise was set (sfm_batch_respawn_rows_device)
+    DevBuf<uint32_t> row_fallbacks;    // [B] chosen rows of the scene's latest respawn that no try could place
     long long max_delay = 0;       // the largest delay: what a restart's int32 fit check adds
 };
 
@@ -313,6 +331,7 @@ constexpr const char* NO_SNAPSHOT = "the batch has no snapshot: call sfm_batch_s
 constexpr const char* STEERING_OFF = "steering is off: call sfm_batch_set_steering first (sfm_batch_upload_state drops it)";
 constexpr const char* OBSERVATIONS_OFF = "observations are off: call sfm_batch_set_observation first (sfm_batch_upload_state drops them)";
 constexpr const char* EPISODES_OFF = "episodes are off: call sfm_batch_set_episodes first (sfm_batch_upload_state drops them)";
+constexpr const char* ROW_EPISODES_OFF = "row episodes are off: call sfm_batch_set_row_episodes first (sfm_batch_upload_state drops them)";
 constexpr const char* NOISE_OFF = "restart noise is off: call sfm_batch_set_restart_noise first (sfm_batch_upload_state drops it)";
 constexpr const char* SCANS_OFF = "scans are off: call sfm_batch_set_scan first (sfm_batch_upload_state drops them)";
 constexpr const char* OBSERVED_OFF = "observed tracks are off: call sfm_batch_set_observed first (sfm_batch_upload_state, setting modes or a "
@@ -372,6 +391,14 @@ hipError_t launch_batch_autopilot_restart(const int* list, const uint8_t* mask, 
                                           int scenes, hipStream_t st);
 constexpr const char* AUTOPILOT_OFF = "the vehicle autopilot is off: call sfm_batch_set_vehicle_autopilot first (sfm_batch_set_vehicle_driving, "
                                       "sfm_batch_set_dynamic_boxes and sfm_batch_set_dynamic_obstacles drop it)";
+// Row episodes and row respawns (sfm_batch_row_episode_capi.hip, sfm_batch_row_episode.hip).  batch_row_restart: the row episodes
+// of the chosen scenes start over, one small launch behind the restart's own (and the noise, the routes and the autopilot's) with the
+// same choice of scenes; nothing while row episodes are off.
+int batch_row_restart(SfmBatch* b, const int* d_list, const uint8_t* d_mask, int scenes);
+hipError_t launch_batch_row_episode(const RowEpisodeArgs& a, int B, hipStream_t st);
+hipError_t launch_batch_row_restart(const int* list, const uint8_t* mask, const int* scene_off, int* row_age, float* row_prev_goal_d2,
+                                    int scenes, hipStream_t st);
+hipError_t launch_batch_row_respawn(const RowRespawnArgs& a, int B, hipStream_t st);
 // The delays go with the tracks they refer to (the caller synchronised the stream).
 inline void drop_noise_delays(SfmBatch* b) { b->noise.delay = {}; b->noise.max_delay = 0; }
 

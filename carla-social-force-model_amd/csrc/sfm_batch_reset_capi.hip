@@ -86,7 +86,11 @@ int sfm_batch_set_restart_noise(SfmBatch* b, const uint32_t* seeds, const float*
     HIP_TRY(b, hipMemcpy(z.gap2, gap2.data(), sizeof(float2) * B, hipMemcpyHostToDevice));
     HIP_TRY(b, hipMemsetAsync(z.resets, 0, sizeof(uint32_t) * B, b->stream));
     HIP_TRY(b, hipMemsetAsync(z.fallbacks, 0, sizeof(uint32_t) * B, b->stream));
+    HIP_TRY(b, z.row_fallbacks.alloc(B));                       // the row respawns' counters (sfm_batch_respawn_rows_device)
+    HIP_TRY(b, hipMemsetAsync(z.row_fallbacks, 0, sizeof(uint32_t) * B, b->stream));
     if (n > 0) {
+        HIP_TRY(b, z.row_resets.alloc(n));
+        HIP_TRY(b, hipMemsetAsync(z.row_resets, 0, sizeof(uint32_t) * n, b->stream));
         HIP_TRY(b, z.pos_box.alloc(n));
         HIP_TRY(b, hipMemcpy(z.pos_box, pos.data(), sizeof(float2) * n, hipMemcpyHostToDevice));
         if (goal_hx) {

@@ -107,7 +107,7 @@ static int build_grid(SfmBatch* b, size_t items, int channels, const char* whose
 
 // One lookup for the device buffers a caller may see: which = SFM_BATCH_PTR_*, or PTR_OBSERVATIONS for sfm_batch_observation_ptr's.
 // off: why there is none (its feature is off, no state was uploaded), else p and bytes -- both 0 where the buffer has no element.
-constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_VEHICLE_GRID + 1;   // (not part of the ABI: sfm_batch_device_ptr refuses it)
+constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_ROW_RESETS + 1;   // (not part of the ABI: sfm_batch_device_ptr refuses it)
 struct BatchBuffer { const char* off; void* p; size_t bytes; };
 static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     const size_t n = (size_t)b->n_total, B = (size_t)b->B;
@@ -123,6 +123,13 @@ static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     case SFM_BATCH_PTR_DONE:
         if (!b->ep.on) return {EPISODES_OFF, nullptr, 0};
         return which == SFM_BATCH_PTR_EPISODES ? have(b->ep.record, 8 * sizeof(float) * B) : have(b->ep.done, B);
+    case SFM_BATCH_PTR_ROW_EPISODES:
+    case SFM_BATCH_PTR_ROW_DONE:
+        if (!b->ep.rows.on) return {ROW_EPISODES_OFF, nullptr, 0};
+        return which == SFM_BATCH_PTR_ROW_EPISODES ? have(b->ep.rows.record, 8 * sizeof(float) * n) : have(b->ep.rows.done, n);
+    case SFM_BATCH_PTR_ROW_RESETS:
+        if (!b->noise.on) return {NOISE_OFF, nullptr, 0};
+        return have(b->noise.row_resets, sizeof(uint32_t) * n);
     case SFM_BATCH_PTR_RESETS:
         if (!b->noise.on) return {NOISE_OFF, nullptr, 0};
         return have(b->noise.resets, sizeof(uint32_t) * B);
@@ -188,13 +195,16 @@ void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes) {
     // word, so a caller of ABI 17 as it was sees no difference
     // (SFM_BATCH_PTR_GRID likewise, while grids are off, SFM_BATCH_PTR_ROW_SCORES / _SCENE_SCORES while observed tracks are off, and
     //  SFM_BATCH_PTR_VEHICLE_COMMANDS / _VEHICLE_OBS while driving / vehicle observations are off; SFM_BATCH_PTR_VEHICLE_SCAN is
-    //  specified as SFM_ERR_STATE while the vehicle scan is off, so it is always known)
+    //  specified as SFM_ERR_STATE while the vehicle scan is off, so it is always known; SFM_BATCH_PTR_ROW_EPISODES / _ROW_DONE while
+    //  row episodes are off and SFM_BATCH_PTR_ROW_RESETS while restart noise is off are refused likewise)
     const bool known = (which >= SFM_BATCH_PTR_COMMANDS && which <= SFM_BATCH_PTR_SCAN) || (which == SFM_BATCH_PTR_RESETS && b->noise.on) ||
                        (which == SFM_BATCH_PTR_GRID && b->grid.on) ||
                        ((which == SFM_BATCH_PTR_ROW_SCORES || which == SFM_BATCH_PTR_SCENE_SCORES) && b->replay.on) ||
                        (which == SFM_BATCH_PTR_VEHICLE_COMMANDS && b->drive.on) || (which == SFM_BATCH_PTR_VEHICLE_OBS && b->vobs.on) ||
                        which == SFM_BATCH_PTR_VEHICLE_SCAN || (which == SFM_BATCH_PTR_VEHICLE_GRID && b->boxes.vgrid.on) ||
-                       ((which == SFM_BATCH_PTR_ROUTE_GOALS || which == SFM_BATCH_PTR_ROUTE_STATUS) && b->routes.on);
+                       ((which == SFM_BATCH_PTR_ROUTE_GOALS || which == SFM_BATCH_PTR_ROUTE_STATUS) && b->routes.on) ||
+                       ((which == SFM_BATCH_PTR_ROW_EPISODES || which == SFM_BATCH_PTR_ROW_DONE) && b->ep.rows.on) ||
+                       (which == SFM_BATCH_PTR_ROW_RESETS && b->noise.on);
     if (!known) { bfail(b, SFM_ERR_INVALID, "which must be SFM_BATCH_PTR_COMMANDS, _STATE, _ZSTATE, _EPISODES, _DONE or _SCAN"); return nullptr; }
     return buffer_ptr(b, which, which == SFM_BATCH_PTR_SCAN ? ", so which = SFM_BATCH_PTR_SCAN has no buffer" :
                                 which == SFM_BATCH_PTR_EPISODES || which == SFM_BATCH_PTR_DONE ? ", so which = SFM_BATCH_PTR_EPISODES / _DONE has no buffer" : "", bytes);
@@ -257,7 +267,9 @@ int sfm_batch_set_episodes(SfmBatch* b, const int32_t* agent, const float* goal_
     if (rc) return rc;
     if (!agent) {
         HIP_TRY(b, hipStreamSynchronize(b->stream));             // an end_step or a restart in flight may still write the buffers
+        BatchRowEpisodeDev rows = std::move(b->ep.rows);         // (the row episodes stay: they have a call of their own)
         b->ep = {};
+        b->ep.rows = std::move(rows);
         return SFM_OK;
     }
     if (!b->have_state) return bfail(b, SFM_ERR_STATE, NO_STATE);
@@ -289,6 +301,7 @@ int sfm_batch_set_episodes(SfmBatch* b, const int32_t* agent, const float* goal_
     HIP_TRY(b, hipMemsetAsync(e.done, 0, B, b->stream));
     e.on = true;
     HIP_TRY(b, hipStreamSynchronize(b->stream));                 // the zero fills; and an end_step or a restart in flight may still write the old buffers
+    e.rows = std::move(b->ep.rows);                              // (the row episodes stay)
     b->ep = std::move(e);
     return SFM_OK;
 }

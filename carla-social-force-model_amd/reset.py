@@ -169,3 +169,100 @@ def resample_scene(scene, seed, episode, pos_box, goal_box=None, min_gap=0.0, po
 
     out = (np.stack([px, py], axis=1), wxy, first, veh, int(opened.sum()))
     return out + ({"round": placed_in, "rejected": counts},) if detail else out
+
+
+RESPAWN_SALT = np.uint32(0x2545F491)
+
+
+def respawn_word(seed, i, e, t, c):
+    """The random word of a row respawn: ``reset_word``'s formula under the constant 0x2545F491, with ``e`` the ROW's respawn counter
+    (``row_resets[i]`` before the respawn) -- so a respawn's words never coincide with a scene restart's and never repeat."""
+    u32 = lambda v: np.asarray(v, dtype=np.uint64).astype(np.uint32)
+    seed, i, e, t, c = (u32(v) for v in (seed, i, e, t, c))
+    with np.errstate(over="ignore"):
+        inner = mix32(RESPAWN_SALT ^ (np.uint32(8) * i + c))
+        return mix32(seed ^ mix32(inner + GOLDEN * (np.uint32(32) * e + t)))
+
+
+def respawn_rows_scene(scene, chosen, snapshot_state, snapshot_waypoints, state, waypoints, row_resets=None, seed=None, pos_box=None,
+                       goal_box=None, min_gap=0.0, point_gap=0.0, tries=8, vehicles=None, detail=False):
+    """One respawn of the chosen rows of one scene (sfm_batch_respawn_rows_device): (loc (N,D) float32, vel (N,D) float32,
+    waypoint_xy (N,2) float32, row_resets (N,) uint32, fallbacks) -- what ``SfmBatch.state()`` and ``waypoints()`` return for the
+    scene after the respawn, the rows' respawn counters, and the scene's entry of ``row_respawns()[1]`` (None: no row is chosen, the
+    device leaves the scene's counter alone).
+
+    ``chosen``: (N,) nonzero = respawn the row.  ``snapshot_state`` = (loc, vel) and ``snapshot_waypoints`` (N,2|3): the rows as
+    the snapshot holds them; ``state`` / ``waypoints``: as they are now.  ``seed=None``: restart noise is off -- the chosen rows are
+    the snapshot's, the others stay (``row_resets`` comes back as given, ``fallbacks`` None).  With a seed the restart noise's
+    rounds run for the chosen rows (``resample_scene``) with three changes: the words are ``respawn_word``'s with e = the row's
+    ``row_resets`` (each chosen row's counter goes up by one); a chosen row is movable if it is live in the snapshot and has a
+    nonzero ``pos_box``, and the blockers from the start are every live row that is not chosen where it stands NOW and every
+    chosen live row with a zero box at its snapshot position; the points are ``scene``'s borders and static obstacles and
+    ``vehicles`` (the scene's list of (center, ring) as they stand now; None: the scene's own).  ``detail=True`` appends the dict of
+    ``resample_scene``."""
+    sloc, svel = (np.asarray(a, dtype=np.float32) for a in snapshot_state)
+    cloc, cvel = (np.asarray(a, dtype=np.float32) for a in state)
+    n = cloc.shape[0] if cloc.ndim == 2 else 0
+    ch = np.asarray(chosen).reshape(-1) != 0
+    if ch.shape[0] != n:
+        raise ValueError(f"{ch.shape[0]} choices for a scene of {n} pedestrians")
+    swp = _f32(np.asarray(snapshot_waypoints, dtype=np.float64).reshape(n, -1)[:, :2], 2) if n else np.zeros((0, 2), np.float32)
+    cwp = _f32(np.asarray(waypoints, dtype=np.float64).reshape(n, -1)[:, :2], 2) if n else np.zeros((0, 2), np.float32)
+    loc, vel, wxy = cloc.copy(), cvel.copy(), cwp.copy()
+    loc[ch], vel[ch], wxy[ch] = sloc[ch], svel[ch], swp[ch]
+    resets = np.zeros(n, np.uint32) if row_resets is None else np.array(row_resets, dtype=np.uint32).reshape(n)
+    info = {"round": np.full(n, NOT_MOVABLE, dtype=np.int64), "rejected": {"blocker": 0, "lower": 0, "point": 0}}
+    if seed is None or not ch.any():
+        out = (loc, vel, wxy, resets, None)
+        return out + (info,) if detail else out
+    tries = int(tries)
+    if not 1 <= tries <= MAX_TRIES:
+        raise ValueError(f"tries must be 1 .. {MAX_TRIES}, got {tries}")
+    seed = int(seed) & 0xFFFFFFFF
+    e = resets.copy()                                                 # read before this respawn
+    resets[ch] += np.uint32(1)
+    gap2, pgap2 = range2(min_gap), range2(point_gap)
+    idx = np.arange(n, dtype=np.uint32)
+    veh = list((_get(scene, "dynamic_obstacles") or []) if vehicles is None else vehicles)
+    points = np.concatenate([_polylines(_get(scene, "borders") or [], False)[0], _polylines(_get(scene, "static_obstacles") or [], True)[0],
+                             _polylines(veh, True)[0]], axis=0)
+    hb = _boxes(pos_box, n, "pos_box")
+    x, y = loc[:, 0].copy(), loc[:, 1].copy()                         # after the copies: the snapshot's for chosen rows, the current for the rest
+    alive = _live(x, y)
+    movable = ch & alive & ~((hb[:, 0] == 0) & (hb[:, 1] == 0))
+    blocker = alive & ~movable
+    px, py = x.copy(), y.copy()
+    opened = movable.copy()
+    placed_in = info["round"]
+    placed_in[movable] = FALLBACK
+    counts = info["rejected"]
+    with np.errstate(over="ignore", invalid="ignore"):
+        for t in range(tries):
+            if not opened.any():
+                break
+            o = np.flatnonzero(opened)
+            qx = x[o] + offset(respawn_word(seed, idx[o], e[o], t, C_POS_X), hb[o, 0])
+            qy = y[o] + offset(respawn_word(seed, idx[o], e[o], t, C_POS_Y), hb[o, 1])
+            bl = np.flatnonzero(blocker)
+            r_block = (_d2(px[bl][None, :] - qx[:, None], py[bl][None, :] - qy[:, None]) < gap2).any(axis=1)
+            lower = o[None, :] < o[:, None]
+            r_lower = ((_d2(qx[None, :] - qx[:, None], qy[None, :] - qy[:, None]) < gap2) & lower).any(axis=1)
+            r_point = np.zeros(o.shape[0], bool)
+            if pgap2 > 0 and points.shape[0]:
+                r_point = (_d2(qx[:, None] - points[None, :, 0], qy[:, None] - points[None, :, 1]) < pgap2).any(axis=1)
+            for key, r in (("blocker", r_block), ("lower", r_lower), ("point", r_point)):
+                counts[key] += int(r.sum())
+            good = ~(r_block | r_lower | r_point)
+            ok = o[good]
+            px[ok], py[ok] = qx[good], qy[good]
+            blocker[ok] = True
+            opened[ok] = False
+            placed_in[ok] = t
+        if goal_box is not None and n:
+            gb = _boxes(goal_box, n, "goal_box")
+            a = np.flatnonzero(ch & alive)
+            wxy[a, 0] = wxy[a, 0] + offset(respawn_word(seed, idx[a], e[a], 0, C_GOAL_X), gb[a, 0])
+            wxy[a, 1] = wxy[a, 1] + offset(respawn_word(seed, idx[a], e[a], 0, C_GOAL_Y), gb[a, 1])
+    loc[:, 0], loc[:, 1] = px, py
+    out = (loc, vel, wxy, resets, int(opened.sum()))
+    return out + (info,) if detail else out

@@ -726,6 +726,86 @@ int sfm_batch_set_restart_noise(SfmBatch* b, const uint32_t* seeds, const float*
                                 const float* goal_hy, const float* min_gap, const float* point_gap, int tries,
                                 const int32_t* track_delay);
 int sfm_batch_download_restart_noise(SfmBatch* b, uint32_t* resets, uint32_t* fallbacks);
+/* Row episodes and row respawns: many agents per scene.  Decentralised multi-agent training makes several or all pedestrians of a
+ * scene agents, each with its own goal, collision test and time limit, and puts an agent that arrives or collides back ALONE while
+ * the scene goes on.  sfm_batch_end_row_step is sfm_batch_end_step asked for every agent ROW, by ONE launch of
+ * sfm_batch_row_episode_kernel (a workgroup per scene); sfm_batch_respawn_rows_device is the restart for chosen rows in place of
+ * chosen scenes, by ONE launch of sfm_batch_row_respawn_kernel.  A batch that never calls sfm_batch_set_row_episodes or a row respawn
+ * launches exactly what it launched before.
+ * These entry points and SFM_BATCH_PTR_ROW_EPISODES / _ROW_DONE / _ROW_RESETS were added WITHOUT a bump of SFM_ABI_VERSION (it stays
+ * 17), like the restart noise: additions only, recognised by the symbols themselves.
+ *
+ * Settings (sfm_batch_set_row_episodes).  agents: [N_total] bytes on the host, nonzero = the row is an agent.  goal_radius,
+ * ped_radius, veh_radius, max_steps: [B], per scene, validated as sfm_batch_set_episodes validates them, r2 = float32(double(r) * r).
+ * The scenes' agent rows are compacted into a list on the host: the list is settings, not state.  Row episodes are independent of
+ * the scene episodes of sfm_batch_set_episodes; both may be set at once.
+ *
+ * State.  Per row row_age (int32, zero-filled) and row_prev_goal_d2 (float, NaN-filled).  A snapshot neither holds nor restores
+ * them.  EVERY restart of a scene -- sfm_batch_restart, sfm_batch_restart_device, the auto restart of sfm_batch_end_step -- sets
+ * row_age = 0 and row_prev_goal_d2 = NaN for ALL rows of the restarted scene, by one small launch behind the restart's own
+ * (sfm_batch_row_restart_kernel; sfm_batch_restart_kernel is unchanged); a respawn does so for the respawned rows.
+ *
+ * Record.  Row i owns SFM_BATCH_EPISODE_WIDTH floats, [N_total][8], and row_done[i] (uint8_t) = slot 0.  The slots, the reason
+ * bits and the rules are those of sfm_batch_end_step above ("Record" and "Rules, all exact") with "the agent a" read as "this agent
+ * row": age and prev_goal_d2 are the row's, the radii and max_steps its scene's, and ped_d2 is the minimum over ALL live rows j != i
+ * of the scene, other agents included.  The kernel never writes the record, the row_done byte or the state of a row that is not an
+ * agent: sfm_batch_set_row_episodes fills them with zeros (row_prev_goal_d2: NaN) and they stay so.
+ * Only minima are taken, a minimum of floats without NaNs does not depend on the order it is taken in, and there are no atomics: the
+ * kernel's split of an agent's candidates over 1 .. 64 lanes (chosen from the scene's agent count) gives the same bits whatever it
+ * is, and a scene's records are bitwise the same alone or anywhere in any batch.  Only x, y of the state are used.
+ *
+ * sfm_batch_set_row_episodes allocates and fills all of it and waits for the batch's stream; agents = NULL switches row episodes off
+ * and frees the buffers.  Refusals are those of sfm_batch_set_episodes (there is no agent index to refuse).  sfm_batch_upload_state
+ * drops the row episodes; every other call keeps them, and they keep the snapshot.  (sfm_batch_set_episodes, also with agent = NULL,
+ * keeps the row episodes, and sfm_batch_set_row_episodes keeps the scene episodes.)
+ * sfm_batch_end_row_step: ONE launch on the batch's stream; the host does not wait.  flags: 0, or SFM_END_ROW_STEP_AUTO_RESPAWN: the
+ * launch is followed by sfm_batch_respawn_rows_device with the row_done it wrote; the record keeps the terminal values.
+ * SFM_ERR_STATE while row episodes are off; with the flag every refusal of the respawn applies to the whole call, and nothing is
+ * launched.  sfm_batch_download_row_episodes synchronises the stream and copies the record ([N_total][8]), row_done ([N_total]
+ * bytes), row_age ([N_total] int32) and row_prev_goal_d2 ([N_total] float); NULL skips a column.
+ *
+ * Row respawns (sfm_batch_respawn_rows_device).  d_mask: [N_total] bytes of DEVICE memory, nonzero = respawn the row -- the batch's
+ * own row_done (SFM_BATCH_PTR_ROW_DONE; d_mask = NULL takes it) or any buffer of the caller's, such as a torch bool tensor; the values
+ * are not validated.  ONE launch of B workgroups: a workgroup counts its scene's chosen rows and leaves at once when there is none
+ * -- such a scene is not written at all, counters included.  For a chosen row i its entries of the per-row arrays of the restart
+ * ({x, y, vx, vy}, {z, vz}, {wx, wy, target_speed, radius}, the waypoint draw counter, and with modes set the mode, its target and
+ * the queue cursor) are copied from the snapshot, and row_age[i] = 0, row_prev_goal_d2[i] = NaN while row episodes are on.  Rows that
+ * are not chosen are not written at all, and neither are the scene's vehicles, clock, tracks, scene episode state or restart counter.
+ * So a despawned row comes back live with the mode it had at the snapshot, into the scene as it is NOW.
+ * Refused with nothing launched: no snapshot (SFM_ERR_STATE); d_mask NULL while row episodes are off (SFM_ERR_INVALID); a spawn
+ * schedule or routes are set (SFM_ERR_STATE).  Re-planning the route of a single row and re-entering the birth machine of the spawn
+ * schedule are deliberately OUT OF SCOPE: such batches restart whole scenes.
+ *
+ * With restart noise set (sfm_batch_set_restart_noise) a respawn SAMPLES: the restart noise's steps 1 to 4 and 6 with three changes.
+ * (a) Random words.  The word of row i (its index inside the scene) is
+ *        h = mix32(seed_b ^ mix32(mix32(0x2545F491 ^ (8 i + c)) + 0x9E3779B9 (32 e + t)))
+ *     with e = row_resets[i], a per-row uint32 counter that sfm_batch_set_restart_noise zero-fills; each chosen row gets
+ *     row_resets[i] += 1.  So the words never coincide with a scene restart's and never repeat.  Scene restarts leave row_resets alone.
+ * (b) Row classes.  A chosen row is movable if it is live after the copy and has a nonzero box.  Blockers from the start: every live
+ *     row of the scene that is NOT chosen, where it stands now, and every chosen live row with a zero box, at its snapshot position.
+ *     Rows that are not live are out of everyone's way.
+ * (c) Geometry.  The points are the scene's borders, static obstacles and vehicle rings as they stand now.  No traffic timing.
+ * Everything else is the restart noise's: proposals around the snapshot position, rejection against blockers, against the
+ * lower-index proposals of the same round and against points, fallbacks at the snapshot position, the goal of every chosen live row
+ * + the offset of components 2 and 3 (t = 0) while goal boxes are set.  row_respawn_fallbacks[b] is the number of chosen movable
+ * rows no try could place at the scene's latest respawn that chose one of its rows.  sfm_batch_download_row_respawns synchronises
+ * the stream and copies row_resets ([N_total] uint32) and row_respawn_fallbacks ([B] uint32); NULL skips a column; SFM_ERR_STATE while
+ * the noise is off.  Without noise a respawn is plain copies and no counter exists.
+ *
+ * sfm_batch_device_ptr: SFM_BATCH_PTR_ROW_EPISODES, the row record ([N_total][8] float); SFM_BATCH_PTR_ROW_DONE, row_done ([N_total]
+ * uint8_t) -- both valid until the next sfm_batch_set_row_episodes or sfm_batch_upload_state; SFM_BATCH_PTR_ROW_RESETS, row_resets
+ * ([N_total] uint32), valid until the next sfm_batch_set_restart_noise or sfm_batch_upload_state.  While their feature is off the
+ * values are refused as the unknown `which` they were before. */
+#define SFM_BATCH_PTR_ROW_EPISODES 16
+#define SFM_BATCH_PTR_ROW_DONE 17
+#define SFM_BATCH_PTR_ROW_RESETS 18
+#define SFM_END_ROW_STEP_AUTO_RESPAWN 1u
+int sfm_batch_set_row_episodes(SfmBatch* b, const uint8_t* agents, const float* goal_radius, const float* ped_radius,
+                               const float* veh_radius, const int32_t* max_steps);
+int sfm_batch_end_row_step(SfmBatch* b, uint32_t flags);
+int sfm_batch_download_row_episodes(SfmBatch* b, float* record, uint8_t* row_done, int32_t* row_age, float* row_prev_goal_d2);
+int sfm_batch_respawn_rows_device(SfmBatch* b, const uint8_t* d_mask);
+int sfm_batch_download_row_respawns(SfmBatch* b, uint32_t* row_resets, uint32_t* fallbacks);
 /* Range scans on the device (ABI 17): the sensor most crowd-navigation policies are trained on.  R rays around a row, each giving
  * the distance to the first thing it meets and what that was, by ONE launch of sfm_batch_scan_kernel (a workgroup per scene)
  * straight from the buffers the tick reads, into a device buffer the caller reads with no copy.  The record is defined bit for bit
