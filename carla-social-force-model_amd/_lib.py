@@ -51,7 +51,9 @@ SINCE = {"sfm_step_packed": 4, "sfm_set_dynamic_obstacles_packed": 4, "sfm_step_
                             "sfm_batch_set_vehicle_autopilot", "sfm_batch_download_vehicle_autopilot",
                             "sfm_batch_vehicle_autopilot_launches",
             "sfm_batch_set_row_episodes", "sfm_batch_end_row_step", "sfm_batch_download_row_episodes",
-            "sfm_batch_respawn_rows_device", "sfm_batch_download_row_respawns")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
+            "sfm_batch_respawn_rows_device", "sfm_batch_download_row_respawns",
+            "sfm_batch_set_vehicle_episodes", "sfm_batch_end_vehicle_step", "sfm_batch_download_vehicle_episodes",
+            "sfm_batch_respawn_vehicles_device")}}      # entry points younger than ABI 3: an OLDER build named by SFM_LIB_PATH (A/B of builds) may lack them
 UNBUMPED = ("sfm_batch_set_restart_noise", "sfm_batch_download_restart_noise",
             "sfm_batch_set_grid", "sfm_batch_grid", "sfm_batch_download_grid",
             "sfm_batch_set_observed", "sfm_batch_run_observed", "sfm_batch_score",
@@ -66,7 +68,9 @@ UNBUMPED = ("sfm_batch_set_restart_noise", "sfm_batch_download_restart_noise",
             "sfm_batch_set_vehicle_autopilot", "sfm_batch_download_vehicle_autopilot",
             "sfm_batch_vehicle_autopilot_launches",
             "sfm_batch_set_row_episodes", "sfm_batch_end_row_step", "sfm_batch_download_row_episodes",
-            "sfm_batch_respawn_rows_device", "sfm_batch_download_row_respawns")   # ... and those a build of the SAME number may lack
+            "sfm_batch_respawn_rows_device", "sfm_batch_download_row_respawns",
+            "sfm_batch_set_vehicle_episodes", "sfm_batch_end_vehicle_step", "sfm_batch_download_vehicle_episodes",
+            "sfm_batch_respawn_vehicles_device")   # ... and those a build of the SAME number may lack
 
 FORCE_NAMES = ("acceleration_force", "pedestrian_force", "border_force",
                "static_obstacle_force", "dynamic_obstacle_force")
@@ -237,6 +241,11 @@ SYMBOLS = {
     "sfm_batch_download_row_episodes": (C.c_int, [_H, _F, _U8, _I, _F]),
     "sfm_batch_respawn_rows_device": (C.c_int, [_H, C.c_void_p]),
     "sfm_batch_download_row_respawns": (C.c_int, [_H, _U32, _U32]),
+    # batch vehicle episodes and vehicle respawns (ABI 17, added without a bump)
+    "sfm_batch_set_vehicle_episodes": (C.c_int, [_H, _U8, _F, _F, _F, _F, _F, _F, _F, _I]),
+    "sfm_batch_end_vehicle_step": (C.c_int, [_H, C.c_uint32]),
+    "sfm_batch_download_vehicle_episodes": (C.c_int, [_H, _F, _U8, _U8]),
+    "sfm_batch_respawn_vehicles_device": (C.c_int, [_H, C.c_void_p]),
 }
 
 _lib = None

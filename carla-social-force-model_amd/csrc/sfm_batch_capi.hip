@@ -283,7 +283,8 @@ int sfm::batch_restart_device(SfmBatch* b, const uint8_t* d_mask, long long shif
     int rc = batch_restart_noise(b, nullptr, d_mask, b->B);
     if (!rc) rc = batch_plan_routes(b, nullptr, d_mask, b->B);          // (routes: from where the rows were placed)
     if (!rc) rc = batch_autopilot_restart(b, nullptr, d_mask, b->B);    // (the autopilot's cursors)
-    return rc ? rc : batch_row_restart(b, nullptr, d_mask, b->B);       // (the row episodes start over)
+    if (!rc) rc = batch_row_restart(b, nullptr, d_mask, b->B);          // (the row episodes start over)
+    return rc ? rc : batch_vehicle_episode_restart(b, nullptr, d_mask, b->B);   // (... and the vehicle episodes)
 }
 
 // sfm_batch_run_recorded, and with want_forces also the [F][K][N_total][C] force record of every recorded tick
@@ -444,6 +445,7 @@ int sfm_batch_upload_state(SfmBatch* b, const int32_t* scene_off, const float* x
     b->replay = {};                                               // ... and its observed tracks (the roles are per row)
     b->vscan = {};                                                // ... and the vehicles' scans of it
     b->boxes.vgrid = {};                                          // ... and the vehicles' grids of it
+    b->boxes.vep = {};                                            // ... and the vehicles' episodes (whatever drops the grids drops them)
     b->snap.on = false;                                           // ... and so is its snapshot
     b->have_state = false;
     if (n > 0) {
@@ -1020,7 +1022,8 @@ int sfm_batch_restart(SfmBatch* b, const uint8_t* mask) {
     rc = batch_restart_noise(b, r.list, nullptr, chosen);
     if (!rc) rc = batch_plan_routes(b, r.list, nullptr, chosen);        // (routes: from where the rows were placed)
     if (!rc) rc = batch_autopilot_restart(b, r.list, nullptr, chosen);  // (the autopilot's cursors)
-    return rc ? rc : batch_row_restart(b, r.list, nullptr, chosen);     // (the row episodes start over)
+    if (!rc) rc = batch_row_restart(b, r.list, nullptr, chosen);        // (the row episodes start over)
+    return rc ? rc : batch_vehicle_episode_restart(b, r.list, nullptr, chosen);   // (... and the vehicle episodes)
 }
 
 // The restart with its mask on the device (ABI 16): no copy, no host scan, no event wait, no pinned list.

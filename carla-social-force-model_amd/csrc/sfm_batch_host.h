@@ -3,7 +3,8 @@
 // read or write; sfm_batch_sense_capi.hip the read-only sensors (observations, episode ends, range scans, occupancy grids) and the device pointers;
 // sfm_batch_reset_capi.hip the restart noise; sfm_batch_replay_capi.hip the observed tracks; sfm_batch_drive_capi.hip the driven
 // vehicles and the vehicle observations (the vehicles' range scans are a sensor: sfm_batch_sense_capi.hip); sfm_batch_route_capi.hip
-// the routes over walk graphs; sfm_batch_row_episode_capi.hip the row episodes and the row respawns.
+// the routes over walk graphs; sfm_batch_row_episode_capi.hip the row episodes and the row respawns; sfm_batch_vehicle_episode_capi.hip
+// the vehicle episodes and the vehicle respawns.
 #pragma once
 #include "sfm_capi_common.h"
 #include "sfm_metres.h"
@@ -37,6 +38,22 @@ struct BatchGridDev {
     size_t vals(int channels) const { return M * (size_t)channels * (size_t)GU * (size_t)GV; }    // (64 bits)
 };
 
+// vehicle episodes (sfm_batch_set_vehicle_episodes): the episodes per VEHICLE -- the settings, the scenes' agent lists, the
+// per-vehicle episode state, and the record and the two masks sfm_batch_end_vehicle_step fills; nothing a tick reads or writes.  They
+// live inside the boxes they refer to, like the vehicles' grids: whatever replaces or drops the boxes drops them.
+struct BatchVehEpisodeDev {
+    bool on = false;           // (not "record is allocated": a batch without vehicles can have vehicle episodes and has no buffers)
+    DevBuf<VehicleEpisodeScene> set;   // [B]
+    DevBuf<int> agent_off;             // [B+1]
+    DevBuf<int> agent_veh;             // [agents] indices over the vehicles of all scenes, ascending
+    DevBuf<float4> goal_ext;           // [M] {goal_x, goal_y, half length, half width}
+    DevBuf<int> age;                   // [M]
+    DevBuf<float> prev;                // [M] prev_goal_d2
+    DevBuf<float> record;              // [M][8]
+    DevBuf<uint8_t> done;              // [M]
+    DevBuf<uint8_t> scene_done;        // [B]
+};
+
 // device-side vehicles (sfm_batch_set_dynamic_boxes): geo[2].ctr / .pts hold the vehicles the next tick sees, ctr_alt / pts_alt
 // (the same sizes) the half an integrating tick writes; batch_launch swaps them after each such launch
 struct BatchBoxesDev {
@@ -47,6 +64,7 @@ struct BatchBoxesDev {
     DevBuf<float2> pts_alt;
     std::vector<int32_t> item_off_h;   // the vehicles' scene_item_off [B+1] on the host
     BatchGridDev vgrid;        // the bird's-eye grids around these vehicles (sfm_batch_set_vehicle_grid)
+    BatchVehEpisodeDev vep;    // the episodes of these vehicles (sfm_batch_set_vehicle_episodes)
 };
 
 // scripted vehicle tracks (sfm_batch_set_vehicle_tracks, ABI 12): read-only on the device; dropped with the boxes they refer to
@@ -344,6 +362,8 @@ constexpr const char* VEHICLE_SCAN_OFF = "vehicle scans are off: call sfm_batch_
                                          "sfm_batch_set_dynamic_boxes and sfm_batch_set_dynamic_obstacles drop them)";
 constexpr const char* VEHICLE_GRID_OFF = "vehicle grids are off: call sfm_batch_set_vehicle_grid first (sfm_batch_upload_state, "
                                          "sfm_batch_set_dynamic_boxes and sfm_batch_set_dynamic_obstacles drop them)";
+constexpr const char* VEHICLE_EPISODES_OFF = "vehicle episodes are off: call sfm_batch_set_vehicle_episodes first (sfm_batch_upload_state, "
+                                             "sfm_batch_set_dynamic_boxes and sfm_batch_set_dynamic_obstacles drop them)";
 constexpr const char* NO_BOXES = "this needs device-side vehicles: call sfm_batch_set_dynamic_boxes first";
 constexpr const char* ROUTES_OFF = "routes are off: call sfm_batch_set_routes first (sfm_batch_upload_state and sfm_batch_set_mode_fsm drop them)";
 constexpr const char* GRIDS_OFF ="grids are off: call sfm_batch_set_grid first (sfm_batch_upload_state drops them)";
@@ -399,6 +419,14 @@ hipError_t launch_batch_row_episode(const RowEpisodeArgs& a, int B, hipStream_t 
 hipError_t launch_batch_row_restart(const int* list, const uint8_t* mask, const int* scene_off, int* row_age, float* row_prev_goal_d2,
                                     int scenes, hipStream_t st);
 hipError_t launch_batch_row_respawn(const RowRespawnArgs& a, int B, hipStream_t st);
+// Vehicle episodes and vehicle respawns (sfm_batch_vehicle_episode_capi.hip, sfm_batch_vehicle_episode.hip).
+// batch_vehicle_episode_restart: the vehicle episodes of the chosen scenes start over, one small launch behind the restart's own (and
+// the noise, the routes, the autopilot's and the row episodes') with the same choice of scenes; nothing while vehicle episodes are off.
+int batch_vehicle_episode_restart(SfmBatch* b, const int* d_list, const uint8_t* d_mask, int scenes);
+hipError_t launch_batch_vehicle_episode(const VehicleEpisodeArgs& a, int B, hipStream_t st);
+hipError_t launch_batch_vehicle_episode_restart(const int* list, const uint8_t* mask, const int* item_off, int* age, float* prev_goal_d2,
+                                                int scenes, hipStream_t st);
+hipError_t launch_batch_vehicle_respawn(const VehicleRespawnArgs& a, int B, hipStream_t st);
 // The delays go with the tracks they refer to (the caller synchronised the stream).
 inline void drop_noise_delays(SfmBatch* b) { b->noise.delay = {}; b->noise.max_delay = 0; }
 

@@ -107,7 +107,7 @@ static int build_grid(SfmBatch* b, size_t items, int channels, const char* whose
 
 // One lookup for the device buffers a caller may see: which = SFM_BATCH_PTR_*, or PTR_OBSERVATIONS for sfm_batch_observation_ptr's.
 // off: why there is none (its feature is off, no state was uploaded), else p and bytes -- both 0 where the buffer has no element.
-constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_ROW_RESETS + 1;   // (not part of the ABI: sfm_batch_device_ptr refuses it)
+constexpr int PTR_OBSERVATIONS = SFM_BATCH_PTR_VEHICLE_SCENE_DONE + 1;   // (not part of the ABI: sfm_batch_device_ptr refuses it)
 struct BatchBuffer { const char* off; void* p; size_t bytes; };
 static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     const size_t n = (size_t)b->n_total, B = (size_t)b->B;
@@ -152,6 +152,13 @@ static BatchBuffer batch_buffer(const SfmBatch* b, int which) {
     case SFM_BATCH_PTR_VEHICLE_GRID:
         if (!b->boxes.vgrid.on) return {VEHICLE_GRID_OFF, nullptr, 0};
         return have(b->boxes.vgrid.buf, sizeof(float) * b->boxes.vgrid.vals(SFM_BATCH_VEHICLE_GRID_CHANNELS));
+    case SFM_BATCH_PTR_VEHICLE_EPISODES:
+    case SFM_BATCH_PTR_VEHICLE_DONE:
+    case SFM_BATCH_PTR_VEHICLE_SCENE_DONE:
+        if (!b->boxes.vep.on) return {VEHICLE_EPISODES_OFF, nullptr, 0};
+        if (which == SFM_BATCH_PTR_VEHICLE_SCENE_DONE) return have(b->boxes.vep.scene_done, B);
+        return which == SFM_BATCH_PTR_VEHICLE_EPISODES ? have(b->boxes.vep.record, 8 * sizeof(float) * (size_t)b->geo[2].K)
+                                                       : have(b->boxes.vep.done, (size_t)b->geo[2].K);
     case SFM_BATCH_PTR_ROUTE_GOALS:
     case SFM_BATCH_PTR_ROUTE_STATUS:
         if (!b->routes.on) return {ROUTES_OFF, nullptr, 0};
@@ -196,7 +203,8 @@ void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes) {
     // (SFM_BATCH_PTR_GRID likewise, while grids are off, SFM_BATCH_PTR_ROW_SCORES / _SCENE_SCORES while observed tracks are off, and
     //  SFM_BATCH_PTR_VEHICLE_COMMANDS / _VEHICLE_OBS while driving / vehicle observations are off; SFM_BATCH_PTR_VEHICLE_SCAN is
     //  specified as SFM_ERR_STATE while the vehicle scan is off, so it is always known; SFM_BATCH_PTR_ROW_EPISODES / _ROW_DONE while
-    //  row episodes are off and SFM_BATCH_PTR_ROW_RESETS while restart noise is off are refused likewise)
+    //  row episodes are off, SFM_BATCH_PTR_ROW_RESETS while restart noise is off and SFM_BATCH_PTR_VEHICLE_EPISODES / _VEHICLE_DONE /
+    //  _VEHICLE_SCENE_DONE while vehicle episodes are off are refused likewise)
     const bool known = (which >= SFM_BATCH_PTR_COMMANDS && which <= SFM_BATCH_PTR_SCAN) || (which == SFM_BATCH_PTR_RESETS && b->noise.on) ||
                        (which == SFM_BATCH_PTR_GRID && b->grid.on) ||
                        ((which == SFM_BATCH_PTR_ROW_SCORES || which == SFM_BATCH_PTR_SCENE_SCORES) && b->replay.on) ||
@@ -204,7 +212,8 @@ void* sfm_batch_device_ptr(SfmBatch* b, int which, int64_t* bytes) {
                        which == SFM_BATCH_PTR_VEHICLE_SCAN || (which == SFM_BATCH_PTR_VEHICLE_GRID && b->boxes.vgrid.on) ||
                        ((which == SFM_BATCH_PTR_ROUTE_GOALS || which == SFM_BATCH_PTR_ROUTE_STATUS) && b->routes.on) ||
                        ((which == SFM_BATCH_PTR_ROW_EPISODES || which == SFM_BATCH_PTR_ROW_DONE) && b->ep.rows.on) ||
-                       (which == SFM_BATCH_PTR_ROW_RESETS && b->noise.on);
+                       (which == SFM_BATCH_PTR_ROW_RESETS && b->noise.on) ||
+                       (which >= SFM_BATCH_PTR_VEHICLE_EPISODES && which <= SFM_BATCH_PTR_VEHICLE_SCENE_DONE && b->boxes.vep.on);
     if (!known) { bfail(b, SFM_ERR_INVALID, "which must be SFM_BATCH_PTR_COMMANDS, _STATE, _ZSTATE, _EPISODES, _DONE or _SCAN"); return nullptr; }
     return buffer_ptr(b, which, which == SFM_BATCH_PTR_SCAN ? ", so which = SFM_BATCH_PTR_SCAN has no buffer" :
                                 which == SFM_BATCH_PTR_EPISODES || which == SFM_BATCH_PTR_DONE ? ", so which = SFM_BATCH_PTR_EPISODES / _DONE has no buffer" : "", bytes);

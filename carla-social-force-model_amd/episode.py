@@ -140,3 +140,95 @@ def row_episode_scene(scene, agents, radii, max_steps, ages=None, prevs=None, st
         r[EP_AGE] = age
         rec[i], done[i], ages[i] = r, bool(reason), age
     return rec, done, ages, prevs
+
+
+REASON_WALL_HIT = 32             # SFM_EPISODE_WALL_HIT: set by vehicle records only
+EP_PED_GAP2, EP_VEH_GAP2, EP_WALL_GAP2 = 5, 6, 7      # slots 5 .. 7 of a VEHICLE record
+
+
+def box_gap2(centre, heading, extent, pts):
+    """gap2 of include/sfm_hip.h for every point of ``pts`` (P,2) fp32: the squared distance to the box of half-extents ``extent``
+    = (ex, ey) around ``centre``, turned by the stored ``heading`` = (cos, sin); 0 inside or on the box.  Bit for bit: the
+    sensors' rotation in exact fused multiply-adds, every other operation one fp32 rounding.  A point that is not live gives +inf
+    (it is no candidate), so the minimum over the result is the record's.  Returns float32 (P,)."""
+    from .scan import _fma32
+    pts = np.asarray(pts, dtype=np.float32).reshape(-1, 2)
+    cx, cy = np.float32(centre[0]), np.float32(centre[1])
+    hx, hy = np.float32(heading[0]), np.float32(heading[1])
+    ex, ey = np.float32(extent[0]), np.float32(extent[1])
+    out = np.full(pts.shape[0], INF, np.float32)
+    ok = _live(pts[:, 0], pts[:, 1])
+    if ok.any():
+        with np.errstate(over="ignore", invalid="ignore"):
+            dx, dy = pts[ok, 0] - cx, pts[ok, 1] - cy
+            u = _fma32(hx, dx, hy * dy)
+            v = _fma32(hx, dy, -(hy * dx))
+            ax = np.fmax(np.abs(u) - ex, np.float32(0.0))
+            ay = np.fmax(np.abs(v) - ey, np.float32(0.0))
+            out[ok] = _fma32(ax, ax, ay * ay)
+    return out
+
+
+def _gap_min(centre, heading, extent, pts):
+    return np.float32(np.fmin.reduce(box_gap2(centre, heading, extent, pts), initial=INF)) if len(pts) else INF
+
+
+def vehicle_episode_scene(scene, agents, goals, extents, radii, max_steps, ages=None, prevs=None, state=None, vehicles=None, headings=None):
+    """One evaluation of every agent VEHICLE of one scene: (records (M,8) float32, done (M,) bool, scene_done bool, ages (M,) int32,
+    prevs (M,) float32) -- the scene's vehicles of ``SfmBatch.vehicle_episodes()`` after ``end_vehicle_step()``, and their episode
+    state after it.
+
+    ``agents``: (M,) nonzero = the vehicle is an agent (or True / False for all).  ``goals`` (M,2), ``extents`` (M,2) half-extents.
+    ``radii``: (goal_radius, ped_radius, veh_radius, wall_radius) in metres; ``max_steps``: 0 = no time limit.  ``ages`` / ``prevs``:
+    the vehicles' episode state before the evaluation (None: zeros / NaN, as after a respawn).  What has changed on the device since
+    the upload is fed in: ``state`` = (loc, vel) of the rows, ``vehicles`` = the scene's list of (center, ring), ``headings`` (M,2)
+    fp32 {cos, sin} (default: ``scenarios.vehicle_headings(scene)``).  Vehicles that are not agents keep what they are given: a zero
+    record, done False and their state."""
+    from .scan import _fma32
+    from .scenarios import vehicle_headings
+    max_steps = int(max_steps)
+    rg2, rp2, rv2, rw2 = (radius2(r) for r in radii)
+    veh = (_get(scene, "dynamic_obstacles") or []) if vehicles is None else vehicles
+    M = len(veh)
+    ag = np.full(M, bool(agents)) if np.ndim(agents) == 0 else np.asarray(agents).reshape(-1) != 0
+    if ag.shape[0] != M:
+        raise ValueError(f"{ag.shape[0]} agent flags for a scene of {M} vehicles")
+    ages = np.zeros(M, np.int32) if ages is None else np.array(ages, dtype=np.int32).reshape(M)
+    prevs = np.full(M, np.nan, np.float32) if prevs is None else np.array(prevs, dtype=np.float32).reshape(M)
+    rec = np.zeros((M, EPISODE_WIDTH), np.float32)
+    done = np.zeros(M, bool)
+    if not ag.any():
+        return rec, done, False, ages, prevs
+    loc = np.asarray(_get(scene, "loc") if state is None else state[0], dtype=np.float64)
+    n = loc.reshape(-1, loc.shape[-1]).shape[0] if loc.size else 0
+    rows = _f32(loc.reshape(n, -1)[:, :2], 2) if n else np.zeros((0, 2), np.float32)
+    g = _f32(goals, 2)
+    ext = _f32(extents, 2)
+    h = _f32(vehicle_headings(scene) if headings is None else headings, 2)
+    ctr = np.stack([_f32(c, 0)[:2] for c, _ in veh])
+    rings = [_f32(r, 2) for _, r in veh]
+    wall = np.concatenate([_polylines(_get(scene, "borders") or [], False)[0], _polylines(_get(scene, "static_obstacles") or [], True)[0]])
+    for k in np.flatnonzero(ag):
+        age = int(ages[k]) + 1
+        r = np.full(EPISODE_WIDTH, INF, np.float32)
+        reason = REASON_NOT_LIVE
+        if _live(ctr[k, 0], ctr[k, 1]):
+            with np.errstate(over="ignore", invalid="ignore"):
+                gx, gy = g[k, 0] - ctr[k, 0], g[k, 1] - ctr[k, 1]
+                goal_d2 = np.float32(_fma32(gx, gx, gy * gy))
+            others = [rings[q] for q in range(M) if q != k]
+            other = np.concatenate(others) if others else np.zeros((0, 2), np.float32)
+            ped, vg, wg = (_gap_min(ctr[k], h[k], ext[k], p) for p in (rows, other, wall))
+            r[EP_GOAL_D2] = goal_d2
+            r[EP_PREV_GOAL_D2] = goal_d2 if np.isnan(prevs[k]) else prevs[k]
+            r[EP_PED_GAP2], r[EP_VEH_GAP2], r[EP_WALL_GAP2] = ped, vg, wg
+            prevs[k] = goal_d2
+            reason = ((REASON_ARRIVED if goal_d2 < rg2 else 0) | (REASON_PED_HIT if ped < rp2 else 0) |
+                      (REASON_VEH_HIT if vg < rv2 else 0) | (REASON_WALL_HIT if wg < rw2 else 0))
+        if max_steps > 0 and age >= max_steps:
+            reason |= REASON_TIME_LIMIT
+        r[EP_DONE] = 1.0 if reason else 0.0
+        r[EP_REASON] = reason
+        r[EP_AGE] = age
+        rec[k], done[k], ages[k] = r, bool(reason), age
+    return rec, done, bool(done.any()), ages, prevs

@@ -483,3 +483,29 @@ def baseline_scenario(name):
     kw = dict(BASELINE_CONFIGS[name])
     forces = kw.pop("forces")
     return make_scenario(**kw), forces
+
+
+def respawn_vehicles_scene(chosen, snapshot, current):
+    """One respawn of the chosen vehicles of one scene (sfm_batch_respawn_vehicles_device), the copy rule: a dict like ``current``
+    in which every per-vehicle entry of a chosen vehicle is the snapshot's and everything else is ``current``'s, untouched.
+
+    ``chosen``: (M,) nonzero = respawn the vehicle.  ``snapshot`` / ``current``: dicts of per-vehicle values as the snapshot holds
+    them and as they are now -- ``centers`` (M,2), ``vel`` (M,2), ``headings`` (M,2), ``rings`` (a list of M (P_k,2) arrays) and,
+    with an autopilot set, ``cursor`` (M,).  With ``age`` (M,) and ``prev`` (M,) in ``current`` (vehicle episodes are on) a chosen
+    vehicle's episode starts over: age 0, prev NaN.  Keys that are not per vehicle pass through."""
+    ch = np.asarray(chosen).reshape(-1) != 0
+    out = dict(current)
+    for key in ("centers", "vel", "headings", "cursor"):
+        if key in current:
+            a = np.array(current[key], copy=True)
+            if a.shape[0] != ch.shape[0]:
+                raise ValueError(f"{ch.shape[0]} choices for {a.shape[0]} vehicles ({key})")
+            a[ch] = np.asarray(snapshot[key])[ch]
+            out[key] = a
+    if "rings" in current:
+        out["rings"] = [np.array(snapshot["rings"][k] if ch[k] else current["rings"][k], copy=True) for k in range(ch.shape[0])]
+    if "age" in current:
+        age, prev = np.array(current["age"], dtype=np.int32, copy=True), np.array(current["prev"], dtype=np.float32, copy=True)
+        age[ch], prev[ch] = 0, np.nan
+        out["age"], out["prev"] = age, prev
+    return out

@@ -806,6 +806,94 @@ int sfm_batch_end_row_step(SfmBatch* b, uint32_t flags);
 int sfm_batch_download_row_episodes(SfmBatch* b, float* record, uint8_t* row_done, int32_t* row_age, float* row_prev_goal_d2);
 int sfm_batch_respawn_rows_device(SfmBatch* b, const uint8_t* d_mask);
 int sfm_batch_download_row_respawns(SfmBatch* b, uint32_t* row_resets, uint32_t* fallbacks);
+/* Vehicle episodes and vehicle respawns: what decides that a DRIVE is over.  A driving policy has commands, an autopilot for the
+ * other cars and three sensors; sfm_batch_end_vehicle_step tells it, for every agent vehicle and by ONE launch of
+ * sfm_batch_vehicle_episode_kernel (a workgroup per scene), whether the car has arrived, run out of time or touched a pedestrian,
+ * another vehicle or a wall -- on exact gaps to the car's oriented BOX, not on the sampled ring the model sees it as.
+ * sfm_batch_respawn_vehicles_device puts chosen vehicles back from the snapshot by ONE launch of sfm_batch_vehicle_respawn_kernel
+ * while their scenes go on.  A batch that never calls sfm_batch_set_vehicle_episodes or a vehicle respawn launches exactly what it
+ * launched before.  These entry points, SFM_EPISODE_WALL_HIT and SFM_BATCH_PTR_VEHICLE_EPISODES / _VEHICLE_DONE / _VEHICLE_SCENE_DONE
+ * were added WITHOUT a bump of SFM_ABI_VERSION (it stays 17), like the restart noise: additions only, recognised by the symbols.
+ *
+ * Settings (sfm_batch_set_vehicle_episodes).  Per vehicle, M over all scenes, indexed as in sfm_batch_set_dynamic_boxes: agents [M]
+ * bytes on the host, nonzero = the vehicle's fate is evaluated; goal_x, goal_y [M], finite; extent [M][2], the half length along the
+ * heading and the half width in metres, for agents finite, > 0 and <= SFM_BATCH_MAX_SENSE_RANGE (the extent of a vehicle that is no
+ * agent is not read).  Per scene, [B] each: goal_radius, ped_radius, veh_radius, wall_radius, validated as sfm_batch_set_episodes
+ * validates its radii, r2 = float32(double(r) * r), 0 switches the test off; max_steps >= 0, 0: no time limit.  The scenes' agent
+ * vehicles are compacted into a list on the host: the list is settings, not state.  Needs device-side vehicles
+ * (sfm_batch_set_dynamic_boxes), else SFM_ERR_STATE.  Vehicle episodes are independent of sfm_batch_set_episodes and
+ * sfm_batch_set_row_episodes; all three may be on at once.
+ *
+ * State.  Per vehicle age (int32, zero-filled) and prev_goal_d2 (float, NaN-filled).  A snapshot neither holds nor restores them.
+ * EVERY restart of a scene -- sfm_batch_restart, sfm_batch_restart_device, the auto restarts of sfm_batch_end_step and of
+ * sfm_batch_end_vehicle_step -- sets age = 0 and prev_goal_d2 = NaN for ALL vehicles of the restarted scene, by one small launch
+ * behind the restart's own (sfm_batch_vehicle_episode_restart_kernel; sfm_batch_restart_kernel is unchanged; nothing is launched
+ * while vehicle episodes are off); a respawn does so for the respawned vehicles.
+ *
+ * Record.  Vehicle k owns SFM_BATCH_EPISODE_WIDTH floats, [M][8].  Slots 0 .. 4 mean what they mean for sfm_batch_end_step: done,
+ * the reason bits, age, goal_d2, prev_goal_d2, with goal_d2 = fmaf(gx, gx, gy * gy), g = goal - centre.  Slots 5 .. 7 are squared
+ * gaps to the vehicle's BOX, not to its centre.  With the centre c = ctr[k].xy, the STORED heading h = rot[k] and the half-extents
+ * (ex, ey), all as the next tick reads them, a candidate point p has
+ *        dx = px - cx;  dy = py - cy
+ *        u  = fmaf(h.x, dx, h.y * dy);   v = fmaf(h.x, dy, -(h.y * dx))        (the sensors' rotation into the heading frame)
+ *        ax = fmaxf(fabsf(u) - ex, 0);   ay = fmaxf(fabsf(v) - ey, 0)
+ *        gap2(p) = fmaf(ax, ax, ay * ay)                                        (0 inside or on the box)
+ *     5  ped_gap2: the minimum of gap2 over the scene's live rows; +inf when there are none
+ *     6  veh_gap2: the minimum over the ring points of the scene's OTHER vehicles (the own ring is skipped by its index range
+ *        [off[k], off[k + 1]), as the vehicle scan skips it)
+ *     7  wall_gap2: the minimum over all border and static-obstacle points of the scene
+ * A point is a candidate ONLY IF it is live (|px|, |py| < 1e12, which a NaN fails).  This rule is load-bearing: an absent tracked
+ * vehicle has its ring at +inf, inf * 0 under a heading with a zero component is NaN, and fmaxf(NaN - ex, 0) is 0 -- a contact with
+ * nothing.  With the rule no NaN enters a minimum.
+ * Rules, all exact, every decision a strict `<`: SFM_EPISODE_ARRIVED iff goal_d2 < goal_r2; _PED_HIT iff ped_gap2 < ped_r2;
+ * _VEH_HIT iff veh_gap2 < veh_r2; SFM_EPISODE_WALL_HIT (32, set by vehicle records only) iff wall_gap2 < wall_r2; _TIME_LIMIT iff
+ * max_steps > 0 and age_old + 1 >= max_steps.  So a pedestrian exactly on the box edge has gap 0 and a radius of 0 never fires.  An
+ * agent whose centre is not live (an absent tracked vehicle, or not finite) gets SFM_EPISODE_NOT_LIVE and +inf in slots 3 .. 7; its
+ * stored prev_goal_d2 is left alone, its age counts.  A heading that is not exactly unit is defined by the rules alone.  done = any
+ * reason bit.  prev_goal_d2 in the record is the stored value, or goal_d2 when the stored value is NaN.
+ * Two masks: vehicle_done [M] bytes, = slot 0; vehicle_scene_done [B] bytes, 1 iff any agent vehicle of the scene is done --
+ * sfm_batch_restart_device takes it as it stands.  Vehicles that are not agents are NEVER written (record, byte, state), and neither
+ * is the vehicle_scene_done byte of a scene without agent vehicles: sfm_batch_set_vehicle_episodes fills all of them with zeros
+ * (prev_goal_d2: NaN).  Only minima are taken, a minimum of floats without NaNs does not depend on the order it is taken in, and
+ * there are no atomics: a vehicle's record is bitwise the same alone, anywhere in any batch, and under any split of the work.
+ *
+ * sfm_batch_set_vehicle_episodes allocates and fills all of it and waits for the batch's stream; agents = NULL switches vehicle
+ * episodes off and frees the buffers.  A refusal changes nothing.  Whatever drops sfm_batch_set_vehicle_grid drops them:
+ * sfm_batch_upload_state, sfm_batch_set_dynamic_boxes and sfm_batch_set_dynamic_obstacles; every other call keeps them, and they keep
+ * the snapshot.
+ * sfm_batch_end_vehicle_step: ONE launch on the batch's stream; the host does not wait.  flags: 0;
+ * SFM_END_VEHICLE_STEP_AUTO_RESTART: the launch is followed by sfm_batch_restart_device on vehicle_scene_done;
+ * SFM_END_VEHICLE_STEP_AUTO_RESPAWN: it is followed by sfm_batch_respawn_vehicles_device on vehicle_done; the record keeps the
+ * terminal values.  Both flags together are refused (SFM_ERR_INVALID).  SFM_ERR_STATE while vehicle episodes are off; with a flag
+ * every refusal of the follow-up call applies to the whole call, and nothing is launched.
+ * sfm_batch_download_vehicle_episodes synchronises the stream and copies the record ([M][8]), vehicle_done ([M] bytes) and
+ * vehicle_scene_done ([B] bytes); NULL skips a column.
+ *
+ * Vehicle respawns (sfm_batch_respawn_vehicles_device).  d_mask: [M] bytes of DEVICE memory, nonzero = respawn the vehicle -- the
+ * batch's own vehicle_done (d_mask = NULL takes it) or any buffer of the caller's; the values are not validated.  ONE launch of B
+ * workgroups: a workgroup counts its scene's chosen vehicles and leaves at once when there is none -- such a scene is not written at
+ * all.  For a chosen vehicle its centre and velocity, its heading, its ring points and, with an autopilot set, its cursor are copied
+ * from the snapshot into the half of the ping-pong the next tick reads, and its vehicle episode starts over.  No pedestrian, clock,
+ * counter, scene episode or other vehicle is touched; the commands are the caller's and stay.  There is no placement noise for
+ * vehicles.  Refused with nothing launched: no snapshot (SFM_ERR_STATE); d_mask NULL while vehicle episodes are off
+ * (SFM_ERR_INVALID); vehicle tracks are set (SFM_ERR_STATE) -- a tracked vehicle's time belongs to its scene's clock, so re-timing
+ * single tracks is deliberately OUT OF SCOPE: such batches restart whole scenes.
+ *
+ * sfm_batch_device_ptr: SFM_BATCH_PTR_VEHICLE_EPISODES, the record ([M][8] float); SFM_BATCH_PTR_VEHICLE_DONE ([M] uint8_t);
+ * SFM_BATCH_PTR_VEHICLE_SCENE_DONE ([B] uint8_t) -- valid until the next sfm_batch_set_vehicle_episodes or a call that drops them.
+ * While vehicle episodes are off the values are refused as the unknown `which` they were before. */
+#define SFM_EPISODE_WALL_HIT 32
+#define SFM_BATCH_PTR_VEHICLE_EPISODES 19
+#define SFM_BATCH_PTR_VEHICLE_DONE 20
+#define SFM_BATCH_PTR_VEHICLE_SCENE_DONE 21
+#define SFM_END_VEHICLE_STEP_AUTO_RESTART 1u
+#define SFM_END_VEHICLE_STEP_AUTO_RESPAWN 2u
+int sfm_batch_set_vehicle_episodes(SfmBatch* b, const uint8_t* agents, const float* goal_x, const float* goal_y, const float* extent,
+                                   const float* goal_radius, const float* ped_radius, const float* veh_radius,
+                                   const float* wall_radius, const int32_t* max_steps);
+int sfm_batch_end_vehicle_step(SfmBatch* b, uint32_t flags);
+int sfm_batch_download_vehicle_episodes(SfmBatch* b, float* record, uint8_t* vehicle_done, uint8_t* vehicle_scene_done);
+int sfm_batch_respawn_vehicles_device(SfmBatch* b, const uint8_t* d_mask);
 /* Range scans on the device (ABI 17): the sensor most crowd-navigation policies are trained on.  R rays around a row, each giving
  * the distance to the first thing it meets and what that was, by ONE launch of sfm_batch_scan_kernel (a workgroup per scene)
  * straight from the buffers the tick reads, into a device buffer the caller reads with no copy.  The record is defined bit for bit
